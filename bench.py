@@ -12,9 +12,10 @@ runs the same batch size on its own GPU (weak scaling, no data-path collective: 
 max-over-ranks time go through RCCL behind the library's C ABI (racinglmpc_amd/parallel.py); value = all ranks' solves /
 max-over-ranks time.  No PyTorch anywhere in the measured path.
 
-Besides the contract's keys the line carries (cheap, a few seconds together): the batch sweep 1..8192, BASELINE configs[2]
-(batch 4096, safe set from 30 laps), configs[4] (N = 40, batch 1024) and configs[3] (closed-loop rollouts sharded over the ranks
-with one all-gather per lap).  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the headline.  With --full the line also carries the batch sweep 1..8192,
+BASELINE configs[2] (batch 4096, safe set from 30 laps), configs[4] (N = 40, batch 1024), independent batches in flight, configs[3]
+(closed-loop rollouts sharded over the ranks with one all-gather per lap) and the CPU baseline.  --dump-outputs DIR writes what the
+last timed step computed (rank 0's batch) as DIR/<name>.npy.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -143,6 +144,24 @@ def time_steps(ctx, B, a, steps, warmup, sync=None):
     dt = time.perf_counter() - t0
     st = ctx.stats(); ctx.set_profiling(False)
     return dt, st
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_KEYS = ("xPred", "uPred", "slack", "lambd", "sTerm", "ztNext", "ztuNext", "ssSel", "A", "B", "C", "status", "iters")   # what the timed call writes (no diagnostics)
+
+
+def dump_outputs(path, ctx, a, B):
+    """--dump-outputs: every output of the last lmpc_step_batch_dev call, as the caller receives it, one DIR/<name>.npy each in float64 (status and
+    interior-point iteration counts converted).  Above 64 MB in all, a fixed seeded sample of the problems is written, its row numbers in sample_rows.npy."""
+    out = ctx.step_dev_fetch(a, B)
+    out = {k: out[k] for k in DUMP_KEYS}
+    per_row = sum(v[0].size for v in out.values()) * 8
+    if B * per_row > DUMP_LIMIT_BYTES - (1 << 16):                  # (64 KB left for the .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(B, (DUMP_LIMIT_BYTES - (1 << 16)) // (per_row + 8), replace=False))
+        out = dict({k: v[rows] for k, v in out.items()}, sample_rows=rows)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def run_config(g, N, B, device, steps, warmup, laps=None, query_lap=None, **kw):
@@ -335,14 +354,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="QPs per GPU per step (BASELINE configs[1]: 256)")
     ap.add_argument("--horizon", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sweep / extra configurations / rollout leg")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the batch sweep, the extra configurations, the rollout leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the sweep / extra configurations / rollout leg")
     ap.add_argument("--rollouts-per-gpu", type=int, default=1024)
-    ap.add_argument("--rollouts-only", action="store_true", help="of the extras, run the closed-loop rollout leg only (developer runs)")
+    ap.add_argument("--rollouts-only", action="store_true", help="with --full: of the extras, run the closed-loop rollout leg only (developer runs)")
     ap.add_argument("--dry-run", action="store_true", help="start the ranks and the rendezvous only (no GPU needed): proves the N-rank launch path")
     ap.add_argument("--dry-run-rccl", action="store_true", help="communicator set-up, one barrier and one gather only -- on a box with fewer GPUs than ranks the ranks share "
                     "device 0 and RCCL refuses: the failure path of lmpc_comm_init with world > 1 (one JSON line with rccl_error, exit status 3)")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, sys.argv[1:])
@@ -381,7 +403,7 @@ def main():
                 "rccl_error": message, "note": "value, if any, is rank 0's own rate over its K steps (no cross-rank barrier closed the region)"}
     wd = Watchdog(rank, world, minimal_line)
     try:
-        ctx = make_ctx(g, N, max(B, 1 if args.no_extras else args.rollouts_per_gpu), local)
+        ctx = make_ctx(g, N, max(B, args.rollouts_per_gpu if extras else 1), local)
     except Exception:                                # noqa: BLE001
         if not args.dry_run_rccl or local == 0:
             raise
@@ -429,6 +451,8 @@ def main():
     n_ok = int(comm.allgather(np.array([np.sum(status == 0)], dtype=np.int64)).sum())
     comm_info = ctx.comm_info()
     wd.disarm()                                      # the headline is complete: every collective it needs has returned
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, a, B)
 
     out = None
     if rank == 0:
@@ -479,7 +503,7 @@ def main():
         ctx.dev_free(p)
 
     # ---- extra configurations (rank 0's GPU; the other ranks sleep on a host-side event meanwhile: no rank spins in a collective) ----------
-    if not args.no_extras:
+    if extras:
         host_event = world > 1 and parallel._is_local(addr)
         if rank != 0 and host_event:
             parallel.host_wait("extras", port)
@@ -531,7 +555,7 @@ def main():
             watchdog.cancel()
         if rank == 0:
             out["config_rollouts"] = dict(leg, note="BASELINE configs[3]: closed-loop LMPC laps sharded over the ranks, lap stores replicated, one all-gather per lap")
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(N, B) if world == 1 else None
     def drain_stdio():   # librccl announces its version through C stdio (buffered when stdout is a pipe): push it out NOW
         try:
@@ -542,7 +566,7 @@ def main():
     # the JSON line must be the LAST thing on the job's stdout: every rank drains its buffers, THEN the ranks meet at the barrier, then rank 0 prints
     drain_stdio()
     comm.barrier()
-    if rank == 0 and not args.no_extras and world > 1 and parallel._is_local(addr):
+    if rank == 0 and extras and world > 1 and parallel._is_local(addr):
         try:
             os.remove(sig_path)
         except (OSError, NameError):

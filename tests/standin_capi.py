@@ -1,7 +1,7 @@
 """tests/standin_capi.py -- a CPU stand-in for racinglmpc_amd._capi, backed by the oracle (test infrastructure, never product).
 
 Purpose: run the reference's UNCHANGED main.py (and plot.py) against the drop-in Python layer in a container that has the reference but no GPU
-(tests/test_reference_main_seam.py, tools/run_reference_main.py).  Installed as sys.modules["racinglmpc_amd._capi"] BEFORE the drop-in modules are
+(tools/run_reference_main.py).  Installed as sys.modules["racinglmpc_amd._capi"] BEFORE the drop-in modules are
 imported, it offers the names and call signatures those modules use (config_from, Context.step_batch / regress_batch / qp_solve_batch / select_batch /
 assemble_batch / ss_* / model_add_trajectory, lti_regression, the ST_* bits) and records every call; the arithmetic behind them is the oracle's
 restatement (oracle/lmpc_oracle.py), each QP solved to its certified optimum as the GPU path does.  What this proves is the SEAM: every module

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Collect the measurement set of one round on the GPU box (run through gpurun from the repo root):
 #   tools/collect_profiles.sh r2a [batch ...]
-# writes gpurun_out/<tag>_bench.json (the driver's command: every configuration in one line) and, per batch size B (default 256 4096),
-# gpurun_out/<tag>_B<B>_kernel_stats.csv and _B<B>_pmc_pass{1..6}.csv.  Copy them to profiles/ and run
+# writes $OUT/<tag>_bench.json (bench.py --full: every configuration in one line) and, per batch size B (default 256 4096),
+# $OUT/<tag>_B<B>_kernel_stats.csv and _B<B>_pmc_pass{1..6}.csv.  Copy them to profiles/ and run
 # tools/make_traffic.py profiles/<tag> to refresh profiles/traffic.json (read by bench.py's roofline object).
 set -u
 TAG=${1:-r2x}
@@ -12,7 +12,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 H=${HORIZON:-12}                                   # HORIZON=40 tools/collect_profiles.sh r3m_N40 1024: kernel stats + PMC passes of another horizon only
-if [ "$H" = "12" ]; then python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; fi
+if [ "$H" = "12" ]; then python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; fi
 cd /tmp && export TMPDIR=/tmp
 for B in $BATCHES; do
   CMD="python $ROOT/bench.py --batch $B --horizon $H --steps 30 --warmup 5 --no-cpu-baseline --no-extras"
@@ -35,4 +35,4 @@ if [ "$H" != "12" ]; then exit 0; fi
 # phase timings of one QP (developer build with cycle stamps) and the RCCL branch on one rank
 LMPC_TIMING_MW=1 python tools/phase_timing.py > $OUT/${TAG}_phase_timing_mw4.txt 2>&1
 python tools/phase_timing.py > $OUT/${TAG}_phase_timing_1w.txt 2>&1
-LMPC_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --rollouts-per-gpu 256 > $OUT/${TAG}_bench_rccl_1rank.json 2> $OUT/${TAG}_bench_rccl_1rank.err
+LMPC_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --rollouts-per-gpu 256 > $OUT/${TAG}_bench_rccl_1rank.json 2> $OUT/${TAG}_bench_rccl_1rank.err
