@@ -99,8 +99,15 @@ int lmpc_solver_kind(lmpc_ctx *);                                /* 0: built-in 
 int lmpc_destroy(lmpc_ctx *ctx);
 const char *lmpc_last_error(void);
 const char *lmpc_active_knobs(void);                             /* developer environment variables this process has acted on ("NAME=value;..."; "" = none): LMPC_K1_QG,
-                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG -- route / grid choices
-                                                                    with identical results, each announced once on stderr; no reference counterpart */
+                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG -- route / grid choices,
+                                                                    each announced once on stderr; no reference counterpart.  Bit-identical results: LMPC_K1_QG, LMPC_K1_RPL16
+                                                                    (regression grid / scan build: A, B, C do not depend on either), LMPC_FUSE (fused one-wave step against the
+                                                                    two-kernel one-wave step; ignored by the runtime-(N, S) kernel, which has no fused form), LMPC_NO_ABG
+                                                                    ([A_k | B_k] in LDS instead of global memory).  LMPC_MW_MAX_BATCH and LMPC_MW2_MAX_BATCH move a batch to
+                                                                    another solve kernel (four / two / one wave(s) per QP): A, B, C, the selection and the status word stay
+                                                                    bit-identical, the QP answer agrees to the termination rule's bound (x, u within 2e-7: measured by
+                                                                    tests/test_gpu_routes.py).  LMPC_CD (condensed kernel, opt-in builds only): another QP method, same optimum
+                                                                    to the stated tolerances (tests/test_gpu_condensed.py) */
 int lmpc_version(void);
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes);
         /* hipMemGetInfo of `device`: what is left of the 288 GB for max_batch, the lap stores (lmpc_config: max_laps x max_points) and rollout sessions -- and what a
@@ -177,8 +184,9 @@ int lmpc_dev_sync(lmpc_ctx *);
 typedef struct {          /* all device pointers, layouts as in lmpc_step_batch.  Optional (NULL = not wanted): slack, lambda, sTerm, ztNext, ztuNext,
                              ssSel, A, Bm, C, mu, resid, qSel.  With LMPC_FUSE=1 in the environment, batches that run one wavefront per QP take
                              the step as ONE kernel: each wave first runs the regression (MPC.computeLTVdynamics, :140-145) of its own QP,
-                             A_i / B_i / C_i stay in LDS and are copied out only if A / Bm / C are given (bit-identical results; measured
-                             slower than the two-kernel step, hence off by default). */
+                             A_i / B_i / C_i stay in LDS and are copied out only if A / Bm / C are given (results bit-identical to the
+                             two-kernel step on the one-wave kernel; measured slower, hence off by default; contexts served by the
+                             runtime-(N, S) kernel ignore the knob). */
     const double *x0, *xLin, *uLin, *uOld, *zt, *xPredPrev; const int *hasPred, *timeStep;
     double *xPred, *uPred, *slack, *lambda, *sTerm, *ztNext, *ztuNext, *ssSel, *A, *Bm, *C, *mu, *resid;
     int *status, *iters;

@@ -138,6 +138,15 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _npz_path(path):
+    """The file np.savez_compressed writes for `path`: it appends .npz to a path without that extension (file objects are taken as they are)."""
+    if isinstance(path, (str, os.PathLike)):
+        path = os.fspath(path)
+        if not path.endswith(".npz"):
+            path += ".npz"
+    return path
+
+
 def default_config():
     cfg = LmpcConfig()
     _chk(load().lmpc_config_default(C.byref(cfg)))
@@ -440,12 +449,13 @@ class Context:
         for i in range(ns):
             x, u, q = self.store_read_lap(1, i); out["ss_x%d" % i] = x; out["ss_u%d" % i] = u; out["ss_q%d" % i] = q
             out["ss_laptime%d" % i] = np.int64(self.ss_lap_time(i))
-        np.savez_compressed(path, n_model=np.int64(nm.value), n_ss=np.int64(ns), N=np.int64(self.N), **out)
+        np.savez_compressed(_npz_path(path), n_model=np.int64(nm.value), n_ss=np.int64(ns), N=np.int64(self.N), **out)
 
     def restore_stores(self, path):
         """Into a context whose stores are EMPTY: the regression laps in their sorted order (a stable sorted insert keeps it), the safe-set laps at their addTrajectory-time
-        length followed by the rows addPoint had appended and their Q-function.  The restored context answers every later call bit for bit like the one that was saved."""
-        with np.load(path) as d:
+        length followed by the rows addPoint had appended and their Q-function.  The restored context answers every later call bit for bit like the one that was saved.
+        `path` is what save_stores was given, with or without the .npz extension."""
+        with np.load(_npz_path(path)) as d:
             nm = C.c_int(); _chk(self.lib.lmpc_model_num_laps(self._h, C.byref(nm)))
             if nm.value or self.ss_num_laps():
                 raise LmpcError("restore_stores needs a context with empty lap stores")
@@ -652,6 +662,11 @@ class ContextPool:
                 return out
             return forward
         return getattr(self.members[0], name)
+
+    def restore_stores(self, path):
+        """Context.restore_stores into every member (step_batch_dev deals steps to all of them; save_stores may go to any one: their stores are equal)."""
+        for m in self.members:
+            m.restore_stores(path)
 
     def step_dev_buffers(self, inp, diagnostics=True):
         """One set of device buffers per member: [(args, allocations)], in member order."""

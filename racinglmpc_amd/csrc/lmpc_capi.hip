@@ -263,6 +263,8 @@ static int create_body(lmpc_ctx *c) {
     // at batch 8192 with eight: the regression's short dependent chains (DPP minima, 5 x 5 Cholesky, scattered L2 reads) want the four waves
     // per SIMD its own kernel gets, the solve kernel runs two.  Off unless LMPC_FUSE=1.
     { const char *e = dev_knob("LMPC_FUSE"); c->fuse_k1 = e ? atoi(e) : 0; }
+    // (the runtime-(N, S) kernel has no fused form: it would take io.mode & 4 for a plain solve and read A / B / C nobody wrote -- the step runs as two kernels there)
+    if (c->solver_kind == 2) c->fuse_k1 = 0;
     if (c->fuse_k1 && (size_t)(54 * cfg->N + k1_fused_doubles(cfg->N, cfg->trToUse, cfg->maxNumPoint)) * sizeof(double) > (size_t)160 * 1024) c->fuse_k1 = 0;   // (many laps: the regression's work space does not fit beside the solve)
     {   // condensed kernel (lmpc_solve_cd.hip.h): built for 2N <= 32 and one terminal-block column per lane; it takes the state cost as diagonal Q, Qf
         bool diag = true; c->cd_hasq = 0;
@@ -386,10 +388,13 @@ int lmpc_destroy(lmpc_ctx *c) {
 }
 
 static int resolve_retries(lmpc_ctx *c);
-// Every entry point that changes what a deferred retry pass would read -- the lap stores, caller-visible device buffers (lmpc_dev_upload) -- or
-// hands results to someone else (lmpc_comm_allgather_dev, lmpc_ss_get_qfun) first gives the launches still pending their retry pass: a flagged
-// problem is then re-solved against the data of ITS launch, never against a changed safe set or overwritten inputs.  (No launch pending -- the
-// drop-in flow, where lmpc_step_batch resolves before it returns -- costs nothing: no stream drain is added.)
+// Every entry point that changes what a deferred retry pass would read -- the lap stores, caller-visible device buffers (lmpc_dev_upload), the
+// context's A / B / C hand-over buffers w_A / w_B / w_C (lmpc_regress_batch, lmpc_regress_points, lmpc_qp_solve_batch, lmpc_assemble_batch; a
+// lmpc_step_batch_dev launch with A / Bm / C NULL hands over through them and is the only kind of launch left pending) -- or hands results to
+// someone else (lmpc_comm_allgather_dev, lmpc_ss_get_qfun) first gives the launches still pending their retry pass: a flagged problem is then
+// re-solved against the data of ITS launch, never against a changed safe set or overwritten inputs.  (No launch pending -- the drop-in flow,
+// where lmpc_step_batch resolves before it returns -- costs nothing: no stream drain is added.)  The retry pass reads nothing else of the
+// context's: not the per-point regression status (it keeps the first pass's bits), not the [A_k | B_k] scratch (it stages them in LDS).
 #define RESOLVE_PENDING() do { const int rc_ = resolve_retries(c); if (rc_) return rc_; } while (0)
 
 // ---------------------------------------------------------------------------------------------- stores
@@ -755,7 +760,7 @@ int lmpc_regress_batch(lmpc_ctx *c, int B, const double *xLin, int xLinRowStride
     ARGCHK(c && xLin && uLin && A && Bm && C && B >= 1 && B <= c->cfg.max_batch);
     const int N = c->cfg.N;
     ARGCHK(xLinRowStride == N * 6 || xLinRowStride == (N + 1) * 6);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (a pending launch may hand its A / B / C over through w_A / w_B / w_C: its retry pass first)
     H2D(c->w_xLin, xLin, (size_t)B * xLinRowStride); H2D(c->w_uLin, uLin, (size_t)B * N * 2);
     int rc = launch_regress(c, B, c->w_xLin, xLinRowStride, c->w_uLin, c->w_A, c->w_B, c->w_C, c->w_rstatus); if (rc) return rc;
     D2H(A, c->w_A, (size_t)B * N * 36); D2H(Bm, c->w_B, (size_t)B * N * 12); D2H(C, c->w_C, (size_t)B * N * 6); D2H(status, c->w_rstatus, (size_t)B * N);
@@ -774,7 +779,7 @@ int lmpc_regress_points(lmpc_ctx *c, int n, const double *x, const double *u, do
     // PredictiveModel.regressionAndLinearization (PredictiveModel.py:48-197) for n independent linearisation points (x (n x 6), u (n x 2)): the reference's own call
     // shape -- one point per call -- without a horizon around it.  The regression kernel runs with a parameter block whose horizon is 1: one query per work-group.
     ARGCHK(c && x && u && A && Bm && C && n >= 1 && (long long)n <= (long long)c->cfg.max_batch * c->cfg.N);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
     H2D(c->w_xLin, x, (size_t)n * 6); H2D(c->w_uLin, u, (size_t)n * 2);
     int rc = refresh_params(c, true, false); if (rc) return rc;
     {
@@ -820,7 +825,7 @@ int lmpc_qp_solve_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     ARGCHK(c && A && Bm && C && x0 && uOld && xPred && uPred && B >= 1 && B <= c->cfg.max_batch);
     const int N = c->cfg.N, S = c->cfg.numSS_it > 0 ? c->cfg.numSS_points : 0, M = 8 * N + S;
     if (S > 0) ARGCHK(ssSel && qSel);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch: the copies below overwrite w_A / w_B / w_C)
     H2D(c->w_A, A, (size_t)B * N * 36); H2D(c->w_B, Bm, (size_t)B * N * 12); H2D(c->w_C, C, (size_t)B * N * 6);
     H2D(c->w_x0, x0, (size_t)B * 6); H2D(c->w_uOld, uOld, (size_t)B * 2);
     if (S > 0) { H2D(c->w_ssSel, ssSel, (size_t)B * S * 6); H2D(c->w_qSel, qSel, (size_t)B * S); }
@@ -967,7 +972,7 @@ int lmpc_assemble_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     int nz, mi, me; lmpc_qp_dims(c, &nz, &mi, &me); const int mm = mi + me;
     const int N = c->cfg.N, S = c->cfg.numSS_it > 0 ? c->cfg.numSS_points : 0;
     if (S > 0) ARGCHK(ssSel && qSel);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
     double *dP, *dq, *dA, *dl, *du;
     HIPCHK(hipMalloc(&dP, sizeof(double) * (size_t)B * nz * nz)); HIPCHK(hipMalloc(&dq, sizeof(double) * (size_t)B * nz));
     HIPCHK(hipMalloc(&dA, sizeof(double) * (size_t)B * mm * nz)); HIPCHK(hipMalloc(&dl, sizeof(double) * (size_t)B * mm)); HIPCHK(hipMalloc(&du, sizeof(double) * (size_t)B * mm));
@@ -998,7 +1003,7 @@ int lmpc_debug_timing(lmpc_ctx *c, const double *A, const double *Bm, const doub
                       const double *ssSel, const double *qSel, long long *tbuf_host, int nt) {
     ARGCHK(c && tbuf_host && nt >= 2);
     const int N = c->cfg.N, S = c->cfg.numSS_it > 0 ? c->cfg.numSS_points : 0;
-    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
     H2D(c->w_A, A, (size_t)N * 36); H2D(c->w_B, Bm, (size_t)N * 12); H2D(c->w_C, C, (size_t)N * 6); H2D(c->w_x0, x0, 6); H2D(c->w_uOld, uOld, 2);
     if (S > 0) { H2D(c->w_ssSel, ssSel, (size_t)S * 6); H2D(c->w_qSel, qSel, S); }
     long long *dt; HIPCHK(hipMalloc(&dt, sizeof(long long) * nt)); HIPCHK(hipMemsetAsync(dt, 0, sizeof(long long) * nt, c->stream));
@@ -1017,7 +1022,7 @@ int lmpc_debug_timing(lmpc_ctx *c, const double *A, const double *Bm, const doub
 int lmpc_debug_k1_timing(lmpc_ctx *c, int B, const double *xLin, const double *uLin, long long *tbuf_host) {
     ARGCHK(c && xLin && uLin && tbuf_host && B >= 1 && B <= c->cfg.max_batch);
     const int N = c->cfg.N;
-    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
     H2D(c->w_xLin, xLin, (size_t)B * (N + 1) * 6); H2D(c->w_uLin, uLin, (size_t)B * N * 2);
     long long *dt; HIPCHK(hipMalloc(&dt, sizeof(long long) * 24)); HIPCHK(hipMemsetAsync(dt, 0, sizeof(long long) * 24, c->stream));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_k1_tbuf), &dt, sizeof(dt)));

@@ -223,3 +223,44 @@ def zt_face_err(zt, ztu, Succ, SuccU, SS, Qsel, lam_star):
         width = max(width, c - a)
         err = max(err, max(a - v, v - c, 0.0) / (1 + abs(v)))
     return float(err), float(width)
+
+
+def compare_with_oracle(out, res, N, what):
+    """K1 / K2 of every oracle record in `res` (tests/oracle_pool.oracle_batch), K3 of those that carry the certified optimum: A, B, C to TOL_ABC relative,
+    SS_sel / Qfun_sel identical, |xPred, uPred - z*| < TOL_XU, objective to 1e-8 relative.  zt / zt_u (feasibleStateInput, :382-384):
+      * always: ztNext = Succ lambda_gpu and ztuNext = SuccU lambda_gpu to rounding, with the ORACLE's successor rows and the kernel's own lambda -- and that
+        lambda is optimal (objective of the kernel's full primal vector = the certified optimum's, feasibility: feasibility_properties / certificates);
+      * against Succ lambda* to TOL_ZT (1 + |zt|) wherever lambda* is determined by the QP: the oracle's two methods (active-set polished ADMM, dense interior
+        point) agree on Succ lambda* to 1e-7.  Where they do not, the QP has a face of optimal lambda (x, u unique, lambda not: SURVEY 8(c)-3), the reference
+        itself returns whichever point its solver lands on, and the count is printed."""
+    worst_abc = worst_xu = worst_zt = worst_id = worst_obj = worst_zt_free = 0.0; n_opt = n_det = 0
+    nxu = 6 * (N + 1) + 2 * N
+    for r in res:
+        b = r["b"]
+        for got, ref in ((out["A"][b], r["A"]), (out["B"][b], r["B"]), (out["C"][b], r["C"])):
+            worst_abc = max(worst_abc, (np.abs(got - ref) / (1 + np.abs(ref))).max())
+        assert np.array_equal(out["ssSel"][b], r["SSsel"].T) and np.array_equal(out["qSel"][b], r["Qsel"]), (what, b)
+        if "opt" in r:
+            n_opt += 1
+            assert r["cert"] < 1e-7 and r["cert2"] < 1e-8, (what, b, r["cert"], r["cert2"])
+            w = np.concatenate([out["xPred"][b].ravel(), out["uPred"][b].ravel()])
+            # SURVEY 8(c)-3: |xPred, uPred - z*| <= 1e-6 (1 + |z*|), against the nearer of the oracle's two certified optima
+            worst_xu = max(worst_xu, min((np.abs(w - o[:nxu]) / (1 + np.abs(o[:nxu]))).max() for o in (r["opt"], r["opt2"])))
+            S = r["Qsel"].shape[0]
+            sl = slice(nxu + 2 * N, nxu + 2 * N + S)
+            worst_id = max(worst_id, zt_err(out["ztNext"][b], out["ztuNext"][b], r["Succ"], r["SuccU"], out["lambd"][b]))
+            full = np.concatenate([w, out["slack"][b], out["lambd"][b], out["sTerm"][b]])
+            # objective of the kernel's primal vector on the ORACLE-assembled QP = the certified optimum's (0.5 z'Pz + q'z, P and q rebuilt from the records)
+            worst_obj = max(worst_obj, abs(r["objf"](full) - r["obj"]) / (1 + abs(r["obj"])))
+            determinate = zt_err(r["Succ"] @ r["opt"][sl], r["SuccU"] @ r["opt"][sl], r["Succ"], r["SuccU"], r["opt2"][sl]) < 1e-7
+            e = min(zt_err(out["ztNext"][b], out["ztuNext"][b], r["Succ"], r["SuccU"], o[sl]) for o in (r["opt"], r["opt2"]))
+            if determinate:
+                n_det += 1; worst_zt = max(worst_zt, e)
+            else:
+                worst_zt_free = max(worst_zt_free, e)
+    print("%s: %d problems: worst relative |A,B,C - oracle| %.2e, selections identical; %d against the certified optimum: |xu - z*| / (1 + |z*|) %.2e, objective %.1e relative, "
+          "|zt - Succ lambda_gpu| %.1e; lambda* determined on %d of them: |zt - Succ lambda*| / (1 + |zt|) %.2e (on the others: %.2e)"
+          % (what, len(res), worst_abc, n_opt, worst_xu, worst_obj, worst_id, n_det, worst_zt, worst_zt_free))
+    assert worst_abc < TOL_ABC and worst_xu < TOL_XU and worst_zt < TOL_ZT and worst_id < 1e-10 and worst_obj < 1e-8, what
+    assert n_opt == 0 or n_det >= n_opt // 2, (what, n_det, n_opt)
+    return dict(abc=worst_abc, xu=worst_xu, zt=worst_zt, obj=worst_obj)

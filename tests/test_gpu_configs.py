@@ -319,46 +319,6 @@ def test_fused_step_matches_two_kernel_step(built):
 ORACLE_STRIDE = int(os.environ.get("LMPC_TEST_ORACLE_STRIDE", "4"))       # K3 against the oracle's optimum on every 4th problem of the big batches (smaller strides: the restated ADMM needs up to 20 s on some problems -- stride 1 did not finish in 16 minutes)
 
 
-def _compare_with_oracle(out, res, N, what):
-    """K1 / K2 of every oracle record in `res` (tests/oracle_pool.oracle_batch), K3 of those that carry the certified optimum: A, B, C to TOL_ABC relative,
-    SS_sel / Qfun_sel identical, |xPred, uPred - z*| < TOL_XU, objective to 1e-8 relative.  zt / zt_u (feasibleStateInput, :382-384):
-      * always: ztNext = Succ lambda_gpu and ztuNext = SuccU lambda_gpu to rounding, with the ORACLE's successor rows and the kernel's own lambda -- and that
-        lambda is optimal (objective of the kernel's full primal vector = the certified optimum's, feasibility: feasibility_properties / certificates);
-      * against Succ lambda* to TOL_ZT (1 + |zt|) wherever lambda* is determined by the QP: the oracle's two methods (active-set polished ADMM, dense interior
-        point) agree on Succ lambda* to 1e-7.  Where they do not, the QP has a face of optimal lambda (x, u unique, lambda not: SURVEY 8(c)-3), the reference
-        itself returns whichever point its solver lands on, and the count is printed."""
-    worst_abc = worst_xu = worst_zt = worst_id = worst_obj = worst_zt_free = 0.0; n_opt = n_det = 0
-    nxu = 6 * (N + 1) + 2 * N
-    for r in res:
-        b = r["b"]
-        for got, ref in ((out["A"][b], r["A"]), (out["B"][b], r["B"]), (out["C"][b], r["C"])):
-            worst_abc = max(worst_abc, (np.abs(got - ref) / (1 + np.abs(ref))).max())
-        assert np.array_equal(out["ssSel"][b], r["SSsel"].T) and np.array_equal(out["qSel"][b], r["Qsel"]), (what, b)
-        if "opt" in r:
-            n_opt += 1
-            assert r["cert"] < 1e-7 and r["cert2"] < 1e-8, (what, b, r["cert"], r["cert2"])
-            w = np.concatenate([out["xPred"][b].ravel(), out["uPred"][b].ravel()])
-            # SURVEY 8(c)-3: |xPred, uPred - z*| <= 1e-6 (1 + |z*|), against the nearer of the oracle's two certified optima
-            worst_xu = max(worst_xu, min((np.abs(w - o[:nxu]) / (1 + np.abs(o[:nxu]))).max() for o in (r["opt"], r["opt2"])))
-            S = r["Qsel"].shape[0]
-            sl = slice(nxu + 2 * N, nxu + 2 * N + S)
-            worst_id = max(worst_id, common.zt_err(out["ztNext"][b], out["ztuNext"][b], r["Succ"], r["SuccU"], out["lambd"][b]))
-            full = np.concatenate([w, out["slack"][b], out["lambd"][b], out["sTerm"][b]])
-            # objective of the kernel's primal vector on the ORACLE-assembled QP = the certified optimum's (0.5 z'Pz + q'z, P and q rebuilt from the records)
-            worst_obj = max(worst_obj, abs(r["objf"](full) - r["obj"]) / (1 + abs(r["obj"])))
-            determinate = common.zt_err(r["Succ"] @ r["opt"][sl], r["SuccU"] @ r["opt"][sl], r["Succ"], r["SuccU"], r["opt2"][sl]) < 1e-7
-            e = min(common.zt_err(out["ztNext"][b], out["ztuNext"][b], r["Succ"], r["SuccU"], o[sl]) for o in (r["opt"], r["opt2"]))
-            if determinate:
-                n_det += 1; worst_zt = max(worst_zt, e)
-            else:
-                worst_zt_free = max(worst_zt_free, e)
-    print("%s: %d problems: worst relative |A,B,C - oracle| %.2e, selections identical; %d against the certified optimum: |xu - z*| / (1 + |z*|) %.2e, objective %.1e relative, "
-          "|zt - Succ lambda_gpu| %.1e; lambda* determined on %d of them: |zt - Succ lambda*| / (1 + |zt|) %.2e (on the others: %.2e)"
-          % (what, len(res), worst_abc, n_opt, worst_xu, worst_obj, worst_id, n_det, worst_zt, worst_zt_free))
-    assert worst_abc < common.TOL_ABC and worst_xu < common.TOL_XU and worst_zt < common.TOL_ZT and worst_id < 1e-10 and worst_obj < 1e-8, what
-    assert n_opt == 0 or n_det >= n_opt // 2, (what, n_det, n_opt)
-
-
 def test_k1_k2_k3_match_oracle_on_every_bench_problem(built):
     """K1 (regression) and K2 (selection) against the oracle on ALL 256 problems of bench.synth_batch -- the inputs the driver times -- and on 256
     evenly spaced problems of the 4096-problem / 30-lap batch: A, B, C to 1e-9 relative, SS_sel and Qfun_sel np.array_equal; round 5: K3 against the
@@ -387,7 +347,7 @@ def test_k1_k2_k3_match_oracle_on_every_bench_problem(built):
         ctx.model_add_trajectory(*pid); ctx.ss_add_trajectory(*pid)
     out = ctx.step_batch(inp_a["x0"], inp_a["xLin"], inp_a["uLin"], inp_a["uOld"], zt=inp_a["zt"], timeStep=inp_a["timeStep"])
     assert np.all(out["status"] == 0)
-    _compare_with_oracle(out, res_a, N, "bench batch (four waves per QP)")
+    common.compare_with_oracle(out, res_a, N, "bench batch (four waves per QP)")
     ctx.close()
     # (b) 4096 problems / 30 laps, every 4th problem
     cfg, _ = common.lmpc_config(g, N, max_batch=4096, max_laps=40, max_lap_len=1024)
@@ -396,7 +356,7 @@ def test_k1_k2_k3_match_oracle_on_every_bench_problem(built):
         ctx.model_add_trajectory(x, u); ctx.ss_add_trajectory(x, u)
     out = ctx.step_batch(inp_b["x0"], inp_b["xLin"], inp_b["uLin"], inp_b["uOld"], zt=inp_b["zt"], timeStep=inp_b["timeStep"])
     assert np.all(out["status"] == 0)
-    _compare_with_oracle(out, res_b, N, "4096 / 30 laps (one wave per QP), every %s problem" % ("4th" if ORACLE_STRIDE == 4 else "%d-th" % ORACLE_STRIDE))
+    common.compare_with_oracle(out, res_b, N, "4096 / 30 laps (one wave per QP), every %s problem" % ("4th" if ORACLE_STRIDE == 4 else "%d-th" % ORACLE_STRIDE))
     ctx.close()
 
 
@@ -422,7 +382,7 @@ def test_wide_safe_sets_against_oracle(built, L, B, stride):
         ctx.model_add_trajectory(x, u); ctx.ss_add_trajectory(x, u)
     out = ctx.step_batch(inp["x0"], inp["xLin"], inp["uLin"], inp["uOld"], zt=inp["zt"], timeStep=inp["timeStep"])
     assert np.all(out["status"] == 0)
-    _compare_with_oracle(out, res, N, "%d laps / %d safe-set points, batch %d (%d wave(s) per QP), every %d-th problem" % (L, 12 * L, B, ctx.solver_waves(B), stride))
+    common.compare_with_oracle(out, res, N, "%d laps / %d safe-set points, batch %d (%d wave(s) per QP), every %d-th problem" % (L, 12 * L, B, ctx.solver_waves(B), stride))
     ctx.close()
 
 
@@ -446,15 +406,15 @@ def test_n40_every_problem_against_oracle(built):
         ctx.model_add_trajectory(*pid); ctx.ss_add_trajectory(*pid)
     out = ctx.step_batch(inp["x0"], inp["xLin"], inp["uLin"], inp["uOld"], zt=inp["zt"], timeStep=inp["timeStep"])
     assert np.all(out["status"] == 0) and ctx.solver_waves(B) == 1 and int(ctx.stats().n_retry) == 0
-    _compare_with_oracle(out, res, N, "N = 40, batch 1024 (one wave per QP)")
+    common.compare_with_oracle(out, res, N, "N = 40, batch 1024 (one wave per QP)")
     sub5 = {k: v[:512] for k, v in inp.items()}          # 512 problems: one wave per QP with [A_k | B_k] in LDS (the other long-horizon kernel)
     out5 = ctx.step_batch(sub5["x0"], sub5["xLin"], sub5["uLin"], sub5["uOld"], zt=sub5["zt"], timeStep=sub5["timeStep"])
     assert np.all(out5["status"] == 0) and ctx.solver_waves(512) == 1 and int(ctx.stats().n_retry) == 0
-    _compare_with_oracle(out5, res[:512], N, "N = 40, batch 512 (one wave per QP, matrices in LDS)")
+    common.compare_with_oracle(out5, res[:512], N, "N = 40, batch 512 (one wave per QP, matrices in LDS)")
     sub = {k: v[:256] for k, v in inp.items()}
     out4 = ctx.step_batch(sub["x0"], sub["xLin"], sub["uLin"], sub["uOld"], zt=sub["zt"], timeStep=sub["timeStep"])
     assert np.all(out4["status"] == 0) and ctx.solver_waves(256) == 4 and int(ctx.stats().n_retry) == 0
-    _compare_with_oracle(out4, res[:256], N, "N = 40, batch 256 (four waves per QP)")
+    common.compare_with_oracle(out4, res[:256], N, "N = 40, batch 256 (four waves per QP)")
     ctx.close()
 
 
@@ -478,7 +438,7 @@ def test_other_horizons_against_oracle(built, N, B, stride):
         ctx.model_add_trajectory(*pid); ctx.ss_add_trajectory(*pid)
     out = ctx.step_batch(inp["x0"], inp["xLin"], inp["uLin"], inp["uOld"], zt=inp["zt"], timeStep=inp["timeStep"])
     assert np.all(out["status"] == 0) and int(ctx.stats().n_retry) == 0
-    _compare_with_oracle(out, res, N, "N = %d, batch %d (%d wave(s) per QP), every %d-th problem" % (N, B, ctx.solver_waves(B), stride))
+    common.compare_with_oracle(out, res, N, "N = %d, batch %d (%d wave(s) per QP), every %d-th problem" % (N, B, ctx.solver_waves(B), stride))
     ctx.close()
 
 

@@ -102,3 +102,64 @@ def test_deferred_retry_runs_against_its_own_launch(built):
     for p in keep1 + keep2:
         ctx.dev_free(p)
     ctx.close()
+
+
+# Entry points that may run between a deferred launch and its drain.  r: the interleaved call's own inputs that only a solve provides (A, B, C, selection).
+_INTERLEAVED = {
+    "regress_batch": lambda c, i, r: c.regress_batch(i["xLin"], i["uLin"]),
+    "regress_points": lambda c, i, r: c.regress_points(i["xLin"][:, :-1].reshape(-1, 6), i["uLin"].reshape(-1, 2)),    # B x N points: every row of the hand-over
+    "qp_solve_batch": lambda c, i, r: c.qp_solve_batch(r["A"], r["B"], r["C"], i["x0"], i["uOld"], r["ssSel"], r["qSel"]),
+    "assemble_batch": lambda c, i, r: c.assemble_batch(r["A"], r["B"], r["C"], i["x0"], i["uOld"], r["ssSel"], r["qSel"]),
+    "select_batch": lambda c, i, r: c.select_batch(i["x0"], i["zt"], timeStep=i["timeStep"]),
+    "step_batch": lambda c, i, r: c.step_batch(i["x0"], i["xLin"], i["uLin"], i["uOld"], zt=i["zt"], timeStep=i["timeStep"]),
+}
+
+
+def _arrays(out):
+    return out.items() if isinstance(out, dict) else enumerate(out)
+
+
+@pytest.mark.parametrize("runtime_kernel", [False, True], ids=["fast_kernel", "runtime_kernel"])
+@pytest.mark.parametrize("entry", list(_INTERLEAVED))
+def test_deferred_retry_survives_an_interleaved_host_call(built, entry, runtime_kernel):
+    """A device-resident launch with A / Bm / C NULL hands its regression over through the context's own buffers and leaves its retry pass pending
+    until the next drain.  Whatever host entry point runs in between -- with different inputs -- the launch's answer is the one a fresh context gives
+    (its retry pass runs against ITS A, B, C), and the interleaved call's answer is the one it gives on a fresh context."""
+    from racinglmpc_amd import _capi
+    g = common.load_lmpc_golden()
+    B = 48
+    inp1 = bench.synth_batch(g, B, 12, seed=1)
+    inp2 = {k: v[::-1].copy() for k, v in bench.synth_batch(g, B, 12, seed=2).items()}
+
+    def fresh():
+        cfg, _ = common.lmpc_config(g, 12, max_batch=B, max_iter=7)          # most problems end at the limit: every launch asks for its retry pass
+        c = _capi.Context(cfg, runtime_kernel=runtime_kernel)
+        assert c.solver_kind == (2 if runtime_kernel else 0)
+        for _ in range(4):
+            c.model_add_trajectory(g["xPID"], g["uPID"]); c.ss_add_trajectory(g["xPID"], g["uPID"])
+        return c
+    call = _INTERLEAVED[entry]
+    ctx = fresh()
+    ref1 = ctx.step_batch(inp1["x0"], inp1["xLin"], inp1["uLin"], inp1["uOld"], zt=inp1["zt"], timeStep=inp1["timeStep"])
+    assert ((ref1["status"] & _capi.ST_MAXITER) != 0).any() and ctx.stats().n_retry == 1
+    ctx.close()
+    ctx = fresh()
+    ref2 = ctx.step_batch(inp2["x0"], inp2["xLin"], inp2["uLin"], inp2["uOld"], zt=inp2["zt"], timeStep=inp2["timeStep"])
+    ctx.close()
+    ctx = fresh()
+    want = call(ctx, inp2, ref2)
+    ctx.close()
+
+    ctx = fresh()
+    a1, keep1 = ctx.step_dev_buffers(inp1, diagnostics=False)
+    a1.A = None; a1.Bm = None; a1.C = None
+    ctx.step_batch_dev(B, a1)
+    got = call(ctx, inp2, ref2)
+    out1 = ctx.step_dev_fetch(a1, B)
+    bad1 = [k for k in ("xPred", "uPred", "lambd", "ztNext", "status", "iters") if not np.array_equal(out1[k], ref1[k])]
+    bad2 = [k for k, v in _arrays(want) if not np.array_equal(dict(_arrays(got))[k], v)]
+    for p in keep1:
+        ctx.dev_free(p)
+    ctx.close()
+    assert not bad1, "%s between the launch and its drain: the pending launch's %s differ from a fresh context's" % (entry, bad1)
+    assert not bad2, "%s between the launch and its drain: its own %s differ from a fresh context's" % (entry, bad2)

@@ -73,6 +73,48 @@ def test_lap_stores_checkpoint_and_resume(built, tmp_path):
     ctx.close(); ctx2.close()
 
 
+def test_restored_context_pool_answers_like_a_restored_context(built, tmp_path):
+    """ContextPool.restore_stores fills EVERY member (step_batch_dev deals the steps to the members in turn): each member of a restored depth-2 pool returns,
+    bit for bit, what a single restored context returns.  save_stores / restore_stores take the same path string with or without the .npz extension."""
+    from racinglmpc_amd import _capi
+    g = common.load_lmpc_golden()
+    ctx, par = common.make_lmpc_ctx(g, 5, max_batch=4)
+    for t in range(3):
+        ctx.ss_add_point(g["all_x0"][t], g["all_u0"][t])
+    path = str(tmp_path / "stores.npz")
+    ctx.save_stores(path)
+    cfg, _ = common.lmpc_config(g, 12, max_batch=4)
+    single = _capi.Context(cfg)
+    single.restore_stores(path)
+    pool = _capi.ContextPool(cfg, depth=2)
+    pool.restore_stores(path)
+    assert [m.ss_num_laps() for m in pool.members] == [single.ss_num_laps()] * 2
+    rs = np.where(g["rec_lap"] == 5)[0][:4]
+    inp = dict(x0=g["rec_x0"][rs], xLin=g["rec_xLin"][rs], uLin=g["rec_uLin"][rs], uOld=g["rec_OldInput"][rs], zt=g["rec_zt"][rs],
+               xPredPrev=g["rec_xPredPrev"][rs], hasPred=g["rec_hasPred"][rs].astype(np.int32), timeStep=g["rec_t"][rs].astype(np.int32))
+    B = len(rs)
+    ref = single.step_batch(inp["x0"], inp["xLin"], inp["uLin"], inp["uOld"], zt=inp["zt"], xPredPrev=inp["xPredPrev"], hasPred=inp["hasPred"], timeStep=inp["timeStep"])
+    assert np.all(ref["status"] == 0)
+    bufs = pool.step_dev_buffers(inp, diagnostics=False)
+    assert [pool.step_batch_dev(B, bufs) for _ in range(2)] == [0, 1]
+    pool.sync()
+    for i, (m, (a, keep)) in enumerate(zip(pool.members, bufs)):
+        got = m.step_dev_fetch(a, B)
+        for k in ("xPred", "uPred", "slack", "lambd", "sTerm", "ztNext", "ztuNext", "ssSel", "A", "B", "C", "status", "iters"):
+            assert np.array_equal(got[k], ref[k]), (i, k)
+        for p in keep:
+            m.dev_free(p)
+    pool.close()
+    # a path without the extension: np.savez_compressed appends it, restore_stores finds the same file
+    base = str(tmp_path / "stores_noext")
+    single.save_stores(base)
+    again = _capi.Context(cfg)
+    again.restore_stores(base)
+    for i in range(single.ss_num_laps()):
+        assert all(np.array_equal(p, q) for p, q in zip(single.store_read_lap(1, i), again.store_read_lap(1, i)))
+    again.close(); single.close(); ctx.close()
+
+
 def test_contexts_and_rollout_sessions_return_their_device_memory(built):
     """Create -> solve a batch -> a closed-loop rollout session -> destroy, a dozen times over: the device's free memory ends where it was after the first cycle
     (lmpc_destroy / lmpc_rollout_end release every buffer of the context, its work space, the host-mapped retry ring and the session; a long-lived service that

@@ -160,3 +160,50 @@ def test_context_pool_releases_its_members_when_one_fails(monkeypatch):
         assert pool.ss_add_point(1.0, 2.0) == 1 and [m.calls for m in made] == [[(1.0, 2.0)]] * 2      # store edits reach every member
         assert pool.ss_num_laps() == 7                                                                    # queries go to the first
     assert [m.closed for m in made] == [1, 1]
+
+
+def test_context_pool_restores_every_member(monkeypatch):
+    """ContextPool.restore_stores reaches every member, not only the first (a member with empty stores answers nothing: step_batch_dev deals steps to it
+    in turn).  No GPU needed: Context is replaced by a recording stand-in."""
+    from racinglmpc_amd import _capi
+    made = []
+
+    class _Ctx:
+        def __init__(self, cfg):
+            self.restored = []; made.append(self)
+
+        def restore_stores(self, path):
+            self.restored.append(path)
+
+        def close(self):
+            pass
+
+    monkeypatch.setattr(_capi, "Context", _Ctx)
+    with _capi.ContextPool(None, depth=3) as pool:
+        pool.restore_stores("laps.npz")
+    assert [m.restored for m in made] == [["laps.npz"]] * 3
+
+
+def test_save_and_restore_stores_take_the_same_path(tmp_path):
+    """Context.save_stores / restore_stores: np.savez_compressed appends .npz to a path without it, so restore_stores with the SAME string must find that
+    file.  No GPU needed: the real methods run around a stand-in library whose lap stores are empty."""
+    import ctypes as C
+    import os
+    from racinglmpc_amd import _capi
+
+    class _Lib:
+        def lmpc_model_num_laps(self, h, n):
+            n._obj.value = 0; return 0
+
+        def lmpc_ss_num_laps(self, h, n):
+            n._obj.value = 0; return 0
+
+    ctx = _capi.Context.__new__(_capi.Context)
+    ctx.lib = _Lib(); ctx._h = C.c_void_p(); ctx._pid = os.getpid(); ctx.N = 12
+    base = str(tmp_path / "stores")
+    ctx.save_stores(base)
+    assert sorted(os.listdir(str(tmp_path))) == ["stores.npz"]
+    ctx.restore_stores(base)
+    ctx.restore_stores(base + ".npz")
+    ctx.save_stores(base + ".npz")                     # (a path with the extension is taken as it is)
+    assert sorted(os.listdir(str(tmp_path))) == ["stores.npz"]
