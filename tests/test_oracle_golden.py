@@ -317,3 +317,24 @@ def test_dense_ipm_active_set_finish_reaches_the_optimum():
         assert np.abs(r2.x[:102] - g["rec_sol_opt"][r][:102]).max() < 1e-9     # (x, u) are unique
         r3 = orc.dense_ipm_solve(P, q, A, l, u, polish=False)
         assert r3.interior and np.abs(r3.x[:102] - r2.x[:102]).max() < 1e-5
+
+
+def test_longdouble_plant_reference_is_pinned_to_the_oracle():
+    """tests/plant_ref.dyn_model_ld (the high-precision plant the GPU plant tests measure against) against orc.dyn_model on every state family
+    of tests/test_gpu_plant_track.py: the raise / no-raise decision agrees on every state, and on the smooth families the states agree to
+    1e-13 (1 + |x|).  The other families are judged by the oracle itself (headings beyond 1.5e3, segment and lap boundaries) or by the
+    longdouble reference alone (|1 - cur ey| down to 1e-6, where the float64 oracle loses 1e-10 relative)."""
+    from tests import plant_ref as pr
+    g = common.load_lmpc_golden()
+    pt = np.array(g["track"])
+    for f in pr.families(g):
+        xn, xgn, raised, _ = pr.dyn_model_ld(pt, f.x, f.xg, f.u, f.nz)
+        worst = 0.0
+        for b in range(len(f)):
+            o = pr.oracle_step(pt, f.x[b], f.xg[b], f.u[b], f.nz[b])
+            assert (o is None) == bool(raised[b]), (f.name, b, f.x[b])
+            if o is not None:
+                worst = max(worst, pr.scaled_err(xn[b:b + 1], o[0])[0], pr.scaled_err(xgn[b:b + 1], o[1])[0])
+        print("%-18s %4d states  %3d raise  longdouble vs oracle %.2e" % (f.name, len(f), raised.sum(), worst))
+        if f.smooth:
+            assert worst <= 1e-13, f.name
