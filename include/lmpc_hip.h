@@ -204,6 +204,23 @@ int lmpc_plant_step_batch(lmpc_ctx *, int B, const double *x /*B x 6*/, const do
         /* Simulator.dynModel, fnc/simulator/SysModel.py:56-147 (100 Euler sub-steps, clipped noise) */
 int lmpc_rollout_begin(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/,
                        const double *xLin0 /*B x (N+1) x 6*/, const double *uLin0 /*B x N x 2*/, const double *noise /*T_max x B x 3*/);
+int lmpc_rollout_begin_mpc(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/,
+                           const double *xLin0 /*B x (N+1) x 6 or NULL*/, const double *uLin0 /*B x N x 2 or NULL*/,
+                           const double *A_lti /*B x 6 x 6 or NULL*/, const double *B_lti /*B x 6 x 2 or NULL*/, const double *noise /*T_max x B x 3*/, int stop_at_line);
+        /* Simulator.sim with one plain MPC per rollout (main.py:72-95; MPC.solve, PredictiveControllers.py:110-137), state resident on the device.  Valid only on a
+         * context with numSS_it == 0 (lmpc_rollout_begin keeps refusing those), B <= max_batch, no session active.  A_lti / B_lti given: the LTI path-following MPC on the
+         * model of Utilities.Regression (main.py:74-82) -- rollout b solves with A_b, B_b at every stage and C = 0 (buildEqConstr :216-218); xLin0 / uLin0 are not used.
+         * Both NULL: the LTV-MPC (timeVarying, main.py:85-95) on the regression store -- trToUse laps must be stored (else LMPC_E_STATE, as lmpc_step_batch); per step
+         * xLin <- [xPred[1:], xPred[N]], uLin <- [uPred[1:], uPred[N-1]], OldInput <- uPred[0] (:129-137, feasibleStateInput :157-159).  stop_at_line = 1:
+         * Simulator(multiLap = False), lmpc_rollout_run ends once every car has crossed the line (SysModel.py:45); 0: all T_max steps (multiLap = True, main.py:57),
+         * doneAt still the first crossing.  lmpc_rollout_run / _fetch / _end / _release, lmpc_debug_rollout_peek and lmpc_debug_rollout_qp (selection outputs NULL)
+         * work on the session as on one of lmpc_rollout_begin */
+int lmpc_rollout_pid(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/, const double *vt /*B*/,
+                     const double *noise_u /*T_max x B x 2 N(0,1) draws*/, const double *noise /*T_max x B x 3*/, int stop_at_line, int *steps_total, int *n_done);
+        /* Simulator.sim driven by Utilities.PID (main.py:61-70; PID.solve, fnc/Utilities.py:60-67: u0 = -0.6 ey - 0.9 epsi + clip(0.25 n0, +-0.9),
+         * u1 = 1.5 (vt - vx) + clip(0.10 n1, +-0.2)) for B cars, the whole lap in ONE kernel launch: begins a session, runs it to the end (all T_max steps; with
+         * stop_at_line a car is logged up to its crossing step only), and leaves it active for lmpc_rollout_fetch / _end.  Needs only the track: valid on any context
+         * (B <= max_batch, T_max <= 100000, no session active).  The plant step is the device function of lmpc_plant_step_batch: same state and draws, same bits */
 int lmpc_rollout_run(lmpc_ctx *, int max_steps, int *steps_total, int *n_done);
 int lmpc_rollout_fetch(lmpc_ctx *, int t0, int t1, double *X /*(t1-t0) x B x 6*/, double *U /*.. x B x 2*/, double *Xglob,
                        int *doneAt /*B*/, int *status /*B*/, double *finalX /*B x 6*/, double *finalXglob /*B x 6*/);
@@ -220,6 +237,11 @@ int lmpc_ss_truncate_lap(lmpc_ctx *, int lap, int T);
 int lmpc_lti_regression(int device, const double *x /*T x 6*/, const double *u /*T x 2*/, int T, double lamb,
                         double *A /*6 x 6*/, double *B /*6 x 2*/, double *Error /*2 x 6: max; min of the fit residual*/, int *status /*or NULL*/);
         /* Utilities.Regression, fnc/Utilities.py:5-28 (main.py:74-77: the LTI model of the path-following MPC); ridge least squares over one lap */
+
+int lmpc_lti_regression_batch(int device, int B, const double *x /*B x ldT x 6*/, const double *u /*B x ldT x 2*/, const int *T /*B: rows of lap b, 3 <= T[b] <= ldT*/, int ldT,
+                              double lamb, double *A /*B x 6 x 6*/, double *Bm /*B x 6 x 2*/, double *Error /*B x 2 x 6*/, int *status /*B or NULL*/);
+        /* Utilities.Regression (fnc/Utilities.py:5-28) for B laps in one launch (one work-group per lap; main.py:74-77 for a batch of PID laps).  lmpc_lti_regression is
+         * its B = 1 call: same bits */
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI.  The QPs / rollouts of a batch are independent given the
  * read-only safe set, so the data path has no collective; the ONE exchange is per lap.  The reference has no counterpart (single

@@ -52,9 +52,9 @@ EXPORTS = [
     "lmpc_ss_add_trajectory", "lmpc_ss_add_point", "lmpc_ss_replace_lap", "lmpc_ss_set_selected", "lmpc_ss_num_laps", "lmpc_ss_get_qfun", "lmpc_ss_get_laptime", "lmpc_store_read_lap",
     "lmpc_regress_batch", "lmpc_regress_points", "lmpc_select_batch", "lmpc_qp_solve_batch", "lmpc_step_batch", "lmpc_assemble_batch", "lmpc_qp_dims",
     "lmpc_dev_alloc", "lmpc_dev_free", "lmpc_dev_upload", "lmpc_dev_download", "lmpc_dev_sync", "lmpc_step_batch_dev",
-    "lmpc_lti_regression", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
+    "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
-    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_global_position_batch", "lmpc_rollout_begin", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
+    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_global_position_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -79,6 +79,12 @@ def load():
         lib.lmpc_active_knobs.restype = C.c_char_p
         # (declared argument types let the hot call take plain integers as addresses: no c_void_p object per array)
         lib.lmpc_step_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 24
+        # (the batched stages of main.py:61-95, argument types as include/lmpc_hip.h declares them)
+        lib.lmpc_rollout_begin_mpc.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int]
+        lib.lmpc_rollout_pid.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.lmpc_lti_regression_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 4
+        for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch):
+            f.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -110,6 +116,21 @@ def lti_regression(x, u, lamb, device=0):
     A = np.zeros((6, 6)); B = np.zeros((6, 2)); E = np.zeros((2, 6)); st = C.c_int()
     _chk(load().lmpc_lti_regression(C.c_int(int(device)), _d(x), _d(u), C.c_int(x.shape[0]), C.c_double(float(lamb)), _d(A), _d(B), _d(E), C.byref(st)))
     return A, B, E, st.value
+
+
+def lti_regression_batch(laps, lamb, device=0):
+    """Utilities.Regression for a batch of laps [(x (T_b, 6), u (T_b, 2)), ...] of any lengths in one launch (lmpc_lti_regression_batch):
+    returns (A (B, 6, 6), B (B, 6, 2), Error (B, 2, 6), status (B,))."""
+    laps = [(_f64(x), _f64(u)) for x, u in laps]
+    n = len(laps)
+    assert n >= 1 and all(x.ndim == 2 and x.shape[1] == 6 and u.shape == (x.shape[0], 2) for x, u in laps)
+    T = _i32([x.shape[0] for x, _ in laps]); ld = int(T.max())
+    X = np.zeros((n, ld, 6)); U = np.zeros((n, ld, 2))
+    for b, (x, u) in enumerate(laps):
+        X[b, :T[b]] = x; U[b, :T[b]] = u
+    A = np.zeros((n, 6, 6)); Bm = np.zeros((n, 6, 2)); E = np.zeros((n, 2, 6)); st = np.zeros(n, np.int32)
+    _chk(load().lmpc_lti_regression_batch(int(device), n, X.ctypes.data, U.ctypes.data, T.ctypes.data, ld, float(lamb), A.ctypes.data, Bm.ctypes.data, E.ctypes.data, st.ctypes.data))
+    return A, Bm, E, st
 
 
 def _chk(rc):
@@ -413,6 +434,34 @@ class Context:
         assert xl.shape == (B, self.N + 1, 6) and ul.shape == (B, self.N, 2) and nz.shape[1:] == (B, 3)
         self._ro = (B, nz.shape[0]); self._ro_t = 0
         _chk(self.lib.lmpc_rollout_begin(self._h, C.c_int(B), C.c_int(nz.shape[0]), _d(x0), _d(xg), _d(xl), _d(ul), _d(nz)))
+
+    def rollout_begin_mpc(self, x0, xglob0, noise, xLin0=None, uLin0=None, A=None, B=None, stop_at_line=False):
+        """Session of B plain-MPC laps on a numSS_it == 0 context (lmpc_rollout_begin_mpc).  A (B, 6, 6) and B (B, 6, 2) given: the LTI MPC on those models;
+        else the LTV-MPC from the linearisation trajectories xLin0 (B, N + 1, 6), uLin0 (B, N, 2).  noise: (T_max, B, 3)."""
+        x0 = _f64(x0); xg = _f64(xglob0); nz = _f64(noise); nb = x0.shape[0]
+        assert nz.ndim == 3 and nz.shape[1:] == (nb, 3) and xg.shape == x0.shape == (nb, 6)
+        lti = A is not None or B is not None
+        if lti:
+            A = _f64(A); B = _f64(B); xl = ul = None
+            assert A.shape == (nb, 6, 6) and B.shape == (nb, 6, 2), (A.shape, B.shape)
+        else:
+            xl = _f64(xLin0); ul = _f64(uLin0); A = B = None
+            assert xl.shape == (nb, self.N + 1, 6) and ul.shape == (nb, self.N, 2), (xl.shape, ul.shape)
+        pa = lambda a: None if a is None else a.ctypes.data
+        _chk(self.lib.lmpc_rollout_begin_mpc(self._h, nb, nz.shape[0], pa(x0), pa(xg), pa(xl), pa(ul), pa(A), pa(B), pa(nz), 1 if stop_at_line else 0))
+        self._ro = (nb, nz.shape[0]); self._ro_t = 0
+
+    def rollout_pid(self, x0, xglob0, vt, noise_u, noise, stop_at_line=False):
+        """B whole PID laps in one launch (lmpc_rollout_pid): vt (B,) target speeds, noise_u (T_max, B, 2) and noise (T_max, B, 3) N(0, 1) draws of the control law and
+        of the plant.  Returns (steps logged, cars that crossed the line); the session stays open for rollout_fetch / rollout_end."""
+        x0 = _f64(x0); xg = _f64(xglob0); nb = x0.shape[0]
+        vt = _f64(np.broadcast_to(np.asarray(vt, float), (nb,))); nu = _f64(noise_u); nz = _f64(noise)
+        assert nz.ndim == 3 and nz.shape[1:] == (nb, 3) and nu.shape == (nz.shape[0], nb, 2) and xg.shape == x0.shape == (nb, 6)
+        t = C.c_int(); nd = C.c_int()
+        _chk(self.lib.lmpc_rollout_pid(self._h, nb, nz.shape[0], x0.ctypes.data, xg.ctypes.data, vt.ctypes.data, nu.ctypes.data, nz.ctypes.data,
+                                       1 if stop_at_line else 0, C.byref(t), C.byref(nd)))
+        self._ro = (nb, nz.shape[0]); self._ro_t = t.value
+        return t.value, nd.value
 
     def rollout_run(self, max_steps):
         t = C.c_int(); nd = C.c_int()

@@ -172,7 +172,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 100; }
+int lmpc_version(void) { return 101; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -1079,6 +1079,8 @@ int lmpc_global_position_batch(lmpc_ctx *c, int n, const double *s, const double
 struct lmpc_rollout_session {
     bool active;                                                // between lmpc_rollout_begin and lmpc_rollout_end; the buffers outlive the session (see lmpc_rollout_begin)
     int B, T_max, t;
+    int kind, stop_at_line;                                     // RO_LMPC / RO_LTV / RO_LTI / RO_PID (what one simulated step launches); 0: the run does not end when every car has crossed the line
+    double *d_noiseU, *d_vt;                                    // RO_PID only: controller noise T_max x B x 2, target speed per car
     hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
     std::vector<void *> keep;
     double *d_x, *d_xg, *d_xLin, *d_uLin, *d_uOld, *d_zt, *d_xPP, *d_xPred, *d_uPred, *d_slack, *d_lam, *d_sT, *d_ztN, *d_ztuN, *d_A, *d_B, *d_C, *d_resid;
@@ -1087,6 +1089,9 @@ struct lmpc_rollout_session {
     double *d_ssSel, *d_qSel, *d_succ, *d_succU;                // only with lmpc_debug_rollout_capture on (else null: the step does not write them)
 };
 
+enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
+#define LMPC_PID_MAX_STEPS 100000                             // host bound on the one launch that holds a whole lap (the reference simulates 1000 steps, main.py:57): ~seconds of kernel at most
+
 static void rollout_free(lmpc_ctx *c) {
     if (!c->ro) return;
     for (void *q : c->ro->keep) (void)g_free(q);
@@ -1094,22 +1099,22 @@ static void rollout_free(lmpc_ctx *c) {
     delete c->ro; c->ro = nullptr;
 }
 
-int lmpc_rollout_begin(lmpc_ctx *c, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
-    // B closed-loop LMPC laps, state resident on the device.  xLin0 / uLin0: per-rollout first linearisation trajectories
-    // (B x (N+1) x 6, B x N x 2) -- LMPC.addTrajectory :431-433.  noise: T_max x B x 3 N(0,1) draws.
-    ARGCHK(c && x0 && xg0 && xLin0 && uLin0 && noise && B >= 1 && T_max >= 1 && c->cfg.numSS_it > 0);
+}  // extern "C"
+// Session set-up shared by lmpc_rollout_begin (kind RO_LMPC), lmpc_rollout_begin_mpc (RO_LTV / RO_LTI) and lmpc_rollout_pid (RO_PID): buffers, initial state, noise.
+// xLin0 / uLin0 may be NULL (RO_LTI, RO_PID: no linearisation trajectory; the buffers are zeroed).
+static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
     HIPCHK(hipSetDevice(c->cfg.device));
     const size_t N = c->cfg.N, S = c->cfg.numSS_points, Bz = B;
     // A generation loop begins a session of the same shape every lap: its ~35 device buffers (55 MB of logs at 1024 rollouts x 400 steps), the plant stream and
     // the two events are kept from one session to the next (round 5: allocating and freeing them was ~5 ms of every generation) and released by
     // lmpc_destroy or by a session of another shape.
     if (c->ro && !c->ro->active && c->ro->B == B && c->ro->T_max == T_max && (c->ro->d_ssSel != nullptr) == (c->dbg_capture != 0)) {
-        lmpc_rollout_session *r = c->ro; r->t = 0; r->active = true;
+        lmpc_rollout_session *r = c->ro; r->t = 0; r->active = true; r->kind = kind; r->stop_at_line = stop_at_line;
         goto init_state;
     }
     rollout_free(c);
     {
-    lmpc_rollout_session *r = new lmpc_rollout_session(); c->ro = r; r->B = B; r->T_max = T_max; r->t = 0; r->pstream = nullptr; r->active = true;
+    lmpc_rollout_session *r = new lmpc_rollout_session(); c->ro = r; r->B = B; r->T_max = T_max; r->t = 0; r->pstream = nullptr; r->active = true; r->kind = kind; r->stop_at_line = stop_at_line;
     HIPCHK(hipStreamCreate(&r->pstream)); HIPCHK(hipEventCreateWithFlags(&r->e_solved, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&r->e_plant, hipEventDisableTiming));
     bool ok = true;
     auto dalloc = [&](size_t bytes) -> void * { void *q = nullptr; if (g_malloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) { ok = false; return nullptr; } r->keep.push_back(q); return q; };
@@ -1122,6 +1127,7 @@ int lmpc_rollout_begin(lmpc_ctx *c, int B, int T_max, const double *x0, const do
     r->d_ssSel = nullptr; r->d_qSel = nullptr; r->d_succ = nullptr; r->d_succU = nullptr;
     if (c->dbg_capture) { DA(double, d_ssSel, Bz * S * 6) DA(double, d_qSel, Bz * S) DA(double, d_succ, Bz * S * 6) DA(double, d_succU, Bz * S * 2) }
     DA(double, d_logX, (size_t)T_max * Bz * 6) DA(double, d_logU, (size_t)T_max * Bz * 2) DA(double, d_logG, (size_t)T_max * Bz * 6) DA(double, d_noise, (size_t)T_max * Bz * 3)
+    r->d_noiseU = nullptr; r->d_vt = nullptr;                   // (allocated by the first lmpc_rollout_pid on the session's buffers, kept with them)
 #undef DA
     if (!ok) { rollout_free(c); return set_err(LMPC_E_HIP, "hipMalloc", "rollout buffers"); }
     }
@@ -1130,7 +1136,9 @@ init_state:
     std::vector<double> ztv((size_t)B * 6, 0.0);
     for (int b = 0; b < B; b++) ztv[(size_t)b * 6 + 4] = 10.0;                                   // LMPC.__init__ :330
     std::vector<int> neg((size_t)B, -1);
-    H2D(r->d_x, x0, Bz * 6); H2D(r->d_xg, xg0, Bz * 6); H2D(r->d_xLin, xLin0, Bz * (N + 1) * 6); H2D(r->d_uLin, uLin0, Bz * N * 2); H2D(r->d_zt, ztv.data(), ztv.size());
+    H2D(r->d_x, x0, Bz * 6); H2D(r->d_xg, xg0, Bz * 6); H2D(r->d_zt, ztv.data(), ztv.size());
+    if (xLin0) H2D(r->d_xLin, xLin0, Bz * (N + 1) * 6); else HIPCHK(hipMemsetAsync(r->d_xLin, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
+    if (uLin0) H2D(r->d_uLin, uLin0, Bz * N * 2); else HIPCHK(hipMemsetAsync(r->d_uLin, 0, sizeof(double) * Bz * N * 2, c->stream));
     H2D(r->d_done, neg.data(), Bz); H2D(r->d_noise, noise, (size_t)T_max * Bz * 3);
     HIPCHK(hipMemsetAsync(r->d_uOld, 0, sizeof(double) * Bz * 2, c->stream)); HIPCHK(hipMemsetAsync(r->d_xPP, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
     HIPCHK(hipMemsetAsync(r->d_hasPred, 0, sizeof(int) * Bz, c->stream)); HIPCHK(hipMemsetAsync(r->d_tstep, 0, sizeof(int) * Bz, c->stream));
@@ -1145,30 +1153,120 @@ init_state:
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
+static void rollout_state(lmpc_rollout_session *r, lmpc_rollout_state &st) {
+    st.x = r->d_x; st.xg = r->d_xg; st.xLin = r->d_xLin; st.uLin = r->d_uLin; st.uOld = r->d_uOld; st.zt = r->d_zt; st.xPP = r->d_xPP;
+    st.hasPred = r->d_hasPred; st.timeStep = r->d_tstep; st.doneAt = r->d_done; st.xPred = r->d_xPred; st.uPred = r->d_uPred; st.ztNext = r->d_ztN; st.ztuNext = r->d_ztuN;
+    st.status = r->d_status; st.logX = r->d_logX; st.logU = r->d_logU; st.logG = r->d_logG; st.noise = r->d_noise; st.nDone = r->d_nDone; st.statusAcc = r->d_stAcc;
+    st.finX = r->d_finX; st.finG = r->d_finG;
+}
+extern "C" {
+int lmpc_rollout_begin(lmpc_ctx *c, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
+    // B closed-loop LMPC laps, state resident on the device.  xLin0 / uLin0: per-rollout first linearisation trajectories
+    // (B x (N+1) x 6, B x N x 2) -- LMPC.addTrajectory :431-433.  noise: T_max x B x 3 N(0,1) draws.
+    ARGCHK(c && x0 && xg0 && xLin0 && uLin0 && noise && B >= 1 && T_max >= 1 && c->cfg.numSS_it > 0);
+    return rollout_setup(c, RO_LMPC, 1, B, T_max, x0, xg0, xLin0, uLin0, noise);
+}
+
+int lmpc_rollout_begin_mpc(lmpc_ctx *c, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0,
+                           const double *A_lti, const double *B_lti, const double *noise, int stop_at_line) {
+    // B closed-loop laps of the plain MPC (numSS_it == 0: no terminal set), main.py:72-95.  A_lti / B_lti given (B x 6 x 6, B x 6 x 2): the LTI path-following MPC
+    // on the model of Utilities.Regression -- every stage of rollout b uses A_b, B_b and C = 0 (MPC.buildEqConstr, PredictiveControllers.py:216-218), expanded here
+    // once; xLin0 / uLin0 are not used.  Both NULL: the LTV-MPC (timeVarying, :110-145) on the regression store, first linearisation trajectories xLin0 / uLin0.
+    ARGCHK(c && x0 && xg0 && noise && B >= 1 && T_max >= 1 && c->cfg.numSS_it == 0);
+    ARGCHK((A_lti != nullptr) == (B_lti != nullptr) && (A_lti || (xLin0 && uLin0)));
+    ARGCHK(B <= c->cfg.max_batch);
+    ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const bool lti = A_lti != nullptr;
+    if (!lti) { const int rc = refresh_params(c, true, false); if (rc) return rc; }       // LMPC_E_STATE without trToUse stored laps, as lmpc_step_batch
+    RESOLVE_PENDING();
+    int rc = rollout_setup(c, lti ? RO_LTI : RO_LTV, stop_at_line ? 1 : 0, B, T_max, x0, xg0, lti ? nullptr : xLin0, lti ? nullptr : uLin0, noise);
+    if (rc) return rc;
+    if (lti) {
+        lmpc_rollout_session *r = c->ro; const size_t N = c->cfg.N, Bz = B;
+        std::vector<double> eA(Bz * N * 36), eB(Bz * N * 12);
+        for (size_t b = 0; b < Bz; b++) for (size_t k = 0; k < N; k++) {
+            memcpy(&eA[(b * N + k) * 36], A_lti + b * 36, sizeof(double) * 36); memcpy(&eB[(b * N + k) * 12], B_lti + b * 12, sizeof(double) * 12);
+        }
+        hipError_t e = hipMemcpyAsync(r->d_A, eA.data(), sizeof(double) * eA.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(r->d_B, eB.data(), sizeof(double) * eB.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(r->d_C, 0, sizeof(double) * Bz * N * 6, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                      // (the pageable host arrays must outlive the copies)
+        if (e != hipSuccess) { r->active = false; return set_err(LMPC_E_HIP, "lmpc_rollout_begin_mpc", hipGetErrorString(e)); }
+    }
+    return LMPC_OK;
+}
+
+int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const double *xg0, const double *vt, const double *noise_u, const double *noise,
+                     int stop_at_line, int *steps_total, int *n_done) {
+    // B PID laps (main.py:61-70: Simulator.sim with Utilities.PID, Utilities.py:42-68), the whole lap in ONE launch (lmpc_pid_rollout_kernel).  vt: target speed per
+    // car (B); noise_u: T_max x B x 2 N(0,1) draws of the control law; noise: T_max x B x 3 of the plant.  Needs only the track: valid on any context.  Leaves an
+    // active session whose logs lmpc_rollout_fetch returns; lmpc_rollout_run has nothing left to do on it.  steps_total: rows the logs hold (T_max, or with
+    // stop_at_line the last crossing step if every car crossed).
+    ARGCHK(c && x0 && xg0 && vt && noise_u && noise && B >= 1 && T_max >= 1 && T_max <= LMPC_PID_MAX_STEPS);
+    ARGCHK(B <= c->cfg.max_batch);
+    ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
+    HIPCHK(hipSetDevice(c->cfg.device));
+    RESOLVE_PENDING();
+    int rc = rollout_setup(c, RO_PID, stop_at_line ? 1 : 0, B, T_max, x0, xg0, nullptr, nullptr, noise);
+    if (rc) return rc;
+    lmpc_rollout_session *r = c->ro; const size_t Bz = B;
+    auto fail = [&](int code) { r->active = false; return code; };
+    if (!r->d_noiseU) {                     // beside the kept set: sessions of the same shape reuse the buffers whatever their kind
+        void *q = nullptr;
+        if (g_malloc(&q, sizeof(double) * ((size_t)T_max * Bz * 2 + Bz)) != hipSuccess) return fail(set_err(LMPC_E_HIP, "hipMalloc", "control-law noise"));
+        r->keep.push_back(q); r->d_noiseU = (double *)q; r->d_vt = r->d_noiseU + (size_t)T_max * Bz * 2;
+    }
+    hipError_t e = hipMemcpyAsync(r->d_noiseU, noise_u, sizeof(double) * (size_t)T_max * Bz * 2, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_vt, vt, sizeof(double) * Bz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && stop_at_line) {      // rows behind a car's crossing step are not written: a reused session must not show the previous lap's there
+        e = hipMemsetAsync(r->d_logX, 0, sizeof(double) * (size_t)T_max * Bz * 6, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(r->d_logU, 0, sizeof(double) * (size_t)T_max * Bz * 2, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(r->d_logG, 0, sizeof(double) * (size_t)T_max * Bz * 6, c->stream);
+    }
+    if (e != hipSuccess) return fail(set_err(LMPC_E_HIP, "lmpc_rollout_pid", hipGetErrorString(e)));
+    lmpc_rollout_state st; rollout_state(r, st);
+    hipLaunchKernelGGL(lmpc_pid_rollout_kernel, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0,
+                       (const double *)r->d_vt, (const double *)r->d_noiseU, st);
+    e = hipGetLastError();
+    std::vector<int> done(Bz);
+    if (e == hipSuccess) e = hipMemcpyAsync(done.data(), r->d_done, sizeof(int) * Bz, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(set_err(LMPC_E_HIP, "lmpc_rollout_pid", hipGetErrorString(e)));
+    int nd = 0, last = 0;
+    for (int b = 0; b < B; b++) if (done[b] >= 0) { nd++; last = std::max(last, done[b]); }
+    r->t = (stop_at_line && nd == B) ? last : T_max;
+    if (steps_total) *steps_total = r->t;
+    if (n_done) *n_done = nd;
+    return LMPC_OK;
+}
 
 int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) {
     // advance every rollout by up to max_steps simulated steps (four launches per step on two streams, no host round trip except a
     // finished-lap poll every 8 steps); stops early once every rollout has crossed the finish line
-    ARGCHK(c && c->ro && c->ro->active && max_steps >= 1);
+    // Sessions of lmpc_rollout_begin_mpc run the same chain without the safe-set selection (io.mode 2: the S = 0 solve kernels write ztNext = xPred[N],
+    // ztuNext = uPred[N - 1], MPC.feasibleStateInput :157-159, which the shift kernel appends to xLin / uLin); the LTI form has no regression launch and no
+    // linearisation trajectory to shift, only OldInput.  A session of lmpc_rollout_pid has run to its end already.
+    ARGCHK(c && c->ro && c->ro->active && max_steps >= 1 && c->ro->kind != RO_PID);
     lmpc_rollout_session *r = c->ro;
     const int B = r->B; const size_t N = c->cfg.N;
+    const bool lmpc = r->kind == RO_LMPC, lti = r->kind == RO_LTI;
     HIPCHK(hipSetDevice(c->cfg.device));
-    lmpc_rollout_state st; st.x = r->d_x; st.xg = r->d_xg; st.xLin = r->d_xLin; st.uLin = r->d_uLin; st.uOld = r->d_uOld; st.zt = r->d_zt; st.xPP = r->d_xPP;
-    st.hasPred = r->d_hasPred; st.timeStep = r->d_tstep; st.doneAt = r->d_done; st.xPred = r->d_xPred; st.uPred = r->d_uPred; st.ztNext = r->d_ztN; st.ztuNext = r->d_ztuN;
-    st.status = r->d_status; st.logX = r->d_logX; st.logU = r->d_logU; st.logG = r->d_logG; st.noise = r->d_noise; st.nDone = r->d_nDone; st.statusAcc = r->d_stAcc;
-    st.finX = r->d_finX; st.finG = r->d_finG;
+    lmpc_rollout_state st; rollout_state(r, st);
     int nd = 0, rc = LMPC_OK;
     const int t_end = std::min(r->T_max, r->t + max_steps);
     while (r->t < t_end) {
-        rc = refresh_params(c, true, true); if (rc) return rc;
+        if (!lti) {
+        rc = refresh_params(c, true, lmpc); if (rc) return rc;
         ev_begin(c, 0);
         { int qg, nblk; k1_grid(c, B, &qg, &nblk);
           launch_k1(c, nblk, B, qg, (const double *)r->d_xLin, (int)(N + 1) * 6, (const double *)r->d_uLin, r->d_A, r->d_B, r->d_C, r->d_rst); }
         ev_end(c); c->stats.n_regress++;
+        }
         lmpc_solve_io io; memset(&io, 0, sizeof(io));
-        io.mode = 3; io.A = r->d_A; io.Bm = r->d_B; io.C = r->d_C; io.x0 = r->d_x; io.uOld = r->d_uOld; io.zt = r->d_zt; io.xPredPrev = r->d_xPP; io.hasPred = r->d_hasPred;
+        io.mode = lmpc ? 3 : 2; io.A = r->d_A; io.Bm = r->d_B; io.C = r->d_C; io.x0 = r->d_x; io.uOld = r->d_uOld; io.zt = r->d_zt; io.xPredPrev = r->d_xPP; io.hasPred = r->d_hasPred;
         io.timeStep = r->d_tstep; io.xPred = r->d_xPred; io.uPred = r->d_uPred; io.slack = r->d_slack; io.lambda = r->d_lam; io.sTerm = r->d_sT; io.ztNext = r->d_ztN;
-        io.ztuNext = r->d_ztuN; io.resid = r->d_resid; io.status = r->d_status; io.iters = r->d_iters; io.rstatus = r->d_rst;
+        io.ztuNext = r->d_ztuN; io.resid = r->d_resid; io.status = r->d_status; io.iters = r->d_iters; io.rstatus = lti ? nullptr : r->d_rst;
         io.ssSelOut = r->d_ssSel; io.qSelOut = r->d_qSel; io.succOut = r->d_succ; io.succUOut = r->d_succU;
         if (r->t > 0) HIPCHK(hipStreamWaitEvent(c->stream, r->e_plant, 0));          // the solve needs the plant's new state
         rc = launch_solve(c, B, io, true); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
@@ -1176,13 +1274,14 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         HIPCHK(hipStreamWaitEvent(r->pstream, r->e_solved, 0));
         hipLaunchKernelGGL(lmpc_rollout_plant_kernel, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
         HIPCHK(hipEventRecord(r->e_plant, r->pstream));
-        hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression
+        if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->d_uPred, r->d_uOld);
+        else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression
         HIPCHK(hipGetLastError());
         r->t++;
         if ((r->t & 7) == 0 || r->t == t_end) {
             HIPCHK(hipStreamSynchronize(r->pstream));
             HIPCHK(hipMemcpyAsync(&nd, r->d_nDone, sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-            if (nd >= B) break;
+            if (nd >= B && r->stop_at_line) break;
         }
     }
     if (steps_total) *steps_total = r->t;
@@ -1312,26 +1411,38 @@ int lmpc_ss_truncate_lap(lmpc_ctx *c, int lap, int T) {
     return LMPC_OK;
 }
 
-int lmpc_lti_regression(int device, const double *x, const double *u, int T, double lamb, double *A, double *B, double *Error, int *status) {
-    // Utilities.Regression (fnc/Utilities.py:5-28), called by main.py:74-77 before any controller exists: no context needed
-    ARGCHK(x && u && A && B && Error && T >= 3);
+int lmpc_lti_regression_batch(int device, int B, const double *x, const double *u, const int *T, int ldT, double lamb, double *A, double *Bm, double *Error, int *status) {
+    // Utilities.Regression (fnc/Utilities.py:5-28) for B laps in one launch, one work-group per lap: lap b has T[b] rows at x + b * ldT * 6 (u + b * ldT * 2), rows beyond
+    // T[b] are not read.  A: B x 6 x 6, Bm: B x 6 x 2, Error: B x 2 x 6, status: B or NULL.  No context needed (main.py:74-77 runs before any controller exists).
+    ARGCHK(x && u && T && A && Bm && Error && B >= 1 && ldT >= 3);
+    for (int b = 0; b < B; b++) ARGCHK(T[b] >= 3 && T[b] <= ldT);
     HIPCHK(hipSetDevice(device));
-    double *d; HIPCHK(hipMalloc(&d, sizeof(double) * ((size_t)T * 8 + 60) + sizeof(int)));
-    double *dx = d, *du = d + (size_t)T * 6, *dout = du + (size_t)T * 2; int *dst = (int *)(dout + 60);
-    hipError_t e = hipMemcpy(dx, x, sizeof(double) * (size_t)T * 6, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(du, u, sizeof(double) * (size_t)T * 2, hipMemcpyHostToDevice);
-    double hout[60]; int hst = 0;
+    const size_t Bz = B, rows = Bz * (size_t)ldT;
+    double *d; HIPCHK(hipMalloc(&d, sizeof(double) * (rows * 8 + Bz * 60) + sizeof(int) * 2 * Bz));
+    double *dx = d, *du = d + rows * 6, *dout = du + rows * 2; int *dst = (int *)(dout + Bz * 60), *dT = dst + Bz;
+    hipError_t e = hipMemcpy(dx, x, sizeof(double) * rows * 6, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(du, u, sizeof(double) * rows * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dT, T, sizeof(int) * Bz, hipMemcpyHostToDevice);
+    std::vector<double> hout(Bz * 60); std::vector<int> hst(Bz, 0);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(lmpc_lti_regress_kernel, dim3(1), dim3(LTI_NT), 0, 0, (const double *)dx, (const double *)du, T, lamb, dout, dst);
+        hipLaunchKernelGGL(lmpc_lti_regress_kernel, dim3(B), dim3(LTI_NT), 0, 0, (const double *)dx, (const double *)du, (const int *)dT, ldT, lamb, dout, dst);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(hout, dout, sizeof(hout), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&hst, dst, sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hout.data(), dout, sizeof(double) * hout.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hst.data(), dst, sizeof(int) * Bz, hipMemcpyDeviceToHost);
     (void)hipFree(d);
-    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_lti_regression", hipGetErrorString(e));
-    memcpy(A, hout, sizeof(double) * 36); memcpy(B, hout + 36, sizeof(double) * 12); memcpy(Error, hout + 48, sizeof(double) * 12);
-    if (status) *status = hst;
+    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_lti_regression_batch", hipGetErrorString(e));
+    for (size_t b = 0; b < Bz; b++) {
+        memcpy(A + b * 36, &hout[b * 60], sizeof(double) * 36); memcpy(Bm + b * 12, &hout[b * 60 + 36], sizeof(double) * 12); memcpy(Error + b * 12, &hout[b * 60 + 48], sizeof(double) * 12);
+        if (status) status[b] = hst[b];
+    }
     return LMPC_OK;
+}
+
+int lmpc_lti_regression(int device, const double *x, const double *u, int T, double lamb, double *A, double *B, double *Error, int *status) {
+    // Utilities.Regression (fnc/Utilities.py:5-28), called by main.py:74-77 before any controller exists: no context needed.  The one-lap call of the batched form.
+    ARGCHK(x && u && A && B && Error && T >= 3);
+    return lmpc_lti_regression_batch(device, 1, x, u, &T, T, lamb, A, B, Error, status);
 }
 
 int lmpc_selftest(lmpc_ctx *c) {

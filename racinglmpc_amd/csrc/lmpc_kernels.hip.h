@@ -2460,6 +2460,69 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_p
     }
 }
 
+// LTI path-following MPC (MPC.solve with timeVarying = False, PredictiveControllers.py:110-137): A, B are fixed and C = 0, so no linearisation trajectory feeds
+// a regression; of the tail of MPC.solve only OldInput = uPred[0] (:134) reaches the next QP.
+__global__ __launch_bounds__(256) void lmpc_rollout_oldinput_kernel(int B, int N, const double *__restrict__ uPred, double *__restrict__ uOld) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < B * 2) uOld[e] = uPred[(size_t)(e >> 1) * N * 2 + (e & 1)];
+}
+
+// Whole PID laps in ONE launch (main.py:61-70: Simulator.sim driven by Utilities.PID.solve, Utilities.py:60-67).  There is no QP between two steps, so the
+// loop over t runs inside the kernel: per step the control law u0 = -0.6 ey - 0.9 epsi + clip(0.25 n0, +-0.9), u1 = 1.5 (vt_b - vx) + clip(0.10 n1, +-0.2), then
+// the plant (plant_step_duo: the device function lmpc_plant_kernel and lmpc_rollout_plant_kernel call), the log rows and the finish-line bookkeeping of
+// lmpc_rollout_plant_kernel.  State and input of a car live in LDS between steps (wave 1 produces them, wave 0 needs vx, vy, wz and u).  The control law is
+// written with contraction into FMAs switched off (pid_control_law), in the order NumPy evaluates Utilities.py:67-68, so that u is the double a
+// host loop computes from the same state.  stop_at_line: Simulator(multiLap = False) -- a car is no longer logged once s > TrackLength (SysModel.py:45); else
+// every car is logged for all T_max steps (main.py:57, 66), doneAt still holding the first crossing.  The loop bound is T_max alone.  statusAcc carries
+// LMPC_ST_NO_SEGMENT only (up to the crossing step, as in lmpc_rollout_plant_kernel): there is no solver whose status could be added.
+__device__ __forceinline__ void pid_control_law(const double *x, double vt, const double *nu, double &u0, double &u1) {
+#pragma clang fp contract(off)                                        // every product and sum rounded on its own, as NumPy evaluates Utilities.py:67-68
+    const double c0 = fmin(fmax(nu[0] * 0.25, -0.9), 0.9), c1 = fmin(fmax(nu[1] * 0.10, -0.2), 0.2);
+    u0 = -0.6 * x[5] - 0.9 * x[3] + c0;
+    u1 = 1.5 * (vt - x[0]) + c1;
+}
+__global__ __launch_bounds__(PLANT_NT) void lmpc_pid_rollout_kernel(lmpc_dev_params p, int B, int T_max, int stop_at_line, const double *__restrict__ vt,
+                                                                    const double *__restrict__ noise_u /* T_max x B x 2 */, lmpc_rollout_state r) {
+    __shared__ plant_lds L;
+    __shared__ double sx[PLANT_CARS][6], sg[PLANT_CARS][6], su[PLANT_CARS][2];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, cl = lane >> 1, role = lane & 1;
+    const int b0 = blockIdx.x * PLANT_CARS + cl; const bool on = b0 < B; const int b = on ? b0 : B - 1;      // (a lane without a car repeats the last one: barriers inside)
+    const bool keeper = wave == 1 && role == 0;                        // the lane that owns car cl's LDS rows; it writes to global memory only if `on`
+    const double vtb = vt[b];
+    int done = -1, acc = 0;
+    if (keeper) for (int j = 0; j < 6; j++) { sx[cl][j] = r.x[(size_t)b * 6 + j]; sg[cl][j] = r.xg[(size_t)b * 6 + j]; }
+    for (int t = 0; t < T_max; t++) {
+        if (keeper) {
+            const double *nu = noise_u + ((size_t)t * B + b) * 2;
+            double u0, u1; pid_control_law(sx[cl], vtb, nu, u0, u1);
+            su[cl][0] = u0; su[cl][1] = u1;
+            if (on && !(stop_at_line && done >= 0)) {
+                for (int j = 0; j < 6; j++) { r.logX[((size_t)t * B + b) * 6 + j] = sx[cl][j]; r.logG[((size_t)t * B + b) * 6 + j] = sg[cl][j]; }
+                r.logU[((size_t)t * B + b) * 2] = u0; r.logU[((size_t)t * B + b) * 2 + 1] = u1;
+            }
+        }
+        __syncthreads();
+        int bad = 0; double xo[6], go[6];
+        plant_step_duo(p, L, sx[cl], sg[cl], su[cl], r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl);
+        if (keeper) {
+            for (int j = 0; j < 6; j++) { sx[cl][j] = xo[j]; sg[cl][j] = go[j]; }
+            if (done < 0) {
+                acc |= bad ? LMPC_ST_NO_SEGMENT : 0;
+                if (xo[4] > p.TL) {                                                             // lap completed, SysModel.py:45
+                    done = t + 1;
+                    if (on) for (int j = 0; j < 6; j++) { r.finX[(size_t)b * 6 + j] = xo[j]; r.finG[(size_t)b * 6 + j] = go[j]; }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (keeper && on) {
+        for (int j = 0; j < 6; j++) { r.x[(size_t)b * 6 + j] = sx[cl][j]; r.xg[(size_t)b * 6 + j] = sg[cl][j]; }
+        r.doneAt[b] = done; r.statusAcc[b] = acc;
+        if (done >= 0) atomicAdd(r.nDone, 1);
+    }
+}
+
 // =====================================================================================================
 // Utilities.Regression (fnc/Utilities.py:5-28): the LTI model of main.py's second stage (main.py:74-77), one ridge least-squares fit
 // over a whole lap: rows r = 0..T-3, z_r = [x_{r+1}, u_{r+1}] (8), y_r = x_{r+2} (6); W = (Z'Z + lamb I)^-1 Z'Y; A = W'[:, 0:6],
@@ -2469,8 +2532,12 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_p
 // =====================================================================================================
 #define LTI_NT 1024
 #define LTI_PARTS 12
-__global__ __launch_bounds__(LTI_NT) void lmpc_lti_regress_kernel(const double *__restrict__ x, const double *__restrict__ u, int T, double lamb,
+// Batched form: work-group b fits lap b -- T[b] rows at x + b * ldT * 6 / u + b * ldT * 2 -- into out + b * 60 and status[b]; the laps share nothing, and the
+// arithmetic of a lap does not depend on the grid (lmpc_lti_regression is the one-lap launch of it).
+__global__ __launch_bounds__(LTI_NT) void lmpc_lti_regress_kernel(const double *__restrict__ x, const double *__restrict__ u, const int *__restrict__ Tlap, int ldT, double lamb,
                                                                   double *__restrict__ out, int *__restrict__ status) {
+    const int T = Tlap[blockIdx.x];
+    x += (size_t)blockIdx.x * ldT * 6; u += (size_t)blockIdx.x * ldT * 2; out += (size_t)blockIdx.x * 60; status += blockIdx.x;
     __shared__ double part[LTI_PARTS][84];
     __shared__ double G[8][8], bv[8][6], W[8][6];
     __shared__ double emax[LTI_NT / WAVE][6], emin[LTI_NT / WAVE][6];

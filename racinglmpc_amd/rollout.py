@@ -7,6 +7,9 @@ ranks exchange their fastest VALID laps once (lmpc_rollout_exchange: device-pack
 identical inserts.  A lap is valid when the car crossed the finish line and no status bit other than LMPC_ST_INEXACT was
 raised up to the crossing step; anything else never reaches a lap store -- neither as a new lap nor as the rows that extend a
 stored lap past the finish line (the batched LMPC.addPoint): those are checked for status bits and finiteness first.
+
+The three stages in front of the LMPC laps (main.py:61-95) run the same way: BatchedRollouts.run_pid_laps (whole PID laps in one launch), run_mpc_laps (LTI path-following
+MPC / LTV-MPC sessions on a numSS_it == 0 context) and bootstrap(), which chains them -- PID laps -> batched Utilities.Regression -> LTI-MPC laps -> LTV-MPC laps.
 """
 import numpy as np
 
@@ -16,7 +19,7 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False):
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True):
         """global_noise: the plant noise of a lap is drawn for ALL rollouts of the job (same seed on every rank) and this rank keeps the columns
         of its shard (`noise_shard` = (lo, hi, total), set by LmpcGeneration) -- a rollout then sees the same draws however the job is split over
         ranks.  Default: every rank draws for its own shard only (seed per rank)."""
@@ -26,21 +29,25 @@ class BatchedRollouts:
         self.global_noise, self.noise_shard = bool(global_noise), None
         self.last_status = None
         self.last_done = None
+        self.prefetch = bool(prefetch) # False: every array is drawn when it is asked for, no worker thread (same draws, same order: tests compare the two)
         self._pre = None               # (shape key, generator state before the draw, future): the NEXT lap's plant noise, drawn by a worker thread while this lap runs
 
-    def _draw_noise(self, max_steps, B, prefetch_only=False):
-        """Plant noise of one lap, (max_steps, B, 3) N(0, 1) draws.  A generation loop asks for the same shape lap after lap, and 1.2 M draws are ~15 ms of one
+    def _draw_noise(self, max_steps, B, prefetch_only=False, width=3):
+        """Plant noise of one lap, (max_steps, B, 3) N(0, 1) draws; width = 2: the control-law noise of a PID lap, a draw of its own.
+          A generation loop asks for the same shape lap after lap, and 1.2 M draws are ~15 ms of one
         host core -- a tenth of a 1024-rollout lap on the GPU: the next lap's array is drawn by a worker thread while the device runs this one (NumPy releases
         the GIL inside the fill).  The generator is consumed in exactly the order it would be without the prefetch: a prefetched array of another shape is
         discarded together with its draws (the generator state from before the draw is restored)."""
         if self.global_noise and self.noise_shard is not None:
             lo, hi, total = self.noise_shard
             assert hi - lo == B, (lo, hi, B)
-            key = (max_steps, total, lo, hi)
-            draw = lambda: np.ascontiguousarray(self.rng.standard_normal((max_steps, total, 3))[:, lo:hi])
+            key = (max_steps, total, lo, hi, width)
+            draw = lambda: np.ascontiguousarray(self.rng.standard_normal((max_steps, total, width))[:, lo:hi])
         else:
-            key = (max_steps, B)
-            draw = lambda: self.rng.standard_normal((max_steps, B, 3))
+            key = (max_steps, B, width)
+            draw = lambda: self.rng.standard_normal((max_steps, B, width))
+        if not getattr(self, "prefetch", True):    # (objects built without __init__ -- tests/test_host_checks.py -- prefetch)
+            return None if prefetch_only else draw()
         if prefetch_only:                          # (prefetch_noise: start the draw of the FIRST lap; the generator is consumed in the same order)
             if self._pre is None:
                 from concurrent.futures import ThreadPoolExecutor
@@ -121,6 +128,107 @@ class BatchedRollouts:
             T = int(done[b]) if done[b] >= 0 else X.shape[0]
             laps.append((X[:T, b].copy(), U[:T, b].copy(), G[:T, b].copy(), np.concatenate([fx[b], fg[b]]), int(done[b]), int(st[b])))
         return laps
+
+
+    def _collect(self, B, X, U, G, done, st, fx, fg, whole, keep_invalid):
+        """Lap tuples (x, u, x_glob, final12, done_at, status) of a finished session: the rows up to the crossing step, or (whole: a multiLap run, main.py:57) every logged row."""
+        self.last_status, self.last_done = st, done
+        laps = []
+        for b in range(B):
+            valid = done[b] >= 0 and (st[b] & ~_capi.ST_INEXACT) == 0
+            if not (valid or keep_invalid):
+                continue
+            T = X.shape[0] if (whole or done[b] < 0) else int(done[b])
+            laps.append((X[:T, b].copy(), U[:T, b].copy(), G[:T, b].copy(), np.concatenate([fx[b], fg[b]]), int(done[b]), int(st[b])))
+        return laps
+
+    def run_pid_laps(self, vt, x0=None, max_steps=1000, stop_at_line=False, keep_invalid=False):
+        """len(vt) PID laps (main.py:61-70; Utilities.PID.solve, Utilities.py:60-67), car b at target speed vt[b], the whole lap in one kernel launch (Context.rollout_pid).
+        Generator consumption, in this order, with or without the prefetcher: the control-law noise (max_steps, B, 2), then the plant noise (max_steps, B, 3); step t
+        of car b uses rows [t, b] of both.  Returns the valid laps as run_lap_device does; stop_at_line = False (the reference's multiLap simulator, main.py:57) keeps
+        all max_steps rows of a lap -- the rows past the finish line are what an LMPC safe set seeded from the lap needs there --, True the rows up to the crossing."""
+        vt = np.atleast_1d(np.asarray(vt, float)); B = vt.shape[0]
+        x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1)) if x0 is None else np.asarray(x0, float)
+        noise_u = self._draw_noise(max_steps, B, width=2)
+        noise = self._draw_noise(max_steps, B)
+        t, _ = self.ctx.rollout_pid(x0, x0, vt, noise_u, noise, stop_at_line=stop_at_line)
+        out = self.ctx.rollout_fetch(0, t)
+        self.ctx.rollout_end()
+        return self._collect(B, *out, whole=not stop_at_line, keep_invalid=keep_invalid)
+
+    def run_mpc_laps(self, x0, A=None, B=None, xLin0=None, uLin0=None, max_steps=1000, stop_at_line=False, keep_invalid=False):
+        """x0.shape[0] closed-loop laps of the plain MPC on a numSS_it == 0 context, state resident on the device (Context.rollout_begin_mpc): with A (nb, 6, 6) / B (nb, 6, 2) the LTI
+        path-following MPC of main.py:72-80 on those models, else the LTV-MPC of main.py:85-95 from xLin0 / uLin0 (one trajectory for all, or one per rollout) on the
+        context's regression store.  Generator consumption: one plant-noise draw (max_steps, nb, 3).  Returns lap tuples as run_pid_laps does."""
+        x0 = np.asarray(x0, float); nb = x0.shape[0]
+        noise = self._draw_noise(max_steps, nb)
+        if A is not None:
+            self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line)
+        else:
+            self.ctx.rollout_begin_mpc(x0, x0, noise, xLin0=self._per_rollout(xLin0, nb), uLin0=self._per_rollout(uLin0, nb), stop_at_line=stop_at_line)
+        t, _ = self.ctx.rollout_run(max_steps)
+        out = self.ctx.rollout_fetch(0, t)
+        self.ctx.rollout_end()
+        return self._collect(nb, *out, whole=not stop_at_line, keep_invalid=keep_invalid)
+
+
+LTI_LAMB = 0.0000001                   # main.py:74
+BOOTSTRAP_STORE_LAPS = 4               # PID laps in the shared regression store of bootstrap()'s LTV-MPC stage (main.py:102-104 gives its LMPC model four as well)
+
+
+def mpc_stage_config(track, N, vt, max_batch, trToUse=1, device=0):
+    """LmpcConfig of main.py's two MPC stages: the values of initMPCParams (initControllerParameters.py:4-26), no terminal set."""
+    track = np.asarray(track, float)
+    Fx = np.array([[0., 0., 0., 0., 0., 1.], [0., 0., 0., 0., 0., -1.]])
+    Fu = np.kron(np.eye(2), np.array([1, -1])).T
+    return _capi.config_from(N, np.diag([1.0, 1.0, 1, 1, 0.0, 100.0]), np.diag([1.0, 10.0]), np.zeros((6, 6)), np.zeros(2), np.array([0., 50.]),
+                             Fx, [2., 2.], Fu, [0.5, 0.5, 10.0, 10.0], np.array([float(vt), 0, 0, 0, 0, 0]), numSS_it=0, trToUse=int(trToUse), track=track,
+                             trackLength=float(track[-1, 3] + track[-1, 4]), max_batch=int(max_batch), device=int(device))
+
+
+def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None):
+    """main.py:61-95 for B cars without a host round trip inside a lap: PID laps -> one LTI model per car (batched Utilities.Regression, lamb = 1e-7) -> LTI-MPC laps,
+    car b on its own (A_b, B_b) -> LTV-MPC laps.  vt: the PID target speed, one value (main.py:50) or one per car; the MPC stages track vt_mpc (default: vt, or the
+    mean of the per-car values).  Every stage runs max_steps steps from x0 = [0.5, 0, 0, 0, 0, 0] like the reference's multiLap simulator (main.py:45, 57).
+
+    The LTV-MPC rollouts share ONE regression store (the context's): it holds the min(B, 4) PID laps whose target speed is nearest to vt_mpc, lowest car index
+    first among equals -- the local regression weighs stored points by their distance to the linearisation point, so laps driven near the speed the MPC tracks
+    are the data it uses, and four is what main.py:102-104 gives the LMPC's model.  Every rollout starts its linearisation from the first N + 1 rows of the LAST
+    stored lap (MPC.__init__, PredictiveControllers.py:88-90).  With B = 1 that is the car's own single PID lap, main.py:88-89.
+
+    One generator seeded with `seed` feeds all stages in the order PID control-law noise, PID plant noise, LTI-MPC plant noise, LTV-MPC plant noise.
+    Returns dict(pid=, mpc=, ltvmpc= lists of lap tuples (x, u, x_glob, final12, done_at, status) with every car in it, flagged or not -- check `status` and
+    `done_at` --, A=, B=, Error=, lti_status=, store_laps= the cars whose PID laps went into the shared store): seed_lmpc(ctx, [pid[b] for b in store_laps]) seeds an
+    LMPC context with them as main.py:102-110 does with its PID lap."""
+    track = np.asarray(track, float)
+    vt = np.broadcast_to(np.asarray(vt, float), (B,)).copy()
+    vt_mpc = float(vt.mean()) if vt_mpc is None else float(vt_mpc)
+    n_store = min(B, BOOTSTRAP_STORE_LAPS)
+    ctx = _capi.Context(mpc_stage_config(track, N, vt_mpc, B, trToUse=n_store, device=device))
+    ro = BatchedRollouts(ctx, track, seed=seed)
+    try:
+        x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1))
+        pid = ro.run_pid_laps(vt, x0, max_steps=max_steps, keep_invalid=True)
+        A, Bm, Err, lst = _capi.lti_regression_batch([(l[0], l[1]) for l in pid], LTI_LAMB, device=device)
+        mpc = ro.run_mpc_laps(x0, A=A, B=Bm, max_steps=max_steps, keep_invalid=True)
+        order = sorted(range(B), key=lambda b: (abs(vt[b] - vt_mpc), b))[:n_store]
+        for b in order:
+            ctx.model_add_trajectory(pid[b][0], pid[b][1])
+        last = pid[order[-1]]                       # xStored[-1]: laps of equal length keep their insertion order (PredictiveModel.py:35-46)
+        ltv = ro.run_mpc_laps(x0, xLin0=last[0][0:N + 1], uLin0=last[1][0:N], max_steps=max_steps, keep_invalid=True)
+    finally:
+        ro.close()
+        ctx.close()
+    return dict(pid=pid, mpc=mpc, ltvmpc=ltv, A=A, B=Bm, Error=Err, lti_status=lst, store_laps=order)
+
+
+def seed_lmpc(ctx, laps):
+    """main.py:102-110 with laps of bootstrap(): every (x, u, ...) tuple goes into the regression store (PredictiveModel.addTrajectory) and into the safe set
+    (LMPC.addTrajectory) of the LMPC context `ctx`, in the order given; an LMPC context needs numSS_it / trToUse of them.  The reference passes its one PID lap four
+    times; bootstrap()'s "pid" laps are such laps -- max_steps rows of a multiLap run, s running past TrackLength -- one per car."""
+    for lap in laps:
+        ctx.model_add_trajectory(lap[0], lap[1])
+        ctx.ss_add_trajectory(lap[0], lap[1])
 
 
 class LmpcGeneration:

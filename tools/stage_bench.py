@@ -1,0 +1,113 @@
+"""The three stages in front of the LMPC laps (main.py:61-95) as device sessions against the host-stepped loops that were the only way before them:
+
+    python tools/stage_bench.py --stage pid      # lmpc_rollout_pid        vs  bench.pid_laps' loop (NumPy control law + lmpc_plant_step_batch per step)
+    python tools/stage_bench.py --stage mpc      # LTI-MPC session         vs  lmpc_qp_solve_batch + lmpc_plant_step_batch per step
+    python tools/stage_bench.py --stage ltvmpc   # LTV-MPC session         vs  lmpc_step_batch + lmpc_plant_step_batch + the shift in NumPy per step
+
+One JSON line: per batch size (default 1, 256, 1024; N = 12) simulated steps/s of both ways (car-steps: B x T / seconds; for the MPC stages that is also the rate of
+closed-loop QP solves) and the seconds behind them.  Wall clock around work that ends in a drained stream (the session's fetch, the host loop's last download), uploads
+of start states and noise included on both sides; every shape is run once untimed first, then `--repeats` times alternating the two ways, medians reported.  Both ways
+are fed the same draws, and the tool checks that their logs are equal bit for bit before it reports a time.  --out also writes the line to a file."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+X0 = np.array([0.5, 0, 0, 0, 0, 0.0])
+
+
+def pid_u(x, vt, nu):
+    return np.stack([-0.6 * x[:, 5] - 0.9 * x[:, 3] + np.clip(nu[:, 0] * 0.25, -0.9, 0.9), 1.5 * (vt - x[:, 0]) + np.clip(nu[:, 1] * 0.10, -0.2, 0.2)], axis=1)
+
+
+def run_stage(stage, g, B, T):
+    from racinglmpc_amd import _capi, rollout
+    N = 12
+    ctx = _capi.Context(rollout.mpc_stage_config(g["track"], N, 0.8, B, trToUse=1))
+    rng = np.random.default_rng(7)
+    noise = rng.standard_normal((T, B, 3)); nu = rng.standard_normal((T, B, 2))
+    x0 = np.tile(X0, (B, 1)); x0[:, 5] = np.linspace(-0.1, 0.1, B) if B > 1 else 0.0
+    vt = 0.6 + 0.02 * (np.arange(B) % 30)
+    if stage == "mpc":
+        A1, B1, _, _ = _capi.lti_regression(g["xPID"], g["uPID"], 1e-7)
+        A = np.tile(A1[None], (B, 1, 1)); Bm = np.tile(B1[None], (B, 1, 1))
+        At = np.tile(A[:, None], (1, N, 1, 1)); Bt = np.tile(Bm[:, None], (1, N, 1, 1)); Ct = np.zeros((B, N, 6))
+    if stage == "ltvmpc":
+        ctx.model_add_trajectory(g["xPID"], g["uPID"])
+        xl0 = np.tile(np.array(g["xPID"])[None, 0:N + 1], (B, 1, 1)); ul0 = np.tile(np.array(g["uPID"])[None, 0:N], (B, 1, 1))
+
+    def device():
+        if stage == "pid":
+            t, _ = ctx.rollout_pid(x0, x0, vt, nu, noise)
+        else:
+            if stage == "mpc":
+                ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=Bm)
+            else:
+                ctx.rollout_begin_mpc(x0, x0, noise, xLin0=xl0, uLin0=ul0)
+            t, _ = ctx.rollout_run(T)
+        X, U, G = ctx.rollout_fetch(0, t)[:3]
+        ctx.rollout_end()
+        return X, U, G
+
+    def host():
+        x = x0.copy(); xg = x0.copy(); uOld = np.zeros((B, 2)); X, U, G = [], [], []
+        if stage == "ltvmpc":
+            xLin, uLin = xl0, ul0
+        for t in range(T):
+            if stage == "pid":
+                u = pid_u(x, vt, nu[t])
+            elif stage == "mpc":
+                u = ctx.qp_solve_batch(At, Bt, Ct, x, uOld)["uPred"][:, 0].copy()
+            else:
+                o = ctx.step_batch(x, xLin, uLin, uOld)
+                u = o["uPred"][:, 0].copy()
+                xLin = np.concatenate([o["xPred"][:, 1:], o["xPred"][:, N:N + 1]], axis=1); uLin = np.concatenate([o["uPred"][:, 1:], o["uPred"][:, N - 1:N]], axis=1)
+            X.append(x); U.append(u); G.append(xg)
+            x, xg, _ = ctx.plant_step_batch(x, xg, u, noise[t])
+            uOld = u
+        return np.stack(X), np.stack(U), np.stack(G)
+    return ctx, device, host
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--stage", choices=("pid", "mpc", "ltvmpc"), required=True)
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 256, 1024])
+    ap.add_argument("--steps", type=int, default=0, help="simulated steps per lap (default: 400 for pid, 100 for the MPC stages)")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    import __graft_entry__ as ge
+    ge.build()
+    from tests import common
+    g = common.load_lmpc_golden()
+    T = args.steps or (400 if args.stage == "pid" else 100)
+    rows = []
+    for B in args.batches:
+        ctx, device, host = run_stage(args.stage, g, B, T)
+        d, h = device(), host()                                        # untimed: code objects, session buffers, pooled scratch
+        same = all(np.array_equal(a, b) for a, b in zip(d, h))
+        td, th = [], []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter(); device(); td.append(time.perf_counter() - t0)
+            t0 = time.perf_counter(); host(); th.append(time.perf_counter() - t0)
+        ctx.close()
+        sd, sh = float(np.median(td)), float(np.median(th))
+        rows.append(dict(B=B, steps=T, device_s=sd, host_stepped_s=sh, device_steps_per_s=B * T / sd, host_stepped_steps_per_s=B * T / sh,
+                         device_s_all=td, host_stepped_s_all=th, logs_bit_identical=bool(same)))
+    line = dict(tool="stage_bench", stage=args.stage, N=12, unit="car-steps per second of wall time" + ("" if args.stage == "pid" else " = closed-loop QP solves per second"),
+                results=rows)
+    print(json.dumps(line))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(line, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
