@@ -202,6 +202,22 @@ int lmpc_global_position_batch(lmpc_ctx *, int n, const double *s /*n*/, const d
 int lmpc_plant_step_batch(lmpc_ctx *, int B, const double *x /*B x 6*/, const double *x_glob /*B x 6*/, const double *u /*B x 2*/,
                           const double *noise /*B x 3 N(0,1) draws*/, double *x_next, double *x_glob_next, int *status);
         /* Simulator.dynModel, fnc/simulator/SysModel.py:56-147 (100 Euler sub-steps, clipped noise) */
+
+/* Per-car vehicle constants of the plant.  The reference's Simulator.dynModel carries one vehicle as literals (SysModel.py:60-70); a row of
+ * LMPC_PLANT_NPAR doubles holds those ten values in the reference's order: m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br.  As in the reference the rear slip
+ * angle is taken with lf (SysModel.py:97); lr enters the yaw equation only (:106). */
+#define LMPC_PLANT_NPAR 10
+int lmpc_plant_params_default(double *par /*10*/);
+        /* the literals of SysModel.py:60-70: m = 1.98, lf = lr = 0.125, Iz = 0.024, Cf = Cr = 1.25, Bf = Br = 1.0, Df = Dr = 0.8 * m * 9.81 / 2.0 evaluated in that
+         * order.  Needs no device */
+int lmpc_plant_set_params(lmpc_ctx *, int n, const double *par /*n x 10, or NULL with n = 0*/);
+        /* the vehicle(s) of every later lmpc_plant_step_batch, lmpc_rollout_begin, lmpc_rollout_begin_mpc and lmpc_rollout_pid on this context (Simulator.dynModel,
+         * SysModel.py:56-147, with the constants of :60-70 replaced).  n = 0: the reference's vehicle (the kernels that carry the literals).  n = 1: every car uses
+         * that row.  n > 1: car b uses row b, n <= max_batch; a later call with B > n returns LMPC_E_ARG and says so in lmpc_last_error.  LMPC_E_ARG for a non-finite
+         * entry, m <= 0 or Iz <= 0: the parameters in force stay.  A rollout session takes a snapshot when it begins: setting parameters while a session is active
+         * is allowed and reaches the next session only; kept session buffers of the same shape are reused whatever the parameters */
+int lmpc_plant_get_params(lmpc_ctx *, int *n, double *par /*capacity rows x 10, or NULL*/, int capacity);
+        /* the rows in force (n = 0: the reference's vehicle, SysModel.py:60-70); par receives min(n, capacity) rows */
 int lmpc_rollout_begin(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/,
                        const double *xLin0 /*B x (N+1) x 6*/, const double *uLin0 /*B x N x 2*/, const double *noise /*T_max x B x 3*/);
 int lmpc_rollout_begin_mpc(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/,

@@ -21,6 +21,9 @@ CREATE_RUNTIME_KERNEL, CREATE_FORCE_RUNTIME_KERNEL = 1, 2
 
 ST_MAXITER, ST_REG_SINGULAR, ST_NO_SEGMENT, ST_WINDOW, ST_NUMERIC, ST_NOT_INTERIOR, ST_INEXACT, ST_INFEASIBLE = 1, 2, 4, 8, 16, 32, 64, 128
 
+PLANT_NPAR = 10
+PLANT_PARAM_NAMES = ("m", "lf", "lr", "Iz", "Df", "Cf", "Bf", "Dr", "Cr", "Br")       # one row of vehicle constants, the order of SysModel.py:60-70
+
 
 class LmpcConfig(C.Structure):
     _fields_ = [
@@ -54,7 +57,7 @@ EXPORTS = [
     "lmpc_dev_alloc", "lmpc_dev_free", "lmpc_dev_upload", "lmpc_dev_download", "lmpc_dev_sync", "lmpc_step_batch_dev",
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
-    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_global_position_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
+    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_global_position_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -131,6 +134,45 @@ def lti_regression_batch(laps, lamb, device=0):
     A = np.zeros((n, 6, 6)); Bm = np.zeros((n, 6, 2)); E = np.zeros((n, 2, 6)); st = np.zeros(n, np.int32)
     _chk(load().lmpc_lti_regression_batch(int(device), n, X.ctypes.data, U.ctypes.data, T.ctypes.data, ld, float(lamb), A.ctypes.data, Bm.ctypes.data, E.ctypes.data, st.ctypes.data))
     return A, Bm, E, st
+
+
+def plant_params_default():
+    """The reference's vehicle (SysModel.py:60-70) as one row of PLANT_PARAM_NAMES (lmpc_plant_params_default: needs the library, not a device)."""
+    par = np.zeros(PLANT_NPAR)
+    _chk(load().lmpc_plant_params_default(_d(par)))
+    return par
+
+
+def check_plant_params(par):
+    """(n, 10) float64 rows, or ValueError for what lmpc_plant_set_params refuses: a wrong shape, a non-finite entry, m <= 0 or Iz <= 0."""
+    par = np.array(par, dtype=np.float64, ndmin=2)
+    if par.ndim != 2 or par.shape[1] != PLANT_NPAR:
+        raise ValueError("plant parameters: rows of %d values %s expected, got shape %s" % (PLANT_NPAR, PLANT_PARAM_NAMES, par.shape))
+    if not np.all(np.isfinite(par)):
+        raise ValueError("plant parameters: non-finite entry in row(s) %s" % np.where(~np.isfinite(par).all(1))[0].tolist())
+    if not (np.all(par[:, 0] > 0) and np.all(par[:, 3] > 0)):
+        raise ValueError("plant parameters: m and Iz must be positive (rows %s)" % np.where(~((par[:, 0] > 0) & (par[:, 3] > 0)))[0].tolist())
+    return np.ascontiguousarray(par)
+
+
+def plant_params(B, m=1.98, lf=0.125, lr=0.125, Iz=0.024, mu_f=0.8, mu_r=0.8, Cf=1.25, Bf=1.0, Cr=1.25, Br=1.0, Df=None, Dr=None):
+    """(B, 10) rows of vehicle constants for Context.plant_set_params, columns PLANT_PARAM_NAMES; needs neither the library nor a device.  Every argument is a
+    scalar or a (B,) array.  The peak tyre forces are D = mu * m * 9.81 / 2.0, evaluated left to right as SysModel.py:68, 73 do (the defaults give the reference's
+    bits), unless Df / Dr are given.  Raises ValueError on what lmpc_plant_set_params would refuse."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("plant_params: B must be at least 1")
+
+    def col(name, v):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != B):
+            raise ValueError("plant_params: %s must be a scalar or a (%d,) array, got shape %s" % (name, B, v.shape))
+        return np.broadcast_to(v, (B,)).astype(np.float64)
+    m = col("m", m)
+    Df = col("mu_f", mu_f) * m * 9.81 / 2.0 if Df is None else col("Df", Df)
+    Dr = col("mu_r", mu_r) * m * 9.81 / 2.0 if Dr is None else col("Dr", Dr)
+    cols = [m, col("lf", lf), col("lr", lr), col("Iz", Iz), Df, col("Cf", Cf), col("Bf", Bf), Dr, col("Cr", Cr), col("Br", Br)]
+    return check_plant_params(np.stack(cols, axis=1))
 
 
 def _chk(rc):
@@ -428,6 +470,25 @@ class Context:
         _chk(self.lib.lmpc_plant_step_batch(self._h, C.c_int(B), _d(x), _d(xg), _d(u), _d(nz), _d(xn), _d(xgn), _d(st)))
         return xn, xgn, st
 
+    def plant_set_params(self, par):
+        """Vehicle constants of the plant for every later plant_step_batch / rollout_begin / rollout_begin_mpc / rollout_pid (lmpc_plant_set_params): None or no rows --
+        the reference's vehicle; one row of PLANT_PARAM_NAMES -- every car; (n, 10) -- car b uses row b (n <= max_batch; a later call with more cars is refused).
+        A session uses the rows in force when it began.  plant_params() builds the rows."""
+        if par is None or np.size(par) == 0:
+            _chk(self.lib.lmpc_plant_set_params(self._h, C.c_int(0), None))
+            return
+        par = _f64(par).reshape(-1, PLANT_NPAR)
+        _chk(self.lib.lmpc_plant_set_params(self._h, C.c_int(par.shape[0]), _d(par)))
+
+    def plant_params(self):
+        """The rows in force, (n, 10); n = 0: the reference's vehicle (lmpc_plant_get_params)."""
+        n = C.c_int()
+        _chk(self.lib.lmpc_plant_get_params(self._h, C.byref(n), None, C.c_int(0)))
+        par = np.zeros((n.value, PLANT_NPAR))
+        if n.value:
+            _chk(self.lib.lmpc_plant_get_params(self._h, C.byref(n), _d(par), C.c_int(par.shape[0])))
+        return par
+
     def rollout_begin(self, x0, xglob0, xLin0, uLin0, noise):
         x0 = _f64(x0); xg = _f64(xglob0); xl = _f64(xLin0); ul = _f64(uLin0); nz = _f64(noise)
         B = x0.shape[0]
@@ -703,7 +764,7 @@ class ContextPool:
     def __getattr__(self, name):                       # lap-store edits (model_add_trajectory, ss_add_trajectory, ss_add_point, ss_set_selected, ...): the same call on every member
         if name in ("members", "_next"):               # (not set yet: a failed __init__ must not recurse through this hook)
             raise AttributeError(name)
-        if name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num")):
+        if name == "plant_set_params" or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num"))):   # (the vehicle too: the same on every member)
             def forward(*a, **kw):
                 out = None
                 for m in self.members:

@@ -115,6 +115,7 @@ struct lmpc_ctx {
     double *dbg_trace;                       // developer builds (-DLMPC_TRACE): device buffer of the per-iteration side channel, see lmpc_debug_set_trace
     double tr_s[4]; long long tr_n;          // developer trace of lmpc_step_batch's one-QP path (lmpc_debug_step_trace): seconds spent staging / launching / waiting / unstaging
     struct lmpc_rollout_session *ro;
+    std::vector<double> plant_par; int plant_n;   // lmpc_plant_set_params: plant_n rows of LMPC_PLANT_NPAR vehicle constants (0: the reference's vehicle, the kernels with the literals)
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     double *ext_rows; size_t ext_rows_bytes;   // staging buffer of lmpc_ss_extend_lap
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
@@ -172,7 +173,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 101; }
+int lmpc_version(void) { return 102; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -1047,15 +1048,65 @@ static int pooled_scratch(lmpc_ctx *c, size_t bytes, void **out) {
     *out = c->scr_dev;
     return LMPC_OK;
 }
+// Per-car vehicle constants (lmpc_plant_set_params).  The rows in force for a call of B cars, one per car: the single row repeated, or the first B of the n rows.
+static int plant_rows_for(lmpc_ctx *c, int B, std::vector<double> &rows) {
+    if (c->plant_n > 1 && B > c->plant_n) {
+        char msg[128]; snprintf(msg, sizeof(msg), "B = %d cars but lmpc_plant_set_params holds %d per-car rows", B, c->plant_n);
+        return set_err(LMPC_E_ARG, "plant parameters", msg);
+    }
+    rows.resize((size_t)B * LMPC_PLANT_NPAR);
+    for (int b = 0; b < B; b++) memcpy(&rows[(size_t)b * LMPC_PLANT_NPAR], &c->plant_par[(size_t)(c->plant_n == 1 ? 0 : b) * LMPC_PLANT_NPAR], sizeof(double) * LMPC_PLANT_NPAR);
+    return LMPC_OK;
+}
 extern "C" {
+int lmpc_plant_params_default(double *par) {
+    // the literals of Simulator.dynModel, SysModel.py:60-70, in the order the reference lists them
+    if (!par) return set_err(LMPC_E_ARG, "argument check failed", "par");
+    const double m = 1.98, lf = 0.125, lr = 0.125, Iz = 0.024;
+    const double Df = 0.8 * m * 9.81 / 2.0, Cf = 1.25, Bf = 1.0;
+    const double Dr = 0.8 * m * 9.81 / 2.0, Cr = 1.25, Br = 1.0;
+    const double v[LMPC_PLANT_NPAR] = {m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br};
+    memcpy(par, v, sizeof(v));
+    return LMPC_OK;
+}
+
+int lmpc_plant_set_params(lmpc_ctx *c, int n, const double *par) {
+    // the constants of Simulator.dynModel (SysModel.py:60-70) per car; n = 0 returns to the reference's vehicle.  Checked in full before anything is changed.
+    ARGCHK(c && n >= 0 && (n == 0 || par) && n <= c->cfg.max_batch);
+    for (int b = 0; b < n; b++) {
+        const double *q = par + (size_t)b * LMPC_PLANT_NPAR;
+        for (int j = 0; j < LMPC_PLANT_NPAR; j++)
+            if (!std::isfinite(q[j])) { char msg[96]; snprintf(msg, sizeof(msg), "row %d, entry %d is not finite", b, j); return set_err(LMPC_E_ARG, "plant parameters", msg); }
+        if (!(q[0] > 0.0) || !(q[3] > 0.0)) { char msg[96]; snprintf(msg, sizeof(msg), "row %d: m and Iz must be positive", b); return set_err(LMPC_E_ARG, "plant parameters", msg); }
+    }
+    c->plant_par.assign(par, par + (size_t)n * LMPC_PLANT_NPAR); c->plant_n = n;
+    return LMPC_OK;
+}
+
+int lmpc_plant_get_params(lmpc_ctx *c, int *n, double *par, int capacity) {
+    // the rows lmpc_plant_set_params left in force (n = 0: the literals of SysModel.py:60-70, see lmpc_plant_params_default)
+    ARGCHK(c && n && capacity >= 0);
+    *n = c->plant_n;
+    if (par) memcpy(par, c->plant_par.data(), sizeof(double) * LMPC_PLANT_NPAR * (size_t)std::min(capacity, c->plant_n));
+    return LMPC_OK;
+}
+
 int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg, const double *u, const double *noise, double *xn, double *xgn, int *status) {
     ARGCHK(c && x && xg && u && noise && xn && xgn && B >= 1);
     HIPCHK(hipSetDevice(c->cfg.device));
-    double *d; { void *q; const int rc = pooled_scratch(c, sizeof(double) * (size_t)B * 29 + sizeof(int) * (size_t)B, &q); if (rc) return rc; d = (double *)q; }
-    int *ds = (int *)(d + (size_t)B * 29);
+    const bool par = c->plant_n > 0;
+    std::vector<double> rows;
+    if (par) { const int rc = plant_rows_for(c, B, rows); if (rc) return rc; }
+    double *d; { void *q; const int rc = pooled_scratch(c, sizeof(double) * (size_t)B * (29 + LMPC_PLANT_NPAR) + sizeof(int) * (size_t)B, &q); if (rc) return rc; d = (double *)q; }
+    double *dp = d + (size_t)B * 29;
+    int *ds = (int *)(d + (size_t)B * (29 + LMPC_PLANT_NPAR));
     double *dx = d, *dg = d + (size_t)B * 6, *du = d + (size_t)B * 12, *dn = d + (size_t)B * 14, *dxn = d + (size_t)B * 17, *dgn = d + (size_t)B * 23;
     H2D(dx, x, (size_t)B * 6); H2D(dg, xg, (size_t)B * 6); H2D(du, u, (size_t)B * 2); H2D(dn, noise, (size_t)B * 3);
-    hipLaunchKernelGGL(lmpc_plant_kernel, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds);
+    const dim3 grid((B + PLANT_CARS - 1) / PLANT_CARS);
+    if (par) {
+        H2D(dp, rows.data(), rows.size());                            // (`rows` lives until the stream is drained below)
+        hipLaunchKernelGGL(lmpc_plant_kernel<true>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds, (const double *)dp);
+    } else hipLaunchKernelGGL(lmpc_plant_kernel<false>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds, (const double *)nullptr);
     HIPCHK(hipGetLastError());
     D2H(xn, dxn, (size_t)B * 6); D2H(xgn, dgn, (size_t)B * 6); D2H(status, ds, B);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1081,6 +1132,7 @@ struct lmpc_rollout_session {
     int B, T_max, t;
     int kind, stop_at_line;                                     // RO_LMPC / RO_LTV / RO_LTI / RO_PID (what one simulated step launches); 0: the run does not end when every car has crossed the line
     double *d_noiseU, *d_vt;                                    // RO_PID only: controller noise T_max x B x 2, target speed per car
+    double *d_par; bool has_par;                                // the session's snapshot of the per-car vehicle constants (B x LMPC_PLANT_NPAR), taken when it begins; has_par: the PAR kernels run
     hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
     std::vector<void *> keep;
     double *d_x, *d_xg, *d_xLin, *d_uLin, *d_uOld, *d_zt, *d_xPP, *d_xPred, *d_uPred, *d_slack, *d_lam, *d_sT, *d_ztN, *d_ztuN, *d_A, *d_B, *d_C, *d_resid;
@@ -1105,6 +1157,8 @@ static void rollout_free(lmpc_ctx *c) {
 static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
     HIPCHK(hipSetDevice(c->cfg.device));
     const size_t N = c->cfg.N, S = c->cfg.numSS_points, Bz = B;
+    std::vector<double> par_rows;                               // refused before any session state changes (B beyond the per-car rows)
+    if (c->plant_n > 0) { const int rc = plant_rows_for(c, B, par_rows); if (rc) return rc; }
     // A generation loop begins a session of the same shape every lap: its ~35 device buffers (55 MB of logs at 1024 rollouts x 400 steps), the plant stream and
     // the two events are kept from one session to the next (round 5: allocating and freeing them was ~5 ms of every generation) and released by
     // lmpc_destroy or by a session of another shape.
@@ -1124,6 +1178,7 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     DA(double, d_xPred, Bz * (N + 1) * 6) DA(double, d_uPred, Bz * N * 2) DA(double, d_slack, Bz * N * 2) DA(double, d_lam, Bz * S) DA(double, d_sT, Bz * 6)
     DA(double, d_ztN, Bz * 6) DA(double, d_ztuN, Bz * 2) DA(double, d_A, Bz * N * 36) DA(double, d_B, Bz * N * 12) DA(double, d_C, Bz * N * 6)
     DA(double, d_resid, Bz * 3) DA(int, d_status, Bz) DA(int, d_iters, Bz) DA(int, d_rst, Bz * N) DA(double, d_finX, Bz * 6) DA(double, d_finG, Bz * 6)
+    DA(double, d_par, Bz * LMPC_PLANT_NPAR)
     r->d_ssSel = nullptr; r->d_qSel = nullptr; r->d_succ = nullptr; r->d_succU = nullptr;
     if (c->dbg_capture) { DA(double, d_ssSel, Bz * S * 6) DA(double, d_qSel, Bz * S) DA(double, d_succ, Bz * S * 6) DA(double, d_succU, Bz * S * 2) }
     DA(double, d_logX, (size_t)T_max * Bz * 6) DA(double, d_logU, (size_t)T_max * Bz * 2) DA(double, d_logG, (size_t)T_max * Bz * 6) DA(double, d_noise, (size_t)T_max * Bz * 3)
@@ -1140,6 +1195,8 @@ init_state:
     if (xLin0) H2D(r->d_xLin, xLin0, Bz * (N + 1) * 6); else HIPCHK(hipMemsetAsync(r->d_xLin, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
     if (uLin0) H2D(r->d_uLin, uLin0, Bz * N * 2); else HIPCHK(hipMemsetAsync(r->d_uLin, 0, sizeof(double) * Bz * N * 2, c->stream));
     H2D(r->d_done, neg.data(), Bz); H2D(r->d_noise, noise, (size_t)T_max * Bz * 3);
+    r->has_par = !par_rows.empty();                             // the snapshot: lmpc_plant_set_params during the session reaches the next one only
+    if (r->has_par) H2D(r->d_par, par_rows.data(), par_rows.size());
     HIPCHK(hipMemsetAsync(r->d_uOld, 0, sizeof(double) * Bz * 2, c->stream)); HIPCHK(hipMemsetAsync(r->d_xPP, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
     HIPCHK(hipMemsetAsync(r->d_hasPred, 0, sizeof(int) * Bz, c->stream)); HIPCHK(hipMemsetAsync(r->d_tstep, 0, sizeof(int) * Bz, c->stream));
     HIPCHK(hipMemsetAsync(r->d_nDone, 0, sizeof(int), c->stream)); HIPCHK(hipMemsetAsync(r->d_stAcc, 0, sizeof(int) * Bz, c->stream));
@@ -1157,7 +1214,7 @@ static void rollout_state(lmpc_rollout_session *r, lmpc_rollout_state &st) {
     st.x = r->d_x; st.xg = r->d_xg; st.xLin = r->d_xLin; st.uLin = r->d_uLin; st.uOld = r->d_uOld; st.zt = r->d_zt; st.xPP = r->d_xPP;
     st.hasPred = r->d_hasPred; st.timeStep = r->d_tstep; st.doneAt = r->d_done; st.xPred = r->d_xPred; st.uPred = r->d_uPred; st.ztNext = r->d_ztN; st.ztuNext = r->d_ztuN;
     st.status = r->d_status; st.logX = r->d_logX; st.logU = r->d_logU; st.logG = r->d_logG; st.noise = r->d_noise; st.nDone = r->d_nDone; st.statusAcc = r->d_stAcc;
-    st.finX = r->d_finX; st.finG = r->d_finG;
+    st.finX = r->d_finX; st.finG = r->d_finG; st.plantPar = r->d_par;
 }
 extern "C" {
 int lmpc_rollout_begin(lmpc_ctx *c, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
@@ -1226,8 +1283,9 @@ int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const doub
     }
     if (e != hipSuccess) return fail(set_err(LMPC_E_HIP, "lmpc_rollout_pid", hipGetErrorString(e)));
     lmpc_rollout_state st; rollout_state(r, st);
-    hipLaunchKernelGGL(lmpc_pid_rollout_kernel, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0,
-                       (const double *)r->d_vt, (const double *)r->d_noiseU, st);
+    const dim3 grid((B + PLANT_CARS - 1) / PLANT_CARS);
+    if (r->has_par) hipLaunchKernelGGL(lmpc_pid_rollout_kernel<true>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0, (const double *)r->d_vt, (const double *)r->d_noiseU, st);
+    else hipLaunchKernelGGL(lmpc_pid_rollout_kernel<false>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0, (const double *)r->d_vt, (const double *)r->d_noiseU, st);
     e = hipGetLastError();
     std::vector<int> done(Bz);
     if (e == hipSuccess) e = hipMemcpyAsync(done.data(), r->d_done, sizeof(int) * Bz, hipMemcpyDeviceToHost, c->stream);
@@ -1272,7 +1330,8 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         rc = launch_solve(c, B, io, true); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
         HIPCHK(hipEventRecord(r->e_solved, c->stream));
         HIPCHK(hipStreamWaitEvent(r->pstream, r->e_solved, 0));
-        hipLaunchKernelGGL(lmpc_rollout_plant_kernel, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
+        if (r->has_par) hipLaunchKernelGGL(lmpc_rollout_plant_kernel<true>, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
+        else hipLaunchKernelGGL(lmpc_rollout_plant_kernel<false>, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
         HIPCHK(hipEventRecord(r->e_plant, r->pstream));
         if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->d_uPred, r->d_uOld);
         else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression

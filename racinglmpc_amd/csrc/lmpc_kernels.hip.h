@@ -2314,10 +2314,17 @@ __device__ __forceinline__ double plant_curvature(const lmpc_dev_params &p, doub
 struct plant_lds { double v[2][PLANT_CARS][3]; };
 // every thread of the work-group must call this (barriers inside); `on` = this lane's car exists.  Wave 1's lanes return the new state in xn / xgn
 // (both lanes of a pair hold the same values); wave 0's return nothing.
+// PAR = false: the reference's vehicle (SysModel.py:60-70) as literals.  PAR = true: the car's own ten constants, par[LMPC_PLANT_NPAR] = m, lf, lr, Iz, Df, Cf, Bf,
+// Dr, Cr, Br, read ONCE before the sub-steps into vector registers (they are per-lane values): wave 0 keeps lf, lr, 1 / m, 1 / Iz and the D, C, B of ITS tyre -- lane
+// `role` 0 the front one, lane 1 the rear one --, seven doubles; wave 1 integrates the velocities only and reads none.  The reference writes 1 / m * Fyf * ..., left to
+// right: (1 / m) is a value of its own there, so dividing once in front of the loop gives the same bits (IEEE division: the build has no fast-math flag).  The rear
+// slip angle uses lf, as the reference does (SysModel.py:97); lr enters the yaw equation only (:106).  The guards test the computed arguments, so a car whose B or C
+// pushes one out of the fast range takes the ocml routines like a sliding car.
+template <bool PAR>
 __device__ __forceinline__ void plant_step_duo(const lmpc_dev_params &p, plant_lds &L, const double *x, const double *xg, const double *u, const double *nz,
-                                               double *xn, double *xgn, int *bad, const int wave, const int role, const int cl) {
-    const double m = 1.98, lf = 0.125, lr = 0.125, Iz = 0.024;
-    const double Df = 0.8 * m * 9.81 / 2.0, Cf = 1.25, Bf = 1.0;                     // rear tyre: same D, C, B (SysModel.py:68-76)
+                                               double *xn, double *xgn, int *bad, const int wave, const int role, const int cl, const double *par = nullptr) {
+    constexpr double m0 = 1.98, lf0 = 0.125, lr0 = 0.125, Iz0 = 0.024;
+    constexpr double Df0 = 0.8 * m0 * 9.81 / 2.0, Cf0 = 1.25, Bf0 = 1.0;             // rear tyre: same D, C, B (SysModel.py:68-76)
     const double deltaT = 0.001;
     const double delta = u[0], a = u[1];
     plant_coeffs kc; kc.load();
@@ -2325,6 +2332,11 @@ __device__ __forceinline__ void plant_step_duo(const lmpc_dev_params &p, plant_l
         // ---- velocity dynamics: lane `role` 0 the front tyre, 1 the rear tyre ----
         double vx = x[0], vy = x[1], wz = x[2];
         const double sd = sin(delta), cd = cos(delta);
+        double lf = lf0, lr = lr0, rm = 1 / m0, rIz = 1 / Iz0, Dt = Df0, Ct = Cf0, Bt = Bf0;       // Dt, Ct, Bt: this lane's tyre
+        if constexpr (PAR) {
+            const double *ty = par + (role ? 7 : 4);
+            lf = par[1]; lr = par[2]; rm = 1 / par[0]; rIz = 1 / par[3]; Dt = ty[0]; Ct = ty[1]; Bt = ty[2];
+        }
         if (role == 0) { L.v[0][cl][0] = vx; L.v[0][cl][1] = vy; L.v[0][cl][2] = wz; }
         PLANT_BARRIER();
 #pragma unroll 1
@@ -2334,18 +2346,18 @@ __device__ __forceinline__ void plant_step_duo(const lmpc_dev_params &p, plant_l
             double zq = yq * rvx; zq = fma(fma(-zq, vx, yq), rvx, zq);   // yq / vx to ~1 ulp
             double at = plant_atan_poly(kc, zq);
             double alpha = role ? -at : delta - at;                  // alpha_r = -atan2(vy - lf wz, vx), alpha_f = delta - atan2(vy + lf wz, vx)
-            const double ba = Bf * alpha;
-            const double xs = Cf * plant_atan_poly(kc, ba);
-            double F = Df * plant_sin1_poly(kc, xs);
+            const double ba = Bt * alpha;
+            const double xs = Ct * plant_atan_poly(kc, ba);
+            double F = Dt * plant_sin1_poly(kc, xs);
             if (!(vx > 0.0 && fabs(yq) <= vx && fabs(ba) <= 1.0 && fabs(xs) <= 1.0)) {      // a sliding or diverged car: the general routines
                 at = atan2(yq, vx); alpha = role ? -at : delta - at;
-                F = Df * sin(Cf * atan(Bf * alpha));
+                F = Dt * sin(Ct * atan(Bt * alpha));
             }
             const double Fo = dpp_mov<DPP_QP_X1>(F);
             const double Fyf = role ? Fo : F, Fyr = role ? F : Fo;
-            const double nvx = vx + deltaT * (a - 1 / m * Fyf * sd + wz * vy);
-            const double nvy = vy + deltaT * (1 / m * (Fyf * cd + Fyr) - wz * vx);
-            const double nwz = wz + deltaT * (1 / Iz * (lf * Fyf * cd - lr * Fyr));
+            const double nvx = vx + deltaT * (a - rm * Fyf * sd + wz * vy);
+            const double nvy = vy + deltaT * (rm * (Fyf * cd + Fyr) - wz * vx);
+            const double nwz = wz + deltaT * (rIz * (lf * Fyf * cd - lr * Fyr));
             vx = nvx; vy = nvy; wz = nwz;
             if (role == 0) { double *d_ = L.v[(i + 1) & 1][cl]; d_[0] = vx; d_[1] = vy; d_[2] = wz; }
             PLANT_BARRIER();
@@ -2385,14 +2397,16 @@ __device__ __forceinline__ void plant_step_duo(const lmpc_dev_params &p, plant_l
     }
 }
 
+// PAR (here and in the two rollout kernels below): car b integrates with row b of par (B x LMPC_PLANT_NPAR) instead of the reference's vehicle; see plant_step_duo.
+template <bool PAR>
 __global__ __launch_bounds__(PLANT_NT) void lmpc_plant_kernel(lmpc_dev_params p, int B, const double *__restrict__ x, const double *__restrict__ xg, const double *__restrict__ u,
-                                  const double *__restrict__ nz, double *__restrict__ xn, double *__restrict__ xgn, int *__restrict__ status) {
+                                  const double *__restrict__ nz, double *__restrict__ xn, double *__restrict__ xgn, int *__restrict__ status, const double *__restrict__ par) {
     __shared__ plant_lds L;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, cl = lane >> 1, role = lane & 1;
     const int b0 = blockIdx.x * PLANT_CARS + cl; const bool on = b0 < B; const int b = on ? b0 : B - 1;      // (a lane without a car repeats the last one: barriers inside)
     int bad = 0;
     double xo[6], go[6];
-    plant_step_duo(p, L, x + (size_t)b * 6, xg + (size_t)b * 6, u + (size_t)b * 2, nz + (size_t)b * 3, xo, go, &bad, wave, role, cl);
+    plant_step_duo<PAR>(p, L, x + (size_t)b * 6, xg + (size_t)b * 6, u + (size_t)b * 2, nz + (size_t)b * 3, xo, go, &bad, wave, role, cl, PAR ? par + (size_t)b * LMPC_PLANT_NPAR : nullptr);
     if (wave == 1 && role == 0 && on) {
         for (int j = 0; j < 6; j++) { xn[(size_t)b * 6 + j] = xo[j]; xgn[(size_t)b * 6 + j] = go[j]; }
         if (status) status[b] = bad ? LMPC_ST_NO_SEGMENT : 0;
@@ -2406,6 +2420,7 @@ struct lmpc_rollout_state {
     const double *xPred, *uPred, *ztNext, *ztuNext; const int *status;                        // outputs of the step just taken
     double *logX, *logU, *logG; const double *noise; int *nDone, *statusAcc;                   // logs [T][B][..], noise [T][B][3]
     double *finX, *finG;                                                                       // state right after the crossing step
+    const double *plantPar;                                                                    // B x LMPC_PLANT_NPAR, the session's snapshot of the per-car vehicle constants (PAR kernels only)
 };
 // The step's bookkeeping and its plant integration are two kernels on two streams: the shift of the linearisation trajectory
 // feeds the NEXT step's regression kernel, which does not need the plant's result and runs concurrently with it; only the next
@@ -2433,6 +2448,7 @@ __global__ __launch_bounds__(256) void lmpc_rollout_shift_kernel(lmpc_dev_params
     }
     if (e == 0) { r.hasPred[b] = 1; r.timeStep[b] = t + 1; }
 }
+template <bool PAR>
 __global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_params p, int B, int t, lmpc_rollout_state r) {
     __shared__ plant_lds L;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, cl = lane >> 1, role = lane & 1;     // two waves per 32 cars, see plant_step_duo
@@ -2447,7 +2463,7 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_p
         r.logU[((size_t)t * B + b) * 2] = u0[0]; r.logU[((size_t)t * B + b) * 2 + 1] = u0[1];
     }
     int bad = 0; double xo[6], go[6];
-    plant_step_duo(p, L, x, xg, u0, r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl);
+    plant_step_duo<PAR>(p, L, x, xg, u0, r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl, PAR ? r.plantPar + (size_t)b * LMPC_PLANT_NPAR : nullptr);
     if (writer) {
         for (int j = 0; j < 6; j++) { x[j] = xo[j]; xg[j] = go[j]; }
         // status bits count only up to and including the step that crosses the line: a finished car keeps being simulated until
@@ -2481,6 +2497,7 @@ __device__ __forceinline__ void pid_control_law(const double *x, double vt, cons
     u0 = -0.6 * x[5] - 0.9 * x[3] + c0;
     u1 = 1.5 * (vt - x[0]) + c1;
 }
+template <bool PAR>
 __global__ __launch_bounds__(PLANT_NT) void lmpc_pid_rollout_kernel(lmpc_dev_params p, int B, int T_max, int stop_at_line, const double *__restrict__ vt,
                                                                     const double *__restrict__ noise_u /* T_max x B x 2 */, lmpc_rollout_state r) {
     __shared__ plant_lds L;
@@ -2503,7 +2520,7 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_pid_rollout_kernel(lmpc_dev_par
         }
         __syncthreads();
         int bad = 0; double xo[6], go[6];
-        plant_step_duo(p, L, sx[cl], sg[cl], su[cl], r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl);
+        plant_step_duo<PAR>(p, L, sx[cl], sg[cl], su[cl], r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl, PAR ? r.plantPar + (size_t)b * LMPC_PLANT_NPAR : nullptr);
         if (keeper) {
             for (int j = 0; j < 6; j++) { sx[cl][j] = xo[j]; sg[cl][j] = go[j]; }
             if (done < 0) {

@@ -19,8 +19,11 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True):
-        """global_noise: the plant noise of a lap is drawn for ALL rollouts of the job (same seed on every rank) and this rank keeps the columns
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None):
+        """plant_params: vehicle constants of the cars of THIS object (this rank's shard), rows of _capi.PLANT_PARAM_NAMES as _capi.plant_params builds them -- one row
+        for all cars or one per car; handed to the context (Context.plant_set_params) before every begin, run_pid_laps and run_mpc_laps.  None: the context's
+        parameters are left as they are (the reference's vehicle unless the caller set others).
+        global_noise: the plant noise of a lap is drawn for ALL rollouts of the job (same seed on every rank) and this rank keeps the columns
         of its shard (`noise_shard` = (lo, hi, total), set by LmpcGeneration) -- a rollout then sees the same draws however the job is split over
         ranks.  Default: every rank draws for its own shard only (seed per rank)."""
         self.ctx, self.track = ctx, np.asarray(track, float)
@@ -29,6 +32,7 @@ class BatchedRollouts:
         self.global_noise, self.noise_shard = bool(global_noise), None
         self.last_status = None
         self.last_done = None
+        self.plant_params = None if plant_params is None else _capi.check_plant_params(plant_params)
         self.prefetch = bool(prefetch) # False: every array is drawn when it is asked for, no worker thread (same draws, same order: tests compare the two)
         self._pre = None               # (shape key, generator state before the draw, future): the NEXT lap's plant noise, drawn by a worker thread while this lap runs
 
@@ -92,6 +96,15 @@ class BatchedRollouts:
         if wait and self._pre is not None:
             self._pre[2].result()
 
+    def _apply_plant_params(self, B):
+        """The vehicle rows of this object's cars go to the context in front of a session (the session takes its snapshot when it begins)."""
+        par = getattr(self, "plant_params", None)      # (objects built without __init__ -- tests/test_host_checks.py -- have none)
+        if par is None:
+            return
+        if par.shape[0] not in (1, B):
+            raise ValueError("plant_params: one row or one per car (%d) expected, got %d" % (B, par.shape[0]))
+        self.ctx.plant_set_params(par)
+
     @staticmethod
     def _per_rollout(a, B):
         a = np.asarray(a, float)
@@ -101,6 +114,7 @@ class BatchedRollouts:
         B = x0.shape[0]
         xl = self._per_rollout(xLin0, B); ul = self._per_rollout(uLin0, B)
         noise = self._draw_noise(max_steps, B)
+        self._apply_plant_params(B)
         self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, noise)
 
     def run_lap_device(self, x0, xLin0, uLin0, xglob0=None, max_steps=400, ext=0, on_ext=None, keep_invalid=False):
@@ -151,6 +165,7 @@ class BatchedRollouts:
         x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1)) if x0 is None else np.asarray(x0, float)
         noise_u = self._draw_noise(max_steps, B, width=2)
         noise = self._draw_noise(max_steps, B)
+        self._apply_plant_params(B)
         t, _ = self.ctx.rollout_pid(x0, x0, vt, noise_u, noise, stop_at_line=stop_at_line)
         out = self.ctx.rollout_fetch(0, t)
         self.ctx.rollout_end()
@@ -162,6 +177,7 @@ class BatchedRollouts:
         context's regression store.  Generator consumption: one plant-noise draw (max_steps, nb, 3).  Returns lap tuples as run_pid_laps does."""
         x0 = np.asarray(x0, float); nb = x0.shape[0]
         noise = self._draw_noise(max_steps, nb)
+        self._apply_plant_params(nb)
         if A is not None:
             self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line)
         else:
@@ -186,7 +202,7 @@ def mpc_stage_config(track, N, vt, max_batch, trToUse=1, device=0):
                              trackLength=float(track[-1, 3] + track[-1, 4]), max_batch=int(max_batch), device=int(device))
 
 
-def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None):
+def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None):
     """main.py:61-95 for B cars without a host round trip inside a lap: PID laps -> one LTI model per car (batched Utilities.Regression, lamb = 1e-7) -> LTI-MPC laps,
     car b on its own (A_b, B_b) -> LTV-MPC laps.  vt: the PID target speed, one value (main.py:50) or one per car; the MPC stages track vt_mpc (default: vt, or the
     mean of the per-car values).  Every stage runs max_steps steps from x0 = [0.5, 0, 0, 0, 0, 0] like the reference's multiLap simulator (main.py:45, 57).
@@ -195,6 +211,9 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None):
     first among equals -- the local regression weighs stored points by their distance to the linearisation point, so laps driven near the speed the MPC tracks
     are the data it uses, and four is what main.py:102-104 gives the LMPC's model.  Every rollout starts its linearisation from the first N + 1 rows of the LAST
     stored lap (MPC.__init__, PredictiveControllers.py:88-90).  With B = 1 that is the car's own single PID lap, main.py:88-89.
+
+    plant_params: vehicle constants (one row, or one per car; _capi.plant_params) of all three stages -- car b drives the same vehicle in its PID, LTI-MPC and LTV-MPC
+    lap; None: the reference's vehicle.
 
     One generator seeded with `seed` feeds all stages in the order PID control-law noise, PID plant noise, LTI-MPC plant noise, LTV-MPC plant noise.
     Returns dict(pid=, mpc=, ltvmpc= lists of lap tuples (x, u, x_glob, final12, done_at, status) with every car in it, flagged or not -- check `status` and
@@ -205,7 +224,11 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None):
     vt_mpc = float(vt.mean()) if vt_mpc is None else float(vt_mpc)
     n_store = min(B, BOOTSTRAP_STORE_LAPS)
     ctx = _capi.Context(mpc_stage_config(track, N, vt_mpc, B, trToUse=n_store, device=device))
-    ro = BatchedRollouts(ctx, track, seed=seed)
+    try:
+        ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params)
+    except Exception:
+        ctx.close()
+        raise
     try:
         x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1))
         pid = ro.run_pid_laps(vt, x0, max_steps=max_steps, keep_invalid=True)
@@ -237,7 +260,11 @@ class LmpcGeneration:
     safe set of every rank in identical order.  Generation g+1 starts its rollouts from the states in which those K laps crossed
     the finish line (the reference's xF, SysModel.py:50), and the first `ext` steps of the rollout continuing lap k extend stored
     lap k past the finish line -- the batched form of LMPC.addPoint (:466-474), without which no safe-set point lies beyond the
-    line and the terminal constraint would stop the cars in front of it."""
+    line and the terminal constraint would stop the cars in front of it.
+
+    The rollouts may drive different vehicles (BatchedRollouts(plant_params=...): rows for the cars of the rank's shard).  The safe set and the regression store
+    stay SHARED: a lap driven by one vehicle then serves as terminal set and as regression data for the others.  Whether that is wanted -- robustness of a
+    learned safe set against model mismatch -- or not is the caller's decision; nothing here keeps vehicles apart."""
 
     def __init__(self, rollouts, total_rollouts, K=4, T_max=400, ext=40, comm=None):
         self.ro, self.total, self.K, self.T_max, self.ext = rollouts, total_rollouts, K, T_max, ext

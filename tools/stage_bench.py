@@ -7,7 +7,10 @@
 One JSON line: per batch size (default 1, 256, 1024; N = 12) simulated steps/s of both ways (car-steps: B x T / seconds; for the MPC stages that is also the rate of
 closed-loop QP solves) and the seconds behind them.  Wall clock around work that ends in a drained stream (the session's fetch, the host loop's last download), uploads
 of start states and noise included on both sides; every shape is run once untimed first, then `--repeats` times alternating the two ways, medians reported.  Both ways
-are fed the same draws, and the tool checks that their logs are equal bit for bit before it reports a time.  --out also writes the line to a file."""
+are fed the same draws, and the tool checks that their logs are equal bit for bit before it reports a time.  --out also writes the line to a file.
+
+--plant-params: every batch size is measured a second time with per-car vehicle constants in force (Context.plant_set_params: all ten constants of every car scaled
+by U(0.9, 1.1), generator seeded with 7) -- the per-car instantiations of the plant kernels beside the nominal ones; those rows carry "plant_params": true."""
 import argparse
 import json
 import os
@@ -26,10 +29,12 @@ def pid_u(x, vt, nu):
     return np.stack([-0.6 * x[:, 5] - 0.9 * x[:, 3] + np.clip(nu[:, 0] * 0.25, -0.9, 0.9), 1.5 * (vt - x[:, 0]) + np.clip(nu[:, 1] * 0.10, -0.2, 0.2)], axis=1)
 
 
-def run_stage(stage, g, B, T):
+def run_stage(stage, g, B, T, plant_params=False):
     from racinglmpc_amd import _capi, rollout
     N = 12
     ctx = _capi.Context(rollout.mpc_stage_config(g["track"], N, 0.8, B, trToUse=1))
+    if plant_params:
+        ctx.plant_set_params(_capi.plant_params_default()[None] * np.random.default_rng(7).uniform(0.9, 1.1, (B, _capi.PLANT_NPAR)))
     rng = np.random.default_rng(7)
     noise = rng.standard_normal((T, B, 3)); nu = rng.standard_normal((T, B, 2))
     x0 = np.tile(X0, (B, 1)); x0[:, 5] = np.linspace(-0.1, 0.1, B) if B > 1 else 0.0
@@ -81,6 +86,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 256, 1024])
     ap.add_argument("--steps", type=int, default=0, help="simulated steps per lap (default: 400 for pid, 100 for the MPC stages)")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--plant-params", action="store_true", help="also measure every batch size with per-car vehicle constants (+-10 % around the reference's, seed 7)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -89,8 +95,8 @@ def main():
     g = common.load_lmpc_golden()
     T = args.steps or (400 if args.stage == "pid" else 100)
     rows = []
-    for B in args.batches:
-        ctx, device, host = run_stage(args.stage, g, B, T)
+    for B, par in [(B, par) for B in args.batches for par in ([False, True] if args.plant_params else [False])]:
+        ctx, device, host = run_stage(args.stage, g, B, T, plant_params=par)
         d, h = device(), host()                                        # untimed: code objects, session buffers, pooled scratch
         same = all(np.array_equal(a, b) for a, b in zip(d, h))
         td, th = [], []
@@ -99,7 +105,7 @@ def main():
             t0 = time.perf_counter(); host(); th.append(time.perf_counter() - t0)
         ctx.close()
         sd, sh = float(np.median(td)), float(np.median(th))
-        rows.append(dict(B=B, steps=T, device_s=sd, host_stepped_s=sh, device_steps_per_s=B * T / sd, host_stepped_steps_per_s=B * T / sh,
+        rows.append(dict(B=B, steps=T, plant_params=par, device_s=sd, host_stepped_s=sh, device_steps_per_s=B * T / sd, host_stepped_steps_per_s=B * T / sh,
                          device_s_all=td, host_stepped_s_all=th, logs_bit_identical=bool(same)))
     line = dict(tool="stage_bench", stage=args.stage, N=12, unit="car-steps per second of wall time" + ("" if args.stage == "pid" else " = closed-loop QP solves per second"),
                 results=rows)
