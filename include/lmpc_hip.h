@@ -218,11 +218,37 @@ int lmpc_plant_set_params(lmpc_ctx *, int n, const double *par /*n x 10, or NULL
          * is allowed and reaches the next session only; kept session buffers of the same shape are reused whatever the parameters */
 int lmpc_plant_get_params(lmpc_ctx *, int *n, double *par /*capacity rows x 10, or NULL*/, int capacity);
         /* the rows in force (n = 0: the reference's vehicle, SysModel.py:60-70); par receives min(n, capacity) rows */
+
+/* Counter-based N(0,1) draws generated on the device.  The reference has no counterpart beyond np.random.randn() at SysModel.py:139-141 (plant) and
+ * Utilities.py:67-68 (PID control law).  The draw for (seed, stream, lap, t, car) is a pure function of those five numbers: its four 64-bit words are what
+ * numpy.random.Philox(counter=[t, car, lap, stream], key=[seed, 0]).random_raw(4) returns (Philox4x64-10; NumPy increments word 0 of the counter before its first
+ * block, so the block function runs on [t + 1, car, lap, stream]); Box-Muller in FP64 turns the pairs (w0, w1), (w2, w3) into z0, z1 and z2, z3:
+ * u1 = ((w0 >> 11) + 1) 2^-53, u2 = (w1 >> 11) 2^-53, r = sqrt(-2 log u1), z0 = r cos(2 pi u2), z1 = r sin(2 pi u2).  stream 0: plant noise (width 3: z0, z1, z2);
+ * stream 1: control-law noise of a PID lap (width 2: z0, z1).  car: the GLOBAL rollout index; t: the simulated step; lap: a session counter the caller chooses. */
+int lmpc_noise_raw(lmpc_ctx *, unsigned long long seed, unsigned long long stream, unsigned long long lap, long long t0, int T, long long car0, int B,
+                   unsigned long long *words /*host, T x B x 4*/);
+        /* the four raw words of steps t0 .. t0 + T - 1 and cars car0 .. car0 + B - 1 (checks of the block function and its addressing).  No reference counterpart beyond
+         * np.random.randn() at SysModel.py:139-141 and Utilities.py:67-68.  LMPC_E_ARG for T < 1, B < 1, t0 < 0 or car0 < 0 */
+int lmpc_noise_fill(lmpc_ctx *, unsigned long long seed, unsigned long long stream, unsigned long long lap, long long t0, int T, long long car0, int B,
+                    int width /*2 or 3*/, double *out /*host, T x B x width*/);
+        /* the normal draws of the same range, in the layout of the `noise` / `noise_u` arguments below: out[((t - t0) B + b) width + j].  No reference counterpart beyond
+         * np.random.randn() at SysModel.py:139-141 and Utilities.py:67-68.  LMPC_E_ARG for width outside {2, 3}, T < 1, B < 1, t0 < 0 or car0 < 0 */
+int lmpc_rollout_set_noise(lmpc_ctx *, int on, unsigned long long seed, unsigned long long lap, long long car0);
+        /* the noise source of later sessions on this context.  No reference counterpart beyond np.random.randn() at SysModel.py:139-141 and Utilities.py:67-68.
+         * on != 0: lmpc_rollout_begin, lmpc_rollout_begin_mpc and lmpc_rollout_pid accept noise = NULL (lmpc_rollout_pid also noise_u = NULL) and then fill the session's
+         * buffer on the device, on the context's stream in front of the first step: steps 0 .. T_max - 1, cars car0 .. car0 + B - 1, `lap` as given, stream 0 (noise) /
+         * stream 1 (noise_u) -- no host draw, no host-to-device copy of noise.  A non-NULL array is used exactly as without this call.  on == 0 (the state after
+         * lmpc_create): a NULL array is LMPC_E_ARG and every path returns the bits it returned before this entry point existed.  A session takes (seed, lap, car0) when it
+         * begins, as it does the vehicle rows: setting the source while a session is active reaches the next session only.  The library never advances `lap` on its own.
+         * LMPC_E_ARG for car0 < 0 */
+int lmpc_rollout_get_noise(lmpc_ctx *, int *on, unsigned long long *seed, unsigned long long *lap, long long *car0);
+        /* what lmpc_rollout_set_noise left in force (on = 0 after lmpc_create); any pointer may be NULL.  No reference counterpart beyond np.random.randn() at
+         * SysModel.py:139-141 and Utilities.py:67-68 */
 int lmpc_rollout_begin(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/,
-                       const double *xLin0 /*B x (N+1) x 6*/, const double *uLin0 /*B x N x 2*/, const double *noise /*T_max x B x 3*/);
+                       const double *xLin0 /*B x (N+1) x 6*/, const double *uLin0 /*B x N x 2*/, const double *noise /*T_max x B x 3, or NULL: lmpc_rollout_set_noise*/);
 int lmpc_rollout_begin_mpc(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/,
                            const double *xLin0 /*B x (N+1) x 6 or NULL*/, const double *uLin0 /*B x N x 2 or NULL*/,
-                           const double *A_lti /*B x 6 x 6 or NULL*/, const double *B_lti /*B x 6 x 2 or NULL*/, const double *noise /*T_max x B x 3*/, int stop_at_line);
+                           const double *A_lti /*B x 6 x 6 or NULL*/, const double *B_lti /*B x 6 x 2 or NULL*/, const double *noise /*T_max x B x 3, or NULL: lmpc_rollout_set_noise*/, int stop_at_line);
         /* Simulator.sim with one plain MPC per rollout (main.py:72-95; MPC.solve, PredictiveControllers.py:110-137), state resident on the device.  Valid only on a
          * context with numSS_it == 0 (lmpc_rollout_begin keeps refusing those), B <= max_batch, no session active.  A_lti / B_lti given: the LTI path-following MPC on the
          * model of Utilities.Regression (main.py:74-82) -- rollout b solves with A_b, B_b at every stage and C = 0 (buildEqConstr :216-218); xLin0 / uLin0 are not used.
@@ -232,7 +258,7 @@ int lmpc_rollout_begin_mpc(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 
          * doneAt still the first crossing.  lmpc_rollout_run / _fetch / _end / _release, lmpc_debug_rollout_peek and lmpc_debug_rollout_qp (selection outputs NULL)
          * work on the session as on one of lmpc_rollout_begin */
 int lmpc_rollout_pid(lmpc_ctx *, int B, int T_max, const double *x0 /*B x 6*/, const double *xglob0 /*B x 6*/, const double *vt /*B*/,
-                     const double *noise_u /*T_max x B x 2 N(0,1) draws*/, const double *noise /*T_max x B x 3*/, int stop_at_line, int *steps_total, int *n_done);
+                     const double *noise_u /*T_max x B x 2 N(0,1) draws, or NULL: lmpc_rollout_set_noise*/, const double *noise /*T_max x B x 3, or NULL*/, int stop_at_line, int *steps_total, int *n_done);
         /* Simulator.sim driven by Utilities.PID (main.py:61-70; PID.solve, fnc/Utilities.py:60-67: u0 = -0.6 ey - 0.9 epsi + clip(0.25 n0, +-0.9),
          * u1 = 1.5 (vt - vx) + clip(0.10 n1, +-0.2)) for B cars, the whole lap in ONE kernel launch: begins a session, runs it to the end (all T_max steps; with
          * stop_at_line a car is logged up to its crossing step only), and leaves it active for lmpc_rollout_fetch / _end.  Needs only the track: valid on any context

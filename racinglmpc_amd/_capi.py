@@ -57,7 +57,7 @@ EXPORTS = [
     "lmpc_dev_alloc", "lmpc_dev_free", "lmpc_dev_upload", "lmpc_dev_download", "lmpc_dev_sync", "lmpc_step_batch_dev",
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
-    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_global_position_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
+    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -86,7 +86,13 @@ def load():
         lib.lmpc_rollout_begin_mpc.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int]
         lib.lmpc_rollout_pid.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.lmpc_lti_regression_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 4
-        for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch):
+        # (device noise: 64-bit seeds, laps and car indices must not pass through ctypes' default int conversion)
+        lib.lmpc_noise_raw.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_void_p]
+        lib.lmpc_noise_fill.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p]
+        lib.lmpc_rollout_set_noise.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_longlong]
+        lib.lmpc_rollout_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)]
+        for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
+                  lib.lmpc_rollout_get_noise):
             f.restype = C.c_int
         _lib = lib
     return _lib
@@ -489,18 +495,63 @@ class Context:
             _chk(self.lib.lmpc_plant_get_params(self._h, C.byref(n), _d(par), C.c_int(par.shape[0])))
         return par
 
-    def rollout_begin(self, x0, xglob0, xLin0, uLin0, noise):
-        x0 = _f64(x0); xg = _f64(xglob0); xl = _f64(xLin0); ul = _f64(uLin0); nz = _f64(noise)
-        B = x0.shape[0]
-        assert xl.shape == (B, self.N + 1, 6) and ul.shape == (B, self.N, 2) and nz.shape[1:] == (B, 3)
-        self._ro = (B, nz.shape[0]); self._ro_t = 0
-        _chk(self.lib.lmpc_rollout_begin(self._h, C.c_int(B), C.c_int(nz.shape[0]), _d(x0), _d(xg), _d(xl), _d(ul), _d(nz)))
+    # ---- counter-based noise generated on the device (lmpc_noise_*, lmpc_rollout_set_noise; csrc/lmpc_noise.hip.h)
+    def noise_raw(self, seed, stream, lap, t0, T, car0, B):
+        """The four raw 64-bit words of steps t0 .. t0 + T - 1 and cars car0 .. car0 + B - 1, (T, B, 4) uint64: row [t - t0, b] is what
+        numpy.random.Philox(counter=[t, car0 + b, lap, stream], key=[seed, 0]).random_raw(4) returns (lmpc_noise_raw)."""
+        T = int(T); B = int(B)
+        out = np.zeros((max(T, 0), max(B, 0), 4), np.uint64)
+        _chk(self.lib.lmpc_noise_raw(self._h, int(seed), int(stream), int(lap), int(t0), T, int(car0), B, out.ctypes.data))
+        return out
 
-    def rollout_begin_mpc(self, x0, xglob0, noise, xLin0=None, uLin0=None, A=None, B=None, stop_at_line=False):
+    def noise_fill(self, seed, stream, lap, t0, T, car0, B, width=3):
+        """The N(0, 1) draws of the same range, (T, B, width) float64 (lmpc_noise_fill): stream 0 / width 3 is the plant noise a session with the device source on sees
+        at step t for global car index car0 + b, stream 1 / width 2 the control-law noise of a PID lap."""
+        T = int(T); B = int(B); width = int(width)
+        out = np.zeros((max(T, 0), max(B, 0), max(width, 0)))
+        _chk(self.lib.lmpc_noise_fill(self._h, int(seed), int(stream), int(lap), int(t0), T, int(car0), B, width, out.ctypes.data))
+        return out
+
+    def rollout_set_noise(self, on, seed=0, lap=0, car0=0):
+        """Noise source of the sessions begun after this call (lmpc_rollout_set_noise).  on: rollout_begin / rollout_begin_mpc / rollout_pid take noise=None (rollout_pid
+        also noise_u=None) and the session's draws are generated on the device for steps 0 .. T_max - 1 and global car indices car0 .. car0 + B - 1 of session `lap`;
+        an array given is used as it is.  off (a new context): noise=None is refused."""
+        _chk(self.lib.lmpc_rollout_set_noise(self._h, 1 if on else 0, int(seed), int(lap), int(car0)))
+
+    def rollout_get_noise(self):
+        """(on, seed, lap, car0) in force (lmpc_rollout_get_noise)."""
+        on = C.c_int(); seed = C.c_ulonglong(); lap = C.c_ulonglong(); car0 = C.c_longlong()
+        _chk(self.lib.lmpc_rollout_get_noise(self._h, C.byref(on), C.byref(seed), C.byref(lap), C.byref(car0)))
+        return bool(on.value), int(seed.value), int(lap.value), int(car0.value)
+
+    @staticmethod
+    def _session_noise(noise, nb, width, T_max):
+        """(array or None, T_max) of a session's noise argument: an array (T_max, nb, width), or None with T_max given -- the device source (rollout_set_noise)."""
+        if noise is None:
+            if T_max is None:
+                raise ValueError("noise=None (the device source, rollout_set_noise) needs T_max")
+            return None, int(T_max)
+        nz = _f64(noise)
+        assert nz.ndim == 3 and nz.shape[1:] == (nb, width) and (T_max is None or int(T_max) == nz.shape[0]), (nz.shape, nb, width, T_max)
+        return nz, nz.shape[0]
+
+    def rollout_begin(self, x0, xglob0, xLin0, uLin0, noise, T_max=None):
+        """noise: (T_max, B, 3) N(0, 1) draws, or None with T_max given: the device source (rollout_set_noise; NULL goes to the library, which refuses it while the
+        source is off)."""
+        x0 = _f64(x0); xg = _f64(xglob0); xl = _f64(xLin0); ul = _f64(uLin0)
+        B = x0.shape[0]
+        nz, T = self._session_noise(noise, B, 3, T_max)
+        assert xl.shape == (B, self.N + 1, 6) and ul.shape == (B, self.N, 2)
+        _chk(self.lib.lmpc_rollout_begin(self._h, C.c_int(B), C.c_int(T), _d(x0), _d(xg), _d(xl), _d(ul), _d(nz)))
+        self._ro = (B, T); self._ro_t = 0
+
+    def rollout_begin_mpc(self, x0, xglob0, noise, xLin0=None, uLin0=None, A=None, B=None, stop_at_line=False, T_max=None):
         """Session of B plain-MPC laps on a numSS_it == 0 context (lmpc_rollout_begin_mpc).  A (B, 6, 6) and B (B, 6, 2) given: the LTI MPC on those models;
-        else the LTV-MPC from the linearisation trajectories xLin0 (B, N + 1, 6), uLin0 (B, N, 2).  noise: (T_max, B, 3)."""
-        x0 = _f64(x0); xg = _f64(xglob0); nz = _f64(noise); nb = x0.shape[0]
-        assert nz.ndim == 3 and nz.shape[1:] == (nb, 3) and xg.shape == x0.shape == (nb, 6)
+        else the LTV-MPC from the linearisation trajectories xLin0 (B, N + 1, 6), uLin0 (B, N, 2).  noise: (T_max, B, 3), or None with T_max given: the device
+        source (rollout_set_noise)."""
+        x0 = _f64(x0); xg = _f64(xglob0); nb = x0.shape[0]
+        nz, T = self._session_noise(noise, nb, 3, T_max)
+        assert xg.shape == x0.shape == (nb, 6)
         lti = A is not None or B is not None
         if lti:
             A = _f64(A); B = _f64(B); xl = ul = None
@@ -509,19 +560,25 @@ class Context:
             xl = _f64(xLin0); ul = _f64(uLin0); A = B = None
             assert xl.shape == (nb, self.N + 1, 6) and ul.shape == (nb, self.N, 2), (xl.shape, ul.shape)
         pa = lambda a: None if a is None else a.ctypes.data
-        _chk(self.lib.lmpc_rollout_begin_mpc(self._h, nb, nz.shape[0], pa(x0), pa(xg), pa(xl), pa(ul), pa(A), pa(B), pa(nz), 1 if stop_at_line else 0))
-        self._ro = (nb, nz.shape[0]); self._ro_t = 0
+        _chk(self.lib.lmpc_rollout_begin_mpc(self._h, nb, T, pa(x0), pa(xg), pa(xl), pa(ul), pa(A), pa(B), pa(nz), 1 if stop_at_line else 0))
+        self._ro = (nb, T); self._ro_t = 0
 
-    def rollout_pid(self, x0, xglob0, vt, noise_u, noise, stop_at_line=False):
+    def rollout_pid(self, x0, xglob0, vt, noise_u, noise, stop_at_line=False, T_max=None):
         """B whole PID laps in one launch (lmpc_rollout_pid): vt (B,) target speeds, noise_u (T_max, B, 2) and noise (T_max, B, 3) N(0, 1) draws of the control law and
-        of the plant.  Returns (steps logged, cars that crossed the line); the session stays open for rollout_fetch / rollout_end."""
+        of the plant -- either or both None with T_max given: the device source (rollout_set_noise).  Returns (steps logged, cars that crossed the line); the session
+        stays open for rollout_fetch / rollout_end."""
         x0 = _f64(x0); xg = _f64(xglob0); nb = x0.shape[0]
-        vt = _f64(np.broadcast_to(np.asarray(vt, float), (nb,))); nu = _f64(noise_u); nz = _f64(noise)
-        assert nz.ndim == 3 and nz.shape[1:] == (nb, 3) and nu.shape == (nz.shape[0], nb, 2) and xg.shape == x0.shape == (nb, 6)
+        vt = _f64(np.broadcast_to(np.asarray(vt, float), (nb,)))
+        if T_max is None:                         # (one array given: it sets the length of the other, generated one)
+            T_max = next((np.shape(a)[0] for a in (noise, noise_u) if a is not None), None)
+        nz, T = self._session_noise(noise, nb, 3, T_max)
+        nu, T = self._session_noise(noise_u, nb, 2, T)
+        assert xg.shape == x0.shape == (nb, 6)
+        pa = lambda a: None if a is None else a.ctypes.data
         t = C.c_int(); nd = C.c_int()
-        _chk(self.lib.lmpc_rollout_pid(self._h, nb, nz.shape[0], x0.ctypes.data, xg.ctypes.data, vt.ctypes.data, nu.ctypes.data, nz.ctypes.data,
+        _chk(self.lib.lmpc_rollout_pid(self._h, nb, T, x0.ctypes.data, xg.ctypes.data, vt.ctypes.data, pa(nu), pa(nz),
                                        1 if stop_at_line else 0, C.byref(t), C.byref(nd)))
-        self._ro = (nb, nz.shape[0]); self._ro_t = t.value
+        self._ro = (nb, T); self._ro_t = t.value
         return t.value, nd.value
 
     def rollout_run(self, max_steps):

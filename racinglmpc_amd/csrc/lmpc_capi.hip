@@ -2,6 +2,7 @@
 // Owns the device lap stores, work buffers, stream and HIP-event timers; launches the kernels of
 // lmpc_kernels.hip.h.  No CPU compute path exists here: if HIP fails, the call fails.
 #include "lmpc_variant.hip.h"
+#include "lmpc_noise.hip.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <algorithm>
@@ -115,6 +116,7 @@ struct lmpc_ctx {
     double *dbg_trace;                       // developer builds (-DLMPC_TRACE): device buffer of the per-iteration side channel, see lmpc_debug_set_trace
     double tr_s[4]; long long tr_n;          // developer trace of lmpc_step_batch's one-QP path (lmpc_debug_step_trace): seconds spent staging / launching / waiting / unstaging
     struct lmpc_rollout_session *ro;
+    int noise_on; unsigned long long noise_seed, noise_lap; long long noise_car0;   // lmpc_rollout_set_noise: sessions begun with noise = NULL fill their buffer on the device (lmpc_noise.hip.h); 0 after lmpc_create
     std::vector<double> plant_par; int plant_n;   // lmpc_plant_set_params: plant_n rows of LMPC_PLANT_NPAR vehicle constants (0: the reference's vehicle, the kernels with the literals)
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     double *ext_rows; size_t ext_rows_bytes;   // staging buffer of lmpc_ss_extend_lap
@@ -173,7 +175,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 102; }
+int lmpc_version(void) { return 103; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -1091,6 +1093,51 @@ int lmpc_plant_get_params(lmpc_ctx *c, int *n, double *par, int capacity) {
     return LMPC_OK;
 }
 
+// ---- counter-based noise (lmpc_noise.hip.h).  No reference counterpart beyond np.random.randn() at SysModel.py:139-141 and Utilities.py:67-68.
+#define NOISE_RANGE_CHK() do { ARGCHK(T >= 1 && B >= 1 && t0 >= 0 && car0 >= 0); ARGCHK(((unsigned long long)T * (unsigned long long)B + LMPC_NOISE_NT - 1) / LMPC_NOISE_NT <= 0x7fffffffull); } while (0)
+int lmpc_noise_raw(lmpc_ctx *c, unsigned long long seed, unsigned long long stream, unsigned long long lap, long long t0, int T, long long car0, int B, unsigned long long *words) {
+    // the four Philox4x64-10 words of every (t, car) of the range: what numpy.random.Philox(counter=[t, car, lap, stream], key=[seed, 0]).random_raw(4) returns
+    ARGCHK(c && words); NOISE_RANGE_CHK();
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t total = (size_t)T * (size_t)B;
+    unsigned long long *d; { void *q; const int rc = pooled_scratch(c, sizeof(unsigned long long) * total * 4, &q); if (rc) return rc; d = (unsigned long long *)q; }
+    hipLaunchKernelGGL(lmpc_noise_raw_kernel, dim3((unsigned)((total + LMPC_NOISE_NT - 1) / LMPC_NOISE_NT)), dim3(LMPC_NOISE_NT), 0, c->stream, seed, stream, lap,
+                       (unsigned long long)t0, T, (unsigned long long)car0, B, d);
+    HIPCHK(hipGetLastError());
+    D2H(words, d, total * 4);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+int lmpc_noise_fill(lmpc_ctx *c, unsigned long long seed, unsigned long long stream, unsigned long long lap, long long t0, int T, long long car0, int B, int width, double *out) {
+    // the N(0, 1) draws of the range, T x B x width, by the kernel that fills a session's buffer (lmpc_rollout_set_noise): same launch, same bits
+    ARGCHK(c && out && (width == 2 || width == 3)); NOISE_RANGE_CHK();
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t total = (size_t)T * (size_t)B;
+    double *d; { void *q; const int rc = pooled_scratch(c, sizeof(double) * total * (size_t)width, &q); if (rc) return rc; d = (double *)q; }
+    lmpc_noise_fill_launch(c->stream, seed, stream, lap, t0, T, car0, B, width, d);
+    HIPCHK(hipGetLastError());
+    D2H(out, d, total * (size_t)width);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+int lmpc_rollout_set_noise(lmpc_ctx *c, int on, unsigned long long seed, unsigned long long lap, long long car0) {
+    // the noise source of the sessions begun after this call (an active session keeps the snapshot it took); needs no device
+    ARGCHK(c && car0 >= 0);
+    c->noise_on = on ? 1 : 0; c->noise_seed = seed; c->noise_lap = lap; c->noise_car0 = car0;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_get_noise(lmpc_ctx *c, int *on, unsigned long long *seed, unsigned long long *lap, long long *car0) {
+    ARGCHK(c);
+    if (on) *on = c->noise_on;
+    if (seed) *seed = c->noise_seed;
+    if (lap) *lap = c->noise_lap;
+    if (car0) *car0 = c->noise_car0;
+    return LMPC_OK;
+}
+
 int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg, const double *u, const double *noise, double *xn, double *xgn, int *status) {
     ARGCHK(c && x && xg && u && noise && xn && xgn && B >= 1);
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -1132,6 +1179,7 @@ struct lmpc_rollout_session {
     int B, T_max, t;
     int kind, stop_at_line;                                     // RO_LMPC / RO_LTV / RO_LTI / RO_PID (what one simulated step launches); 0: the run does not end when every car has crossed the line
     double *d_noiseU, *d_vt;                                    // RO_PID only: controller noise T_max x B x 2, target speed per car
+    unsigned long long nz_seed, nz_lap; long long nz_car0;      // the session's snapshot of the noise source (lmpc_rollout_set_noise), taken when it begins
     double *d_par; bool has_par;                                // the session's snapshot of the per-car vehicle constants (B x LMPC_PLANT_NPAR), taken when it begins; has_par: the PAR kernels run
     hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
     std::vector<void *> keep;
@@ -1194,7 +1242,12 @@ init_state:
     H2D(r->d_x, x0, Bz * 6); H2D(r->d_xg, xg0, Bz * 6); H2D(r->d_zt, ztv.data(), ztv.size());
     if (xLin0) H2D(r->d_xLin, xLin0, Bz * (N + 1) * 6); else HIPCHK(hipMemsetAsync(r->d_xLin, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
     if (uLin0) H2D(r->d_uLin, uLin0, Bz * N * 2); else HIPCHK(hipMemsetAsync(r->d_uLin, 0, sizeof(double) * Bz * N * 2, c->stream));
-    H2D(r->d_done, neg.data(), Bz); H2D(r->d_noise, noise, (size_t)T_max * Bz * 3);
+    H2D(r->d_done, neg.data(), Bz);
+    // the snapshot of the noise source: lmpc_rollout_set_noise during the session reaches the next one only.  noise == NULL (the callers have checked that the source
+    // is on): the buffer the plant kernels read is written by one launch on the context's stream, in front of the first step -- no host draw, no upload
+    r->nz_seed = c->noise_seed; r->nz_lap = c->noise_lap; r->nz_car0 = c->noise_car0;
+    if (noise) H2D(r->d_noise, noise, (size_t)T_max * Bz * 3);
+    else { lmpc_noise_fill_launch(c->stream, r->nz_seed, 0ull, r->nz_lap, 0, T_max, r->nz_car0, B, 3, r->d_noise); HIPCHK(hipGetLastError()); }
     r->has_par = !par_rows.empty();                             // the snapshot: lmpc_plant_set_params during the session reaches the next one only
     if (r->has_par) H2D(r->d_par, par_rows.data(), par_rows.size());
     HIPCHK(hipMemsetAsync(r->d_uOld, 0, sizeof(double) * Bz * 2, c->stream)); HIPCHK(hipMemsetAsync(r->d_xPP, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
@@ -1220,7 +1273,9 @@ extern "C" {
 int lmpc_rollout_begin(lmpc_ctx *c, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
     // B closed-loop LMPC laps, state resident on the device.  xLin0 / uLin0: per-rollout first linearisation trajectories
     // (B x (N+1) x 6, B x N x 2) -- LMPC.addTrajectory :431-433.  noise: T_max x B x 3 N(0,1) draws.
-    ARGCHK(c && x0 && xg0 && xLin0 && uLin0 && noise && B >= 1 && T_max >= 1 && c->cfg.numSS_it > 0);
+    // noise == NULL with lmpc_rollout_set_noise on: the draws are generated on the device (steps 0 .. T_max - 1, cars car0 .. car0 + B - 1, stream 0).
+    ARGCHK(c && x0 && xg0 && xLin0 && uLin0 && B >= 1 && T_max >= 1 && c->cfg.numSS_it > 0);
+    ARGCHK(noise || c->noise_on);                                                           // (no array and no device source)
     return rollout_setup(c, RO_LMPC, 1, B, T_max, x0, xg0, xLin0, uLin0, noise);
 }
 
@@ -1229,7 +1284,8 @@ int lmpc_rollout_begin_mpc(lmpc_ctx *c, int B, int T_max, const double *x0, cons
     // B closed-loop laps of the plain MPC (numSS_it == 0: no terminal set), main.py:72-95.  A_lti / B_lti given (B x 6 x 6, B x 6 x 2): the LTI path-following MPC
     // on the model of Utilities.Regression -- every stage of rollout b uses A_b, B_b and C = 0 (MPC.buildEqConstr, PredictiveControllers.py:216-218), expanded here
     // once; xLin0 / uLin0 are not used.  Both NULL: the LTV-MPC (timeVarying, :110-145) on the regression store, first linearisation trajectories xLin0 / uLin0.
-    ARGCHK(c && x0 && xg0 && noise && B >= 1 && T_max >= 1 && c->cfg.numSS_it == 0);
+    ARGCHK(c && x0 && xg0 && B >= 1 && T_max >= 1 && c->cfg.numSS_it == 0);
+    ARGCHK(noise || c->noise_on);                                                           // (no array and no device source: lmpc_rollout_set_noise)
     ARGCHK((A_lti != nullptr) == (B_lti != nullptr) && (A_lti || (xLin0 && uLin0)));
     ARGCHK(B <= c->cfg.max_batch);
     ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
@@ -1260,7 +1316,9 @@ int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const doub
     // car (B); noise_u: T_max x B x 2 N(0,1) draws of the control law; noise: T_max x B x 3 of the plant.  Needs only the track: valid on any context.  Leaves an
     // active session whose logs lmpc_rollout_fetch returns; lmpc_rollout_run has nothing left to do on it.  steps_total: rows the logs hold (T_max, or with
     // stop_at_line the last crossing step if every car crossed).
-    ARGCHK(c && x0 && xg0 && vt && noise_u && noise && B >= 1 && T_max >= 1 && T_max <= LMPC_PID_MAX_STEPS);
+    // noise / noise_u == NULL with lmpc_rollout_set_noise on: generated on the device, stream 0 into the plant's buffer and stream 1 into the control law's.
+    ARGCHK(c && x0 && xg0 && vt && B >= 1 && T_max >= 1 && T_max <= LMPC_PID_MAX_STEPS);
+    ARGCHK((noise_u && noise) || c->noise_on);                                              // (an array missing and no device source: lmpc_rollout_set_noise)
     ARGCHK(B <= c->cfg.max_batch);
     ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -1274,7 +1332,9 @@ int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const doub
         if (g_malloc(&q, sizeof(double) * ((size_t)T_max * Bz * 2 + Bz)) != hipSuccess) return fail(set_err(LMPC_E_HIP, "hipMalloc", "control-law noise"));
         r->keep.push_back(q); r->d_noiseU = (double *)q; r->d_vt = r->d_noiseU + (size_t)T_max * Bz * 2;
     }
-    hipError_t e = hipMemcpyAsync(r->d_noiseU, noise_u, sizeof(double) * (size_t)T_max * Bz * 2, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipSuccess;
+    if (noise_u) e = hipMemcpyAsync(r->d_noiseU, noise_u, sizeof(double) * (size_t)T_max * Bz * 2, hipMemcpyHostToDevice, c->stream);
+    else { lmpc_noise_fill_launch(c->stream, r->nz_seed, 1ull, r->nz_lap, 0, T_max, r->nz_car0, B, 2, r->d_noiseU); e = hipGetLastError(); }   // (the session's snapshot, as d_noise)
     if (e == hipSuccess) e = hipMemcpyAsync(r->d_vt, vt, sizeof(double) * Bz, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && stop_at_line) {      // rows behind a car's crossing step are not written: a reused session must not show the previous lap's there
         e = hipMemsetAsync(r->d_logX, 0, sizeof(double) * (size_t)T_max * Bz * 6, c->stream);

@@ -19,13 +19,19 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None):
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False):
         """plant_params: vehicle constants of the cars of THIS object (this rank's shard), rows of _capi.PLANT_PARAM_NAMES as _capi.plant_params builds them -- one row
         for all cars or one per car; handed to the context (Context.plant_set_params) before every begin, run_pid_laps and run_mpc_laps.  None: the context's
         parameters are left as they are (the reference's vehicle unless the caller set others).
         global_noise: the plant noise of a lap is drawn for ALL rollouts of the job (same seed on every rank) and this rank keeps the columns
         of its shard (`noise_shard` = (lo, hi, total), set by LmpcGeneration) -- a rollout then sees the same draws however the job is split over
-        ranks.  Default: every rank draws for its own shard only (seed per rank)."""
+        ranks.  Default: every rank draws for its own shard only (seed per rank).
+        device_noise: the disturbance is generated on the device by the counter-based generator of csrc/lmpc_noise.hip.h (Context.rollout_set_noise): the draw of
+        (seed, session, step, GLOBAL car index, component) is a pure function of those numbers, so nothing is drawn or uploaded by the host and a car sees the same
+        disturbance however the job is split over ranks (`noise_shard[0]` is the first global index of this rank's cars; 0 without an LmpcGeneration) -- what global_noise
+        buys with a draw for the whole job on every rank.  `seed` is then an integer in [0, 2**64), the same on every rank; `rng` is never touched, no worker thread is
+        started, prefetch_noise and close have nothing to do; `lap` counts the sessions begun (begin, run_pid_laps, each run_mpc_laps) and is the generator's session
+        counter.  The stream is the device generator's own: it does not reproduce the draws of `rng`."""
         self.ctx, self.track = ctx, np.asarray(track, float)
         self.TL = float(self.track[-1, 3] + self.track[-1, 4])
         self.rng = np.random.default_rng(seed)
@@ -33,6 +39,13 @@ class BatchedRollouts:
         self.last_status = None
         self.last_done = None
         self.plant_params = None if plant_params is None else _capi.check_plant_params(plant_params)
+        self.device_noise = bool(device_noise)
+        if self.device_noise:
+            import operator
+            self.seed = operator.index(seed)
+            if not 0 <= self.seed < 2 ** 64:
+                raise ValueError("device_noise: seed must be an integer in [0, 2**64), got %r" % (seed,))
+        self.lap = 0                   # device_noise: sessions begun so far -- the `lap` word of the generator's counter for the NEXT session
         self.prefetch = bool(prefetch) # False: every array is drawn when it is asked for, no worker thread (same draws, same order: tests compare the two)
         self._pre = None               # (shape key, generator state before the draw, future): the NEXT lap's plant noise, drawn by a worker thread while this lap runs
 
@@ -42,6 +55,8 @@ class BatchedRollouts:
         host core -- a tenth of a 1024-rollout lap on the GPU: the next lap's array is drawn by a worker thread while the device runs this one (NumPy releases
         the GIL inside the fill).  The generator is consumed in exactly the order it would be without the prefetch: a prefetched array of another shape is
         discarded together with its draws (the generator state from before the draw is restored)."""
+        if getattr(self, "device_noise", False):   # (the session's buffer is filled on the device: _device_noise_session)
+            return None
         if self.global_noise and self.noise_shard is not None:
             lo, hi, total = self.noise_shard
             assert hi - lo == B, (lo, hi, B)
@@ -96,6 +111,20 @@ class BatchedRollouts:
         if wait and self._pre is not None:
             self._pre[2].result()
 
+    def _device_noise_session(self, B):
+        """device_noise: hand the context the source of the session about to begin -- (seed, this object's session counter, first global car index) -- and count the
+        session.  Returns True when the session is to be begun with noise=None; False (host draws) leaves the context alone."""
+        if not getattr(self, "device_noise", False):  # (objects built without __init__ -- tests/test_host_checks.py -- draw on the host)
+            return False
+        car0 = 0
+        if self.noise_shard is not None:
+            lo, hi, total = self.noise_shard
+            assert hi - lo == B, (lo, hi, B)
+            car0 = int(lo)
+        self.ctx.rollout_set_noise(True, self.seed, self.lap, car0)
+        self.lap += 1
+        return True
+
     def _apply_plant_params(self, B):
         """The vehicle rows of this object's cars go to the context in front of a session (the session takes its snapshot when it begins)."""
         par = getattr(self, "plant_params", None)      # (objects built without __init__ -- tests/test_host_checks.py -- have none)
@@ -115,7 +144,10 @@ class BatchedRollouts:
         xl = self._per_rollout(xLin0, B); ul = self._per_rollout(uLin0, B)
         noise = self._draw_noise(max_steps, B)
         self._apply_plant_params(B)
-        self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, noise)
+        if self._device_noise_session(B):
+            self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, None, T_max=max_steps)
+        else:
+            self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, noise)
 
     def run_lap_device(self, x0, xLin0, uLin0, xglob0=None, max_steps=400, ext=0, on_ext=None, keep_invalid=False):
         """The whole lap stays on the GPU: four kernel launches per simulated step.  If ext > 0 the lap pauses after `ext` steps
@@ -159,14 +191,17 @@ class BatchedRollouts:
     def run_pid_laps(self, vt, x0=None, max_steps=1000, stop_at_line=False, keep_invalid=False):
         """len(vt) PID laps (main.py:61-70; Utilities.PID.solve, Utilities.py:60-67), car b at target speed vt[b], the whole lap in one kernel launch (Context.rollout_pid).
         Generator consumption, in this order, with or without the prefetcher: the control-law noise (max_steps, B, 2), then the plant noise (max_steps, B, 3); step t
-        of car b uses rows [t, b] of both.  Returns the valid laps as run_lap_device does; stop_at_line = False (the reference's multiLap simulator, main.py:57) keeps
+        of car b uses rows [t, b] of both (device_noise: no consumption -- streams 1 and 0 of one session of the device generator).  Returns the valid laps as run_lap_device does; stop_at_line = False (the reference's multiLap simulator, main.py:57) keeps
         all max_steps rows of a lap -- the rows past the finish line are what an LMPC safe set seeded from the lap needs there --, True the rows up to the crossing."""
         vt = np.atleast_1d(np.asarray(vt, float)); B = vt.shape[0]
         x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1)) if x0 is None else np.asarray(x0, float)
         noise_u = self._draw_noise(max_steps, B, width=2)
         noise = self._draw_noise(max_steps, B)
         self._apply_plant_params(B)
-        t, _ = self.ctx.rollout_pid(x0, x0, vt, noise_u, noise, stop_at_line=stop_at_line)
+        if self._device_noise_session(B):
+            t, _ = self.ctx.rollout_pid(x0, x0, vt, None, None, stop_at_line=stop_at_line, T_max=max_steps)
+        else:
+            t, _ = self.ctx.rollout_pid(x0, x0, vt, noise_u, noise, stop_at_line=stop_at_line)
         out = self.ctx.rollout_fetch(0, t)
         self.ctx.rollout_end()
         return self._collect(B, *out, whole=not stop_at_line, keep_invalid=keep_invalid)
@@ -174,14 +209,15 @@ class BatchedRollouts:
     def run_mpc_laps(self, x0, A=None, B=None, xLin0=None, uLin0=None, max_steps=1000, stop_at_line=False, keep_invalid=False):
         """x0.shape[0] closed-loop laps of the plain MPC on a numSS_it == 0 context, state resident on the device (Context.rollout_begin_mpc): with A (nb, 6, 6) / B (nb, 6, 2) the LTI
         path-following MPC of main.py:72-80 on those models, else the LTV-MPC of main.py:85-95 from xLin0 / uLin0 (one trajectory for all, or one per rollout) on the
-        context's regression store.  Generator consumption: one plant-noise draw (max_steps, nb, 3).  Returns lap tuples as run_pid_laps does."""
+        context's regression store.  Generator consumption: one plant-noise draw (max_steps, nb, 3) (device_noise: none, one session of the device generator).  Returns lap tuples as run_pid_laps does."""
         x0 = np.asarray(x0, float); nb = x0.shape[0]
         noise = self._draw_noise(max_steps, nb)
         self._apply_plant_params(nb)
+        kw = dict(T_max=max_steps) if self._device_noise_session(nb) else {}       # (noise is None then: the session's buffer is filled on the device)
         if A is not None:
-            self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line)
+            self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line, **kw)
         else:
-            self.ctx.rollout_begin_mpc(x0, x0, noise, xLin0=self._per_rollout(xLin0, nb), uLin0=self._per_rollout(uLin0, nb), stop_at_line=stop_at_line)
+            self.ctx.rollout_begin_mpc(x0, x0, noise, xLin0=self._per_rollout(xLin0, nb), uLin0=self._per_rollout(uLin0, nb), stop_at_line=stop_at_line, **kw)
         t, _ = self.ctx.rollout_run(max_steps)
         out = self.ctx.rollout_fetch(0, t)
         self.ctx.rollout_end()
@@ -202,7 +238,7 @@ def mpc_stage_config(track, N, vt, max_batch, trToUse=1, device=0):
                              trackLength=float(track[-1, 3] + track[-1, 4]), max_batch=int(max_batch), device=int(device))
 
 
-def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None):
+def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None, device_noise=False):
     """main.py:61-95 for B cars without a host round trip inside a lap: PID laps -> one LTI model per car (batched Utilities.Regression, lamb = 1e-7) -> LTI-MPC laps,
     car b on its own (A_b, B_b) -> LTV-MPC laps.  vt: the PID target speed, one value (main.py:50) or one per car; the MPC stages track vt_mpc (default: vt, or the
     mean of the per-car values).  Every stage runs max_steps steps from x0 = [0.5, 0, 0, 0, 0, 0] like the reference's multiLap simulator (main.py:45, 57).
@@ -216,6 +252,7 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     lap; None: the reference's vehicle.
 
     One generator seeded with `seed` feeds all stages in the order PID control-law noise, PID plant noise, LTI-MPC plant noise, LTV-MPC plant noise.
+    device_noise: the disturbances are generated on the device instead (BatchedRollouts(device_noise=True)): the three stages are sessions 0, 1 and 2 of `seed`.
     Returns dict(pid=, mpc=, ltvmpc= lists of lap tuples (x, u, x_glob, final12, done_at, status) with every car in it, flagged or not -- check `status` and
     `done_at` --, A=, B=, Error=, lti_status=, store_laps= the cars whose PID laps went into the shared store): seed_lmpc(ctx, [pid[b] for b in store_laps]) seeds an
     LMPC context with them as main.py:102-110 does with its PID lap."""
@@ -225,7 +262,7 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     n_store = min(B, BOOTSTRAP_STORE_LAPS)
     ctx = _capi.Context(mpc_stage_config(track, N, vt_mpc, B, trToUse=n_store, device=device))
     try:
-        ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params)
+        ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params, device_noise=device_noise)
     except Exception:
         ctx.close()
         raise

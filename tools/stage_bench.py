@@ -10,7 +10,14 @@ of start states and noise included on both sides; every shape is run once untime
 are fed the same draws, and the tool checks that their logs are equal bit for bit before it reports a time.  --out also writes the line to a file.
 
 --plant-params: every batch size is measured a second time with per-car vehicle constants in force (Context.plant_set_params: all ten constants of every car scaled
-by U(0.9, 1.1), generator seeded with 7) -- the per-car instantiations of the plant kernels beside the nominal ones; those rows carry "plant_params": true."""
+by U(0.9, 1.1), generator seeded with 7) -- the per-car instantiations of the plant kernels beside the nominal ones; those rows carry "plant_params": true.
+
+    python tools/stage_bench.py --device-noise   # host wall clock of a session's begin: host draw + upload  vs  the noise generated on the device
+
+--device-noise (no --stage): BatchedRollouts.begin of an LMPC session at B = 1024, T_max = 400 on the golden N = 12 stores, timed three ways in one run, alternating:
+the host draw (numpy standard_normal, no prefetcher) plus the upload -- unchanged code, so it stands for the library before the device generator --, the upload alone
+(the array drawn beforehand: what a prefetcher that hides the draw completely leaves), and device_noise=True (one fill launch, nothing drawn or copied).  begin returns
+with the stream drained, so the wall clock covers the fill kernel.  Medians and all samples go to profiles/device_noise_begin.json (or --out).  A record, not a gate."""
 import argparse
 import json
 import os
@@ -80,19 +87,60 @@ def run_stage(stage, g, B, T, plant_params=False):
     return ctx, device, host
 
 
+def device_noise_begin(g, B=1024, T=400, repeats=7):
+    """Seconds of BatchedRollouts.begin (host wall clock, stream drained when it returns) with the noise drawn on the host and uploaded, uploaded only, and generated on
+    the device."""
+    from racinglmpc_amd import rollout
+    from tests import common
+    ctx, _ = common.make_lmpc_ctx(g, 4, max_batch=B)
+    track = np.array(g["track"])
+    x0 = np.zeros((B, 6)); x0[:, 0] = np.linspace(0.5, 0.9, B); x0[:, 5] = np.linspace(-0.1, 0.1, B)[::-1]
+    xl = np.tile(g["SS0"][1:14][None], (B, 1, 1)); ul = np.tile(g["uSS0"][1:13][None], (B, 1, 1))
+    host = rollout.BatchedRollouts(ctx, track, seed=7, prefetch=False)
+    dev = rollout.BatchedRollouts(ctx, track, seed=7, device_noise=True)
+    drawn = np.random.default_rng(7).standard_normal((T, B, 3))
+
+    def timed(f):
+        t0 = time.perf_counter(); f(); dt = time.perf_counter() - t0
+        ctx.rollout_end()
+        return dt
+    ways = dict(host_draw_and_upload=lambda: host.begin(x0, xl, ul, max_steps=T), upload_only=lambda: ctx.rollout_begin(x0, x0, xl, ul, drawn),
+                device_noise=lambda: dev.begin(x0, xl, ul, max_steps=T))
+    for f in ways.values():                                            # untimed: session buffers, code objects
+        timed(f)
+    samples = {k: [] for k in ways}
+    for _ in range(repeats):
+        for k, f in ways.items():
+            if k != "device_noise":
+                ctx.rollout_set_noise(False)
+            samples[k].append(timed(f))
+    ctx.close()
+    return dict(tool="stage_bench", mode="device_noise_begin", N=12, B=B, T_max=T, noise_bytes=int(drawn.nbytes), unit="seconds of host wall clock per BatchedRollouts.begin",
+                median_s={k: float(np.median(v)) for k, v in samples.items()}, samples_s=samples)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--stage", choices=("pid", "mpc", "ltvmpc"), required=True)
+    ap.add_argument("--stage", choices=("pid", "mpc", "ltvmpc"))
+    ap.add_argument("--device-noise", action="store_true", help="time a session's begin with host-drawn and with device-generated noise (B = 1024, T_max = 400); no --stage")
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 256, 1024])
     ap.add_argument("--steps", type=int, default=0, help="simulated steps per lap (default: 400 for pid, 100 for the MPC stages)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--plant-params", action="store_true", help="also measure every batch size with per-car vehicle constants (+-10 % around the reference's, seed 7)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if not args.device_noise and not args.stage:
+        ap.error("--stage is required (or --device-noise)")
     import __graft_entry__ as ge
     ge.build()
     from tests import common
     g = common.load_lmpc_golden()
+    if args.device_noise:
+        line = device_noise_begin(g, repeats=max(args.repeats, 7))
+        print(json.dumps(line))
+        with open(args.out or os.path.join(ROOT, "profiles", "device_noise_begin.json"), "w") as f:
+            f.write(json.dumps(line, indent=1) + "\n")
+        return
     T = args.steps or (400 if args.stage == "pid" else 100)
     rows = []
     for B, par in [(B, par) for B in args.batches for par in ([False, True] if args.plant_params else [False])]:
