@@ -199,6 +199,22 @@ int lmpc_step_batch_dev(lmpc_ctx *, int B, const lmpc_step_dev_args *args);   /*
  * in lmpc_config.track (plotting / logging export, plot.py:50-175).  status[e] = LMPC_ST_NO_SEGMENT where the reference raises. */
 int lmpc_global_position_batch(lmpc_ctx *, int n, const double *s /*n*/, const double *ey /*n*/, double *xy /*n x 2*/, int *status /*n*/);
 
+/* The inverse of that map.  Map.getLocalPosition (Track.py:191-290), batched: inertial pose (X, Y, psi) -> curvilinear (s, ey, epsi) for n points, the reference's
+ * walk over the track rows branch for branch (exact end-point tests, the two-angle test of a straight row, the arc test of a curved row; the first row that
+ * completes wins).  max_ey is the reference's halfWidth + slack (0.85 on its track; the track table does not carry it): a projection further from the centre line
+ * does not complete its row.  status[e] = LMPC_ST_NO_SEGMENT and s = ey = epsi = 10000.0 where no row completes (the values the reference returns after its
+ * message) or an input is not finite.  psi may be any multiple of 2 pi away from the track's angle (np.unwrap against the row's angle, as the reference).
+ * Map.getAngle (Track.py:312-349), batched: (s, epsi) -> psi; status[e] = LMPC_ST_NO_SEGMENT and psi = 0 where the reference raises (s on no row).
+ * LMPC_E_ARG for n < 1, a NULL pointer, a non-finite or negative max_ey. */
+int lmpc_local_position_batch(lmpc_ctx *, int n, const double *x /*n*/, const double *y /*n*/, const double *psi /*n*/, double max_ey,
+                              double *s /*n*/, double *ey /*n*/, double *epsi /*n*/, int *status /*n*/);
+int lmpc_track_angle_batch(lmpc_ctx *, int n, const double *s /*n*/, const double *epsi /*n*/, double *psi /*n*/, int *status /*n*/);
+int lmpc_state_from_global_batch(lmpc_ctx *, int T, int B, const double *xglob /*T x B x 6: vx vy wz psi X Y*/, double max_ey,
+                                 double *x /*T x B x 6: vx vy wz epsi s ey*/, int *status /*T x B*/);
+        /* Map.getLocalPosition (Track.py:191-290) on every row of a session log in the layout of lmpc_rollout_fetch: the device function of
+         * lmpc_local_position_batch per row, vx, vy, wz copied through.  Rows are independent: s lies on the first lap, it is NOT made continuous across the finish
+         * line (racinglmpc_amd.rollout.lap_from_global adds the lap count on the host).  LMPC_E_ARG for T < 1, B < 1, a NULL pointer, a non-finite or negative max_ey */
+
 int lmpc_plant_step_batch(lmpc_ctx *, int B, const double *x /*B x 6*/, const double *x_glob /*B x 6*/, const double *u /*B x 2*/,
                           const double *noise /*B x 3 N(0,1) draws*/, double *x_next, double *x_glob_next, int *status);
         /* Simulator.dynModel, fnc/simulator/SysModel.py:56-147 (100 Euler sub-steps, clipped noise) */

@@ -57,7 +57,7 @@ EXPORTS = [
     "lmpc_dev_alloc", "lmpc_dev_free", "lmpc_dev_upload", "lmpc_dev_download", "lmpc_dev_sync", "lmpc_step_batch_dev",
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
-    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
+    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -91,8 +91,12 @@ def load():
         lib.lmpc_noise_fill.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p]
         lib.lmpc_rollout_set_noise.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_longlong]
         lib.lmpc_rollout_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)]
+        # (inverse track map: max_ey is a double passed by value)
+        lib.lmpc_local_position_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmpc_track_angle_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmpc_state_from_global_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
-                  lib.lmpc_rollout_get_noise):
+                  lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
         _lib = lib
     return _lib
@@ -723,6 +727,36 @@ class Context:
         xy = np.zeros((n, 2)); st = np.zeros(n, np.int32)
         _chk(self.lib.lmpc_global_position_batch(self._h, C.c_int(n), _d(s), _d(ey), _d(xy), _d(st)))
         return xy, st
+
+    def local_position(self, x, y, psi, max_ey):
+        """Map.getLocalPosition (Track.py:191-290) for arrays of inertial poses (x, y, psi): returns s, ey, epsi (n,) and status (n,) -- ST_NO_SEGMENT with
+        s = ey = epsi = 10000 where no track row completes or an input is not finite.  max_ey: the reference's halfWidth + slack (0.85 on its track)."""
+        x = _f64(np.ravel(x)); y = _f64(np.ravel(y)); psi = _f64(np.ravel(psi)); n = x.shape[0]
+        if y.shape[0] != n or psi.shape[0] != n:
+            raise ValueError("local_position: x, y, psi must have the same number of elements, got %d, %d, %d" % (n, y.shape[0], psi.shape[0]))
+        s = np.zeros(n); ey = np.zeros(n); epsi = np.zeros(n); st = np.zeros(n, np.int32)
+        _chk(self.lib.lmpc_local_position_batch(self._h, n, x.ctypes.data, y.ctypes.data, psi.ctypes.data, float(max_ey), s.ctypes.data, ey.ctypes.data, epsi.ctypes.data, st.ctypes.data))
+        return s, ey, epsi, st
+
+    def track_angle(self, s, epsi):
+        """Map.getAngle (Track.py:312-349) for arrays of (s, epsi): returns psi (n,) and status (n,) -- ST_NO_SEGMENT with psi = 0 where the reference raises."""
+        s = _f64(np.ravel(s)); epsi = _f64(np.ravel(epsi)); n = s.shape[0]
+        if epsi.shape[0] != n:
+            raise ValueError("track_angle: s and epsi must have the same number of elements, got %d, %d" % (n, epsi.shape[0]))
+        psi = np.zeros(n); st = np.zeros(n, np.int32)
+        _chk(self.lib.lmpc_track_angle_batch(self._h, n, s.ctypes.data, epsi.ctypes.data, psi.ctypes.data, st.ctypes.data))
+        return psi, st
+
+    def state_from_global(self, xglob, max_ey):
+        """Rows [vx, vy, wz, psi, X, Y] of a session log, (T, B, 6) or (T, 6), to rows [vx, vy, wz, epsi, s, ey] of the same shape (lmpc_state_from_global_batch):
+        returns (x, status) with status (T, B) or (T,).  Every row on its own: s lies on the first lap (rollout.lap_from_global makes it continuous)."""
+        xg = _f64(xglob)
+        if xg.ndim not in (2, 3) or xg.shape[-1] != 6:
+            raise ValueError("state_from_global: (T, B, 6) or (T, 6) rows [vx, vy, wz, psi, X, Y] expected, got shape %s" % (xg.shape,))
+        T = xg.shape[0]; B = xg.shape[1] if xg.ndim == 3 else 1
+        x = np.zeros(xg.shape); st = np.zeros(xg.shape[:-1], np.int32)
+        _chk(self.lib.lmpc_state_from_global_batch(self._h, T, B, xg.ctypes.data, float(max_ey), x.ctypes.data, st.ctypes.data))
+        return x, st
 
     def selftest(self):
         _chk(self.lib.lmpc_selftest(self._h))

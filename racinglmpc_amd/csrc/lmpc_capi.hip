@@ -3,6 +3,7 @@
 // lmpc_kernels.hip.h.  No CPU compute path exists here: if HIP fails, the call fails.
 #include "lmpc_variant.hip.h"
 #include "lmpc_noise.hip.h"
+#include "lmpc_track.hip.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <algorithm>
@@ -16,7 +17,13 @@
 #include <vector>
 
 static thread_local std::string g_err;
-static int set_err(int code, const char *what, const char *detail) { g_err = std::string(what) + ": " + (detail ? detail : ""); return code; }
+static int set_err(int code, const char *what, const char *detail) {
+    g_err = std::string(what) + ": " + (detail ? detail : "");
+    // A failed HIP call also stays behind as the thread's "last error", and the launch checks below read that with hipGetLastError(): reported here, it is consumed
+    // here -- an allocation that did not fit (lmpc_create, lmpc_dev_alloc) must not come back as the result of the next entry point's kernel launch.
+    if (code == LMPC_E_HIP) (void)hipGetLastError();
+    return code;
+}
 // Developer knobs read from the environment (round 6, ADVICE r5: a stray variable must not change behaviour silently).  Every knob that is SET is recorded
 // here, announced once on stderr and listed by lmpc_active_knobs(); knobs that change RESULTS (LMPC_NO_RETRY) exist in developer flavours only.
 static std::mutex g_knob_mu;
@@ -175,7 +182,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 103; }
+int lmpc_version(void) { return 104; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -1170,6 +1177,58 @@ int lmpc_global_position_batch(lmpc_ctx *c, int n, const double *s, const double
     hipLaunchKernelGGL(lmpc_global_position_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->dp, n, d, d + n, d + 2 * (size_t)n, ds);
     HIPCHK(hipGetLastError());
     D2H(xy, d + 2 * (size_t)n, (size_t)n * 2); D2H(status, ds, (size_t)n);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+// ---- the inverse track map (lmpc_track.hip.h): Map.getLocalPosition, Track.py:191-290, and Map.getAngle, Track.py:312-349, batched.  max_ey is the reference's
+// halfWidth + slack (0.85 on its track), which the track table in lmpc_config does not carry.
+int lmpc_local_position_batch(lmpc_ctx *c, int n, const double *x, const double *y, const double *psi, double max_ey, double *s, double *ey, double *epsi, int *status) {
+    ARGCHK(c && x && y && psi && s && ey && epsi && status && n >= 1 && std::isfinite(max_ey) && max_ey >= 0.0);
+    HIPCHK(hipSetDevice(c->cfg.device));
+    int rc = refresh_params(c, false, false); if (rc) return rc;
+    const size_t m = (size_t)n;
+    double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * m * 6 + sizeof(int) * m, &q); if (rc2) return rc2; d = (double *)q; }
+    int *ds = (int *)(d + m * 6);
+    H2D(d, x, m); H2D(d + m, y, m); H2D(d + 2 * m, psi, m);
+    hipLaunchKernelGGL(lmpc_local_position_kernel, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m, (const double *)d, (const double *)(d + m),
+                       (const double *)(d + 2 * m), (size_t)1, max_ey, d + 3 * m, d + 4 * m, d + 5 * m, (size_t)1, ds, (const double *)nullptr, (double *)nullptr);
+    HIPCHK(hipGetLastError());
+    D2H(s, d + 3 * m, m); D2H(ey, d + 4 * m, m); D2H(epsi, d + 5 * m, m); D2H(status, ds, m);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+int lmpc_track_angle_batch(lmpc_ctx *c, int n, const double *s, const double *epsi, double *psi, int *status) {
+    ARGCHK(c && s && epsi && psi && status && n >= 1);
+    HIPCHK(hipSetDevice(c->cfg.device));
+    int rc = refresh_params(c, false, false); if (rc) return rc;
+    const size_t m = (size_t)n;
+    double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * m * 3 + sizeof(int) * m, &q); if (rc2) return rc2; d = (double *)q; }
+    int *ds = (int *)(d + m * 3);
+    H2D(d, s, m); H2D(d + m, epsi, m);
+    hipLaunchKernelGGL(lmpc_track_angle_kernel, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m, (const double *)d, (const double *)(d + m), d + 2 * m, ds);
+    HIPCHK(hipGetLastError());
+    D2H(psi, d + 2 * m, m); D2H(status, ds, m);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+int lmpc_state_from_global_batch(lmpc_ctx *c, int T, int B, const double *xglob, double max_ey, double *x, int *status) {
+    // rows of a session log (lmpc_rollout_fetch): x_glob = [vx vy wz psi X Y] -> x = [vx vy wz epsi s ey], one thread per row by the device function of
+    // lmpc_local_position_batch.  Rows are independent: s is NOT made continuous across the finish line here (rollout.lap_from_global adds the lap count on the host)
+    ARGCHK(c && xglob && x && status && T >= 1 && B >= 1 && std::isfinite(max_ey) && max_ey >= 0.0);
+    ARGCHK(((unsigned long long)T * (unsigned long long)B + LMPC_TRACK_NT - 1) / LMPC_TRACK_NT <= 0x7fffffffull);
+    HIPCHK(hipSetDevice(c->cfg.device));
+    int rc = refresh_params(c, false, false); if (rc) return rc;
+    const size_t m = (size_t)T * (size_t)B;
+    double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * m * 12 + sizeof(int) * m, &q); if (rc2) return rc2; d = (double *)q; }
+    double *dx = d + m * 6; int *ds = (int *)(d + m * 12);
+    H2D(d, xglob, m * 6);
+    hipLaunchKernelGGL(lmpc_local_position_kernel, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m, (const double *)(d + 4), (const double *)(d + 5),
+                       (const double *)(d + 3), (size_t)6, max_ey, dx + 4, dx + 5, dx + 3, (size_t)6, ds, (const double *)d, dx);
+    HIPCHK(hipGetLastError());
+    D2H(x, dx, m * 6); D2H(status, ds, m);
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }

@@ -282,10 +282,38 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     return dict(pid=pid, mpc=mpc, ltvmpc=ltv, A=A, B=Bm, Error=Err, lti_status=lst, store_laps=order)
 
 
-def seed_lmpc(ctx, laps):
+def lap_from_global(ctx, xglob, max_ey, TL=None):
+    """One lap recorded in the inertial frame -- (T, 6) rows [vx, vy, wz, psi, X, Y], the reference's x_glob -- as the (T, 6) curvilinear rows [vx, vy, wz, epsi, s, ey]
+    the lap stores take (Context.state_from_global: Map.getLocalPosition per row, Track.py:191-290).  The map returns s on the first lap; here s is made continuous
+    across finish-line crossings: from every row whose s drops by more than TrackLength / 2 against the row before, one more TrackLength is added, so a multi-lap
+    PID lap comes back with s running past TrackLength, as seed_lmpc expects.  TL: the track length (default: the context's).  max_ey: the reference's
+    halfWidth + slack.  Raises LmpcError naming the first row the map places on no segment (ST_NO_SEGMENT)."""
+    xg = np.asarray(xglob, float)
+    if xg.ndim != 2 or xg.shape[1] != 6 or xg.shape[0] < 1:
+        raise ValueError("lap_from_global: (T, 6) rows [vx, vy, wz, psi, X, Y] expected, got shape %s" % (xg.shape,))
+    TL = float(ctx.cfg.trackLength if TL is None else TL)
+    x, st = ctx.state_from_global(xg, max_ey)
+    x = np.array(x, float).reshape(xg.shape); st = np.asarray(st).reshape(-1)
+    bad = np.nonzero(st & _capi.ST_NO_SEGMENT)[0]
+    if bad.size:
+        r = int(bad[0])
+        raise _capi.LmpcError("lap_from_global: row %d (X = %r, Y = %r, psi = %r) lies on no track segment within max_ey = %r (LMPC_ST_NO_SEGMENT)"
+                              % (r, xg[r, 4], xg[r, 5], xg[r, 3], float(max_ey)))
+    laps = np.concatenate([[0], np.cumsum(np.diff(x[:, 4]) < -TL / 2)])
+    x[:, 4] = x[:, 4] + laps * TL
+    return x
+
+
+def seed_lmpc(ctx, laps, from_global=False, max_ey=None):
     """main.py:102-110 with laps of bootstrap(): every (x, u, ...) tuple goes into the regression store (PredictiveModel.addTrajectory) and into the safe set
     (LMPC.addTrajectory) of the LMPC context `ctx`, in the order given; an LMPC context needs numSS_it / trToUse of them.  The reference passes its one PID lap four
-    times; bootstrap()'s "pid" laps are such laps -- max_steps rows of a multiLap run, s running past TrackLength -- one per car."""
+    times; bootstrap()'s "pid" laps are such laps -- max_steps rows of a multiLap run, s running past TrackLength -- one per car.
+    from_global: each lap is (x_glob, u, ...) recorded in the inertial frame (motion capture, another simulator, the reference's x_glob log) and is converted with
+    lap_from_global(ctx, x_glob, max_ey) first; max_ey (the reference's halfWidth + slack) must then be given."""
+    if from_global:
+        if max_ey is None:
+            raise ValueError("seed_lmpc(from_global=True) needs max_ey (the reference's halfWidth + slack)")
+        laps = [(lap_from_global(ctx, lap[0], max_ey), lap[1]) for lap in laps]
     for lap in laps:
         ctx.model_add_trajectory(lap[0], lap[1])
         ctx.ss_add_trajectory(lap[0], lap[1])
