@@ -121,6 +121,25 @@ int lmpc_model_add_trajectory(lmpc_ctx *, const double *x /*T x 6*/, const doubl
         /* PredictiveModel.addTrajectory, PredictiveModel.py:35-46: sorted insert, ascending T, ties append */
 int lmpc_model_num_laps(lmpc_ctx *, int *n);
 int lmpc_model_replace_lap(lmpc_ctx *, int pos /*position in sorted order*/, const double *x, const double *u, int T);
+int lmpc_model_set_lap_table(lmpc_ctx *, int n, const int *laps /*n x trToUse insertion indices, or NULL with n = 0*/);
+        /* Per-problem regression laps: which stored laps the regression (PredictiveModel.regressionAndLinearization) of each problem of a batch reads -- each car's
+         * LTV model from its own data, main.py:88-89 per car.  An entry is the INSERTION index of a regression-store lap (0 = the first lmpc_model_add_trajectory):
+         * stable under later inserts and store growth, unrelated to the lap's position in the sorted order.  Duplicates inside a row are allowed (main.py:103-104 adds
+         * one lap four times).  Each row is used in the order a context holding only those laps would use them -- ascending length, ties by insertion index
+         * (PredictiveModel.py:35-46) -- whatever order the caller lists them in.  n = 0: back to the context-wide default, the first trToUse laps of the sorted
+         * order.  n = 1: that row serves every problem.  n > 1: problem b of a call uses row b, and a call whose batch B != n returns LMPC_E_ARG and says so in
+         * lmpc_last_error (the context stays usable).  LMPC_E_ARG for an index < 0 or >= the laps stored, n < 0, NULL with n > 0, n > max_batch x N: after such an
+         * argument error the table in force stays (a HIP failure while the device image is uploaded, LMPC_E_HIP, leaves the context without a table).  The table applies wherever the regression kernel runs: lmpc_regress_batch, lmpc_regress_points (point e uses row e), lmpc_step_batch,
+         * lmpc_step_batch_dev, lmpc_rollout_begin and the LTV form of lmpc_rollout_begin_mpc with every step of their sessions -- a session takes a snapshot when it
+         * begins, a later call reaches the next session only.  On an LMPC context (numSS_it > 0) ONLY THE REGRESSION follows the table: the safe set, its selection and
+         * the terminal constraint stay shared by all problems.  With a table in force the fused one-wave step (LMPC_FUSE=1) is not taken: the two-kernel step runs.
+         * The table lives on the device as resolved (slot, rows) pairs, uploaded here and not per launch; it is rebuilt from the indices when the stores are
+         * reallocated or a lap is replaced.  As for the regression grid and scan build, A, B, C of a problem do not depend on which other rows the table holds */
+int lmpc_model_get_lap_table(lmpc_ctx *, int *n, int *laps /*capacity rows x trToUse, or NULL*/, int capacity);
+        /* the rows in force as lmpc_model_set_lap_table received them (n = 0: the default); laps receives min(n, capacity) rows */
+int lmpc_model_lap_info(lmpc_ctx *, int lap /*insertion index*/, int *rows /*or NULL*/, int *sorted_pos /*or NULL*/);
+        /* the regression-store lap with that insertion index: its rows, and its position in the sorted order -- the index lmpc_store_read_lap (store 0) and
+         * lmpc_model_replace_lap take.  Needs no device.  LMPC_E_ARG for an index that names no stored lap */
 int lmpc_ss_add_trajectory(lmpc_ctx *, const double *x, const double *u, int T);
         /* LMPC.addTrajectory + computeCost, PredictiveControllers.py:418-464 (it += 1) */
 int lmpc_ss_add_point(lmpc_ctx *, const double *x /*6*/, const double *u /*2*/);

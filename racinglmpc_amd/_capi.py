@@ -51,7 +51,7 @@ class StepDevArgs(C.Structure):
 
 EXPORTS = [
     "lmpc_config_default", "lmpc_create", "lmpc_create_ex", "lmpc_solver_kind", "lmpc_destroy", "lmpc_last_error", "lmpc_active_knobs", "lmpc_version", "lmpc_device_memory",
-    "lmpc_model_add_trajectory", "lmpc_model_num_laps", "lmpc_model_replace_lap",
+    "lmpc_model_add_trajectory", "lmpc_model_num_laps", "lmpc_model_replace_lap", "lmpc_model_set_lap_table", "lmpc_model_get_lap_table", "lmpc_model_lap_info",
     "lmpc_ss_add_trajectory", "lmpc_ss_add_point", "lmpc_ss_replace_lap", "lmpc_ss_set_selected", "lmpc_ss_num_laps", "lmpc_ss_get_qfun", "lmpc_ss_get_laptime", "lmpc_store_read_lap",
     "lmpc_regress_batch", "lmpc_regress_points", "lmpc_select_batch", "lmpc_qp_solve_batch", "lmpc_step_batch", "lmpc_assemble_batch", "lmpc_qp_dims",
     "lmpc_dev_alloc", "lmpc_dev_free", "lmpc_dev_upload", "lmpc_dev_download", "lmpc_dev_sync", "lmpc_step_batch_dev",
@@ -95,6 +95,11 @@ def load():
         lib.lmpc_local_position_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lmpc_track_angle_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lmpc_state_from_global_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        # (per-problem regression laps: rows of int32 insertion indices)
+        lib.lmpc_model_set_lap_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.lmpc_model_get_lap_table.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]
+        lib.lmpc_model_lap_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.lmpc_model_set_lap_table.restype = lib.lmpc_model_get_lap_table.restype = lib.lmpc_model_lap_info.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
@@ -163,6 +168,24 @@ def check_plant_params(par):
     if not (np.all(par[:, 0] > 0) and np.all(par[:, 3] > 0)):
         raise ValueError("plant parameters: m and Iz must be positive (rows %s)" % np.where(~((par[:, 0] > 0) & (par[:, 3] > 0)))[0].tolist())
     return np.ascontiguousarray(par)
+
+
+def check_lap_table(rows, trToUse):
+    """(n, trToUse) int32 rows of a per-problem lap table, or None for "no table" (None or no rows); ValueError for a shape that is not rows of trToUse entries or
+    for a negative index (the library checks the upper end against the laps stored).  A flat list is one row per entry when trToUse is 1, else one row."""
+    if rows is None or np.size(rows) == 0:
+        return None
+    L = int(trToUse)
+    a = np.asarray(rows)
+    if L < 1 or not np.issubdtype(a.dtype, np.integer) or a.ndim > 2:
+        raise ValueError("lap table: integer rows of trToUse = %d lap indices expected, got dtype %s, shape %s" % (L, a.dtype, a.shape))
+    if a.ndim < 2:
+        a = a.reshape(-1, 1) if L == 1 else a.reshape(1, -1)
+    if a.shape[1] != L:
+        raise ValueError("lap table: rows of trToUse = %d lap indices expected, got shape %s" % (L, a.shape))
+    if a.min() < 0:
+        raise ValueError("lap table: negative lap index in row(s) %s" % np.where((a < 0).any(1))[0].tolist())
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def plant_params(B, m=1.98, lf=0.125, lr=0.125, Iz=0.024, mu_f=0.8, mu_r=0.8, Cf=1.25, Bf=1.0, Cr=1.25, Br=1.0, Df=None, Dr=None):
@@ -290,6 +313,34 @@ class Context:
     def model_replace_lap(self, pos, x, u):
         x = _f64(x); u = _f64(u)
         _chk(self.lib.lmpc_model_replace_lap(self._h, C.c_int(pos), _d(x), _d(u), C.c_int(x.shape[0])))
+
+    def model_set_lap_table(self, rows):
+        """Per-problem regression laps (lmpc_model_set_lap_table): rows (n, trToUse) of INSERTION indices of regression-store laps (0 = the first
+        model_add_trajectory; duplicates allowed, any order inside a row).  None or no rows -- the default, the first trToUse laps of the sorted order for every
+        problem; one row -- every problem; n rows -- problem b of a later regress_batch / regress_points / step_batch / step_batch_dev / rollout_begin /
+        LTV rollout_begin_mpc uses row b, and a call with another batch size is refused.  A session uses the table in force when it began.  On an LMPC context
+        only the regression follows the table: the safe set stays shared."""
+        L = int(self.cfg.trToUse)
+        rows = check_lap_table(rows, L)
+        if rows is None:
+            _chk(self.lib.lmpc_model_set_lap_table(self._h, 0, None))
+            return
+        _chk(self.lib.lmpc_model_set_lap_table(self._h, rows.shape[0], rows.ctypes.data))
+
+    def model_lap_info(self, lap):
+        """(rows, position in the sorted order) of the regression-store lap with insertion index `lap` (lmpc_model_lap_info)."""
+        T = C.c_int(); pos = C.c_int()
+        _chk(self.lib.lmpc_model_lap_info(self._h, int(lap), C.byref(T), C.byref(pos)))
+        return T.value, pos.value
+
+    def model_lap_table(self):
+        """The rows in force, (n, trToUse) int32 as model_set_lap_table received them; n = 0: the default (lmpc_model_get_lap_table)."""
+        n = C.c_int()
+        _chk(self.lib.lmpc_model_get_lap_table(self._h, C.byref(n), None, 0))
+        rows = np.zeros((n.value, int(self.cfg.trToUse)), np.int32)
+        if n.value:
+            _chk(self.lib.lmpc_model_get_lap_table(self._h, C.byref(n), rows.ctypes.data, rows.shape[0]))
+        return rows
 
     def ss_add_trajectory(self, x, u):
         x = _f64(x); u = _f64(u)
@@ -620,6 +671,13 @@ class Context:
         for i in range(ns):
             x, u, q = self.store_read_lap(1, i); out["ss_x%d" % i] = x; out["ss_u%d" % i] = u; out["ss_q%d" % i] = q
             out["ss_laptime%d" % i] = np.int64(self.ss_lap_time(i))
+        # The lap table names laps by insertion index; the file holds the laps in their SORTED order and restore_stores inserts them in that order, so the
+        # table is written in terms of sorted positions -- the insertion indices of the restored context.  Laps of equal length keep their insertion order in
+        # the sorted order, hence a row's own order (length, then index) is the same before and after.
+        tab = self.model_lap_table() if nm.value else np.zeros((0, 0), np.int32)      # (no laps stored: no table can be in force)
+        if tab.shape[0]:
+            pos = np.array([self.model_lap_info(k)[1] for k in range(nm.value)], np.int32)      # insertion index -> sorted position
+            out["model_lap_table"] = pos[tab]
         np.savez_compressed(_npz_path(path), n_model=np.int64(nm.value), n_ss=np.int64(ns), N=np.int64(self.N), **out)
 
     def restore_stores(self, path):
@@ -632,6 +690,8 @@ class Context:
                 raise LmpcError("restore_stores needs a context with empty lap stores")
             for i in range(int(d["n_model"])):
                 self.model_add_trajectory(d["model_x%d" % i], d["model_u%d" % i])
+            if "model_lap_table" in d.files:                 # (per-problem regression laps, in terms of the insertion indices the loop above has just given)
+                self.model_set_lap_table(d["model_lap_table"])
             for i in range(int(d["n_ss"])):
                 x, u, q, T0 = d["ss_x%d" % i], d["ss_u%d" % i], d["ss_q%d" % i], int(d["ss_laptime%d" % i])
                 self.ss_add_trajectory(x[:T0], u[:T0])
@@ -855,7 +915,7 @@ class ContextPool:
     def __getattr__(self, name):                       # lap-store edits (model_add_trajectory, ss_add_trajectory, ss_add_point, ss_set_selected, ...): the same call on every member
         if name in ("members", "_next"):               # (not set yet: a failed __init__ must not recurse through this hook)
             raise AttributeError(name)
-        if name == "plant_set_params" or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num"))):   # (the vehicle too: the same on every member)
+        if name == "plant_set_params" or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num", "model_lap"))):   # (the vehicle too: the same on every member; model_set_lap_table goes with the store edits, the queries model_lap_table / model_lap_info to the first)
             def forward(*a, **kw):
                 out = None
                 for m in self.members:

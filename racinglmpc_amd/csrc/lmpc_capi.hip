@@ -125,6 +125,10 @@ struct lmpc_ctx {
     struct lmpc_rollout_session *ro;
     int noise_on; unsigned long long noise_seed, noise_lap; long long noise_car0;   // lmpc_rollout_set_noise: sessions begun with noise = NULL fill their buffer on the device (lmpc_noise.hip.h); 0 after lmpc_create
     std::vector<double> plant_par; int plant_n;   // lmpc_plant_set_params: plant_n rows of LMPC_PLANT_NPAR vehicle constants (0: the reference's vehicle, the kernels with the literals)
+    // lmpc_model_set_lap_table: lt_n rows of trToUse insertion indices as the caller gave them (0 rows: the first trToUse laps of the sorted order serve every problem);
+    // d_lt: the same rows on the device as resolved (slot, rows) pairs in each row's sorted order, uploaded by `set` and rebuilt when the stores move or a lap is
+    // replaced (resolve_lap_table); lt_small: every lap named anywhere has at most 512 rows, i.e. the 8-rows-per-lane scan serves the whole table (launch_k1)
+    std::vector<int> lt_idx; int lt_n; int *d_lt; size_t d_lt_cap; bool lt_small;
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     double *ext_rows; size_t ext_rows_bytes;   // staging buffer of lmpc_ss_extend_lap
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
@@ -182,7 +186,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 104; }
+int lmpc_version(void) { return 105; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -385,7 +389,7 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack};      // (the w_* work buffers are ranges of the two slabs)
+    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt};      // (the w_* work buffers are ranges of the two slabs)
     check_slab_gaps(c);
     for (void *q : ptrs) if (q) (void)g_free(q);
     if (c->h_retry) (void)hipHostFree(c->h_retry);
@@ -413,6 +417,36 @@ static int resolve_retries(lmpc_ctx *c);
 // does not fit, both stores (and the K1 prefilter image) move to allocations of at least twice the size -- strided device-to-device copies,
 // [lap][column][row] with the new row stride -- and the device parameter block is rebuilt.  Amortised O(1) per stored row; no kernel is in
 // flight while it happens (the stream is drained first).
+
+// Per-problem lap table (lmpc_model_set_lap_table).  The context keeps insertion indices; what the regression kernel reads are (slot, rows) pairs.  One row of `idx`
+// (trToUse insertion indices, any order, duplicates allowed) in the order a context holding only those laps would use them: ascending length, ties by insertion
+// index (PredictiveModel.addTrajectory, PredictiveModel.py:35-46: a sorted insert that appends among equals).  *small: no lap of the row exceeds the 8-rows-per-lane scan.
+static void resolve_lap_row(const lmpc_ctx *c, const int *idx, int *pairs, bool *small) {
+    const int L = c->cfg.trToUse;
+    std::vector<int> o(idx, idx + L);
+    std::sort(o.begin(), o.end(), [&](int a, int b) { return c->m_len[a] != c->m_len[b] ? c->m_len[a] < c->m_len[b] : a < b; });
+    for (int i = 0; i < L; i++) { pairs[2 * i] = o[i]; pairs[2 * i + 1] = c->m_len[o[i]]; if (c->m_len[o[i]] - 1 > 8 * WAVE) *small = false; }   // (insertion index == slot)
+}
+// the whole table, resolved: rows x trToUse x 2 ints
+static std::vector<int> resolve_lap_rows(const lmpc_ctx *c, bool *small) {
+    const size_t L = (size_t)c->cfg.trToUse;
+    std::vector<int> pairs((size_t)c->lt_n * L * 2);
+    *small = true;
+    for (int r = 0; r < c->lt_n; r++) resolve_lap_row(c, &c->lt_idx[(size_t)r * L], &pairs[(size_t)r * L * 2], small);
+    return pairs;
+}
+// (re)build the device image from the indices the context keeps: after `set`, after the stores moved, after a lap was replaced.  No kernel is in flight (callers drain the stream).
+static int resolve_lap_table(lmpc_ctx *c) {
+    if (c->lt_n == 0) return LMPC_OK;
+    const std::vector<int> pairs = resolve_lap_rows(c, &c->lt_small);
+    if (pairs.size() > c->d_lt_cap) {
+        if (c->d_lt) { (void)g_free(c->d_lt); c->d_lt = nullptr; c->d_lt_cap = 0; }
+        HIPCHK(g_malloc(&c->d_lt, pairs.size() * sizeof(int))); c->d_lt_cap = pairs.size();
+    }
+    HIPCHK(hipMemcpy(c->d_lt, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice));
+    return LMPC_OK;
+}
+
 static int grow_stores(lmpc_ctx *c, int need_laps, int need_len) {
     const int old_laps = c->cfg.max_laps, old_len = c->cfg.max_lap_len;
     int new_laps = old_laps, new_len = old_len;
@@ -446,7 +480,7 @@ static int grow_stores(lmpc_ctx *c, int need_laps, int need_len) {
     memcpy(c->dp.mslot, keep.mslot, sizeof(keep.mslot)); memcpy(c->dp.mlen, keep.mlen, sizeof(keep.mlen));
     memcpy(c->dp.sslot, keep.sslot, sizeof(keep.sslot)); memcpy(c->dp.sslen, keep.sslen, sizeof(keep.sslen)); memcpy(c->dp.sslapid, keep.sslapid, sizeof(keep.sslapid));
     c->dp.cur_it = keep.cur_it;
-    return LMPC_OK;
+    return resolve_lap_table(c);
 }
 
 static int upload_lap(lmpc_ctx *c, bool model, int slot, const double *x, const double *u, const double *qf, int T) {
@@ -516,7 +550,39 @@ int lmpc_model_replace_lap(lmpc_ctx *c, int pos, const double *x, const double *
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     ARGCHK(T == c->m_len[c->m_order[pos]]);
     int rc = upload_lap(c, true, c->m_order[pos], x, u, nullptr, T); if (rc) return rc;
-    return quantise_lap(c, c->m_order[pos], x, u, T);
+    rc = quantise_lap(c, c->m_order[pos], x, u, T); if (rc) return rc;
+    return resolve_lap_table(c);
+}
+
+int lmpc_model_set_lap_table(lmpc_ctx *c, int n, const int *laps) {
+    // checked in full before anything is changed: a refused table leaves the one in force
+    ARGCHK(c && n >= 0 && (n == 0 || laps));
+    if (n == 0) { c->lt_n = 0; c->lt_idx.clear(); return LMPC_OK; }
+    const int L = c->cfg.trToUse, stored = (int)c->m_len.size();
+    ARGCHK(L >= 1 && (long long)n <= (long long)c->cfg.max_batch * c->cfg.N);         // (lmpc_regress_points serves up to max_batch x N points)
+    for (size_t i = 0; i < (size_t)n * L; i++)
+        if (laps[i] < 0 || laps[i] >= stored) {
+            char msg[128]; snprintf(msg, sizeof(msg), "row %d names lap %d, %d laps are stored", (int)(i / L), laps[i], stored);
+            return set_err(LMPC_E_ARG, "lap table", msg);
+        }
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));   // (a regression still in flight reads the image about to be overwritten)
+    c->lt_idx.assign(laps, laps + (size_t)n * L); c->lt_n = n;
+    const int rc = resolve_lap_table(c);
+    if (rc) { c->lt_n = 0; c->lt_idx.clear(); }
+    return rc;
+}
+int lmpc_model_lap_info(lmpc_ctx *c, int lap, int *rows, int *sorted_pos) {
+    // the lap with insertion index `lap`: its rows and its position in the sorted order (what lmpc_store_read_lap and lmpc_model_replace_lap address laps by)
+    ARGCHK(c && lap >= 0 && lap < (int)c->m_len.size());
+    if (rows) *rows = c->m_len[lap];
+    if (sorted_pos) *sorted_pos = (int)(std::find(c->m_order.begin(), c->m_order.end(), lap) - c->m_order.begin());
+    return LMPC_OK;
+}
+int lmpc_model_get_lap_table(lmpc_ctx *c, int *n, int *laps, int capacity) {
+    ARGCHK(c && n && capacity >= 0);
+    *n = c->lt_n;
+    if (laps && c->lt_n) memcpy(laps, c->lt_idx.data(), sizeof(int) * (size_t)c->cfg.trToUse * (size_t)std::min(capacity, c->lt_n));
+    return LMPC_OK;
 }
 
 int lmpc_ss_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int T) {
@@ -603,11 +669,15 @@ int lmpc_store_read_lap(lmpc_ctx *c, int store, int lap, double *x, double *u, d
 int lmpc_ss_get_laptime(lmpc_ctx *c, int lap, int *T) { ARGCHK(c && T && lap >= 0 && lap < (int)c->s_laptime.size()); *T = c->s_laptime[lap]; return LMPC_OK; }
 
 // refresh the per-launch part of the device parameter block
-static int refresh_params(lmpc_ctx *c, bool need_model, bool need_ss) {
+// model_from_table: the regression launch this refresh is for reads a lap table (the context's, or a session's snapshot), whose rows `set` has checked -- the
+// sorted-order laps of the block are then not needed.  They are refreshed whenever they exist all the same: what decides is what the LAUNCH reads, and a session
+// begun without a table keeps reading the block whatever table the context has been given since.
+static int refresh_params(lmpc_ctx *c, bool need_model, bool need_ss, bool model_from_table = false) {
     lmpc_dev_params &p = c->dp;
     if (need_model) {
-        if ((int)c->m_order.size() < c->cfg.trToUse || c->cfg.trToUse < 1) return set_err(LMPC_E_STATE, "regression needs trToUse stored laps", "");
-        for (int i = 0; i < c->cfg.trToUse; i++) { p.mslot[i] = c->m_order[i]; p.mlen[i] = c->m_len[c->m_order[i]]; }   // usedIt = range(trToUse), PredictiveModel.py:31
+        const bool have = (int)c->m_order.size() >= c->cfg.trToUse && c->cfg.trToUse >= 1;
+        if (!have && !model_from_table) return set_err(LMPC_E_STATE, "regression needs trToUse stored laps", "");
+        if (have) for (int i = 0; i < c->cfg.trToUse; i++) { p.mslot[i] = c->m_order[i]; p.mlen[i] = c->m_len[c->m_order[i]]; }   // usedIt = range(trToUse), PredictiveModel.py:31
     }
     if (need_ss) {
         const int L = c->cfg.numSS_it, nl = (int)c->s_len.size();
@@ -649,19 +719,35 @@ static void k1_grid(lmpc_ctx *c, int B, int *qg, int *nblk) {
 }
 // The regression kernel in the build that fits the launch: the occupancy build when the grid exceeds one work-group per CU, and the
 // 8-rows-per-lane scan when every lap in use lies inside its first quantisation chunk half (<= 512 rows; k1_scan_lap).
-static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, int xstride, const double *uLin, double *dA, double *dB, double *dC, int *dst) {
+// The lap table a regression launch reads: the context's (k1_table_for) or a rollout session's snapshot.  dev == nullptr: none, the laps of the parameter block.
+struct k1_table { const int *dev; int stride; bool small; };
+// the context's table for a call of B problems (B points for lmpc_regress_points): one row serves all, else row b belongs to problem b and the counts must agree
+static int k1_table_for(lmpc_ctx *c, int B, k1_table *t) {
+    t->dev = nullptr; t->stride = 0; t->small = true;
+    if (c->lt_n == 0) return LMPC_OK;
+    if (c->lt_n > 1 && B != c->lt_n) {
+        char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_model_set_lap_table holds %d rows", B, c->lt_n);
+        return set_err(LMPC_E_ARG, "lap table", msg);
+    }
+    t->dev = c->d_lt; t->stride = c->lt_n == 1 ? 0 : 2 * c->cfg.trToUse; t->small = c->lt_small;
+    return LMPC_OK;
+}
+static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, int xstride, const double *uLin, double *dA, double *dB, double *dC, int *dst, const k1_table &t) {
     bool small = true;
-    for (int i = 0; i < c->cfg.trToUse; i++) small = small && c->dp.mlen[i] - 1 <= 8 * WAVE;
+    if (t.dev) small = t.small;                                          // (every lap named anywhere in the table)
+    else for (int i = 0; i < c->cfg.trToUse; i++) small = small && c->dp.mlen[i] - 1 <= 8 * WAVE;
     if (c->k1_force16) small = false;                                    // (LMPC_K1_RPL16 at lmpc_create: A / B of the two scan builds, tests/test_gpu_configs.py)
     const bool occ = nblk > c->n_cu;
     auto k = occ ? (small ? lmpc_regress_kernel<true, 8> : lmpc_regress_kernel<true, K1_RPL>) : (small ? lmpc_regress_kernel<false, 8> : lmpc_regress_kernel<false, K1_RPL>);
-    hipLaunchKernelGGL(k, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst);
+    if (t.dev) k = occ ? (small ? lmpc_regress_kernel<true, 8, true> : lmpc_regress_kernel<true, K1_RPL, true>) : (small ? lmpc_regress_kernel<false, 8, true> : lmpc_regress_kernel<false, K1_RPL, true>);
+    hipLaunchKernelGGL(k, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride);
 }
 static int launch_regress(lmpc_ctx *c, int B, const double *d_xLin, int xstride, const double *d_uLin, double *dA, double *dB, double *dC, int *dst) {
-    int rc = refresh_params(c, true, false); if (rc) return rc;
+    int rc = refresh_params(c, true, false, c->lt_n != 0); if (rc) return rc;
+    k1_table tab; rc = k1_table_for(c, B, &tab); if (rc) return rc;
     ev_begin(c, 0);
     int qg, nblk; k1_grid(c, B, &qg, &nblk);
-    launch_k1(c, nblk, B, qg, d_xLin, xstride, d_uLin, dA, dB, dC, dst);
+    launch_k1(c, nblk, B, qg, d_xLin, xstride, d_uLin, dA, dB, dC, dst, tab);
     ev_end(c);
     HIPCHK(hipGetLastError());
     c->stats.n_regress++;
@@ -771,6 +857,7 @@ int lmpc_regress_batch(lmpc_ctx *c, int B, const double *xLin, int xLinRowStride
     const int N = c->cfg.N;
     ARGCHK(xLinRowStride == N * 6 || xLinRowStride == (N + 1) * 6);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (a pending launch may hand its A / B / C over through w_A / w_B / w_C: its retry pass first)
+    { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows: refused before anything is queued)
     H2D(c->w_xLin, xLin, (size_t)B * xLinRowStride); H2D(c->w_uLin, uLin, (size_t)B * N * 2);
     int rc = launch_regress(c, B, c->w_xLin, xLinRowStride, c->w_uLin, c->w_A, c->w_B, c->w_C, c->w_rstatus); if (rc) return rc;
     D2H(A, c->w_A, (size_t)B * N * 36); D2H(Bm, c->w_B, (size_t)B * N * 12); D2H(C, c->w_C, (size_t)B * N * 6); D2H(status, c->w_rstatus, (size_t)B * N);
@@ -790,13 +877,14 @@ int lmpc_regress_points(lmpc_ctx *c, int n, const double *x, const double *u, do
     // shape -- one point per call -- without a horizon around it.  The regression kernel runs with a parameter block whose horizon is 1: one query per work-group.
     ARGCHK(c && x && u && A && Bm && C && n >= 1 && (long long)n <= (long long)c->cfg.max_batch * c->cfg.N);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
+    k1_table tab; { const int rc = k1_table_for(c, n, &tab); if (rc) return rc; }      // (point e uses row e)
     H2D(c->w_xLin, x, (size_t)n * 6); H2D(c->w_uLin, u, (size_t)n * 2);
-    int rc = refresh_params(c, true, false); if (rc) return rc;
+    int rc = refresh_params(c, true, false, tab.dev != nullptr); if (rc) return rc;
     {
         const lmpc_dev_params keep = c->dp;
         c->dp.N = 1;                                                     // (launch_k1 passes c->dp by value)
         ev_begin(c, 0);
-        launch_k1(c, n, n, 1, c->w_xLin, 6, c->w_uLin, c->w_A, c->w_B, c->w_C, c->w_rstatus);
+        launch_k1(c, n, n, 1, c->w_xLin, 6, c->w_uLin, c->w_A, c->w_B, c->w_C, c->w_rstatus, tab);
         ev_end(c);
         c->dp = keep;
     }
@@ -862,7 +950,9 @@ int lmpc_step_batch_dev(lmpc_ctx *c, int B, const lmpc_step_dev_args *a) {
     // Regression kernel, then the solve kernel; A, Bm, C are optional outputs (the hand-over then uses the context's work buffers).
     // With LMPC_FUSE=1 batches that run one wave per QP take the fused step instead: every wave runs the regression of its own QP in
     // front of the solve and [A_k | B_k], C_k never leave LDS (see lmpc_create for the measurement that keeps it off by default).
-    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1;
+    { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows: refused before anything is queued)
+    // (a lap table in force: the fused form reads the laps of the parameter block -- it lives in the variant libraries -- so the two-kernel step runs)
+    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0;
     double *dA = a->A ? a->A : c->w_A, *dB = a->Bm ? a->Bm : c->w_B, *dC = a->C ? a->C : c->w_C;
     // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
     // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
@@ -889,6 +979,7 @@ int lmpc_step_batch(lmpc_ctx *c, int B, const double *x0, const double *xLin, co
     const int N = c->cfg.N; const bool term = c->cfg.numSS_it > 0; const int S = term ? c->cfg.numSS_points : 0;
     if (term) ARGCHK(zt != nullptr);
     HIPCHK(hipSetDevice(c->cfg.device));
+    { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows)
     const bool one_copy = c->h_in && B == c->cfg.max_batch;          // small contexts (the drop-in classes: max_batch = 1): one copy each way
     const auto tr0 = std::chrono::steady_clock::now();
     if (one_copy) {
@@ -1239,6 +1330,7 @@ struct lmpc_rollout_session {
     int kind, stop_at_line;                                     // RO_LMPC / RO_LTV / RO_LTI / RO_PID (what one simulated step launches); 0: the run does not end when every car has crossed the line
     double *d_noiseU, *d_vt;                                    // RO_PID only: controller noise T_max x B x 2, target speed per car
     unsigned long long nz_seed, nz_lap; long long nz_car0;      // the session's snapshot of the noise source (lmpc_rollout_set_noise), taken when it begins
+    int *d_lt; bool has_lt, lt_small; int lt_stride;            // the session's snapshot of the lap table (resolved (slot, rows) pairs, B x trToUse x 2), taken when it begins; has_lt: the table builds of the regression kernel run
     double *d_par; bool has_par;                                // the session's snapshot of the per-car vehicle constants (B x LMPC_PLANT_NPAR), taken when it begins; has_par: the PAR kernels run
     hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
     std::vector<void *> keep;
@@ -1266,6 +1358,14 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     const size_t N = c->cfg.N, S = c->cfg.numSS_points, Bz = B;
     std::vector<double> par_rows;                               // refused before any session state changes (B beyond the per-car rows)
     if (c->plant_n > 0) { const int rc = plant_rows_for(c, B, par_rows); if (rc) return rc; }
+    std::vector<int> lt_rows; bool lt_small = true;             // sessions that run the regression: the lap table in force, one resolved row per car (refused here as well when B is not its row count)
+    if ((kind == RO_LMPC || kind == RO_LTV) && c->lt_n > 0) {
+        k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc;
+        const std::vector<int> pairs = resolve_lap_rows(c, &lt_small);
+        const size_t rowlen = (size_t)c->cfg.trToUse * 2;
+        lt_rows.resize((size_t)B * rowlen);
+        for (int b = 0; b < B; b++) memcpy(&lt_rows[(size_t)b * rowlen], &pairs[(size_t)(c->lt_n == 1 ? 0 : b) * rowlen], sizeof(int) * rowlen);
+    }
     // A generation loop begins a session of the same shape every lap: its ~35 device buffers (55 MB of logs at 1024 rollouts x 400 steps), the plant stream and
     // the two events are kept from one session to the next (round 5: allocating and freeing them was ~5 ms of every generation) and released by
     // lmpc_destroy or by a session of another shape.
@@ -1285,7 +1385,7 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     DA(double, d_xPred, Bz * (N + 1) * 6) DA(double, d_uPred, Bz * N * 2) DA(double, d_slack, Bz * N * 2) DA(double, d_lam, Bz * S) DA(double, d_sT, Bz * 6)
     DA(double, d_ztN, Bz * 6) DA(double, d_ztuN, Bz * 2) DA(double, d_A, Bz * N * 36) DA(double, d_B, Bz * N * 12) DA(double, d_C, Bz * N * 6)
     DA(double, d_resid, Bz * 3) DA(int, d_status, Bz) DA(int, d_iters, Bz) DA(int, d_rst, Bz * N) DA(double, d_finX, Bz * 6) DA(double, d_finG, Bz * 6)
-    DA(double, d_par, Bz * LMPC_PLANT_NPAR)
+    DA(double, d_par, Bz * LMPC_PLANT_NPAR) DA(int, d_lt, Bz * (size_t)std::max(c->cfg.trToUse, 1) * 2)
     r->d_ssSel = nullptr; r->d_qSel = nullptr; r->d_succ = nullptr; r->d_succU = nullptr;
     if (c->dbg_capture) { DA(double, d_ssSel, Bz * S * 6) DA(double, d_qSel, Bz * S) DA(double, d_succ, Bz * S * 6) DA(double, d_succU, Bz * S * 2) }
     DA(double, d_logX, (size_t)T_max * Bz * 6) DA(double, d_logU, (size_t)T_max * Bz * 2) DA(double, d_logG, (size_t)T_max * Bz * 6) DA(double, d_noise, (size_t)T_max * Bz * 3)
@@ -1309,6 +1409,8 @@ init_state:
     else { lmpc_noise_fill_launch(c->stream, r->nz_seed, 0ull, r->nz_lap, 0, T_max, r->nz_car0, B, 3, r->d_noise); HIPCHK(hipGetLastError()); }
     r->has_par = !par_rows.empty();                             // the snapshot: lmpc_plant_set_params during the session reaches the next one only
     if (r->has_par) H2D(r->d_par, par_rows.data(), par_rows.size());
+    r->has_lt = !lt_rows.empty(); r->lt_small = lt_small; r->lt_stride = 2 * c->cfg.trToUse;   // the snapshot: lmpc_model_set_lap_table during the session reaches the next one only
+    if (r->has_lt) H2D(r->d_lt, lt_rows.data(), lt_rows.size());
     HIPCHK(hipMemsetAsync(r->d_uOld, 0, sizeof(double) * Bz * 2, c->stream)); HIPCHK(hipMemsetAsync(r->d_xPP, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
     HIPCHK(hipMemsetAsync(r->d_hasPred, 0, sizeof(int) * Bz, c->stream)); HIPCHK(hipMemsetAsync(r->d_tstep, 0, sizeof(int) * Bz, c->stream));
     HIPCHK(hipMemsetAsync(r->d_nDone, 0, sizeof(int), c->stream)); HIPCHK(hipMemsetAsync(r->d_stAcc, 0, sizeof(int) * Bz, c->stream));
@@ -1350,7 +1452,7 @@ int lmpc_rollout_begin_mpc(lmpc_ctx *c, int B, int T_max, const double *x0, cons
     ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
     HIPCHK(hipSetDevice(c->cfg.device));
     const bool lti = A_lti != nullptr;
-    if (!lti) { const int rc = refresh_params(c, true, false); if (rc) return rc; }       // LMPC_E_STATE without trToUse stored laps, as lmpc_step_batch
+    if (!lti) { const int rc = refresh_params(c, true, false, c->lt_n != 0); if (rc) return rc; }       // LMPC_E_STATE without trToUse stored laps, as lmpc_step_batch
     RESOLVE_PENDING();
     int rc = rollout_setup(c, lti ? RO_LTI : RO_LTV, stop_at_line ? 1 : 0, B, T_max, x0, xg0, lti ? nullptr : xLin0, lti ? nullptr : uLin0, noise);
     if (rc) return rc;
@@ -1434,10 +1536,11 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
     const int t_end = std::min(r->T_max, r->t + max_steps);
     while (r->t < t_end) {
         if (!lti) {
-        rc = refresh_params(c, true, lmpc); if (rc) return rc;
+        rc = refresh_params(c, true, lmpc, r->has_lt); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
         ev_begin(c, 0);
         { int qg, nblk; k1_grid(c, B, &qg, &nblk);
-          launch_k1(c, nblk, B, qg, (const double *)r->d_xLin, (int)(N + 1) * 6, (const double *)r->d_uLin, r->d_A, r->d_B, r->d_C, r->d_rst); }
+          const k1_table tab = {r->has_lt ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small};
+          launch_k1(c, nblk, B, qg, (const double *)r->d_xLin, (int)(N + 1) * 6, (const double *)r->d_uLin, r->d_A, r->d_B, r->d_C, r->d_rst, tab); }
         ev_end(c); c->stats.n_regress++;
         }
         lmpc_solve_io io; memset(&io, 0, sizeof(io));

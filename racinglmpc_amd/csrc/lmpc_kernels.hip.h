@@ -430,17 +430,23 @@ struct k1_smem {
     int *st_s;                       // [QG]
 };
 
+// Which stored lap is lap c of the problem at hand.  TAB = false: the context-wide choice in the parameter block (p.mslot / p.mlen, the first trToUse laps of the
+// sorted order).  TAB = true: the problem's own row of the per-problem lap table (lmpc_model_set_lap_table) -- trToUse resolved (slot, rows) pairs, ordered by the
+// host as a context holding only those laps would order them.  A work-group serves one problem, so `lt` is uniform and the pairs arrive by scalar loads.
+template <bool TAB> __device__ __forceinline__ int k1_lap_slot(const lmpc_dev_params &p, const int *lt, int c) { if constexpr (TAB) return lt[2 * c]; else return p.mslot[c]; }
+template <bool TAB> __device__ __forceinline__ int k1_lap_len(const lmpc_dev_params &p, const int *lt, int c) { if constexpr (TAB) return lt[2 * c + 1]; else return p.mlen[c]; }
+
 // computeIndices (PredictiveModel.py:180-197) of ONE wave for lap c: the lap's prefilter image is loaded once per 1024-row chunk and scanned
 // for the wave's queries qi = sgi + s nsub, s < nqw; the running selection per (query, lap) stays in sm.seld / seli / nsel.  cs0: first
 // row of this wave in sm.cseg / ccnt.  PAIR: two queries per trip (independent reduction chains interleave; 32 registers more).
 // RPL: rows per lane per trip.  16 = the host's quantisation chunk (K1_CHUNK rows, own range each); 8 only when every lap in use has at
 // most 512 rows, i.e. lies in its first chunk (launch_k1): half the prefilter work and 32 registers less per wave.
-template <bool PAIR, int RPL>
-__device__ __forceinline__ void k1_scan_lap(const lmpc_dev_params &p, const k1_smem &sm, int c, int cs0, int sgi, int nsub, int nq, int lane, int MAXP) {
+template <bool PAIR, int RPL, bool TAB = false>
+__device__ __forceinline__ void k1_scan_lap(const lmpc_dev_params &p, const k1_smem &sm, int c, int cs0, int sgi, int nsub, int nq, int lane, int MAXP, const int *lt = nullptr) {
     const double h = p.h;
-    const double *base = p.mstore + (size_t)p.mslot[c] * LMPC_COLS * p.lap_stride;
+    const double *base = p.mstore + (size_t)k1_lap_slot<TAB>(p, lt, c) * LMPC_COLS * p.lap_stride;
     const int ls = p.lap_stride;
-    const int nrows = p.mlen[c] - 1;
+    const int nrows = k1_lap_len<TAB>(p, lt, c) - 1;
     for (int t0 = 0; t0 < nrows; t0 += RPL * WAVE) {
         // Prefilter image of this lane's rows: the scaled features in 16-bit fixed point, packed (vx, vy | wz, delta | a, flag),
         // quantised by the host when the lap was stored (lmpc_capi.hip: quantise_lap), per 1024-row chunk over the chunk's own
@@ -448,9 +454,9 @@ __device__ __forceinline__ void k1_scan_lap(const lmpc_dev_params &p, const k1_s
         // integer L1 distance; every decision is re-made in FP64 below.  A query outside [min, max] is clamped: that shifts all
         // of a feature's |differences| by the same amount, so the order of the rows is untouched.  Rows beyond the lap carry
         // 0xffff in the unused half-word (the query has 0 there): farther than a full range from everything.
-        const double *qp = p.mqpar + ((size_t)p.mslot[c] * p.mq_chunks + t0 / K1_CHUNK) * 6;
+        const double *qp = p.mqpar + ((size_t)k1_lap_slot<TAB>(p, lt, c) * p.mq_chunks + t0 / K1_CHUNK) * 6;
         const double qsc = qp[5];
-        const unsigned *qb = p.mquant + (size_t)p.mslot[c] * 3 * ls;
+        const unsigned *qb = p.mquant + (size_t)k1_lap_slot<TAB>(p, lt, c) * 3 * ls;
         unsigned qv[3][RPL];
 #pragma unroll
         for (int k = 0; k < 3; k++)
@@ -593,8 +599,9 @@ __device__ __forceinline__ void k1_scan_lap(const lmpc_dev_params &p, const k1_s
 
 // compute_Q_M / compute_b / LMPC_LocLinReg / regressionAndLinearization (PredictiveModel.py:48-178) for the nf queries q0 .. q0 + nf - 1 of the
 // pass (selection in sm.seld / seli / nsel), by the nt threads of the work-group: A_i | B_i | C_i end up in sm.outv[0 .. nf), status bits in
-// sm.st_s[q0 ..].  xq: the problem's xLin rows (6 doubles each, row i0 = first query of the pass).  Work-group barriers inside.
-__device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &sm, int q0, int nf, int tid, int nt, const double *xq_pass, int MAXP) {
+// sm.st_s[q0 ..].  xq: the problem's xLin rows (6 doubles each, row i0 = first query of the pass).  Work-group barriers inside.  TAB / lt: see k1_lap_slot.
+template <bool TAB = false>
+__device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &sm, int q0, int nf, int tid, int nt, const double *xq_pass, int MAXP, const int *lt = nullptr) {
     const int L = p.trToUse, PP = L * MAXP;
     const double h = p.h;
     // ---- assemble A_i, B_i, C_i (:70-135), one thread per query.  The kinematic rows (epsi, s, ey) depend on the query state only: they are
@@ -643,7 +650,7 @@ __device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &
                 }
             }
             const double dd = sd[pick]; const int ii = si[pick];
-            const double *base = p.mstore + (size_t)p.mslot[c] * LMPC_COLS * p.lap_stride;
+            const double *base = p.mstore + (size_t)k1_lap_slot<TAB>(p, lt, c) * LMPC_COLS * p.lap_stride;
             double q = dd / h; q = q * q;
             pt[0] = base[0 * p.lap_stride + ii]; pt[1] = base[1 * p.lap_stride + ii]; pt[2] = base[2 * p.lap_stride + ii];
             pt[3] = base[6 * p.lap_stride + ii]; pt[4] = base[7 * p.lap_stride + ii]; pt[5] = (1.0 - q) * 3.0 / 4.0;        // :193
@@ -718,10 +725,19 @@ __device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &
 
 // OCC: compile for four waves per SIMD (two work-groups per CU; <= 128 VGPRs) -- pays when the grid exceeds one work-group
 // per CU (1.47x at batch 4096); the other variant has the shorter latency when each CU runs a single group.
-template <bool OCC, int RPL>
-__global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? 6 : 4) : 2) void lmpc_regress_kernel(lmpc_dev_params p, int B, int qg, const double *__restrict__ xLin, int xstride,
+// TAB: every problem names its own laps (k1_lap_slot): lapTab holds (slot, rows) pairs, trToUse per row, and problem b reads the row at lapTab + b * tabStride
+// (tabStride = 0: one row for every problem).  The TAB = false builds take neither argument into account.
+// (The table build of the 8-rows-per-lane occupancy kernel is compiled for five waves per SIMD, not six: the 80 registers of six cost its twin seven spilled
+//  VGPRs -- 32 bytes of scratch per lane -- and the table builds are to have none; 89 registers, no scratch.  -DLMPC_K1_TAB_WAVES8=6 builds the six-wave form for
+//  comparison: racinglmpc_amd.build.build_flavour("k1w6", ["LMPC_K1_TAB_WAVES8=6"]), measured by tools/lap_table_k1_cost.py: 7 % faster where the laps sit in L2.)
+#ifndef LMPC_K1_TAB_WAVES8
+#define LMPC_K1_TAB_WAVES8 5
+#endif
+template <bool OCC, int RPL, bool TAB = false>
+__global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 : 6) : 4) : 2) void lmpc_regress_kernel(lmpc_dev_params p, int B, int qg, const double *__restrict__ xLin, int xstride,
                                                              const double *__restrict__ uLin, double *__restrict__ Aout,
-                                                             double *__restrict__ Bout, double *__restrict__ Cout, int *__restrict__ status) {
+                                                             double *__restrict__ Bout, double *__restrict__ Cout, int *__restrict__ status,
+                                                             const int *__restrict__ lapTab, int tabStride) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);             // wave-uniform by construction: lap pointers, row counts and loop bounds stay in SGPRs
     __shared__ double qf[K1_QG][5];
@@ -748,6 +764,7 @@ __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? 6 : 4) : 2) void lmpc_regr
     const int myc = wave % L, sgi = wave / L;
     const int i0 = (blockIdx.x % npass) * QGe;
     const int nq = N - i0 < QGe ? N - i0 : QGe;
+    const int *lt = TAB ? lapTab + (size_t)b * tabStride : nullptr;
     if (tid < nq * 5) {
         const int qi = tid / 5, f = tid % 5;
         qf[qi][f] = f < 3 ? xLin[(size_t)b * xstride + (size_t)(i0 + qi) * 6 + f] : uLin[((size_t)b * N + i0 + qi) * 2 + (f - 3)];
@@ -761,10 +778,10 @@ __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? 6 : 4) : 2) void lmpc_regr
     //  fill the chain's latency, and the second query's 16 distances cost registers it does not have -- spilled registers are scratch
     //  WRITES: 134 MB per launch at batch 4096 before this)
     for (int c = myc; c < L && sgi < nsub; c += K1_NW)                    // (c += K1_NW: more laps than waves -- trToUse up to 32 -- a wave then scans several laps in turn)
-        k1_scan_lap<!OCC, RPL>(p, sm, c, wave * K1_QG, sgi, nsub, nq, lane, MAXP);
+        k1_scan_lap<!OCC, RPL, TAB>(p, sm, c, wave * K1_QG, sgi, nsub, nq, lane, MAXP, lt);
     __syncthreads();
     K1STAMP(2);
-    k1_fit(p, sm, 0, nq, tid, K1_NT, xLin + (size_t)b * xstride + (size_t)i0 * 6, MAXP);
+    k1_fit<TAB>(p, sm, 0, nq, tid, K1_NT, xLin + (size_t)b * xstride + (size_t)i0 * 6, MAXP, lt);
     for (int e = tid; e < nq * 54; e += K1_NT) {
         const int qi = e / 54, le = e % 54; const size_t item = (size_t)b * N + i0 + qi;
         if (le < 36) Aout[item * 36 + le] = outv[qi][le];

@@ -19,8 +19,12 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False):
-        """plant_params: vehicle constants of the cars of THIS object (this rank's shard), rows of _capi.PLANT_PARAM_NAMES as _capi.plant_params builds them -- one row
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None):
+        """lap_table: per-car regression laps of the cars of THIS object, rows of trToUse insertion indices into the context's regression store -- one row for all cars
+        or one per car (Context.model_set_lap_table); handed to the context before every begin and every LTV run_mpc_laps, as plant_params is.  None: the context's
+        table is left as it is (no table unless the caller set one: every car regresses on the first trToUse laps of the store's sorted order).  On an LMPC context
+        the safe set stays shared whatever the table says.
+        plant_params: vehicle constants of the cars of THIS object (this rank's shard), rows of _capi.PLANT_PARAM_NAMES as _capi.plant_params builds them -- one row
         for all cars or one per car; handed to the context (Context.plant_set_params) before every begin, run_pid_laps and run_mpc_laps.  None: the context's
         parameters are left as they are (the reference's vehicle unless the caller set others).
         global_noise: the plant noise of a lap is drawn for ALL rollouts of the job (same seed on every rank) and this rank keeps the columns
@@ -39,6 +43,7 @@ class BatchedRollouts:
         self.last_status = None
         self.last_done = None
         self.plant_params = None if plant_params is None else _capi.check_plant_params(plant_params)
+        self.lap_table = None if lap_table is None else _capi.check_lap_table(lap_table, ctx.cfg.trToUse)
         self.device_noise = bool(device_noise)
         if self.device_noise:
             import operator
@@ -134,6 +139,15 @@ class BatchedRollouts:
             raise ValueError("plant_params: one row or one per car (%d) expected, got %d" % (B, par.shape[0]))
         self.ctx.plant_set_params(par)
 
+    def _apply_lap_table(self, B):
+        """The lap-table rows of this object's cars go to the context in front of a session that runs the regression (the session takes its snapshot when it begins)."""
+        tab = getattr(self, "lap_table", None)         # (objects built without __init__ -- tests/test_host_checks.py -- have none)
+        if tab is None:
+            return
+        if tab.shape[0] not in (1, B):
+            raise ValueError("lap_table: one row or one per car (%d) expected, got %d" % (B, tab.shape[0]))
+        self.ctx.model_set_lap_table(tab)
+
     @staticmethod
     def _per_rollout(a, B):
         a = np.asarray(a, float)
@@ -144,6 +158,7 @@ class BatchedRollouts:
         xl = self._per_rollout(xLin0, B); ul = self._per_rollout(uLin0, B)
         noise = self._draw_noise(max_steps, B)
         self._apply_plant_params(B)
+        self._apply_lap_table(B)
         if self._device_noise_session(B):
             self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, None, T_max=max_steps)
         else:
@@ -213,6 +228,8 @@ class BatchedRollouts:
         x0 = np.asarray(x0, float); nb = x0.shape[0]
         noise = self._draw_noise(max_steps, nb)
         self._apply_plant_params(nb)
+        if A is None:
+            self._apply_lap_table(nb)              # (the LTI form runs no regression)
         kw = dict(T_max=max_steps) if self._device_noise_session(nb) else {}       # (noise is None then: the session's buffer is filled on the device)
         if A is not None:
             self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line, **kw)
@@ -238,7 +255,7 @@ def mpc_stage_config(track, N, vt, max_batch, trToUse=1, device=0):
                              trackLength=float(track[-1, 3] + track[-1, 4]), max_batch=int(max_batch), device=int(device))
 
 
-def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None, device_noise=False):
+def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None, device_noise=False, per_car_store=False):
     """main.py:61-95 for B cars without a host round trip inside a lap: PID laps -> one LTI model per car (batched Utilities.Regression, lamb = 1e-7) -> LTI-MPC laps,
     car b on its own (A_b, B_b) -> LTV-MPC laps.  vt: the PID target speed, one value (main.py:50) or one per car; the MPC stages track vt_mpc (default: vt, or the
     mean of the per-car values).  Every stage runs max_steps steps from x0 = [0.5, 0, 0, 0, 0, 0] like the reference's multiLap simulator (main.py:45, 57).
@@ -247,6 +264,11 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     first among equals -- the local regression weighs stored points by their distance to the linearisation point, so laps driven near the speed the MPC tracks
     are the data it uses, and four is what main.py:102-104 gives the LMPC's model.  Every rollout starts its linearisation from the first N + 1 rows of the LAST
     stored lap (MPC.__init__, PredictiveControllers.py:88-90).  With B = 1 that is the car's own single PID lap, main.py:88-89.
+
+    per_car_store: main.py:88-95 replicated per car instead -- ALL B PID laps go into the store (trToUse = 1), in car order, and a lap table gives car b its own lap
+    as its only regression data (Context.model_set_lap_table, row b = [b]); car b starts its linearisation from the first N + 1 rows of its own lap
+    (PredictiveControllers.py:88-90).  Each car's LTV model is then identified from what that car's vehicle did, which is what matters with plant_params.
+    store_laps lists all B cars.
 
     plant_params: vehicle constants (one row, or one per car; _capi.plant_params) of all three stages -- car b drives the same vehicle in its PID, LTI-MPC and LTV-MPC
     lap; None: the reference's vehicle.
@@ -259,8 +281,8 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     track = np.asarray(track, float)
     vt = np.broadcast_to(np.asarray(vt, float), (B,)).copy()
     vt_mpc = float(vt.mean()) if vt_mpc is None else float(vt_mpc)
-    n_store = min(B, BOOTSTRAP_STORE_LAPS)
-    ctx = _capi.Context(mpc_stage_config(track, N, vt_mpc, B, trToUse=n_store, device=device))
+    n_store = B if per_car_store else min(B, BOOTSTRAP_STORE_LAPS)
+    ctx = _capi.Context(mpc_stage_config(track, N, vt_mpc, B, trToUse=1 if per_car_store else n_store, device=device))
     try:
         ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params, device_noise=device_noise)
     except Exception:
@@ -271,11 +293,15 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
         pid = ro.run_pid_laps(vt, x0, max_steps=max_steps, keep_invalid=True)
         A, Bm, Err, lst = _capi.lti_regression_batch([(l[0], l[1]) for l in pid], LTI_LAMB, device=device)
         mpc = ro.run_mpc_laps(x0, A=A, B=Bm, max_steps=max_steps, keep_invalid=True)
-        order = sorted(range(B), key=lambda b: (abs(vt[b] - vt_mpc), b))[:n_store]
+        order = list(range(B)) if per_car_store else sorted(range(B), key=lambda b: (abs(vt[b] - vt_mpc), b))[:n_store]
         for b in order:
             ctx.model_add_trajectory(pid[b][0], pid[b][1])
-        last = pid[order[-1]]                       # xStored[-1]: laps of equal length keep their insertion order (PredictiveModel.py:35-46)
-        ltv = ro.run_mpc_laps(x0, xLin0=last[0][0:N + 1], uLin0=last[1][0:N], max_steps=max_steps, keep_invalid=True)
+        if per_car_store:                           # car b: insertion index b, its own lap and nothing else; its own first N + 1 rows to linearise about
+            ro.lap_table = _capi.check_lap_table(np.arange(B).reshape(B, 1), 1)
+            ltv = ro.run_mpc_laps(x0, xLin0=np.stack([l[0][0:N + 1] for l in pid]), uLin0=np.stack([l[1][0:N] for l in pid]), max_steps=max_steps, keep_invalid=True)
+        else:
+            last = pid[order[-1]]                   # xStored[-1]: laps of equal length keep their insertion order (PredictiveModel.py:35-46)
+            ltv = ro.run_mpc_laps(x0, xLin0=last[0][0:N + 1], uLin0=last[1][0:N], max_steps=max_steps, keep_invalid=True)
     finally:
         ro.close()
         ctx.close()
@@ -328,7 +354,8 @@ class LmpcGeneration:
     line and the terminal constraint would stop the cars in front of it.
 
     The rollouts may drive different vehicles (BatchedRollouts(plant_params=...): rows for the cars of the rank's shard).  The safe set and the regression store
-    stay SHARED: a lap driven by one vehicle then serves as terminal set and as regression data for the others.  Whether that is wanted -- robustness of a
+    stay SHARED: a lap driven by one vehicle then serves as terminal set and as regression data for the others (BatchedRollouts(lap_table=...) can give each car
+    its own regression laps; the safe set has no such table).  Whether that is wanted -- robustness of a
     learned safe set against model mismatch -- or not is the caller's decision; nothing here keeps vehicles apart."""
 
     def __init__(self, rollouts, total_rollouts, K=4, T_max=400, ext=40, comm=None):
