@@ -43,10 +43,34 @@ class LmpcStats(C.Structure):
                 ("qp_solved", C.c_longlong), ("ipm_iters", C.c_longlong), ("n_regress_timed", C.c_longlong), ("n_solve_timed", C.c_longlong), ("n_retry", C.c_longlong)]
 
 
+# The per-problem arrays of a step, stated once on this side (the library's statement: csrc/lmpc_arrays.h): key of the entry points below, member of lmpc_step_dev_args (None: the
+# selection's own outputs; the members come first, in the C struct's order: StepDevArgs mirrors it), dtype, role, shape for B problems (N1 = N + 1, N2 = 2 N, M = 8 N + S, L1 = max(numSS_it, 1)).
+_f8, _i4 = np.float64, np.int32
+ARRAYS = (
+    ("x0", "x0", _f8, "in", "B 6"), ("xLin", "xLin", _f8, "in", "B N1 6"), ("uLin", "uLin", _f8, "in", "B N 2"), ("uOld", "uOld", _f8, "in", "B 2"),
+    ("zt", "zt", _f8, "in", "B 6"), ("xPredPrev", "xPredPrev", _f8, "in", "B N1 6"), ("hasPred", "hasPred", _i4, "in", "B"), ("timeStep", "timeStep", _i4, "in", "B"),
+    ("xPred", "xPred", _f8, "out", "B N1 6"), ("uPred", "uPred", _f8, "out", "B N 2"), ("slack", "slack", _f8, "out", "B N2"), ("lambd", "lambda_", _f8, "out", "B S"),
+    ("sTerm", "sTerm", _f8, "out", "B 6"), ("ztNext", "ztNext", _f8, "out", "B 6"), ("ztuNext", "ztuNext", _f8, "out", "B 2"), ("ssSel", "ssSel", _f8, "out", "B S 6"),
+    ("A", "A", _f8, "out", "B N 6 6"), ("B", "Bm", _f8, "out", "B N 6 2"), ("C", "C", _f8, "out", "B N 6"), ("mu", "mu", _f8, "out", "B M"),
+    ("resid", "resid", _f8, "out", "B 3"), ("status", "status", _i4, "out", "B"), ("iters", "iters", _i4, "out", "B"), ("qSel", "qSel", _f8, "out", "B S"),
+    ("succ", None, _f8, "select", "B S 6"), ("succU", None, _f8, "select", "B S 2"), ("ztUsed", None, _f8, "select", "B 6"), ("selStart", None, _i4, "select", "B L1"),
+)
+STEP_IN_KEYS, STEP_OUT_KEYS = (tuple(k for k, f, dt, role, shp in ARRAYS if role == r) for r in ("in", "out"))     # STEP_OUT_KEYS: what step_batch and step_dev_fetch return
+QP_OUT_KEYS = ("xPred", "uPred", "slack", "lambd", "sTerm", "mu", "status", "iters", "resid")         # qp_solve_batch, in the order of its arguments
+SELECT_OUT_KEYS = ("ssSel", "qSel", "succ", "succU", "ztUsed", "selStart", "status")                 # select_batch, in the order of its arguments
+DIAGNOSTIC_KEYS = ("qSel", "mu", "resid")                                                             # step_dev_buffers(diagnostics=False) leaves them NULL
+_FIELD = {k: f for k, f, dt, role, shp in ARRAYS}
+
+
+def array_specs(B, N, S, numSS_it, keys=None):
+    """{key: (shape, dtype)} of the arrays of ARRAYS (all, or `keys` in the order given) for B problems of horizon N with S safe-set points in use."""
+    d = dict(B=B, N=N, N1=N + 1, N2=2 * N, S=S, M=8 * N + S, L1=max(numSS_it, 1))
+    spec = {k: (tuple(d[t] if t in d else int(t) for t in shp.split()), dt) for k, f, dt, role, shp in ARRAYS}
+    return spec if keys is None else {k: spec[k] for k in keys}
+
+
 class StepDevArgs(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("x0", "xLin", "uLin", "uOld", "zt", "xPredPrev", "hasPred", "timeStep",
-                                          "xPred", "uPred", "slack", "lambda_", "sTerm", "ztNext", "ztuNext", "ssSel",
-                                          "A", "Bm", "C", "mu", "resid", "status", "iters", "qSel")]
+    _fields_ = [(f, C.c_void_p) for k, f, dt, role, shp in ARRAYS if f is not None]
 
 
 EXPORTS = [
@@ -382,26 +406,24 @@ class Context:
         _chk(self.lib.lmpc_regress_points(self._h, C.c_int(n), _d(x), _d(u), _d(A), _d(Bm), _d(Cc), _d(st)))
         return A, Bm, Cc, st
 
+    def _zeros(self, keys, B):
+        """Fresh zero arrays {key: array} for B problems, shapes and dtypes from ARRAYS."""
+        return {k: np.zeros(shp, dt) for k, (shp, dt) in array_specs(B, self.N, self.S, self.cfg.numSS_it, keys).items()}
+
     def select_batch(self, x0, zt, xPredPrev=None, hasPred=None, timeStep=None):
-        N, S = self.N, self.S
         x0 = _f64(x0); zt = _f64(zt); B = x0.shape[0]
         xpp = None if xPredPrev is None else _f64(xPredPrev)
         hp = None if hasPred is None else _i32(hasPred)
         ts = None if timeStep is None else _i32(timeStep)
-        ss = np.zeros((B, S, 6)); q = np.zeros((B, S)); succ = np.zeros((B, S, 6)); succU = np.zeros((B, S, 2)); ztu = np.zeros((B, 6))
-        st = np.zeros(B, np.int32); start = np.zeros((B, max(self.cfg.numSS_it, 1)), np.int32)
-        _chk(self.lib.lmpc_select_batch(self._h, C.c_int(B), _d(x0), _d(zt), _d(xpp), _d(hp), _d(ts), _d(ss), _d(q), _d(succ), _d(succU), _d(ztu), _d(start), _d(st)))
-        return dict(ssSel=ss, qSel=q, succ=succ, succU=succU, ztUsed=ztu, selStart=start, status=st)
+        out = self._zeros(SELECT_OUT_KEYS, B)
+        _chk(self.lib.lmpc_select_batch(self._h, C.c_int(B), _d(x0), _d(zt), _d(xpp), _d(hp), _d(ts), *[_d(out[k]) for k in SELECT_OUT_KEYS]))
+        return out
 
     def qp_solve_batch(self, A, Bm, Cc, x0, uOld, ssSel=None, qSel=None):
-        N, S, M = self.N, self.S, self.M
         A = _f64(A); Bm = _f64(Bm); Cc = _f64(Cc); x0 = _f64(x0); uOld = _f64(uOld); B = x0.shape[0]
         ss = None if ssSel is None else _f64(ssSel); q = None if qSel is None else _f64(qSel)
-        out = dict(xPred=np.zeros((B, N + 1, 6)), uPred=np.zeros((B, N, 2)), slack=np.zeros((B, 2 * N)), lambd=np.zeros((B, S)),
-                   sTerm=np.zeros((B, 6)), mu=np.zeros((B, M)), status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32), resid=np.zeros((B, 3)))
-        _chk(self.lib.lmpc_qp_solve_batch(self._h, C.c_int(B), _d(A), _d(Bm), _d(Cc), _d(x0), _d(uOld), _d(ss), _d(q),
-                                          _d(out["xPred"]), _d(out["uPred"]), _d(out["slack"]), _d(out["lambd"]), _d(out["sTerm"]), _d(out["mu"]),
-                                          _d(out["status"]), _d(out["iters"]), _d(out["resid"])))
+        out = self._zeros(QP_OUT_KEYS, B)
+        _chk(self.lib.lmpc_qp_solve_batch(self._h, C.c_int(B), _d(A), _d(Bm), _d(Cc), _d(x0), _d(uOld), _d(ss), _d(q), *[_d(out[k]) for k in QP_OUT_KEYS]))
         return out
 
     def step_batch(self, x0, xLin, uLin, uOld, zt=None, xPredPrev=None, hasPred=None, timeStep=None):
@@ -416,12 +438,10 @@ class Context:
         # allocations and twenty-six address look-ups than the library spends outside its two kernels): addresses are base + offset
         plan = self._step_plan.get(B)
         if plan is None:
-            shapes = (("xPred", (B, N + 1, 6)), ("uPred", (B, N, 2)), ("slack", (B, 2 * N)), ("lambd", (B, S)), ("sTerm", (B, 6)), ("ztNext", (B, 6)),
-                      ("ztuNext", (B, 2)), ("ssSel", (B, S, 6)), ("qSel", (B, S)), ("mu", (B, self.M)), ("A", (B, N, 6, 6)), ("B", (B, N, 6, 2)),
-                      ("C", (B, N, 6)), ("resid", (B, 3)))
             offs, o = [], 0
-            for k, shp in shapes:
-                n = int(np.prod(shp)); offs.append((k, shp, o, n)); o += n
+            for k, (shp, dt) in array_specs(B, N, S, self.cfg.numSS_it, STEP_OUT_KEYS).items():
+                if dt is _f8:                              # (status, iters: the int32 buffer)
+                    n = int(np.prod(shp)); offs.append((k, shp, o, n)); o += n
             plan = self._step_plan[B] = (offs, o)
         offs, total = plan
         buf = np.zeros(total); ibuf = np.zeros(2 * B, np.int32)
@@ -485,44 +505,27 @@ class Context:
         xPredPrev, hasPred, timeStep).  Returns (StepDevArgs, device pointers to free with dev_free).  diagnostics=False leaves out what
         the hot path does not need downstream (inequality multipliers mu, residual triple, Q-function values of the selection):
         those pointers stay NULL and the kernels skip the stores."""
-        N, S, M = self.N, self.S, self.M
         B = np.asarray(inp["x0"]).shape[0]
         a = StepDevArgs(); keep = []
-
-        def up(arr, dt):
-            p = self.dev_array(np.ascontiguousarray(arr, dtype=dt)); keep.append(p); return p
-
-        def alloc(nbytes):
-            p = self.dev_alloc(max(int(nbytes), 8)); keep.append(p); return p
-        a.x0, a.xLin, a.uLin, a.uOld = up(inp["x0"], np.float64), up(inp["xLin"], np.float64), up(inp["uLin"], np.float64), up(inp["uOld"], np.float64)
-        a.zt = up(inp["zt"] if inp.get("zt") is not None else np.zeros((B, 6)), np.float64)
-        a.xPredPrev = up(inp["xPredPrev"] if inp.get("xPredPrev") is not None else np.zeros((B, N + 1, 6)), np.float64)
-        a.hasPred = up(inp["hasPred"] if inp.get("hasPred") is not None else np.zeros(B), np.int32)
-        a.timeStep = up(inp["timeStep"] if inp.get("timeStep") is not None else np.zeros(B), np.int32)
-        a.xPred, a.uPred, a.slack = alloc(B * (N + 1) * 6 * 8), alloc(B * N * 2 * 8), alloc(B * N * 2 * 8)
-        a.lambda_, a.sTerm, a.ztNext, a.ztuNext = alloc(B * S * 8), alloc(B * 6 * 8), alloc(B * 6 * 8), alloc(B * 2 * 8)
-        a.ssSel = alloc(B * S * 6 * 8)
-        a.status, a.iters = alloc(B * 4), alloc(B * 4)
-        # A_i / B_i / C_i (MPC.A / B / C of the reference): the hand-over from the regression kernel to the solve kernel.  Caller-owned, so that
-        # launches can be queued back to back (a launch that used the context's own hand-over buffers is drained before the next one overwrites them)
-        a.A, a.Bm, a.C = alloc(B * N * 36 * 8), alloc(B * N * 12 * 8), alloc(B * N * 6 * 8)
-        if diagnostics:
-            a.qSel, a.mu, a.resid = alloc(B * S * 8), alloc(B * M * 8), alloc(B * 3 * 8)
+        # (A_i / B_i / C_i, MPC.A / B / C of the reference, are the hand-over from the regression kernel to the solve kernel.  Caller-owned here, so that launches
+        # can be queued back to back: a launch that used the context's own hand-over buffers is drained before the next one overwrites them)
+        keys = [k for k in STEP_IN_KEYS + STEP_OUT_KEYS if diagnostics or k not in DIAGNOSTIC_KEYS]
+        for k, (shp, dt) in array_specs(B, self.N, self.S, self.cfg.numSS_it, keys).items():
+            if k in STEP_IN_KEYS:                          # (x0, xLin, uLin, uOld must be given; the others default to zeros)
+                p = self.dev_array(np.ascontiguousarray(inp[k] if inp.get(k) is not None or k in ("x0", "xLin", "uLin", "uOld") else np.zeros(shp), dtype=dt))
+            else:
+                p = self.dev_alloc(max(int(np.prod(shp)) * np.dtype(dt).itemsize, 8))
+            keep.append(p); setattr(a, _FIELD[k], p)
         return a, keep
 
     def step_dev_fetch(self, a, B):
         """Download every output of a finished lmpc_step_batch_dev call (same keys as step_batch)."""
-        N, S, M = self.N, self.S, self.M
         self.sync()
-        out = dict(xPred=np.zeros((B, N + 1, 6)), uPred=np.zeros((B, N, 2)), slack=np.zeros((B, 2 * N)), lambd=np.zeros((B, S)),
-                   sTerm=np.zeros((B, 6)), ztNext=np.zeros((B, 6)), ztuNext=np.zeros((B, 2)), ssSel=np.zeros((B, S, 6)), qSel=np.zeros((B, S)),
-                   mu=np.zeros((B, M)), A=np.zeros((B, N, 6, 6)), B=np.zeros((B, N, 6, 2)), C=np.zeros((B, N, 6)),
-                   status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32), resid=np.zeros((B, 3)))
-        src = dict(xPred=a.xPred, uPred=a.uPred, slack=a.slack, lambd=a.lambda_, sTerm=a.sTerm, ztNext=a.ztNext, ztuNext=a.ztuNext, ssSel=a.ssSel,
-                   qSel=a.qSel, mu=a.mu, A=a.A, B=a.Bm, C=a.C, status=a.status, iters=a.iters, resid=a.resid)
+        out = self._zeros(STEP_OUT_KEYS, B)
         for k, arr in out.items():
-            if arr.nbytes and src[k]:                      # (diagnostic outputs that were not requested stay zero)
-                self.dev_download(src[k], arr)
+            src = getattr(a, _FIELD[k])
+            if arr.nbytes and src:                         # (diagnostic outputs that were not requested stay zero)
+                self.dev_download(src, arr)
         return out
 
     def plant_step_batch(self, x, x_glob, u, noise):

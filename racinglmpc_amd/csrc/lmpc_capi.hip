@@ -4,6 +4,7 @@
 #include "lmpc_variant.hip.h"
 #include "lmpc_noise.hip.h"
 #include "lmpc_track.hip.h"
+#include "lmpc_arrays.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 static thread_local std::string g_err;
@@ -50,6 +52,7 @@ static const char *dev_knob(const char *name) {
 #define LMPC_GUARD_BYTES 256
 static int g_guard_failures = 0;
 #ifdef LMPC_GUARD
+#define LMPC_SLAB_GAP LMPC_GUARD_BYTES      // (a zone behind every work-buffer range of the slabs as well, see check_slab_gaps)
 #include <map>
 #include <mutex>
 static std::map<void *, size_t> g_guarded; static std::mutex g_guard_mu;
@@ -76,6 +79,7 @@ static hipError_t g_free(void *p) {
     return hipFree(p);
 }
 #else
+#define LMPC_SLAB_GAP 0
 static hipError_t g_malloc_raw(void **p, size_t bytes) { return hipMalloc(p, bytes); }
 static hipError_t g_free(void *p) { return p ? hipFree(p) : hipSuccess; }
 #endif
@@ -94,14 +98,12 @@ struct lmpc_ctx {
     std::vector<int> s_laptime;              // LMPC.LapTime (rows at addTrajectory time)
     std::vector<double> s_qlast, s_q0;       // last / first Qfun value per lap
     std::vector<int> s_override;             // explicit selection (lmpc_ss_set_selected)
-    // device work buffers (host-pointer entry points), sized for max_batch
-    double *w_x0, *w_xLin, *w_uLin, *w_uOld, *w_zt, *w_xPP, *w_A, *w_B, *w_C, *w_ssSel, *w_qSel, *w_succ, *w_succU, *w_ztUsed;
-    double *w_xPred, *w_uPred, *w_slack, *w_lam, *w_sT, *w_mu, *w_ztN, *w_ztuN, *w_resid;
-    int *w_hasPred, *w_tstep, *w_status, *w_iters, *w_rstatus;
-    // the work buffers are ranges of two device slabs (inputs | outputs); small batches move each slab with ONE copy through pinned host
-    // mirrors (h_in / h_out) instead of one pageable copy per array -- 24 copies of ~10 us each were 60 % of a batch-1 lmpc_step_batch call
-    char *slab_in, *slab_out, *h_in, *h_out; size_t slab_in_bytes, slab_out_bytes;
-    char *dm_in, *dm_out;                    // device addresses of the host-mapped mirrors h_in / h_out (small contexts: the step kernels read / write them directly)
+    // Device work buffers of the host-pointer entry points, sized for max_batch: one pointer per array of lmpc_arrays.h, each a range of two device slabs
+    // (inputs | outputs, laid out by lmpc_slab_layout).  Small contexts also own host-mapped mirrors of both slabs (h_in / h_out) with the same layout: hm holds
+    // the host address of every range, dm the address the device sees -- a full batch of lmpc_step_batch then copies nothing, the kernels read and write the mirrors.
+    lmpc_arrays w, hm, dm;
+    lmpc_dims dims;                          // (N, S, numSS_it) the per-problem sizes of lmpc_arrays.h are taken at
+    char *slab_in, *slab_out, *h_in, *h_out;
     lmpc_variant_api var;                    // launchers of the (N, numSS_points) instantiation of the solve kernels in use
     void *var_dl;                            // dlopen handle when that instantiation lives in its own shared object (lmpc_variant.hip)
     int mw_max_batch, mw2_max_batch, n_cu;   // largest batch served by the four-wave / the two-wave solve kernel
@@ -115,7 +117,6 @@ struct lmpc_ctx {
     struct pending_solve { lmpc_solve_io io; int B; int epoch; lmpc_dev_params dp; bool shared_abc; };   // dp: the parameter block (selected laps, store pointers) of the launch
     std::vector<pending_solve> pending; int *h_retry, *d_retry; int epoch;
     size_t ab_pack_cap;                      // problems ab_pack holds
-    int *w_selStart;                         // lmpc_select_batch: window starts, max_batch x numSS_it
     void *scr_dev; size_t scr_bytes;         // pooled scratch of the small host-buffer entry points (plant step, global position)
     std::vector<char *> gaps;                // guard builds: the 256-byte zones between the work-buffer ranges of the slabs
     unsigned create_flags; int solver_kind;  // lmpc_create_ex flags; which solve kernels serve this context: 0 built-in, 1 variant library, 2 the runtime-(N, S) kernel
@@ -239,8 +240,15 @@ static void fill_params(lmpc_ctx *c) {
 }  // extern "C" (helpers)
 
 #define LMPC_RETRY_RING 64
-#define LMPC_SLAB_COPY_MAX ((size_t)256 * 1024)     // one-copy path of lmpc_step_batch up to this many output bytes (batch 1 .. ~16)
+#define LMPC_SLAB_COPY_MAX ((size_t)256 * 1024)     // contexts whose output slab has at most this many bytes (batch 1 .. ~16) own host-mapped mirrors of their slabs
 
+template <class T> static T *mut(const T *p) { return const_cast<T *>(p); }      // (a caller's input array inside an lmpc_arrays: only ever the source of a copy)
+// temporaries of one call, freed when it returns on any path (not the pooled scratch: lmpc_assemble_batch wants hundreds of KB per problem, not to be kept for the context's life)
+struct call_temps {
+    std::vector<void *> held;
+    ~call_temps() { for (void *q : held) (void)hipFree(q); }
+    template <class T> hipError_t alloc(T **q, size_t bytes) { const hipError_t e = hipMalloc((void **)q, bytes); if (e == hipSuccess) held.push_back(*q); return e; }
+};
 // everything of lmpc_create that can fail; the caller destroys the context on any error (one failure path, no leaks)
 static int create_body(lmpc_ctx *c) {
     const lmpc_config *cfg = &c->cfg;
@@ -305,38 +313,26 @@ static int create_body(lmpc_ctx *c) {
     HIPCHK(hipMemset(c->mquant, 0, (size_t)cfg->max_laps * 3 * cfg->max_lap_len * sizeof(unsigned)));
     HIPCHK(hipMemset(c->mqpar, 0, (size_t)cfg->max_laps * c->mq_chunks * 6 * sizeof(double)));
     HIPCHK(hipMemset(c->sstore, 0, store_elems * sizeof(double)));
-    const size_t B = cfg->max_batch, N = cfg->N, S = cfg->numSS_it > 0 ? cfg->numSS_points : 0, M = 8 * N + S;
-    // two passes over the same list: sizes first, then pointers into the slabs (every range 256-byte aligned)
-    for (int pass = 0; pass < 2; pass++) {
-        size_t oi = 0, oo = 0;
-#ifdef LMPC_GUARD      // (guard builds: a 256-byte zone behind every work-buffer range, see check_slab_gaps)
-#define SLAB_GAP(slab, off) do { if (pass) c->gaps.push_back(c->slab + off); off += LMPC_GUARD_BYTES; } while (0)
-#else
-#define SLAB_GAP(slab, off) do { } while (0)
-#endif
-#define SLAB(ptr, n, slab, off) do { const size_t bytes_ = (std::max<size_t>((n), 1) * sizeof(*c->ptr) + 255) & ~(size_t)255; \
-                                     if (pass) c->ptr = (decltype(c->ptr))(c->slab + off); off += bytes_; SLAB_GAP(slab, off); } while (0)
-        SLAB(w_x0, B * 6, slab_in, oi); SLAB(w_xLin, B * (N + 1) * 6, slab_in, oi); SLAB(w_uLin, B * N * 2, slab_in, oi); SLAB(w_uOld, B * 2, slab_in, oi);
-        SLAB(w_zt, B * 6, slab_in, oi); SLAB(w_xPP, B * (N + 1) * 6, slab_in, oi); SLAB(w_hasPred, B, slab_in, oi); SLAB(w_tstep, B, slab_in, oi);
-        SLAB(w_xPred, B * (N + 1) * 6, slab_out, oo); SLAB(w_uPred, B * N * 2, slab_out, oo); SLAB(w_slack, B * N * 2, slab_out, oo); SLAB(w_lam, B * S, slab_out, oo);
-        SLAB(w_sT, B * 6, slab_out, oo); SLAB(w_ztN, B * 6, slab_out, oo); SLAB(w_ztuN, B * 2, slab_out, oo); SLAB(w_ssSel, B * S * 6, slab_out, oo);
-        SLAB(w_qSel, B * S, slab_out, oo); SLAB(w_mu, B * M, slab_out, oo); SLAB(w_A, B * N * 36, slab_out, oo); SLAB(w_B, B * N * 12, slab_out, oo);
-        SLAB(w_C, B * N * 6, slab_out, oo); SLAB(w_status, B, slab_out, oo); SLAB(w_iters, B, slab_out, oo); SLAB(w_resid, B * 3, slab_out, oo);
-        SLAB(w_succ, B * S * 6, slab_out, oo); SLAB(w_succU, B * S * 2, slab_out, oo); SLAB(w_ztUsed, B * 6, slab_out, oo); SLAB(w_rstatus, B * N, slab_out, oo);
-        SLAB(w_selStart, B * (size_t)std::max(cfg->numSS_it, 1), slab_out, oo);
-#undef SLAB
-#undef SLAB_GAP
-        if (pass) { for (char *g_ : c->gaps) HIPCHK(hipMemset(g_, 0xA5, LMPC_GUARD_BYTES)); }
-        if (!pass) {
-            c->slab_in_bytes = oi; c->slab_out_bytes = oo;
-            HIPCHK(g_malloc(&c->slab_in, oi)); HIPCHK(g_malloc(&c->slab_out, oo));
-            HIPCHK(hipMemset(c->slab_in, 0, oi)); HIPCHK(hipMemset(c->slab_out, 0, oo));
-            if (oo <= LMPC_SLAB_COPY_MAX) {
-                HIPCHK(hipHostMalloc(&c->h_in, oi, hipHostMallocMapped)); HIPCHK(hipHostMalloc(&c->h_out, oo, hipHostMallocMapped)); memset(c->h_in, 0, oi); memset(c->h_out, 0, oo);
-                HIPCHK(hipHostGetDevicePointer((void **)&c->dm_in, c->h_in, 0)); HIPCHK(hipHostGetDevicePointer((void **)&c->dm_out, c->h_out, 0));
-            }
-        }
+    c->dims = {(size_t)cfg->N, (size_t)(cfg->numSS_it > 0 ? cfg->numSS_points : 0), (size_t)cfg->numSS_it};
+    const size_t gap = LMPC_SLAB_GAP;
+    // two passes over the same layout: sizes first, then pointers into the slabs and their mirrors (every range 256-byte aligned)
+    size_t total[2];
+    lmpc_slab_layout(c->dims, (size_t)cfg->max_batch, gap, total, [](const char *, auto, int, size_t, size_t) {});
+    HIPCHK(g_malloc(&c->slab_in, total[0])); HIPCHK(g_malloc(&c->slab_out, total[1]));
+    HIPCHK(hipMemset(c->slab_in, 0, total[0])); HIPCHK(hipMemset(c->slab_out, 0, total[1]));
+    char *mapped[2] = {nullptr, nullptr};    // device addresses of the mirrors
+    if (total[1] <= LMPC_SLAB_COPY_MAX) {
+        HIPCHK(hipHostMalloc(&c->h_in, total[0], hipHostMallocMapped)); HIPCHK(hipHostMalloc(&c->h_out, total[1], hipHostMallocMapped)); memset(c->h_in, 0, total[0]); memset(c->h_out, 0, total[1]);
+        HIPCHK(hipHostGetDevicePointer((void **)&mapped[0], c->h_in, 0)); HIPCHK(hipHostGetDevicePointer((void **)&mapped[1], c->h_out, 0));
     }
+    char *const dev[2] = {c->slab_in, c->slab_out}, *const host[2] = {c->h_in, c->h_out};
+    lmpc_slab_layout(c->dims, (size_t)cfg->max_batch, gap, total, [&](const char *, auto m, int slab, size_t off, size_t bytes) {
+        typedef std::remove_reference_t<decltype(c->w.*m)> ptr_t;
+        c->w.*m = (ptr_t)(dev[slab] + off);
+        if (host[slab]) { c->hm.*m = (ptr_t)(host[slab] + off); c->dm.*m = (ptr_t)(mapped[slab] + off); }
+        if (gap) c->gaps.push_back(dev[slab] + off + bytes);
+    });
+    for (char *g_ : c->gaps) HIPCHK(hipMemset(g_, 0xA5, LMPC_GUARD_BYTES));
     return LMPC_OK;
 }
 
@@ -389,7 +385,7 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt};      // (the w_* work buffers are ranges of the two slabs)
+    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt};      // (the work buffers are ranges of the two slabs)
     check_slab_gaps(c);
     for (void *q : ptrs) if (q) (void)g_free(q);
     if (c->h_retry) (void)hipHostFree(c->h_retry);
@@ -403,13 +399,14 @@ int lmpc_destroy(lmpc_ctx *c) {
 
 static int resolve_retries(lmpc_ctx *c);
 // Every entry point that changes what a deferred retry pass would read -- the lap stores, caller-visible device buffers (lmpc_dev_upload), the
-// context's A / B / C hand-over buffers w_A / w_B / w_C (lmpc_regress_batch, lmpc_regress_points, lmpc_qp_solve_batch, lmpc_assemble_batch; a
+// context's A / B / C hand-over buffers (lmpc_regress_batch, lmpc_regress_points, lmpc_qp_solve_batch, lmpc_assemble_batch; a
 // lmpc_step_batch_dev launch with A / Bm / C NULL hands over through them and is the only kind of launch left pending) -- or hands results to
 // someone else (lmpc_comm_allgather_dev, lmpc_ss_get_qfun) first gives the launches still pending their retry pass: a flagged problem is then
 // re-solved against the data of ITS launch, never against a changed safe set or overwritten inputs.  (No launch pending -- the drop-in flow,
 // where lmpc_step_batch resolves before it returns -- costs nothing: no stream drain is added.)  The retry pass reads nothing else of the
 // context's: not the per-point regression status (it keeps the first pass's bits), not the [A_k | B_k] scratch (it stages them in LDS).
-#define RESOLVE_PENDING() do { const int rc_ = resolve_retries(c); if (rc_) return rc_; } while (0)
+#define RCCHK(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+#define RESOLVE_PENDING() RCCHK(resolve_retries(c))
 
 // ---------------------------------------------------------------------------------------------- stores
 // The reference keeps its laps in Python lists that grow without bound (PredictiveControllers.py:418-445, PredictiveModel.py:35-46; addPoint
@@ -829,7 +826,7 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     c->stats.n_solve++; if (io.mode & 2) c->stats.qp_solved += B;
-    if (deferred) c->pending.push_back({io, B, io.retry_epoch, c->dp, io.A == c->w_A || io.Bm == c->w_B || io.C == c->w_C});
+    if (deferred) c->pending.push_back({io, B, io.retry_epoch, c->dp, io.A == c->w.A || io.Bm == c->w.Bm || io.C == c->w.C});
     else if (io.mode & 2) {
         rc = c->var.launch_retry(c->stream, c->dp, B, io);
         if (rc) return rc;
@@ -841,14 +838,52 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
 #define H2D(dst, src, n) HIPCHK(hipMemcpyAsync(dst, src, sizeof(*(dst)) * (size_t)(n), hipMemcpyHostToDevice, c->stream))
 #define D2H(dst, src, n) do { if (dst) HIPCHK(hipMemcpyAsync(dst, src, sizeof(*(src)) * (size_t)(n), hipMemcpyDeviceToHost, c->stream)); } while (0)
 
-// iteration counts of the batch just solved into the work buffers: copied to the caller (if asked) and added to lmpc_stats.ipm_iters
-// (host-buffer entry points only: the device-resident path leaves the counts in the caller's device buffer)
-static int fetch_iters(lmpc_ctx *c, int B, int *iters) {
-    std::vector<int> tmp; int *dst = iters;
-    if (!dst) { tmp.resize((size_t)B); dst = tmp.data(); }
-    HIPCHK(hipMemcpyAsync(dst, c->w_iters, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < B; b++) c->stats.ipm_iters += dst[b];
+// For B problems, copy every array that both sides name: a NULL pointer on either side skips the array, and so does an array without elements (S = 0).
+// src_first: the first problem on the source side.  hipMemcpyHostToHost: the host-mapped mirrors, a plain memcpy; else asynchronous on the context's stream.
+static int copy_arrays(lmpc_ctx *c, size_t B, const lmpc_dims &d, const lmpc_arrays &dst, const lmpc_arrays &src, hipMemcpyKind kind, size_t src_first = 0) {
+    hipError_t e = hipSuccess;
+    lmpc_arrays_each(d, [&](const char *, auto m, size_t elem, size_t n, int) {
+        if (!(dst.*m) || !(src.*m) || !n || e != hipSuccess) return;
+        if (kind == hipMemcpyHostToHost) memcpy(dst.*m, src.*m + src_first * n, elem * n * B);
+        else e = hipMemcpyAsync(dst.*m, src.*m + src_first * n, elem * n * B, kind, c->stream);
+    });
+    return e == hipSuccess ? LMPC_OK : set_err(LMPC_E_HIP, "hipMemcpyAsync", hipGetErrorString(e));
+}
+// hasPred / timeStep a caller did not give are zeros in the work buffers
+static int zero_absent_flags(lmpc_ctx *c, int B, const lmpc_arrays &in) {
+    if (!in.hasPred) HIPCHK(hipMemsetAsync(c->w.hasPred, 0, sizeof(int) * B, c->stream));
+    if (!in.timeStep) HIPCHK(hipMemsetAsync(c->w.timeStep, 0, sizeof(int) * B, c->stream));
+    return LMPC_OK;
+}
+// What a solve launch reads and writes, from a set of arrays.  mode bit 0 (selection on the device): the selection's inputs and its outputs, else ssSel / qSel are
+// inputs; bit 1 (QP solve): the QP's data and its answer.  An array the caller does not want written it leaves NULL in `a`; what is special to one caller
+// (rstatus, tbuf, the fused step's xLin / uLin / Aout / Bout / Cout) it sets itself.
+static lmpc_solve_io solve_io(int mode, const lmpc_arrays &a) {
+    lmpc_solve_io io; memset(&io, 0, sizeof(io));
+    io.mode = mode; io.x0 = a.x0; io.status = a.status; io.iters = a.iters;
+    if (mode & 1) {
+        io.zt = a.zt; io.xPredPrev = a.xPredPrev; io.hasPred = a.hasPred; io.timeStep = a.timeStep;
+        io.ssSelOut = a.ssSel; io.qSelOut = a.qSel; io.succOut = a.succ; io.succUOut = a.succU; io.ztUsed = a.ztUsed; io.selStartOut = a.selStart;
+    } else { io.ssSelIn = a.ssSel; io.qSelIn = a.qSel; }
+    if (mode & 2) {
+        io.A = a.A; io.Bm = a.Bm; io.C = a.C; io.uOld = a.uOld;
+        io.xPred = a.xPred; io.uPred = a.uPred; io.slack = a.slack; io.lambda = a.lambda; io.sTerm = a.sTerm; io.mu = a.mu;
+        io.ztNext = a.ztNext; io.ztuNext = a.ztuNext; io.resid = a.resid;
+    }
+    return io;
+}
+
+// iteration counts of the batch just solved into the work buffers: copied to the caller (if asked) and added to lmpc_stats.ipm_iters; synchronises the stream.  mirror: they
+// are on the host already (host-mapped route of lmpc_step_batch) and only added.  (host-buffer entry points only: the device-resident path leaves them in the caller's buffer)
+static int fetch_iters(lmpc_ctx *c, int B, int *iters, const int *mirror = nullptr) {
+    std::vector<int> tmp;
+    if (!mirror) {
+        if (!iters) { tmp.resize((size_t)B); iters = tmp.data(); }
+        HIPCHK(hipMemcpyAsync(iters, c->w.iters, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        mirror = iters;
+    }
+    for (int b = 0; b < B; b++) c->stats.ipm_iters += mirror[b];
     return LMPC_OK;
 }
 
@@ -856,11 +891,13 @@ int lmpc_regress_batch(lmpc_ctx *c, int B, const double *xLin, int xLinRowStride
     ARGCHK(c && xLin && uLin && A && Bm && C && B >= 1 && B <= c->cfg.max_batch);
     const int N = c->cfg.N;
     ARGCHK(xLinRowStride == N * 6 || xLinRowStride == (N + 1) * 6);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (a pending launch may hand its A / B / C over through w_A / w_B / w_C: its retry pass first)
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (a pending launch may hand its A / B / C over through the work buffers: its retry pass first)
     { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows: refused before anything is queued)
-    H2D(c->w_xLin, xLin, (size_t)B * xLinRowStride); H2D(c->w_uLin, uLin, (size_t)B * N * 2);
-    int rc = launch_regress(c, B, c->w_xLin, xLinRowStride, c->w_uLin, c->w_A, c->w_B, c->w_C, c->w_rstatus); if (rc) return rc;
-    D2H(A, c->w_A, (size_t)B * N * 36); D2H(Bm, c->w_B, (size_t)B * N * 12); D2H(C, c->w_C, (size_t)B * N * 6); D2H(status, c->w_rstatus, (size_t)B * N);
+    lmpc_arrays in = {}, out = {}; in.uLin = mut(uLin); out.A = A; out.Bm = Bm; out.C = C; out.rstatus = status;
+    H2D(c->w.xLin, xLin, (size_t)B * xLinRowStride);                 // (rows of N or N + 1 points: the caller's stride, not the table's size)
+    RCCHK(copy_arrays(c, B, c->dims, c->w, in, hipMemcpyHostToDevice));
+    RCCHK(launch_regress(c, B, c->w.xLin, xLinRowStride, c->w.uLin, c->w.A, c->w.Bm, c->w.C, c->w.rstatus));
+    RCCHK(copy_arrays(c, B, c->dims, out, c->w, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
@@ -878,19 +915,22 @@ int lmpc_regress_points(lmpc_ctx *c, int n, const double *x, const double *u, do
     ARGCHK(c && x && u && A && Bm && C && n >= 1 && (long long)n <= (long long)c->cfg.max_batch * c->cfg.N);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
     k1_table tab; { const int rc = k1_table_for(c, n, &tab); if (rc) return rc; }      // (point e uses row e)
-    H2D(c->w_xLin, x, (size_t)n * 6); H2D(c->w_uLin, u, (size_t)n * 2);
+    const lmpc_dims one = {1, c->dims.S, c->dims.L};                 // n problems of horizon 1: the table's sizes of uLin, A, Bm, C, rstatus
+    lmpc_arrays in = {}, out = {}; in.uLin = mut(u); out.A = A; out.Bm = Bm; out.C = C; out.rstatus = status;
+    H2D(c->w.xLin, x, (size_t)n * 6);                                // (one row per point, not the two of a horizon-1 trajectory)
+    RCCHK(copy_arrays(c, n, one, c->w, in, hipMemcpyHostToDevice));
     int rc = refresh_params(c, true, false, tab.dev != nullptr); if (rc) return rc;
     {
         const lmpc_dev_params keep = c->dp;
         c->dp.N = 1;                                                     // (launch_k1 passes c->dp by value)
         ev_begin(c, 0);
-        launch_k1(c, n, n, 1, c->w_xLin, 6, c->w_uLin, c->w_A, c->w_B, c->w_C, c->w_rstatus, tab);
+        launch_k1(c, n, n, 1, c->w.xLin, 6, c->w.uLin, c->w.A, c->w.Bm, c->w.C, c->w.rstatus, tab);
         ev_end(c);
         c->dp = keep;
     }
     HIPCHK(hipGetLastError());
     c->stats.n_regress++;
-    D2H(A, c->w_A, (size_t)n * 36); D2H(Bm, c->w_B, (size_t)n * 12); D2H(C, c->w_C, (size_t)n * 6); D2H(status, c->w_rstatus, (size_t)n);
+    RCCHK(copy_arrays(c, n, one, out, c->w, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
@@ -899,76 +939,69 @@ int lmpc_select_batch(lmpc_ctx *c, int B, const double *x0, const double *zt, co
                       double *ssSel, double *qSel, double *succ, double *succU, double *ztUsed, int *selStart, int *status) {
     ARGCHK(c && x0 && zt && B >= 1 && B <= c->cfg.max_batch && c->cfg.numSS_it > 0);
     ARGCHK(pred_args_ok(B, xPredPrev, hasPred));
-    const int N = c->cfg.N, S = c->cfg.numSS_points;
     HIPCHK(hipSetDevice(c->cfg.device));
-    H2D(c->w_x0, x0, (size_t)B * 6); H2D(c->w_zt, zt, (size_t)B * 6);
-    if (xPredPrev) H2D(c->w_xPP, xPredPrev, (size_t)B * (N + 1) * 6);
-    if (hasPred) H2D(c->w_hasPred, hasPred, B); else HIPCHK(hipMemsetAsync(c->w_hasPred, 0, sizeof(int) * B, c->stream));
-    if (timeStep) H2D(c->w_tstep, timeStep, B); else HIPCHK(hipMemsetAsync(c->w_tstep, 0, sizeof(int) * B, c->stream));
-    lmpc_solve_io io; memset(&io, 0, sizeof(io));
-    io.mode = 1; io.x0 = c->w_x0; io.zt = c->w_zt; io.xPredPrev = c->w_xPP; io.hasPred = c->w_hasPred; io.timeStep = c->w_tstep;
-    io.ssSelOut = c->w_ssSel; io.qSelOut = c->w_qSel; io.succOut = c->w_succ; io.succUOut = c->w_succU; io.ztUsed = c->w_ztUsed; io.status = c->w_status; io.iters = c->w_iters;
-    io.selStartOut = c->w_selStart;
-    int rc = launch_solve(c, B, io); if (rc) return rc;
-    D2H(selStart, c->w_selStart, (size_t)B * c->cfg.numSS_it);
-    D2H(ssSel, c->w_ssSel, (size_t)B * S * 6); D2H(qSel, c->w_qSel, (size_t)B * S); D2H(succ, c->w_succ, (size_t)B * S * 6); D2H(succU, c->w_succU, (size_t)B * S * 2);
-    D2H(ztUsed, c->w_ztUsed, (size_t)B * 6); D2H(status, c->w_status, B);
+    lmpc_arrays in = {}, out = {};
+    in.x0 = mut(x0); in.zt = mut(zt); in.xPredPrev = mut(xPredPrev); in.hasPred = mut(hasPred); in.timeStep = mut(timeStep);
+    out.ssSel = ssSel; out.qSel = qSel; out.succ = succ; out.succU = succU; out.ztUsed = ztUsed; out.selStart = selStart; out.status = status;
+    RCCHK(copy_arrays(c, B, c->dims, c->w, in, hipMemcpyHostToDevice)); RCCHK(zero_absent_flags(c, B, in));
+    RCCHK(launch_solve(c, B, solve_io(1, c->w)));
+    RCCHK(copy_arrays(c, B, c->dims, out, c->w, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
+
+// the data of a batch of QPs given as host arrays (lmpc_qp_solve_batch, lmpc_assemble_batch, lmpc_debug_timing) into the work buffers
+static int upload_qp(lmpc_ctx *c, int B, const double *A, const double *Bm, const double *C, const double *x0, const double *uOld, const double *ssSel, const double *qSel) {
+    lmpc_arrays in = {}; in.A = mut(A); in.Bm = mut(Bm); in.C = mut(C); in.x0 = mut(x0); in.uOld = mut(uOld); in.ssSel = mut(ssSel); in.qSel = mut(qSel);
+    return copy_arrays(c, B, c->dims, c->w, in, hipMemcpyHostToDevice);
+}
+// the arrays a plain solve of such a batch works on: everything but ztNext / ztuNext, which these entry points do not return
+static lmpc_arrays qp_arrays(const lmpc_ctx *c) { lmpc_arrays a = c->w; a.ztNext = a.ztuNext = nullptr; return a; }
 
 int lmpc_qp_solve_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, const double *C, const double *x0, const double *uOld,
                         const double *ssSel, const double *qSel, double *xPred, double *uPred, double *slack, double *lambda, double *sTerm,
                         double *mu, int *status, int *iters, double *resid) {
     ARGCHK(c && A && Bm && C && x0 && uOld && xPred && uPred && B >= 1 && B <= c->cfg.max_batch);
-    const int N = c->cfg.N, S = c->cfg.numSS_it > 0 ? c->cfg.numSS_points : 0, M = 8 * N + S;
-    if (S > 0) ARGCHK(ssSel && qSel);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch: the copies below overwrite w_A / w_B / w_C)
-    H2D(c->w_A, A, (size_t)B * N * 36); H2D(c->w_B, Bm, (size_t)B * N * 12); H2D(c->w_C, C, (size_t)B * N * 6);
-    H2D(c->w_x0, x0, (size_t)B * 6); H2D(c->w_uOld, uOld, (size_t)B * 2);
-    if (S > 0) { H2D(c->w_ssSel, ssSel, (size_t)B * S * 6); H2D(c->w_qSel, qSel, (size_t)B * S); }
-    lmpc_solve_io io; memset(&io, 0, sizeof(io));
-    io.mode = 2; io.A = c->w_A; io.Bm = c->w_B; io.C = c->w_C; io.x0 = c->w_x0; io.uOld = c->w_uOld; io.ssSelIn = c->w_ssSel; io.qSelIn = c->w_qSel;
-    io.xPred = c->w_xPred; io.uPred = c->w_uPred; io.slack = c->w_slack; io.lambda = c->w_lam; io.sTerm = c->w_sT; io.mu = c->w_mu; io.resid = c->w_resid;
-    io.status = c->w_status; io.iters = c->w_iters;
-    int rc = launch_solve(c, B, io); if (rc) return rc;
-    rc = resolve_retries(c); if (rc) return rc;          // drains the stream; a flagged problem gets its retry pass before anything is copied out
-    D2H(xPred, c->w_xPred, (size_t)B * (N + 1) * 6); D2H(uPred, c->w_uPred, (size_t)B * N * 2); D2H(slack, c->w_slack, (size_t)B * N * 2);
-    if (S > 0) { D2H(lambda, c->w_lam, (size_t)B * S); D2H(sTerm, c->w_sT, (size_t)B * 6); }
-    D2H(mu, c->w_mu, (size_t)B * M); D2H(status, c->w_status, B); D2H(resid, c->w_resid, (size_t)B * 3);
+    const bool term = c->dims.S > 0;
+    if (term) ARGCHK(ssSel && qSel);
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch: the copies below overwrite the A / B / C work buffers)
+    RCCHK(upload_qp(c, B, A, Bm, C, x0, uOld, ssSel, qSel));
+    RCCHK(launch_solve(c, B, solve_io(2, qp_arrays(c))));
+    RCCHK(resolve_retries(c));                           // drains the stream; a flagged problem gets its retry pass before anything is copied out
+    lmpc_arrays out = {};
+    out.xPred = xPred; out.uPred = uPred; out.slack = slack; out.mu = mu; out.status = status; out.resid = resid;
+    if (term) { out.lambda = lambda; out.sTerm = sTerm; }
+    RCCHK(copy_arrays(c, B, c->dims, out, c->w, hipMemcpyDeviceToHost));
     return fetch_iters(c, B, iters);                     // synchronises the stream
 }
 
-int lmpc_step_batch_dev(lmpc_ctx *c, int B, const lmpc_step_dev_args *a) {
-    ARGCHK(c && a && B >= 1 && a->x0 && a->xLin && a->uLin && a->uOld && a->xPred && a->uPred && a->status && a->iters);
+// one step on device arrays: the body of lmpc_step_batch_dev, which lmpc_step_batch runs on the work buffers or their host-mapped mirrors
+static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
+    ARGCHK(B >= 1 && a.x0 && a.xLin && a.uLin && a.uOld && a.xPred && a.uPred && a.status && a.iters);
     const int N = c->cfg.N; const bool term = c->cfg.numSS_it > 0;
-    if (term) ARGCHK(a->zt != nullptr);
-    ARGCHK(!a->hasPred || a->xPredPrev);                 // (device arrays: a set hasPred[b] would dereference the missing predictions inside the kernel)
+    if (term) ARGCHK(a.zt != nullptr);
+    ARGCHK(!a.hasPred || a.xPredPrev);                   // (device arrays: a set hasPred[b] would dereference the missing predictions inside the kernel)
     HIPCHK(hipSetDevice(c->cfg.device));
     ARGCHK(B <= c->cfg.max_batch);                      // the work buffers (per-point regression status, A, B, C hand-over) are sized for max_batch
-    lmpc_solve_io io; memset(&io, 0, sizeof(io));
     // Regression kernel, then the solve kernel; A, Bm, C are optional outputs (the hand-over then uses the context's work buffers).
     // With LMPC_FUSE=1 batches that run one wave per QP take the fused step instead: every wave runs the regression of its own QP in
     // front of the solve and [A_k | B_k], C_k never leave LDS (see lmpc_create for the measurement that keeps it off by default).
     { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows: refused before anything is queued)
     // (a lap table in force: the fused form reads the laps of the parameter block -- it lives in the variant libraries -- so the two-kernel step runs)
     const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0;
-    double *dA = a->A ? a->A : c->w_A, *dB = a->Bm ? a->Bm : c->w_B, *dC = a->C ? a->C : c->w_C;
+    double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
     // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
     // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
     // A / Bm / C (racinglmpc_amd._capi.Context.step_dev_buffers does) and keep every buffer of a launch untouched until lmpc_dev_sync.
-    if (dA == c->w_A || dB == c->w_B || dC == c->w_C) for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
-    if (fused) { io.mode = 4; io.xLin = a->xLin; io.uLin = a->uLin; io.Aout = a->A; io.Bout = a->Bm; io.Cout = a->C; if (int rc = refresh_params(c, true, false)) return rc; }
-    else { int rc = launch_regress(c, B, a->xLin, (N + 1) * 6, a->uLin, dA, dB, dC, c->w_rstatus); if (rc) return rc; io.rstatus = c->w_rstatus; }
-    int rc = 0;
-    io.mode |= term ? 3 : 2; io.A = dA; io.Bm = dB; io.C = dC; io.x0 = a->x0; io.uOld = a->uOld;
-    io.zt = a->zt; io.xPredPrev = a->xPredPrev; io.hasPred = a->hasPred; io.timeStep = a->timeStep;
-    io.xPred = a->xPred; io.uPred = a->uPred; io.slack = a->slack; io.lambda = a->lambda; io.sTerm = a->sTerm; io.mu = a->mu;
-    io.ztNext = a->ztNext; io.ztuNext = a->ztuNext; io.ssSelOut = a->ssSel; io.qSelOut = a->qSel; io.resid = a->resid; io.status = a->status; io.iters = a->iters;
+    if (dA == c->w.A || dB == c->w.Bm || dC == c->w.C) for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
+    lmpc_solve_io io = solve_io((fused ? 4 : 0) | (term ? 3 : 2), a);
+    io.A = dA; io.Bm = dB; io.C = dC;
     // (io.rstatus / the fused regression: a singular regression or an off-track linearisation point marks status[b]; the reference raises there)
-    rc = launch_solve(c, B, io);
-    return rc;
+    if (fused) { io.xLin = a.xLin; io.uLin = a.uLin; io.Aout = a.A; io.Bout = a.Bm; io.Cout = a.C; RCCHK(refresh_params(c, true, false)); }
+    else { RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, dA, dB, dC, c->w.rstatus)); io.rstatus = c->w.rstatus; }
+    return launch_solve(c, B, io);
 }
+int lmpc_step_batch_dev(lmpc_ctx *c, int B, const lmpc_step_dev_args *a) { ARGCHK(c && a); return step_dev(c, B, lmpc_step_arrays(*a)); }
 
 int lmpc_step_batch(lmpc_ctx *c, int B, const double *x0, const double *xLin, const double *uLin, const double *uOld, const double *zt,
                     const double *xPredPrev, const int *hasPred, const int *timeStep, double *xPred, double *uPred, double *slack, double *lambda,
@@ -976,84 +1009,47 @@ int lmpc_step_batch(lmpc_ctx *c, int B, const double *x0, const double *xLin, co
                     int *status, int *iters, double *resid) {
     ARGCHK(c && x0 && xLin && uLin && uOld && xPred && uPred && B >= 1 && B <= c->cfg.max_batch);
     ARGCHK(pred_args_ok(B, xPredPrev, hasPred));
-    const int N = c->cfg.N; const bool term = c->cfg.numSS_it > 0; const int S = term ? c->cfg.numSS_points : 0;
+    const bool term = c->cfg.numSS_it > 0;
     if (term) ARGCHK(zt != nullptr);
     HIPCHK(hipSetDevice(c->cfg.device));
     { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows)
-    const bool one_copy = c->h_in && B == c->cfg.max_batch;          // small contexts (the drop-in classes: max_batch = 1): one copy each way
+    // the caller's arrays by the table's names (a NULL output is not wanted).  Plain MPC: the S = 0 kernels read no zt / xPredPrev / hasPred / timeStep and write no
+    // lambda / sTerm / ssSel / qSel.  hasPred counts only with the predictions it speaks of; it and timeStep are zeros when not given.
+    lmpc_arrays in = {}, out = {};
+    in.x0 = mut(x0); in.xLin = mut(xLin); in.uLin = mut(uLin); in.uOld = mut(uOld);
+    if (term) { in.zt = mut(zt); in.xPredPrev = mut(xPredPrev); in.hasPred = mut(xPredPrev ? hasPred : nullptr); in.timeStep = mut(timeStep); }
+    out.xPred = xPred; out.uPred = uPred; out.slack = slack; out.mu = mu; out.ztNext = ztNext; out.ztuNext = ztuNext; out.A = Aout; out.Bm = Bout; out.C = Cout;
+    out.status = status; out.iters = iters; out.resid = resid; if (term) { out.lambda = lambda; out.sTerm = sTerm; out.ssSel = ssSel; out.qSel = qSel; }
+    // Two routes.  A full batch of a small context (the drop-in classes: max_batch = 1) runs on the HOST-MAPPED mirrors of the slabs: the kernels read the inputs from and
+    // write the outputs to host memory -- no hipMemcpyAsync in either direction and ONE drain of the stream per call (two copies and two drains were ~25 us of a 0.24 ms
+    // LMPC.solve); a few KB cross the host link inside the kernels instead.  Any other call copies array by array to and from the work buffers.
+    const bool mapped = c->h_in && B == c->cfg.max_batch;
     const auto tr0 = std::chrono::steady_clock::now();
-    if (one_copy) {
-#define STAGE(wptr, src, n) memcpy(c->h_in + ((char *)c->wptr - c->slab_in), src, sizeof(*c->wptr) * (size_t)(n))
-        STAGE(w_x0, x0, (size_t)B * 6); STAGE(w_xLin, xLin, (size_t)B * (N + 1) * 6); STAGE(w_uLin, uLin, (size_t)B * N * 2); STAGE(w_uOld, uOld, (size_t)B * 2);
-        memset(c->h_in + ((char *)c->w_hasPred - c->slab_in), 0, sizeof(int) * B); memset(c->h_in + ((char *)c->w_tstep - c->slab_in), 0, sizeof(int) * B);
-        if (term) {
-            STAGE(w_zt, zt, (size_t)B * 6);
-            if (xPredPrev) STAGE(w_xPP, xPredPrev, (size_t)B * (N + 1) * 6);
-            if (hasPred && xPredPrev) STAGE(w_hasPred, hasPred, B);
-            if (timeStep) STAGE(w_tstep, timeStep, B);
-        }
-#undef STAGE
-        if (!c->dm_in) HIPCHK(hipMemcpyAsync(c->slab_in, c->h_in, c->slab_in_bytes, hipMemcpyHostToDevice, c->stream));
+    lmpc_arrays a = lmpc_step_arrays(mapped ? c->dm : c->w);
+    if (mapped) {
+        memset(c->hm.hasPred, 0, sizeof(int) * B); memset(c->hm.timeStep, 0, sizeof(int) * B);
+        RCCHK(copy_arrays(c, B, c->dims, c->hm, in, hipMemcpyHostToHost));
+        // (A, B, C asked for: the regression writes them to the host, the solve reads them back at its start; else they stay on the device)
+        if (!Aout && !Bout && !Cout) { a.A = c->w.A; a.Bm = c->w.Bm; a.C = c->w.C; }
     } else {
-    H2D(c->w_x0, x0, (size_t)B * 6); H2D(c->w_xLin, xLin, (size_t)B * (N + 1) * 6); H2D(c->w_uLin, uLin, (size_t)B * N * 2); H2D(c->w_uOld, uOld, (size_t)B * 2);
-    if (term) {
-        H2D(c->w_zt, zt, (size_t)B * 6);
-        if (xPredPrev) H2D(c->w_xPP, xPredPrev, (size_t)B * (N + 1) * 6);
-        if (hasPred && xPredPrev) H2D(c->w_hasPred, hasPred, B); else HIPCHK(hipMemsetAsync(c->w_hasPred, 0, sizeof(int) * B, c->stream));
-        if (timeStep) H2D(c->w_tstep, timeStep, B); else HIPCHK(hipMemsetAsync(c->w_tstep, 0, sizeof(int) * B, c->stream));
-    }
-    }
-    lmpc_step_dev_args a; memset(&a, 0, sizeof(a));
-    a.x0 = c->w_x0; a.xLin = c->w_xLin; a.uLin = c->w_uLin; a.uOld = c->w_uOld; a.zt = c->w_zt; a.xPredPrev = c->w_xPP; a.hasPred = c->w_hasPred; a.timeStep = c->w_tstep;
-    a.xPred = c->w_xPred; a.uPred = c->w_uPred; a.slack = c->w_slack; a.lambda = c->w_lam; a.sTerm = c->w_sT; a.ztNext = c->w_ztN; a.ztuNext = c->w_ztuN;
-    a.ssSel = c->w_ssSel; a.qSel = c->w_qSel; a.A = c->w_A; a.Bm = c->w_B; a.C = c->w_C; a.mu = c->w_mu; a.resid = c->w_resid; a.status = c->w_status; a.iters = c->w_iters;
-    const bool zero_copy = one_copy && c->dm_in && c->dm_out;
-    if (zero_copy) {
-        // Small contexts (the drop-in classes: one QP per call): the kernels read the inputs from and write the outputs to HOST-MAPPED memory --
-        // no hipMemcpyAsync in either direction and ONE drain of the stream per call (two copies and two drains were ~25 us of a 0.24 ms LMPC.solve).
-        // A few KB cross the host link inside the kernels instead (every array is read once at a kernel's start, loads issued together).
-#define MAP_IN(f, w) a.f = (decltype(a.f))(c->dm_in + ((char *)c->w - c->slab_in))
-#define MAP_OUT(f, w) a.f = (decltype(a.f))(c->dm_out + ((char *)c->w - c->slab_out))
-        MAP_IN(x0, w_x0); MAP_IN(xLin, w_xLin); MAP_IN(uLin, w_uLin); MAP_IN(uOld, w_uOld); MAP_IN(zt, w_zt); MAP_IN(xPredPrev, w_xPP); MAP_IN(hasPred, w_hasPred); MAP_IN(timeStep, w_tstep);
-        MAP_OUT(xPred, w_xPred); MAP_OUT(uPred, w_uPred); MAP_OUT(slack, w_slack); MAP_OUT(lambda, w_lam); MAP_OUT(sTerm, w_sT); MAP_OUT(ztNext, w_ztN); MAP_OUT(ztuNext, w_ztuN);
-        MAP_OUT(ssSel, w_ssSel); MAP_OUT(qSel, w_qSel); MAP_OUT(mu, w_mu); MAP_OUT(resid, w_resid); MAP_OUT(status, w_status); MAP_OUT(iters, w_iters);
-        if (Aout || Bout || Cout) { MAP_OUT(A, w_A); MAP_OUT(Bm, w_B); MAP_OUT(C, w_C); }      // (asked for: the regression writes them to the host, the solve reads them back at its start)
-#undef MAP_IN
-#undef MAP_OUT
+        RCCHK(copy_arrays(c, B, c->dims, c->w, in, hipMemcpyHostToDevice));
+        if (term) RCCHK(zero_absent_flags(c, B, in));
     }
     const auto tr1 = std::chrono::steady_clock::now();
-    int rc = lmpc_step_batch_dev(c, B, &a); if (rc) return rc;
+    RCCHK(step_dev(c, B, a));
     const auto tr2 = std::chrono::steady_clock::now();
-    rc = resolve_retries(c); if (rc) return rc;          // drains the stream; a flagged problem gets its retry pass before anything is copied out
+    RCCHK(resolve_retries(c));                           // drains the stream; a flagged problem gets its retry pass before anything is copied out
     const auto tr3 = std::chrono::steady_clock::now();
-    if (one_copy) {
-        if (!zero_copy) {
-            // everything up to (not including) the selection-only buffers w_succ ..: one copy into the pinned mirror, then plain memcpys
-            const size_t nbytes = (size_t)((char *)c->w_succ - c->slab_out);
-            HIPCHK(hipMemcpyAsync(c->h_out, c->slab_out, nbytes, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-        }
-#define UNSTAGE(dst, wptr, n) do { if (dst) memcpy(dst, c->h_out + ((char *)c->wptr - c->slab_out), sizeof(*c->wptr) * (size_t)(n)); } while (0)
-        UNSTAGE(xPred, w_xPred, (size_t)B * (N + 1) * 6); UNSTAGE(uPred, w_uPred, (size_t)B * N * 2); UNSTAGE(slack, w_slack, (size_t)B * N * 2);
-        if (term) { UNSTAGE(lambda, w_lam, (size_t)B * S); UNSTAGE(sTerm, w_sT, (size_t)B * 6); UNSTAGE(ssSel, w_ssSel, (size_t)B * S * 6); UNSTAGE(qSel, w_qSel, (size_t)B * S); }
-        UNSTAGE(mu, w_mu, (size_t)B * (8 * N + S)); UNSTAGE(ztNext, w_ztN, (size_t)B * 6); UNSTAGE(ztuNext, w_ztuN, (size_t)B * 2);
-        UNSTAGE(Aout, w_A, (size_t)B * N * 36); UNSTAGE(Bout, w_B, (size_t)B * N * 12); UNSTAGE(Cout, w_C, (size_t)B * N * 6);
-        UNSTAGE(status, w_status, B); UNSTAGE(resid, w_resid, (size_t)B * 3); UNSTAGE(iters, w_iters, B);
-#undef UNSTAGE
-        const int *it_ = (const int *)(c->h_out + ((char *)c->w_iters - c->slab_out));
-        for (int b = 0; b < B; b++) c->stats.ipm_iters += it_[b];
-        const auto tr4 = std::chrono::steady_clock::now();
-        c->tr_s[0] += std::chrono::duration<double>(tr1 - tr0).count(); c->tr_s[1] += std::chrono::duration<double>(tr2 - tr1).count();
-        c->tr_s[2] += std::chrono::duration<double>(tr3 - tr2).count(); c->tr_s[3] += std::chrono::duration<double>(tr4 - tr3).count(); c->tr_n++;
-        return LMPC_OK;
+    if (!mapped) {
+        out.iters = nullptr;                             // (fetch_iters copies them)
+        RCCHK(copy_arrays(c, B, c->dims, out, c->w, hipMemcpyDeviceToHost));
+        return fetch_iters(c, B, iters);                 // synchronises the stream
     }
-    D2H(xPred, c->w_xPred, (size_t)B * (N + 1) * 6); D2H(uPred, c->w_uPred, (size_t)B * N * 2); D2H(slack, c->w_slack, (size_t)B * N * 2);
-    if (term) { D2H(lambda, c->w_lam, (size_t)B * S); D2H(sTerm, c->w_sT, (size_t)B * 6); D2H(ssSel, c->w_ssSel, (size_t)B * S * 6); D2H(qSel, c->w_qSel, (size_t)B * S); }
-    D2H(mu, c->w_mu, (size_t)B * (8 * N + S));
-    D2H(ztNext, c->w_ztN, (size_t)B * 6); D2H(ztuNext, c->w_ztuN, (size_t)B * 2);
-    D2H(Aout, c->w_A, (size_t)B * N * 36); D2H(Bout, c->w_B, (size_t)B * N * 12); D2H(Cout, c->w_C, (size_t)B * N * 6);
-    D2H(status, c->w_status, B); D2H(resid, c->w_resid, (size_t)B * 3);
-    rc = fetch_iters(c, B, iters); if (rc) return rc;    // synchronises the stream
+    RCCHK(copy_arrays(c, B, c->dims, out, c->hm, hipMemcpyHostToHost));
+    RCCHK(fetch_iters(c, B, nullptr, c->hm.iters));
+    const auto tr4 = std::chrono::steady_clock::now();
+    c->tr_s[0] += std::chrono::duration<double>(tr1 - tr0).count(); c->tr_s[1] += std::chrono::duration<double>(tr2 - tr1).count();
+    c->tr_s[2] += std::chrono::duration<double>(tr3 - tr2).count(); c->tr_s[3] += std::chrono::duration<double>(tr4 - tr3).count(); c->tr_n++;
     return LMPC_OK;
 }
 
@@ -1071,20 +1067,16 @@ int lmpc_assemble_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
                         const double *ssSel, const double *qSel, double *Pdense, double *q, double *Adense, double *l, double *u) {
     ARGCHK(c && A && Bm && C && x0 && uOld && Pdense && q && Adense && l && u && B >= 1 && B <= c->cfg.max_batch);
     int nz, mi, me; lmpc_qp_dims(c, &nz, &mi, &me); const int mm = mi + me;
-    const int N = c->cfg.N, S = c->cfg.numSS_it > 0 ? c->cfg.numSS_points : 0;
-    if (S > 0) ARGCHK(ssSel && qSel);
+    if (c->dims.S > 0) ARGCHK(ssSel && qSel);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
-    double *dP, *dq, *dA, *dl, *du;
-    HIPCHK(hipMalloc(&dP, sizeof(double) * (size_t)B * nz * nz)); HIPCHK(hipMalloc(&dq, sizeof(double) * (size_t)B * nz));
-    HIPCHK(hipMalloc(&dA, sizeof(double) * (size_t)B * mm * nz)); HIPCHK(hipMalloc(&dl, sizeof(double) * (size_t)B * mm)); HIPCHK(hipMalloc(&du, sizeof(double) * (size_t)B * mm));
-    H2D(c->w_A, A, (size_t)B * N * 36); H2D(c->w_B, Bm, (size_t)B * N * 12); H2D(c->w_C, C, (size_t)B * N * 6);
-    H2D(c->w_x0, x0, (size_t)B * 6); H2D(c->w_uOld, uOld, (size_t)B * 2);
-    if (S > 0) { H2D(c->w_ssSel, ssSel, (size_t)B * S * 6); H2D(c->w_qSel, qSel, (size_t)B * S); }
-    hipLaunchKernelGGL(lmpc_assemble_kernel, dim3(B), dim3(256), 0, c->stream, c->dp, B, c->w_A, c->w_B, c->w_C, c->w_x0, c->w_uOld, c->w_ssSel, c->w_qSel, dP, dq, dA, dl, du);
+    call_temps tmp; double *dP, *dq, *dA, *dl, *du;
+    HIPCHK(tmp.alloc(&dP, sizeof(double) * (size_t)B * nz * nz)); HIPCHK(tmp.alloc(&dq, sizeof(double) * (size_t)B * nz));
+    HIPCHK(tmp.alloc(&dA, sizeof(double) * (size_t)B * mm * nz)); HIPCHK(tmp.alloc(&dl, sizeof(double) * (size_t)B * mm)); HIPCHK(tmp.alloc(&du, sizeof(double) * (size_t)B * mm));
+    RCCHK(upload_qp(c, B, A, Bm, C, x0, uOld, ssSel, qSel));
+    hipLaunchKernelGGL(lmpc_assemble_kernel, dim3(B), dim3(256), 0, c->stream, c->dp, B, c->w.A, c->w.Bm, c->w.C, c->w.x0, c->w.uOld, c->w.ssSel, c->w.qSel, dP, dq, dA, dl, du);
     HIPCHK(hipGetLastError());
     D2H(Pdense, dP, (size_t)B * nz * nz); D2H(q, dq, (size_t)B * nz); D2H(Adense, dA, (size_t)B * mm * nz); D2H(l, dl, (size_t)B * mm); D2H(u, du, (size_t)B * mm);
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(dP); hipFree(dq); hipFree(dA); hipFree(dl); hipFree(du);
     return LMPC_OK;
 }
 
@@ -1103,18 +1095,15 @@ int lmpc_debug_step_trace(lmpc_ctx *c, double *out5) { ARGCHK(c && out5); for (i
 int lmpc_debug_timing(lmpc_ctx *c, const double *A, const double *Bm, const double *C, const double *x0, const double *uOld,
                       const double *ssSel, const double *qSel, long long *tbuf_host, int nt) {
     ARGCHK(c && tbuf_host && nt >= 2);
-    const int N = c->cfg.N, S = c->cfg.numSS_it > 0 ? c->cfg.numSS_points : 0;
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
-    H2D(c->w_A, A, (size_t)N * 36); H2D(c->w_B, Bm, (size_t)N * 12); H2D(c->w_C, C, (size_t)N * 6); H2D(c->w_x0, x0, 6); H2D(c->w_uOld, uOld, 2);
-    if (S > 0) { H2D(c->w_ssSel, ssSel, (size_t)S * 6); H2D(c->w_qSel, qSel, S); }
-    long long *dt; HIPCHK(hipMalloc(&dt, sizeof(long long) * nt)); HIPCHK(hipMemsetAsync(dt, 0, sizeof(long long) * nt, c->stream));
-    lmpc_solve_io io; memset(&io, 0, sizeof(io));
-    io.mode = 2; io.A = c->w_A; io.Bm = c->w_B; io.C = c->w_C; io.x0 = c->w_x0; io.uOld = c->w_uOld; io.ssSelIn = c->w_ssSel; io.qSelIn = c->w_qSel;
-    io.xPred = c->w_xPred; io.uPred = c->w_uPred; io.slack = c->w_slack; io.lambda = c->w_lam; io.sTerm = c->w_sT; io.mu = c->w_mu; io.resid = c->w_resid;
-    io.status = c->w_status; io.iters = c->w_iters; io.tbuf = dt; io.abPack = c->ab_pack;      // (long horizons: the route a large batch takes, [A_k | B_k] in global memory; LMPC_NO_ABG=1 for the other)
-    int rc = launch_solve(c, 1, io); if (rc) return rc;
+    RCCHK(upload_qp(c, 1, A, Bm, C, x0, uOld, ssSel, qSel));
+    call_temps tmp; long long *dt;
+    HIPCHK(tmp.alloc(&dt, sizeof(long long) * nt)); HIPCHK(hipMemsetAsync(dt, 0, sizeof(long long) * nt, c->stream));
+    lmpc_solve_io io = solve_io(2, qp_arrays(c));
+    io.tbuf = dt; io.abPack = c->ab_pack;      // (long horizons: the route a large batch takes, [A_k | B_k] in global memory; LMPC_NO_ABG=1 for the other)
+    RCCHK(launch_solve(c, 1, io));
     HIPCHK(hipMemcpyAsync(tbuf_host, dt, sizeof(long long) * nt, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); hipFree(dt);
+    HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
 
@@ -1124,13 +1113,16 @@ int lmpc_debug_k1_timing(lmpc_ctx *c, int B, const double *xLin, const double *u
     ARGCHK(c && xLin && uLin && tbuf_host && B >= 1 && B <= c->cfg.max_batch);
     const int N = c->cfg.N;
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
-    H2D(c->w_xLin, xLin, (size_t)B * (N + 1) * 6); H2D(c->w_uLin, uLin, (size_t)B * N * 2);
-    long long *dt; HIPCHK(hipMalloc(&dt, sizeof(long long) * 24)); HIPCHK(hipMemsetAsync(dt, 0, sizeof(long long) * 24, c->stream));
+    lmpc_arrays in = {}; in.xLin = mut(xLin); in.uLin = mut(uLin);
+    RCCHK(copy_arrays(c, B, c->dims, c->w, in, hipMemcpyHostToDevice));
+    // on any way out: the stream is drained, the kernels' stamp pointer is null again, then the buffer goes
+    struct stamp_buffer : call_temps { hipStream_t s; ~stamp_buffer() { long long *nul = nullptr; (void)hipStreamSynchronize(s); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_k1_tbuf), &nul, sizeof(nul)); } } tmp;
+    tmp.s = c->stream;
+    long long *dt; HIPCHK(tmp.alloc(&dt, sizeof(long long) * 24)); HIPCHK(hipMemsetAsync(dt, 0, sizeof(long long) * 24, c->stream));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_k1_tbuf), &dt, sizeof(dt)));
-    for (int rep = 0; rep < 2; rep++) { int rc = launch_regress(c, B, c->w_xLin, (N + 1) * 6, c->w_uLin, c->w_A, c->w_B, c->w_C, c->w_rstatus); if (rc) return rc; }
+    for (int rep = 0; rep < 2; rep++) RCCHK(launch_regress(c, B, c->w.xLin, (N + 1) * 6, c->w.uLin, c->w.A, c->w.Bm, c->w.C, c->w.rstatus));
     HIPCHK(hipMemcpyAsync(tbuf_host, dt, sizeof(long long) * 24, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    long long *nul = nullptr; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_k1_tbuf), &nul, sizeof(nul))); hipFree(dt);
     return LMPC_OK;
 }
 #endif
@@ -1334,10 +1326,11 @@ struct lmpc_rollout_session {
     double *d_par; bool has_par;                                // the session's snapshot of the per-car vehicle constants (B x LMPC_PLANT_NPAR), taken when it begins; has_par: the PAR kernels run
     hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
     std::vector<void *> keep;
-    double *d_x, *d_xg, *d_xLin, *d_uLin, *d_uOld, *d_zt, *d_xPP, *d_xPred, *d_uPred, *d_slack, *d_lam, *d_sT, *d_ztN, *d_ztuN, *d_A, *d_B, *d_C, *d_resid;
-    double *d_logX, *d_logU, *d_logG, *d_noise, *d_finX, *d_finG;
-    int *d_hasPred, *d_tstep, *d_done, *d_nDone, *d_stAcc, *d_status, *d_iters, *d_rst;
-    double *d_ssSel, *d_qSel, *d_succ, *d_succU;                // only with lmpc_debug_rollout_capture on (else null: the step does not write them)
+    // what the session shares with a step, by the names and sizes of lmpc_arrays.h (x0: the cars' states).  Never allocated: mu, ztUsed, selStart; ssSel, qSel, succ,
+    // succU only with lmpc_debug_rollout_capture on (else null: the step does not write them)
+    lmpc_arrays a;
+    double *d_xg, *d_logX, *d_logU, *d_logG, *d_noise, *d_finX, *d_finG;
+    int *d_done, *d_nDone, *d_stAcc;
 };
 
 enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
@@ -1355,7 +1348,7 @@ static void rollout_free(lmpc_ctx *c) {
 // xLin0 / uLin0 may be NULL (RO_LTI, RO_PID: no linearisation trajectory; the buffers are zeroed).
 static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
     HIPCHK(hipSetDevice(c->cfg.device));
-    const size_t N = c->cfg.N, S = c->cfg.numSS_points, Bz = B;
+    const size_t S = c->dims.S, Bz = B;
     std::vector<double> par_rows;                               // refused before any session state changes (B beyond the per-car rows)
     if (c->plant_n > 0) { const int rc = plant_rows_for(c, B, par_rows); if (rc) return rc; }
     std::vector<int> lt_rows; bool lt_small = true;             // sessions that run the regression: the lap table in force, one resolved row per car (refused here as well when B is not its row count)
@@ -1369,7 +1362,7 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     // A generation loop begins a session of the same shape every lap: its ~35 device buffers (55 MB of logs at 1024 rollouts x 400 steps), the plant stream and
     // the two events are kept from one session to the next (round 5: allocating and freeing them was ~5 ms of every generation) and released by
     // lmpc_destroy or by a session of another shape.
-    if (c->ro && !c->ro->active && c->ro->B == B && c->ro->T_max == T_max && (c->ro->d_ssSel != nullptr) == (c->dbg_capture != 0)) {
+    if (c->ro && !c->ro->active && c->ro->B == B && c->ro->T_max == T_max && (c->ro->a.ssSel != nullptr) == (c->dbg_capture != 0)) {
         lmpc_rollout_session *r = c->ro; r->t = 0; r->active = true; r->kind = kind; r->stop_at_line = stop_at_line;
         goto init_state;
     }
@@ -1380,14 +1373,16 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     bool ok = true;
     auto dalloc = [&](size_t bytes) -> void * { void *q = nullptr; if (g_malloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) { ok = false; return nullptr; } r->keep.push_back(q); return q; };
 #define DA(type, name, n) r->name = (type *)dalloc(sizeof(type) * (size_t)(n));
-    DA(double, d_x, Bz * 6) DA(double, d_xg, Bz * 6) DA(double, d_xLin, Bz * (N + 1) * 6) DA(double, d_uLin, Bz * N * 2) DA(double, d_uOld, Bz * 2)
-    DA(double, d_zt, Bz * 6) DA(double, d_xPP, Bz * (N + 1) * 6) DA(int, d_hasPred, Bz) DA(int, d_tstep, Bz) DA(int, d_done, Bz) DA(int, d_nDone, 1) DA(int, d_stAcc, Bz)
-    DA(double, d_xPred, Bz * (N + 1) * 6) DA(double, d_uPred, Bz * N * 2) DA(double, d_slack, Bz * N * 2) DA(double, d_lam, Bz * S) DA(double, d_sT, Bz * 6)
-    DA(double, d_ztN, Bz * 6) DA(double, d_ztuN, Bz * 2) DA(double, d_A, Bz * N * 36) DA(double, d_B, Bz * N * 12) DA(double, d_C, Bz * N * 6)
-    DA(double, d_resid, Bz * 3) DA(int, d_status, Bz) DA(int, d_iters, Bz) DA(int, d_rst, Bz * N) DA(double, d_finX, Bz * 6) DA(double, d_finG, Bz * 6)
+    lmpc_arrays_each(c->dims, [&](const char *, auto m, size_t elem, size_t n, int role) {
+        typedef lmpc_arrays A;
+        // (mu, ztUsed, selStart: no session asks for them; ssSel, qSel and the selection's successors: capture buffers, listed below)
+        const bool shared = role == LMPC_ARR_SEL ? lmpc_is(m, &A::rstatus) : !lmpc_is(m, &A::ssSel) && !lmpc_is(m, &A::qSel) && !lmpc_is(m, &A::mu);
+        if (shared)
+            r->a.*m = (std::remove_reference_t<decltype(r->a.*m)>)dalloc(elem * n * Bz);
+    });
+    DA(double, d_xg, Bz * 6) DA(int, d_done, Bz) DA(int, d_nDone, 1) DA(int, d_stAcc, Bz) DA(double, d_finX, Bz * 6) DA(double, d_finG, Bz * 6)
     DA(double, d_par, Bz * LMPC_PLANT_NPAR) DA(int, d_lt, Bz * (size_t)std::max(c->cfg.trToUse, 1) * 2)
-    r->d_ssSel = nullptr; r->d_qSel = nullptr; r->d_succ = nullptr; r->d_succU = nullptr;
-    if (c->dbg_capture) { DA(double, d_ssSel, Bz * S * 6) DA(double, d_qSel, Bz * S) DA(double, d_succ, Bz * S * 6) DA(double, d_succU, Bz * S * 2) }
+    if (c->dbg_capture) { DA(double, a.ssSel, Bz * S * 6) DA(double, a.qSel, Bz * S) DA(double, a.succ, Bz * S * 6) DA(double, a.succU, Bz * S * 2) }
     DA(double, d_logX, (size_t)T_max * Bz * 6) DA(double, d_logU, (size_t)T_max * Bz * 2) DA(double, d_logG, (size_t)T_max * Bz * 6) DA(double, d_noise, (size_t)T_max * Bz * 3)
     r->d_noiseU = nullptr; r->d_vt = nullptr;                   // (allocated by the first lmpc_rollout_pid on the session's buffers, kept with them)
 #undef DA
@@ -1398,10 +1393,17 @@ init_state:
     std::vector<double> ztv((size_t)B * 6, 0.0);
     for (int b = 0; b < B; b++) ztv[(size_t)b * 6 + 4] = 10.0;                                   // LMPC.__init__ :330
     std::vector<int> neg((size_t)B, -1);
-    H2D(r->d_x, x0, Bz * 6); H2D(r->d_xg, xg0, Bz * 6); H2D(r->d_zt, ztv.data(), ztv.size());
-    if (xLin0) H2D(r->d_xLin, xLin0, Bz * (N + 1) * 6); else HIPCHK(hipMemsetAsync(r->d_xLin, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
-    if (uLin0) H2D(r->d_uLin, uLin0, Bz * N * 2); else HIPCHK(hipMemsetAsync(r->d_uLin, 0, sizeof(double) * Bz * N * 2, c->stream));
-    H2D(r->d_done, neg.data(), Bz);
+    // the step's arrays: the initial state, zt and (if given) the first linearisation trajectories are uploaded, every other one is zeroed -- a reused session is
+    // indistinguishable from a fresh one: what the previous lap left in the solver's outputs and status words goes too
+    lmpc_arrays first = {}; first.x0 = mut(x0); first.zt = ztv.data(); first.xLin = mut(xLin0); first.uLin = mut(uLin0);
+    RCCHK(copy_arrays(c, Bz, c->dims, r->a, first, hipMemcpyHostToDevice));
+    {
+        hipError_t e = hipSuccess;
+        lmpc_arrays_each(c->dims, [&](const char *, auto m, size_t elem, size_t n, int) {
+            if (r->a.*m && !(first.*m) && e == hipSuccess) e = hipMemsetAsync(r->a.*m, 0, elem * n * Bz, c->stream); });
+        HIPCHK(e);
+    }
+    H2D(r->d_xg, xg0, Bz * 6); H2D(r->d_done, neg.data(), Bz);
     // the snapshot of the noise source: lmpc_rollout_set_noise during the session reaches the next one only.  noise == NULL (the callers have checked that the source
     // is on): the buffer the plant kernels read is written by one launch on the context's stream, in front of the first step -- no host draw, no upload
     r->nz_seed = c->noise_seed; r->nz_lap = c->noise_lap; r->nz_car0 = c->noise_car0;
@@ -1411,23 +1413,15 @@ init_state:
     if (r->has_par) H2D(r->d_par, par_rows.data(), par_rows.size());
     r->has_lt = !lt_rows.empty(); r->lt_small = lt_small; r->lt_stride = 2 * c->cfg.trToUse;   // the snapshot: lmpc_model_set_lap_table during the session reaches the next one only
     if (r->has_lt) H2D(r->d_lt, lt_rows.data(), lt_rows.size());
-    HIPCHK(hipMemsetAsync(r->d_uOld, 0, sizeof(double) * Bz * 2, c->stream)); HIPCHK(hipMemsetAsync(r->d_xPP, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream));
-    HIPCHK(hipMemsetAsync(r->d_hasPred, 0, sizeof(int) * Bz, c->stream)); HIPCHK(hipMemsetAsync(r->d_tstep, 0, sizeof(int) * Bz, c->stream));
     HIPCHK(hipMemsetAsync(r->d_nDone, 0, sizeof(int), c->stream)); HIPCHK(hipMemsetAsync(r->d_stAcc, 0, sizeof(int) * Bz, c->stream));
     HIPCHK(hipMemsetAsync(r->d_finX, 0, sizeof(double) * Bz * 6, c->stream)); HIPCHK(hipMemsetAsync(r->d_finG, 0, sizeof(double) * Bz * 6, c->stream));
-    // a reused session is indistinguishable from a fresh one: what the previous lap left in the solver's outputs and status words goes too
-    HIPCHK(hipMemsetAsync(r->d_xPred, 0, sizeof(double) * Bz * (N + 1) * 6, c->stream)); HIPCHK(hipMemsetAsync(r->d_uPred, 0, sizeof(double) * Bz * N * 2, c->stream));
-    HIPCHK(hipMemsetAsync(r->d_lam, 0, sizeof(double) * Bz * S, c->stream)); HIPCHK(hipMemsetAsync(r->d_sT, 0, sizeof(double) * Bz * 6, c->stream));
-    HIPCHK(hipMemsetAsync(r->d_ztN, 0, sizeof(double) * Bz * 6, c->stream)); HIPCHK(hipMemsetAsync(r->d_ztuN, 0, sizeof(double) * Bz * 2, c->stream));
-    HIPCHK(hipMemsetAsync(r->d_status, 0, sizeof(int) * Bz, c->stream)); HIPCHK(hipMemsetAsync(r->d_iters, 0, sizeof(int) * Bz, c->stream));
-    HIPCHK(hipMemsetAsync(r->d_rst, 0, sizeof(int) * Bz * N, c->stream)); HIPCHK(hipMemsetAsync(r->d_resid, 0, sizeof(double) * Bz * 3, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
 static void rollout_state(lmpc_rollout_session *r, lmpc_rollout_state &st) {
-    st.x = r->d_x; st.xg = r->d_xg; st.xLin = r->d_xLin; st.uLin = r->d_uLin; st.uOld = r->d_uOld; st.zt = r->d_zt; st.xPP = r->d_xPP;
-    st.hasPred = r->d_hasPred; st.timeStep = r->d_tstep; st.doneAt = r->d_done; st.xPred = r->d_xPred; st.uPred = r->d_uPred; st.ztNext = r->d_ztN; st.ztuNext = r->d_ztuN;
-    st.status = r->d_status; st.logX = r->d_logX; st.logU = r->d_logU; st.logG = r->d_logG; st.noise = r->d_noise; st.nDone = r->d_nDone; st.statusAcc = r->d_stAcc;
+    const lmpc_arrays &a = r->a; st.x = a.x0; st.xg = r->d_xg; st.xLin = a.xLin; st.uLin = a.uLin; st.uOld = a.uOld; st.zt = a.zt; st.xPP = a.xPredPrev;
+    st.hasPred = a.hasPred; st.timeStep = a.timeStep; st.doneAt = r->d_done; st.xPred = a.xPred; st.uPred = a.uPred; st.ztNext = a.ztNext; st.ztuNext = a.ztuNext;
+    st.status = a.status; st.logX = r->d_logX; st.logU = r->d_logU; st.logG = r->d_logG; st.noise = r->d_noise; st.nDone = r->d_nDone; st.statusAcc = r->d_stAcc;
     st.finX = r->d_finX; st.finG = r->d_finG; st.plantPar = r->d_par;
 }
 extern "C" {
@@ -1462,9 +1456,8 @@ int lmpc_rollout_begin_mpc(lmpc_ctx *c, int B, int T_max, const double *x0, cons
         for (size_t b = 0; b < Bz; b++) for (size_t k = 0; k < N; k++) {
             memcpy(&eA[(b * N + k) * 36], A_lti + b * 36, sizeof(double) * 36); memcpy(&eB[(b * N + k) * 12], B_lti + b * 12, sizeof(double) * 12);
         }
-        hipError_t e = hipMemcpyAsync(r->d_A, eA.data(), sizeof(double) * eA.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(r->d_B, eB.data(), sizeof(double) * eB.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_C, 0, sizeof(double) * Bz * N * 6, c->stream);
+        hipError_t e = hipMemcpyAsync(r->a.A, eA.data(), sizeof(double) * eA.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(r->a.Bm, eB.data(), sizeof(double) * eB.size(), hipMemcpyHostToDevice, c->stream);   // (C = 0: rollout_setup has zeroed it)
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                      // (the pageable host arrays must outlive the copies)
         if (e != hipSuccess) { r->active = false; return set_err(LMPC_E_HIP, "lmpc_rollout_begin_mpc", hipGetErrorString(e)); }
     }
@@ -1540,14 +1533,11 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         ev_begin(c, 0);
         { int qg, nblk; k1_grid(c, B, &qg, &nblk);
           const k1_table tab = {r->has_lt ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small};
-          launch_k1(c, nblk, B, qg, (const double *)r->d_xLin, (int)(N + 1) * 6, (const double *)r->d_uLin, r->d_A, r->d_B, r->d_C, r->d_rst, tab); }
+          launch_k1(c, nblk, B, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
         ev_end(c); c->stats.n_regress++;
         }
-        lmpc_solve_io io; memset(&io, 0, sizeof(io));
-        io.mode = lmpc ? 3 : 2; io.A = r->d_A; io.Bm = r->d_B; io.C = r->d_C; io.x0 = r->d_x; io.uOld = r->d_uOld; io.zt = r->d_zt; io.xPredPrev = r->d_xPP; io.hasPred = r->d_hasPred;
-        io.timeStep = r->d_tstep; io.xPred = r->d_xPred; io.uPred = r->d_uPred; io.slack = r->d_slack; io.lambda = r->d_lam; io.sTerm = r->d_sT; io.ztNext = r->d_ztN;
-        io.ztuNext = r->d_ztuN; io.resid = r->d_resid; io.status = r->d_status; io.iters = r->d_iters; io.rstatus = lti ? nullptr : r->d_rst;
-        io.ssSelOut = r->d_ssSel; io.qSelOut = r->d_qSel; io.succOut = r->d_succ; io.succUOut = r->d_succU;
+        lmpc_solve_io io = solve_io(lmpc ? 3 : 2, r->a);
+        io.rstatus = lti ? nullptr : r->a.rstatus;
         if (r->t > 0) HIPCHK(hipStreamWaitEvent(c->stream, r->e_plant, 0));          // the solve needs the plant's new state
         rc = launch_solve(c, B, io, true); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
         HIPCHK(hipEventRecord(r->e_solved, c->stream));
@@ -1555,7 +1545,7 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         if (r->has_par) hipLaunchKernelGGL(lmpc_rollout_plant_kernel<true>, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
         else hipLaunchKernelGGL(lmpc_rollout_plant_kernel<false>, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
         HIPCHK(hipEventRecord(r->e_plant, r->pstream));
-        if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->d_uPred, r->d_uOld);
+        if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->a.uPred, r->a.uOld);
         else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression
         HIPCHK(hipGetLastError());
         r->t++;
@@ -1587,9 +1577,10 @@ int lmpc_debug_rollout_peek(lmpc_ctx *c, double *xLin, double *uLin, int *status
     // status words of the step just taken (per rollout: B; per horizon point of its regression: B x N).  tools/robustness_sweep.py steps a generation one step at a
     // time with it to capture the inputs of a flagged regression.  Any pointer may be NULL.
     ARGCHK(c && c->ro && c->ro->active);
-    lmpc_rollout_session *r = c->ro; const size_t Bz = r->B, N = c->cfg.N;
+    lmpc_rollout_session *r = c->ro;
     HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(r->pstream)); HIPCHK(hipStreamSynchronize(c->stream));
-    D2H(xLin, r->d_xLin, Bz * (N + 1) * 6); D2H(uLin, r->d_uLin, Bz * N * 2); D2H(status, r->d_status, Bz); D2H(rstatus, r->d_rst, Bz * N);
+    lmpc_arrays out = {}; out.xLin = xLin; out.uLin = uLin; out.status = status; out.rstatus = rstatus;
+    RCCHK(copy_arrays(c, r->B, c->dims, out, r->a, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
@@ -1608,14 +1599,13 @@ int lmpc_debug_rollout_qp(lmpc_ctx *c, int b0, int n, double *A, double *Bm, dou
     // answer (n x (N+1) x 6, n x N x 2, n x S; zt / zt_u of feasibleStateInput: n x 6, n x 2), iterations and status, and (capture on) the selected safe-set points, their
     // Q-values and successors (n x S x 6, n x S, n x S x 6, n x S x 2).  Its x0 / uOld are rows t - 1 / t - 2 of the session's logs (lmpc_rollout_fetch).  Meant to be
     // called between lmpc_rollout_run(ctx, 1, ..) calls; any pointer may be NULL.
-    ARGCHK(c && c->ro && c->ro->active && c->ro->t >= 1 && b0 >= 0 && n >= 1 && b0 + n <= c->ro->B && ((!ssSel && !qSel && !succ && !succU) || c->ro->d_ssSel));
-    lmpc_rollout_session *r = c->ro; const size_t N = c->cfg.N, S = c->cfg.numSS_points, o = b0, nz = n;
+    ARGCHK(c && c->ro && c->ro->active && c->ro->t >= 1 && b0 >= 0 && n >= 1 && b0 + n <= c->ro->B && ((!ssSel && !qSel && !succ && !succU) || c->ro->a.ssSel));
+    lmpc_rollout_session *r = c->ro;
     HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(r->pstream)); HIPCHK(hipStreamSynchronize(c->stream));
-    D2H(A, r->d_A + o * N * 36, nz * N * 36); D2H(Bm, r->d_B + o * N * 12, nz * N * 12); D2H(Cm, r->d_C + o * N * 6, nz * N * 6);
-    D2H(xPred, r->d_xPred + o * (N + 1) * 6, nz * (N + 1) * 6); D2H(uPred, r->d_uPred + o * N * 2, nz * N * 2); D2H(lambda, r->d_lam + o * S, nz * S);
-    D2H(ztNext, r->d_ztN + o * 6, nz * 6); D2H(ztuNext, r->d_ztuN + o * 2, nz * 2);
-    D2H(ssSel, r->d_ssSel + o * S * 6, nz * S * 6); D2H(qSel, r->d_qSel + o * S, nz * S); D2H(succ, r->d_succ + o * S * 6, nz * S * 6); D2H(succU, r->d_succU + o * S * 2, nz * S * 2);
-    D2H(iters, r->d_iters + o, nz); D2H(status, r->d_status + o, nz);
+    lmpc_arrays out = {};
+    out.A = A; out.Bm = Bm; out.C = Cm; out.xPred = xPred; out.uPred = uPred; out.lambda = lambda; out.ztNext = ztNext; out.ztuNext = ztuNext;
+    out.ssSel = ssSel; out.qSel = qSel; out.succ = succ; out.succU = succU; out.iters = iters; out.status = status;
+    RCCHK(copy_arrays(c, n, c->dims, out, r->a, hipMemcpyDeviceToHost, b0));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }

@@ -22,7 +22,8 @@ def _work(b):
     if z[4] - inp["x0"][b][4] > TL / 2:
         z[4] = np.max([z[4] - TL, 0])
     L = len(xS)
-    SSsel, Qsel, Succ, SuccU = orc.terminal_components(xS, uS, Qf, [x.shape[0] for x in xS], z, 12 * L, L, None, L, int(inp["timeStep"][b]), N, TL)
+    xPrev = inp["xPredPrev"][b] if "hasPred" in inp and inp["hasPred"][b] else None          # (the reference's `self.xPred == []` on a first step)
+    SSsel, Qsel, Succ, SuccU = orc.terminal_components(xS, uS, Qf, [x.shape[0] for x in xS], z, 12 * L, L, xPrev, L, int(inp["timeStep"][b]), N, TL)
     res = dict(b=b, A=A, B=B, C=C, SSsel=SSsel, Qsel=Qsel, Succ=Succ, SuccU=SuccU)
     if b in j["solve"]:
         P, q, Ao, l, u = orc.assemble_lmpc_qp(j["par"], A, B, C, inp["x0"][b], inp["uOld"][b], SSsel, Qsel)

@@ -85,12 +85,12 @@ def _batch(P, F, B):
     return {k: np.concatenate([P[k], F[k][P_SIZE:B]]) for k in ("x0", "xLin", "uLin", "uOld", "zt", "timeStep")}
 
 
-def _mpc_oracle(g, par, N, P):
+def _mpc_oracle(g, par, N, P, rows=range(P_SIZE)):
     """Plain LTV-MPC (no terminal set, regression on the one stored PID lap): A, B, C and the certified optimum of the reference-form QP per problem."""
     from oracle import lmpc_oracle as orc
     pt = np.array(g["track"]); xP, uP = np.array(g["xPID"]), np.array(g["uPID"])
     res = []
-    for b in range(P_SIZE):
+    for b in rows:
         A, B, C = orc.compute_ltv_dynamics([xP], [uP], [0], pt, P["xLin"][b], P["uLin"][b], N)
         Pq, q, Ao, lo, up = orc.assemble_mpc_qp(par, A, B, C, P["x0"][b], P["uOld"][b])
         ex, cert = orc.osqp_solve_exact(Pq, q, Ao, lo, up, want=1e-8)
@@ -200,4 +200,62 @@ def test_every_route_gives_one_answer(built, N, S):
     print("\nN = %d, S = %d: route, batch, waves, regression launches, |xu - 4 waves|, |zt - 4 waves| / (1 + |zt|), worst |A,B,C - oracle| rel, worst |xu - z*| rel" % (N, S))
     for r in rows:
         print("  %-36s %5d %d %d  %.2e  %.2e  %.2e  %.2e" % r)
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("N,S", [(12, 48), (12, 0)], ids=["N12_S48", "N12_S0"])
+def test_step_batch_copy_routes_give_one_answer(built, N, S):
+    """lmpc_step_batch moves its arrays in one of two ways, and nothing else tests either beyond one problem: (a) a full batch of a small context runs on the
+    host-mapped mirrors of the work buffers -- here max_batch = 4, B = 4; (b) any other call copies array by array -- the same context with B = 3, which owns
+    mirrors and must not use them, and (c) a max_batch = 64 context, which owns none, with B = 4.  Problems: rows 0..3 of P, every timeStep non-zero, rows 1 and 3
+    with previous predictions whose last rows lie beyond the finish line, so that the selection shifts the Q-function (rows 0 and 2: hasPred = 0).  All three run four
+    waves per QP; every output is bit-identical between them on the rows they share, a second full batch on (a) after the B = 3 call reproduces the first (nothing
+    stale in the mirrors), and every route meets the oracle.  Plain MPC (S = 0) gets the same inputs and must not read the selection's."""
+    import bench
+    from oracle import lmpc_oracle as orc
+    from tests import oracle_pool
+    g = common.load_lmpc_golden()
+    TL = float(g["trackLength"])
+    P = {k: v[:4].copy() for k, v in bench.synth_batch(g, P_SIZE, N, seed=SEED_P).items()}
+    P["timeStep"] = (P["timeStep"] + 3).astype(np.int32)
+    P["hasPred"] = np.array([0, 1, 0, 1], np.int32)
+    P["xPredPrev"] = np.concatenate([P["xLin"][:, 1:], P["zt"][:, None]], axis=1)               # a plausible previous prediction: the linearisation shifted by one ...
+    P["xPredPrev"][:, -3:, 4] = TL + 0.05 * np.arange(1, 4)                                       # ... whose last three rows have crossed the line
+    assert np.all(P["timeStep"] > 0) and np.all(P["xPredPrev"][[1, 3], -1, 4] > TL)
+    if S:
+        pid = (np.array(g["xPID"]), np.array(g["uPID"]))
+        res = oracle_pool.oracle_batch(orc.QPParams.lmpc_default(N), np.array(g["track"]), TL, [pid] * 4, N, P, range(4), solve_idx=range(4))
+        # (the shift is really active: the selected Q-values of rows 1 and 3 differ from the ones a first step would get)
+        plain = oracle_pool.oracle_batch(orc.QPParams.lmpc_default(N), np.array(g["track"]), TL, [pid] * 4, N, dict(P, hasPred=np.zeros(4, np.int32)), [1, 3])
+        assert all(not np.array_equal(res[r["b"]]["Qsel"], r["Qsel"]) for r in plain)
+    else:
+        res = _mpc_oracle(g, orc.QPParams.mpc_default(N, 0.8), N, P, rows=range(4))
+
+    def step(ctx, B):
+        assert ctx.solver_waves(B) == 4 and ctx.solver_kind == 0
+        return ctx.step_batch(P["x0"][:B], P["xLin"][:B], P["uLin"][:B], P["uOld"][:B], zt=P["zt"][:B], xPredPrev=P["xPredPrev"][:B], hasPred=P["hasPred"][:B], timeStep=P["timeStep"][:B])
+    small = _context(g, N, S, 4, {}, False)
+    try:
+        outs = {"(a) max_batch 4, B 4": step(small, 4), "(b) max_batch 4, B 3": step(small, 3), "(a) again": step(small, 4)}
+    finally:
+        small.close()
+    large = _context(g, N, S, P_SIZE, {}, False)
+    try:
+        outs["(c) max_batch 64, B 4"] = step(large, 4)
+    finally:
+        large.close()
+    ref = outs["(a) max_batch 4, B 4"]
+    fails = []
+    for name, out in outs.items():
+        B = out["status"].shape[0]
+        what = "N = %d, S = %d, %s" % (N, S, name)
+        if not np.all(out["status"] == 0):
+            fails.append("%s: status %s" % (what, out["status"]))
+        diff = [k for k in ALL_KEYS + ("resid",) if not np.array_equal(out[k], ref[k][:B])]
+        if diff:
+            fails.append("%s: %s not bit-identical to the full batch on the mirrors" % (what, ", ".join(diff)))
+        try:
+            (common.compare_with_oracle if S else _mpc_compare)(out, [r for r in res if r["b"] < B], N, what)
+        except AssertionError as e:
+            fails.append("%s: oracle: %s" % (what, e))
     assert not fails, "\n".join(fails)
