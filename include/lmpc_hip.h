@@ -132,7 +132,7 @@ int lmpc_model_set_lap_table(lmpc_ctx *, int n, const int *laps /*n x trToUse in
          * argument error the table in force stays (a HIP failure while the device image is uploaded, LMPC_E_HIP, leaves the context without a table).  The table applies wherever the regression kernel runs: lmpc_regress_batch, lmpc_regress_points (point e uses row e), lmpc_step_batch,
          * lmpc_step_batch_dev, lmpc_rollout_begin and the LTV form of lmpc_rollout_begin_mpc with every step of their sessions -- a session takes a snapshot when it
          * begins, a later call reaches the next session only.  On an LMPC context (numSS_it > 0) ONLY THE REGRESSION follows the table: the safe set, its selection and
-         * the terminal constraint stay shared by all problems.  With a table in force the fused one-wave step (LMPC_FUSE=1) is not taken: the two-kernel step runs.
+         * the terminal constraint stay shared by all problems unless the safe set is given its own table, lmpc_ss_set_lap_table.  With a table in force the fused one-wave step (LMPC_FUSE=1) is not taken: the two-kernel step runs.
          * The table lives on the device as resolved (slot, rows) pairs, uploaded here and not per launch; it is rebuilt from the indices when the stores are
          * reallocated or a lap is replaced.  As for the regression grid and scan build, A, B, C of a problem do not depend on which other rows the table holds */
 int lmpc_model_get_lap_table(lmpc_ctx *, int *n, int *laps /*capacity rows x trToUse, or NULL*/, int capacity);
@@ -147,6 +147,33 @@ int lmpc_ss_add_point(lmpc_ctx *, const double *x /*6*/, const double *u /*2*/);
 int lmpc_ss_replace_lap(lmpc_ctx *, int lap, const double *x, const double *u, const double *qfun, int T);
 int lmpc_ss_set_selected(lmpc_ctx *, const int *laps, int n);
         /* override of argsort(LapTime)[0:numSS_it] (:395,402); n = 0 restores the built-in stable sort */
+int lmpc_ss_set_lap_table(lmpc_ctx *, int n, const int *laps /* n x numSS_it safe-set lap indices, lmpc_ss_add_trajectory order; NULL with n = 0 */,
+                          const int *last /* n, or NULL */);
+        /* Per-problem safe sets: which stored laps the selection (LMPC.addTerminalComponents / selectPoints, :386-412, :478-514) of each problem of a batch reads -- each
+         * car's terminal set and terminal cost from its own laps, as every LMPC object of the reference owns SS / uSS / Qfun / LapTime (:395-412).  Row b names the numSS_it
+         * laps problem b selects from, by their index in lmpc_ss_add_trajectory order.  Duplicates are allowed (main.py:109-110 adds one lap four times), so a row may be
+         * served by fewer than numSS_it stored laps.  Each row is used in the order a controller holding only those laps would use them -- ascending LapTime
+         * (lmpc_ss_get_laptime), ties by lap index, a stable argsort(LapTime) -- whatever order the caller lists them in: the columns of ssSel / qSel / succ / succU /
+         * lambda and selStart[b, l] follow that order.  last[b]: the index of car b's most recent lap, the reference's self.it - 1; it need not be in the row.  An entry
+         * of row b takes the "current lap" branch of the Q-function shift (:502-512: timeStep + N - crossed) iff its index equals last[b], every other entry takes
+         * Qfun[it][0]; last[b] = -1: none does.  last = NULL: the context-wide rule for every row -- the latest lap is index lmpc_ss_num_laps - 1 at launch time.
+         * n = 0: back to the shared selection (lmpc_ss_set_selected / the built-in argsort), bit for bit.  n = 1: that row serves every problem.  n > 1: problem b of a
+         * call uses row b, and a launch whose batch B != n returns LMPC_E_ARG and says so in lmpc_last_error (the context stays usable).  LMPC_E_ARG for an index < 0 or
+         * >= the laps stored, last outside [-1, laps stored), n < 0, NULL laps with n > 0, n > 0 on a context with numSS_it = 0: after such an argument error the table
+         * in force stays.  The table names LAPS, not snapshots of them: rows appended or removed by lmpc_ss_add_point, lmpc_ss_extend_lap, lmpc_ss_truncate_lap,
+         * lmpc_ss_replace_lap, a new lmpc_ss_add_trajectory and a growth of the stores are seen by the next launch (the device image of resolved (slot, rows, latest)
+         * entries is uploaded again before the next launch that reads it, after the retry passes of earlier launches have run against the image of their own launch).
+         * The table applies wherever the selection runs on the device: lmpc_select_batch, lmpc_step_batch, lmpc_step_batch_dev and every step of an lmpc_rollout_begin
+         * session.  It is LIVE in a session, as lmpc_ss_set_selected is -- not a snapshot taken at begin like the model table: a `set` between two lmpc_rollout_run
+         * calls reaches the next step, and B is checked against n before the first launch of a step, so a refused lmpc_rollout_run leaves no half-done step.  All solve
+         * kernels (one, two, four waves per QP, the runtime-(N, S) kernel, their retry passes) serve a table -- the fixed-(N, S) ones in instantiations of their own, so
+         * that a launch without a table runs the kernels it ran before; the fused one-wave step (LMPC_FUSE=1) and the condensed
+         * kernel (LMPC_CD=1) do not and are not taken while one is in force: the two-kernel step / the ordinary kernels run.  With a table a launch asks for 256 bytes
+         * more dynamic LDS per QP (slot and rows of the selected laps for the successor rows of feasibleStateInput); without one nothing changes */
+#define LMPC_SS_LAST_SHARED (-2)
+int lmpc_ss_get_lap_table(lmpc_ctx *, int *n, int *laps /* capacity x numSS_it, or NULL */, int *last /* capacity, or NULL */, int capacity);
+        /* the rows in force as lmpc_ss_set_lap_table received them (n = 0: the shared selection); laps / last receive min(n, capacity) rows / entries, every entry of
+         * last LMPC_SS_LAST_SHARED where `set` was given last = NULL */
 int lmpc_ss_num_laps(lmpc_ctx *, int *n);
 int lmpc_ss_get_qfun(lmpc_ctx *, int lap, double *qfun /*T*/, int *T);
 int lmpc_store_read_lap(lmpc_ctx *, int store /*0: regression store (sorted position), 1: safe set*/, int lap, double *x /*T x 6*/, double *u /*T x 2*/, double *qfun /*T, safe set only*/, int *T);

@@ -76,7 +76,7 @@ class StepDevArgs(C.Structure):
 EXPORTS = [
     "lmpc_config_default", "lmpc_create", "lmpc_create_ex", "lmpc_solver_kind", "lmpc_destroy", "lmpc_last_error", "lmpc_active_knobs", "lmpc_version", "lmpc_device_memory",
     "lmpc_model_add_trajectory", "lmpc_model_num_laps", "lmpc_model_replace_lap", "lmpc_model_set_lap_table", "lmpc_model_get_lap_table", "lmpc_model_lap_info",
-    "lmpc_ss_add_trajectory", "lmpc_ss_add_point", "lmpc_ss_replace_lap", "lmpc_ss_set_selected", "lmpc_ss_num_laps", "lmpc_ss_get_qfun", "lmpc_ss_get_laptime", "lmpc_store_read_lap",
+    "lmpc_ss_add_trajectory", "lmpc_ss_add_point", "lmpc_ss_replace_lap", "lmpc_ss_set_selected", "lmpc_ss_set_lap_table", "lmpc_ss_get_lap_table", "lmpc_ss_num_laps", "lmpc_ss_get_qfun", "lmpc_ss_get_laptime", "lmpc_store_read_lap",
     "lmpc_regress_batch", "lmpc_regress_points", "lmpc_select_batch", "lmpc_qp_solve_batch", "lmpc_step_batch", "lmpc_assemble_batch", "lmpc_qp_dims",
     "lmpc_dev_alloc", "lmpc_dev_free", "lmpc_dev_upload", "lmpc_dev_download", "lmpc_dev_sync", "lmpc_step_batch_dev",
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
@@ -124,6 +124,10 @@ def load():
         lib.lmpc_model_get_lap_table.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]
         lib.lmpc_model_lap_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.lmpc_model_set_lap_table.restype = lib.lmpc_model_get_lap_table.restype = lib.lmpc_model_lap_info.restype = C.c_int
+        # (per-problem safe-set laps: rows of int32 lap indices, one "latest lap" index per row)
+        lib.lmpc_ss_set_lap_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.lmpc_ss_get_lap_table.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
+        lib.lmpc_ss_set_lap_table.restype = lib.lmpc_ss_get_lap_table.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
@@ -210,6 +214,33 @@ def check_lap_table(rows, trToUse):
     if a.min() < 0:
         raise ValueError("lap table: negative lap index in row(s) %s" % np.where((a < 0).any(1))[0].tolist())
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+SS_LAST_SHARED = -2        # LMPC_SS_LAST_SHARED: lmpc_ss_get_lap_table's `last` entries when the table was set without one
+
+
+def check_ss_table(rows, numSS_it, last=None):
+    """(rows (n, numSS_it) int32, last (n,) int32 or None) of a per-problem safe-set lap table, or (None, None) for "no table" (rows None or empty).  The shape
+    rules are check_lap_table's, with numSS_it entries per row.  last: one integer entry per row, each -1 ("none of the row's laps is the car's latest") or a lap
+    index; ValueError for another shape, a non-integer dtype, an entry below -1, or a `last` given without rows (the library checks the upper ends against the
+    laps stored)."""
+    try:
+        r = check_lap_table(rows, numSS_it)
+    except ValueError as e:
+        raise ValueError(str(e).replace("lap table:", "safe-set lap table:").replace("trToUse", "numSS_it")) from None
+    if r is None:
+        if last is not None and np.size(last):
+            raise ValueError("safe-set lap table: `last` given without rows")
+        return None, None
+    if last is None:
+        return r, None
+    a = np.asarray(last)
+    if not np.issubdtype(a.dtype, np.integer) or a.ndim > 1 or a.size != r.shape[0]:
+        raise ValueError("safe-set lap table: `last` must hold one integer per row (%d), got dtype %s, shape %s" % (r.shape[0], a.dtype, a.shape))
+    a = a.reshape(-1)
+    if a.min() < -1:
+        raise ValueError("safe-set lap table: `last` below -1 in row(s) %s" % np.where(a < -1)[0].tolist())
+    return r, np.ascontiguousarray(a, dtype=np.int32)
 
 
 def plant_params(B, m=1.98, lf=0.125, lr=0.125, Iz=0.024, mu_f=0.8, mu_r=0.8, Cf=1.25, Bf=1.0, Cr=1.25, Br=1.0, Df=None, Dr=None):
@@ -338,12 +369,17 @@ class Context:
         x = _f64(x); u = _f64(u)
         _chk(self.lib.lmpc_model_replace_lap(self._h, C.c_int(pos), _d(x), _d(u), C.c_int(x.shape[0])))
 
+    def model_num_laps(self):
+        n = C.c_int()
+        _chk(self.lib.lmpc_model_num_laps(self._h, C.byref(n)))
+        return n.value
+
     def model_set_lap_table(self, rows):
         """Per-problem regression laps (lmpc_model_set_lap_table): rows (n, trToUse) of INSERTION indices of regression-store laps (0 = the first
         model_add_trajectory; duplicates allowed, any order inside a row).  None or no rows -- the default, the first trToUse laps of the sorted order for every
         problem; one row -- every problem; n rows -- problem b of a later regress_batch / regress_points / step_batch / step_batch_dev / rollout_begin /
         LTV rollout_begin_mpc uses row b, and a call with another batch size is refused.  A session uses the table in force when it began.  On an LMPC context
-        only the regression follows the table: the safe set stays shared."""
+        only the regression follows the table: the safe set has a table of its own, ss_set_lap_table."""
         L = int(self.cfg.trToUse)
         rows = check_lap_table(rows, L)
         if rows is None:
@@ -381,6 +417,28 @@ class Context:
     def ss_set_selected(self, laps):
         laps = _i32(laps)
         _chk(self.lib.lmpc_ss_set_selected(self._h, _d(laps), C.c_int(len(laps))))
+
+    def ss_set_lap_table(self, rows, last=None):
+        """Per-problem safe sets (lmpc_ss_set_lap_table): rows (n, numSS_it) of safe-set lap indices in ss_add_trajectory order (duplicates allowed, any order inside
+        a row: each row is used in ascending LapTime, ties by index).  last (n,): the index of each car's most recent lap -- the entry of a row that equals it takes
+        the "current lap" branch of the Q-function shift -- or -1 for none; None: the context-wide rule, the last lap stored.  None or no rows -- the shared
+        selection; one row -- every problem; n rows -- problem b of a later select_batch / step_batch / step_batch_dev / rollout step uses row b, and a launch
+        with another batch size is refused.  The table names laps, not snapshots, and is live in a rollout session: a later ss_extend_lap or a new `set` reaches
+        the next step."""
+        rows, last = check_ss_table(rows, int(self.cfg.numSS_it), last)
+        if rows is None:
+            _chk(self.lib.lmpc_ss_set_lap_table(self._h, 0, None, None))
+            return
+        _chk(self.lib.lmpc_ss_set_lap_table(self._h, rows.shape[0], rows.ctypes.data, None if last is None else last.ctypes.data))
+
+    def ss_lap_table(self):
+        """(rows (n, numSS_it) int32, last (n,) int32 or None) in force, as ss_set_lap_table received them; n = 0: the shared selection (lmpc_ss_get_lap_table)."""
+        n = C.c_int()
+        _chk(self.lib.lmpc_ss_get_lap_table(self._h, C.byref(n), None, None, 0))
+        rows = np.zeros((n.value, int(self.cfg.numSS_it)), np.int32); last = np.zeros(n.value, np.int32)
+        if n.value:
+            _chk(self.lib.lmpc_ss_get_lap_table(self._h, C.byref(n), rows.ctypes.data, last.ctypes.data, rows.shape[0]))
+        return rows, (None if n.value == 0 or np.all(last == SS_LAST_SHARED) else last)
 
     def ss_get_qfun(self, lap):
         T = C.c_int()
@@ -681,6 +739,12 @@ class Context:
         if tab.shape[0]:
             pos = np.array([self.model_lap_info(k)[1] for k in range(nm.value)], np.int32)      # insertion index -> sorted position
             out["model_lap_table"] = pos[tab]
+        # (the safe-set table names laps by their addTrajectory index, which restore_stores keeps)
+        srows, slast = self.ss_lap_table() if ns else (np.zeros((0, 0), np.int32), None)
+        if srows.shape[0]:
+            out["ss_lap_table"] = srows
+            if slast is not None:
+                out["ss_lap_last"] = slast
         np.savez_compressed(_npz_path(path), n_model=np.int64(nm.value), n_ss=np.int64(ns), N=np.int64(self.N), **out)
 
     def restore_stores(self, path):
@@ -699,6 +763,8 @@ class Context:
                 x, u, q, T0 = d["ss_x%d" % i], d["ss_u%d" % i], d["ss_q%d" % i], int(d["ss_laptime%d" % i])
                 self.ss_add_trajectory(x[:T0], u[:T0])
                 self.ss_replace_lap(i, x, u, q)          # (always: the saved rows and Q-function, whatever computeCost makes of the first T0 rows)
+            if "ss_lap_table" in d.files:                    # (per-problem safe-set laps; a file written without them restores to "no table")
+                self.ss_set_lap_table(d["ss_lap_table"], d["ss_lap_last"] if "ss_lap_last" in d.files else None)
 
     def rollout_release(self):
         """Free the device buffers a finished session keeps for the next lap (lmpc_rollout_release)."""
@@ -918,7 +984,7 @@ class ContextPool:
     def __getattr__(self, name):                       # lap-store edits (model_add_trajectory, ss_add_trajectory, ss_add_point, ss_set_selected, ...): the same call on every member
         if name in ("members", "_next"):               # (not set yet: a failed __init__ must not recurse through this hook)
             raise AttributeError(name)
-        if name == "plant_set_params" or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num", "model_lap"))):   # (the vehicle too: the same on every member; model_set_lap_table goes with the store edits, the queries model_lap_table / model_lap_info to the first)
+        if name == "plant_set_params" or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num", "model_lap"))):   # (the vehicle too: the same on every member; model_set_lap_table and ss_set_lap_table go with the store edits, the queries model_lap_table / model_lap_info / ss_lap_table to the first)
             def forward(*a, **kw):
                 out = None
                 for m in self.members:

@@ -130,6 +130,10 @@ struct lmpc_ctx {
     // d_lt: the same rows on the device as resolved (slot, rows) pairs in each row's sorted order, uploaded by `set` and rebuilt when the stores move or a lap is
     // replaced (resolve_lap_table); lt_small: every lap named anywhere has at most 512 rows, i.e. the 8-rows-per-lane scan serves the whole table (launch_k1)
     std::vector<int> lt_idx; int lt_n; int *d_lt; size_t d_lt_cap; bool lt_small;
+    // lmpc_ss_set_lap_table: sst_n rows of numSS_it safe-set lap indices and (sst_has_last) one "latest lap" index per row, as the caller gave them.  d_sst: the rows
+    // on the device as the solve kernels read them (LMPC_SSTAB_ENTRY ints per entry: slot, current rows, latest flag, pad; each row in ascending LapTime, ties by
+    // index).  The image names rows of laps, so every edit of the safe set marks it dirty and the next launch that reads it uploads it again (ss_table_for)
+    std::vector<int> sst_idx, sst_last; int sst_n; bool sst_has_last, sst_dirty; int *d_sst; size_t d_sst_cap;
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     double *ext_rows; size_t ext_rows_bytes;   // staging buffer of lmpc_ss_extend_lap
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
@@ -187,7 +191,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 105; }
+int lmpc_version(void) { return 106; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -385,7 +389,7 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt};      // (the work buffers are ranges of the two slabs)
+    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt, c->d_sst};      // (the work buffers are ranges of the two slabs)
     check_slab_gaps(c);
     for (void *q : ptrs) if (q) (void)g_free(q);
     if (c->h_retry) (void)hipHostFree(c->h_retry);
@@ -598,6 +602,7 @@ int lmpc_ss_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int T)
     HIPCHK(hipStreamSynchronize(c->stream));
     int rc = upload_lap(c, false, lap, x, u, cost.data(), T); if (rc) return rc;
     c->s_len.push_back(T); c->s_laptime.push_back(T); c->s_qlast.push_back(cost[T - 1]); c->s_q0.push_back(cost[0]);
+    c->sst_dirty = true;                                             // (last = NULL: which lap is the latest has changed)
     return LMPC_OK;
 }
 
@@ -618,19 +623,49 @@ int lmpc_ss_add_point(lmpc_ctx *c, const double *x, const double *u) {
     hipLaunchKernelGGL(lmpc_store_row_kernel, dim3(1), dim3(64), 0, c->stream, base, c->cfg.max_lap_len, row,
                        x[0], x[1], x[2], x[3], x[4] + c->cfg.trackLength, x[5], u[0], u[1], q);   // :472-473
     HIPCHK(hipGetLastError());
-    c->s_len[lap] = row + 1; c->s_qlast[lap] = q;
+    c->s_len[lap] = row + 1; c->s_qlast[lap] = q; c->sst_dirty = true;
     return LMPC_OK;
 }
 int lmpc_ss_replace_lap(lmpc_ctx *c, int lap, const double *x, const double *u, const double *qfun, int T) {
     ARGCHK(c && x && u && qfun && lap >= 0 && lap < (int)c->s_len.size() && T >= 1);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     int rc = upload_lap(c, false, lap, x, u, qfun, T); if (rc) return rc;
-    c->s_len[lap] = T; c->s_qlast[lap] = qfun[T - 1]; c->s_q0[lap] = qfun[0];
+    c->s_len[lap] = T; c->s_qlast[lap] = qfun[T - 1]; c->s_q0[lap] = qfun[0]; c->sst_dirty = true;
     return LMPC_OK;
 }
 int lmpc_ss_set_selected(lmpc_ctx *c, const int *laps, int n) {
     ARGCHK(c && n >= 0 && n <= LMPC_MAX_USED_LAPS && (n == 0 || laps));
     if (n == 0) c->s_override.clear(); else c->s_override.assign(laps, laps + n);
+    return LMPC_OK;
+}
+int lmpc_ss_set_lap_table(lmpc_ctx *c, int n, const int *laps, const int *last) {
+    // checked in full before anything is changed: a refused table leaves the one in force.  Nothing is uploaded here: the image is built by the next launch that reads it
+    ARGCHK(c && n >= 0 && (n == 0 || laps));
+    if (n == 0) { c->sst_n = 0; c->sst_idx.clear(); c->sst_last.clear(); c->sst_has_last = false; return LMPC_OK; }
+    const int L = c->cfg.numSS_it, stored = (int)c->s_len.size();
+    ARGCHK(L >= 1);
+    char msg[128];
+    for (size_t i = 0; i < (size_t)n * L; i++)
+        if (laps[i] < 0 || laps[i] >= stored) {
+            snprintf(msg, sizeof(msg), "row %d names lap %d, %d laps are stored", (int)(i / L), laps[i], stored);
+            return set_err(LMPC_E_ARG, "safe-set lap table", msg);
+        }
+    for (int r = 0; last && r < n; r++)
+        if (last[r] < -1 || last[r] >= stored) {
+            snprintf(msg, sizeof(msg), "last[%d] = %d, %d laps are stored", r, last[r], stored);
+            return set_err(LMPC_E_ARG, "safe-set lap table", msg);
+        }
+    c->sst_idx.assign(laps, laps + (size_t)n * L); c->sst_n = n; c->sst_has_last = last != nullptr;
+    if (last) c->sst_last.assign(last, last + n); else c->sst_last.clear();
+    c->sst_dirty = true;
+    return LMPC_OK;
+}
+int lmpc_ss_get_lap_table(lmpc_ctx *c, int *n, int *laps, int *last, int capacity) {
+    ARGCHK(c && n && capacity >= 0);
+    *n = c->sst_n;
+    const size_t rows = (size_t)std::min(capacity, c->sst_n);
+    if (laps && rows) memcpy(laps, c->sst_idx.data(), sizeof(int) * (size_t)c->cfg.numSS_it * rows);
+    for (size_t r = 0; last && r < rows; r++) last[r] = c->sst_has_last ? c->sst_last[r] : LMPC_SS_LAST_SHARED;
     return LMPC_OK;
 }
 int lmpc_ss_num_laps(lmpc_ctx *c, int *n) { ARGCHK(c && n); *n = (int)c->s_len.size(); return LMPC_OK; }
@@ -669,14 +704,16 @@ int lmpc_ss_get_laptime(lmpc_ctx *c, int lap, int *T) { ARGCHK(c && T && lap >= 
 // model_from_table: the regression launch this refresh is for reads a lap table (the context's, or a session's snapshot), whose rows `set` has checked -- the
 // sorted-order laps of the block are then not needed.  They are refreshed whenever they exist all the same: what decides is what the LAUNCH reads, and a session
 // begun without a table keeps reading the block whatever table the context has been given since.
-static int refresh_params(lmpc_ctx *c, bool need_model, bool need_ss, bool model_from_table = false) {
+// ss_from_table: likewise for a solve launch that selects from the safe-set lap table (ss_table_for), whose rows `set` has checked: the block's selection is not
+// read and not refreshed -- a row may name one lap numSS_it times, so fewer than numSS_it stored laps are no error then.
+static int refresh_params(lmpc_ctx *c, bool need_model, bool need_ss, bool model_from_table = false, bool ss_from_table = false) {
     lmpc_dev_params &p = c->dp;
     if (need_model) {
         const bool have = (int)c->m_order.size() >= c->cfg.trToUse && c->cfg.trToUse >= 1;
         if (!have && !model_from_table) return set_err(LMPC_E_STATE, "regression needs trToUse stored laps", "");
         if (have) for (int i = 0; i < c->cfg.trToUse; i++) { p.mslot[i] = c->m_order[i]; p.mlen[i] = c->m_len[c->m_order[i]]; }   // usedIt = range(trToUse), PredictiveModel.py:31
     }
-    if (need_ss) {
+    if (need_ss && !ss_from_table) {
         const int L = c->cfg.numSS_it, nl = (int)c->s_len.size();
         if (nl < L) return set_err(LMPC_E_STATE, "safe set holds fewer than numSS_it laps", "");
         std::vector<int> sel;
@@ -784,8 +821,46 @@ static int resolve_retries(lmpc_ctx *c) {
     c->epoch = 0; memset(c->h_retry, 0, sizeof(int) * LMPC_RETRY_RING);
     return rc;
 }
+// Per-problem safe-set laps (lmpc_ss_set_lap_table) for a launch of B problems that selects on the device: B against the rows, the device image brought up to date,
+// io.ssTab / io.ssTabStride set.  No table: io stays as it is (the selection of the parameter block).  Called before the first launch of a step (step_dev,
+// lmpc_rollout_run), so that a refused batch leaves nothing half done, and by launch_solve for every other caller.
+// The image is rebuilt from the indices whenever the safe set has been edited since the last upload: an entry holds the lap's CURRENT rows, and with last = NULL
+// the latest lap is the last one stored at launch time.  Launches still pending their retry pass read the image of THEIR launch: they are resolved, and the
+// stream is drained, before it is overwritten.
+static int ss_table_for(lmpc_ctx *c, int B, lmpc_solve_io *io) {
+    if (c->sst_n == 0 || c->cfg.numSS_it == 0 || !(io->mode & 1)) return LMPC_OK;
+    if (c->sst_n > 1 && B != c->sst_n) {
+        char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_ss_set_lap_table holds %d rows", B, c->sst_n);
+        return set_err(LMPC_E_ARG, "safe-set lap table", msg);
+    }
+    const int L = c->cfg.numSS_it;
+    if (c->sst_dirty) {
+        RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+        const int latest_shared = (int)c->s_len.size() - 1;
+        std::vector<int> img((size_t)c->sst_n * L * LMPC_SSTAB_ENTRY, 0), o((size_t)L);
+        for (int r = 0; r < c->sst_n; r++) {
+            // the order a controller holding only these laps would use them: argsort(LapTime), stable (:395, :402) -- ascending LapTime, ties by lap index
+            std::copy(&c->sst_idx[(size_t)r * L], &c->sst_idx[(size_t)r * L] + L, o.begin());
+            std::sort(o.begin(), o.end(), [&](int a, int b) { return c->s_laptime[a] != c->s_laptime[b] ? c->s_laptime[a] < c->s_laptime[b] : a < b; });
+            const int latest = c->sst_has_last ? c->sst_last[r] : latest_shared;
+            for (int l = 0; l < L; l++) {
+                int *e = &img[((size_t)r * L + l) * LMPC_SSTAB_ENTRY];
+                e[0] = o[l]; e[1] = c->s_len[o[l]]; e[2] = o[l] == latest ? 1 : 0;       // (safe-set lap index == slot)
+            }
+        }
+        if (img.size() > c->d_sst_cap) {
+            if (c->d_sst) { (void)g_free(c->d_sst); c->d_sst = nullptr; c->d_sst_cap = 0; }
+            HIPCHK(g_malloc(&c->d_sst, img.size() * sizeof(int))); c->d_sst_cap = img.size();
+        }
+        HIPCHK(hipMemcpy(c->d_sst, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+        c->sst_dirty = false;
+    }
+    io->ssTab = c->d_sst; io->ssTabStride = c->sst_n == 1 ? 0 : L * LMPC_SSTAB_ENTRY;
+    return LMPC_OK;
+}
 static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false) {
     lmpc_solve_io io = io_in;
+    if (!io.ssTab) { const int rc = ss_table_for(c, B, &io); if (rc) return rc; }
     // [A_k | B_k] from global memory only when the batch does not fit the CUs with it in LDS (N = 40: more than two QPs per CU); a batch that
     // fits runs 3 % faster from LDS (measured at N = 40, batch 512: 0.997 vs 1.030 ms)
     io.abPack = nullptr;
@@ -804,7 +879,7 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
         c->epoch++; io.retry_epoch = c->epoch; io.retry_flag = c->d_retry + (c->epoch % LMPC_RETRY_RING);
     }
     const bool term = c->cfg.numSS_it > 0;
-    int rc = refresh_params(c, false, term && (io.mode & 1)); if (rc) return rc;
+    int rc = refresh_params(c, false, term && (io.mode & 1), false, io.ssTab != nullptr); if (rc) return rc;
     const bool timing_buf = io.tbuf != nullptr;              // (the cycle-stamp build pins the kernel route; the trace build below must not)
 #ifdef LMPC_TRACE
     if (!io.tbuf && c->dbg_trace && (io.mode & 2)) io.tbuf = (long long *)c->dbg_trace;
@@ -818,7 +893,8 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
         rc = nw == 4 ? c->var.launch_mw4(c->stream, c->dp, B, io) : nw == 2 ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
     } else
 #endif
-    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4)) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
+    // (a safe-set lap table: the condensed kernel has no per-problem lookup and is not taken -- the kernels below have it)
+    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.ssTab) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
        : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, B, io)        // fused step: the one-wave kernel runs the regression itself
        : (B <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, B, io)
        : (lmpc_solver_waves(c, B) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
@@ -988,13 +1064,15 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     // front of the solve and [A_k | B_k], C_k never leave LDS (see lmpc_create for the measurement that keeps it off by default).
     { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows: refused before anything is queued)
     // (a lap table in force: the fused form reads the laps of the parameter block -- it lives in the variant libraries -- so the two-kernel step runs)
-    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0;
+    // (likewise a safe-set lap table, lmpc_ss_set_lap_table: the fused form's LDS layout has no room behind it for the selected laps)
+    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0 && !(term && c->sst_n);
     double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
     // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
     // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
     // A / Bm / C (racinglmpc_amd._capi.Context.step_dev_buffers does) and keep every buffer of a launch untouched until lmpc_dev_sync.
     if (dA == c->w.A || dB == c->w.Bm || dC == c->w.C) for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
     lmpc_solve_io io = solve_io((fused ? 4 : 0) | (term ? 3 : 2), a);
+    RCCHK(ss_table_for(c, B, &io));                       // (B against the safe-set lap table's rows: refused before the regression is queued)
     io.A = dA; io.Bm = dB; io.C = dC;
     // (io.rstatus / the fused regression: a singular regression or an off-track linearisation point marks status[b]; the reference raises there)
     if (fused) { io.xLin = a.xLin; io.uLin = a.uLin; io.Aout = a.A; io.Bout = a.Bm; io.Cout = a.C; RCCHK(refresh_params(c, true, false)); }
@@ -1528,15 +1606,17 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
     int nd = 0, rc = LMPC_OK;
     const int t_end = std::min(r->T_max, r->t + max_steps);
     while (r->t < t_end) {
+        lmpc_solve_io io = solve_io(lmpc ? 3 : 2, r->a);
+        // the safe-set lap table is live in a session (as lmpc_ss_set_selected is): B against its rows before the first launch of the step
+        if (lmpc) { rc = ss_table_for(c, B, &io); if (rc) return rc; }
         if (!lti) {
-        rc = refresh_params(c, true, lmpc, r->has_lt); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
+        rc = refresh_params(c, true, lmpc, r->has_lt, io.ssTab != nullptr); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
         ev_begin(c, 0);
         { int qg, nblk; k1_grid(c, B, &qg, &nblk);
           const k1_table tab = {r->has_lt ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small};
           launch_k1(c, nblk, B, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
         ev_end(c); c->stats.n_regress++;
         }
-        lmpc_solve_io io = solve_io(lmpc ? 3 : 2, r->a);
         io.rstatus = lti ? nullptr : r->a.rstatus;
         if (r->t > 0) HIPCHK(hipStreamWaitEvent(c->stream, r->e_plant, 0));          // the solve needs the plant's new state
         rc = launch_solve(c, B, io, true); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
@@ -1668,7 +1748,7 @@ int lmpc_ss_extend_lap(lmpc_ctx *c, int lap, const double *x, const double *u, i
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the pageable host rows must outlive the copy)
     if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_ss_extend_lap", hipGetErrorString(e));
-    c->s_len[lap] += n; c->s_qlast[lap] = q;
+    c->s_len[lap] += n; c->s_qlast[lap] = q; c->sst_dirty = true;
     return LMPC_OK;
 }
 
@@ -1678,7 +1758,7 @@ int lmpc_ss_truncate_lap(lmpc_ctx *c, int lap, int T) {
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     double q = 0.0;                                                  // Qfun of the new last row (addPoint counts on from it, :474)
     HIPCHK(hipMemcpy(&q, c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len + (T - 1), sizeof(double), hipMemcpyDeviceToHost));
-    c->s_len[lap] = T; c->s_qlast[lap] = q;
+    c->s_len[lap] = T; c->s_qlast[lap] = q; c->sst_dirty = true;
     return LMPC_OK;
 }
 

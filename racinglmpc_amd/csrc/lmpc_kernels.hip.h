@@ -17,7 +17,7 @@
 #include "../../include/lmpc_hip.h"
 
 #define WAVE 64
-#define LMPC_VARIANT_ABI_REV 7          // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
+#define LMPC_VARIANT_ABI_REV 8          // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
                                         // (LMPC_VARIANT_ABI, lmpc_variant.hip.h) also folds in the three struct sizes, so that layout drift cannot pass on the number alone
 #define LMPC_COLS 9                 // lap-store columns: x0..x5, u0, u1, Qfun
 
@@ -123,7 +123,23 @@ struct lmpc_solve_io {
     double *abPack;           // one-wave kernel, long horizons (ABG): global scratch for [A_k | B_k] in the kernel's 6 x 8 layout, 48 N doubles per problem
     int *retry_flag;          // optional (host-mapped): a problem that ends at the iteration limit / breaks down writes retry_epoch here (atomic max, system
     int retry_epoch;          // scope), so that the host launches the retry pass only when one is needed (lmpc_capi.hip: resolve_retries)
+    const int *ssTab;         // optional: per-problem safe-set laps (lmpc_ss_set_lap_table), resolved on the host: numSS_it entries of LMPC_SSTAB_ENTRY ints per row --
+    int ssTabStride;          // (slot, rows, is the car's latest lap, pad), 16 bytes -- in the row's sorted order; ints between rows (0: one row serves every problem)
 };
+#define LMPC_SSTAB_ENTRY 4
+// With a table the selection keeps (slot, rows) of every selected lap for the successor rows of feasibleStateInput, beside sel_start: in LMPC_SSTAB_LDS bytes of
+// dynamic LDS behind the kernel's layout, which the launchers add only when io.ssTab is set -- a launch without a table has the footprint it always had.
+// The fixed-(N, S) solve kernels are templates on TAB, as the regression kernel is: the TAB = false instantiations, which serve every launch without a table, carry
+// none of this; the runtime-(N, S) kernel branches at run time.
+#define LMPC_SSTAB_LDS (2 * LMPC_MAX_USED_LAPS * sizeof(int))
+// The lap K2 reads as entry l of problem b: from the table row (b and l are uniform over the wave: one 16-byte scalar load), else from the parameter block.
+// latest: the entry takes the "current lap" branch of the Q-function shift (:502-512)
+struct k2_lap { int slot, rows, latest; };
+template <bool TAB>
+__device__ __forceinline__ k2_lap k2_lap_of(const lmpc_dev_params &p, const lmpc_solve_io &io, int b, int l) {
+    if (TAB) { const int4 e = *(const int4 *)(io.ssTab + (size_t)b * io.ssTabStride + LMPC_SSTAB_ENTRY * l); return {e.x, e.y, e.z}; }
+    return {p.sslot[l], p.sslen[l], p.sslapid[l] < p.cur_it - 1 ? 0 : 1};
+}
 __device__ __forceinline__ void flag_retry(const lmpc_solve_io &io, int st) {
     if (io.retry_flag && (st & (LMPC_ST_MAXITER | LMPC_ST_NUMERIC))) __hip_atomic_fetch_max(io.retry_flag, io.retry_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -1404,11 +1420,12 @@ __device__ __forceinline__ int term_factor7(const double *Wl, double *Ri, int la
 // ------------------------------------------------------------------------------------------------
 // K2: safe-set selection.  LMPC.addTerminalComponents :392-412 and selectPoints :478-514.  Shared by the one-wave and the
 // multi-wave solve kernels: wave `wave` of NW handles laps wave, wave + NW, ...; results go to SS (6 x S, row-major), Qsel (S),
-// sel_start (window start per lap, kept for the successor rows of feasibleStateInput) and the optional global outputs.
+// sel_start (window start per lap, kept for the successor rows of feasibleStateInput) and the optional global outputs.  io.ssTab set: the laps are those of
+// the problem's table row (k2_lap_of) and sel_lap receives their (slot, rows) pairs; else sel_lap is not touched.
 // ------------------------------------------------------------------------------------------------
-template <int N, int S, int NW>
+template <int N, int S, int NW, bool TAB = false>
 __device__ __forceinline__ void k2_select(const lmpc_dev_params &p, const lmpc_solve_io &io, int b, int lane, int wave, double *SS, double *Qsel,
-                                          int *sel_start, int *st_sh) {
+                                          int *sel_start, int *sel_lap, int *st_sh) {
     if (io.mode & 1) {
         double ztv[6];
 #pragma unroll
@@ -1432,8 +1449,10 @@ __device__ __forceinline__ void k2_select(const lmpc_dev_params &p, const lmpc_s
         const int tstep = io.timeStep ? io.timeStep[b] : 0;
         const int ppl = p.ppl, npw = ppl + 1;                                   // numSS_Points/numSS_it + 1 (=13)
         for (int l = wave; l < p.L; l += NW) {
-            const double *base = p.sstore + (size_t)p.sslot[l] * LMPC_COLS * p.lap_stride;
-            const int T = p.sslen[l], ls = p.lap_stride;
+            int slot_ = p.sslot[l], T_ = p.sslen[l], latest_ = 0; (void)latest_;
+            if constexpr (TAB) { const k2_lap lp = k2_lap_of<true>(p, io, b, l); slot_ = lp.slot; T_ = lp.rows; latest_ = lp.latest; if (lane == 0) { sel_lap[2 * l] = lp.slot; sel_lap[2 * l + 1] = lp.rows; } }
+            const double *base = p.sstore + (size_t)slot_ * LMPC_COLS * p.lap_stride;
+            const int T = T_, ls = p.lap_stride;
             double best = INFINITY; int bi = 0x7fffffff;
             for (int r = lane; r < T; r += WAVE) {
                 double nrm = fabs(base[r] - ztv[0]);                            // la.norm(x - zt, 1, axis=1)
@@ -1453,7 +1472,9 @@ __device__ __forceinline__ void k2_select(const lmpc_dev_params &p, const lmpc_s
             if (lane == 0) { sel_start[l] = start; if (io.selStartOut) io.selStartOut[(size_t)b * p.L + l] = start; if (start + npw > T) atomicOr(st_sh, LMPC_ST_WINDOW); }
             double shift = 0.0;                                                 // :502-512
             if (hasPred && crossed > 0) {
-                if (p.sslapid[l] < p.cur_it - 1) shift = base[8 * ls];
+                bool earlier = p.sslapid[l] < p.cur_it - 1;
+                if constexpr (TAB) earlier = !latest_;
+                if (earlier) shift = base[8 * ls];
                 else shift = (double)tstep + (double)(N - crossed);
             }
             if (lane < ppl) {
@@ -1482,7 +1503,7 @@ __device__ __forceinline__ void k2_select(const lmpc_dev_params &p, const lmpc_s
     }
 }
 
-template <int N, int S, bool EQ = false, bool ABG = false>
+template <int N, int S, bool EQ = false, bool ABG = false, bool TAB = false>
 // (two waves per SIMD -- at most 256 registers -- only where the LDS footprint lets more than four QPs share a CU and the terminal
 // block keeps one column per lane)
 #ifdef LMPC_AB_OCC3     // (developer A / B, tools/resource_usage.py: what a third resident wave per SIMD -- at most 168 registers -- would cost this kernel; profiles/r6_onewave_occ3_resource_usage.txt)
@@ -1522,6 +1543,7 @@ __global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 
                  *R2 = par + PAR_R2, *dR2 = par + PAR_DR2, *T2p = par + PAR_T2, *xRef = par + PAR_XREF;
     __shared__ int st_sh;
     __shared__ int sel_start[LMPC_MAX_USED_LAPS];
+    int *sel_lap = (int *)(sm + LL::tot);                   // (io.ssTab only: LMPC_SSTAB_LDS bytes behind the layout)
     int tcnt = 0; (void)tcnt;
     TSTAMP(0);
     // (retry variant: the regression's per-point bits are taken over from the first pass's status word -- the per-point buffer may belong to
@@ -1560,7 +1582,7 @@ __global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 
         FOR_LANES_T(i, t, 6 * N) c_r[t] = io.C[(size_t)b * 6 * N + i];
     }
     // K2: safe-set selection (k2_select), then the regression status bits of this problem's N points
-    if constexpr (term) { k2_select<N, S, 1>(p, io, b, lane, 0, SS, Qsel, sel_start, &st_sh); __syncthreads(); }
+    if constexpr (term) { k2_select<N, S, 1, TAB>(p, io, b, lane, 0, SS, Qsel, sel_start, sel_lap, &st_sh); __syncthreads(); }
     if (!EQ && io.rstatus && lane < N) { const int rs_ = io.rstatus[(size_t)b * N + lane]; if (rs_) atomicOr(&st_sh, rs_); }
     TSTAMP(1);
     if (!(io.mode & 2)) { if (lane == 0) io.status[b] = st_sh; return; }
@@ -2198,8 +2220,10 @@ __global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 
             for (int j = 0; j < 8; j++) acc[j] = 0.0;
             FOR_LANES(c, S) {
                 const int l = c / p.ppl, cc = c % p.ppl;
-                const double *base = p.sstore + (size_t)p.sslot[l] * LMPC_COLS * p.lap_stride;
-                int r1 = sel_start[l] + cc + 1; r1 = r1 > p.sslen[l] - 1 ? p.sslen[l] - 1 : r1;
+                int slot = p.sslot[l], T = p.sslen[l];
+                if constexpr (TAB) { slot = sel_lap[2 * l]; T = sel_lap[2 * l + 1]; }
+                const double *base = p.sstore + (size_t)slot * LMPC_COLS * p.lap_stride;
+                int r1 = sel_start[l] + cc + 1; r1 = r1 > T - 1 ? T - 1 : r1;
                 const double lv = lam[c];
 #pragma unroll
                 for (int j = 0; j < 8; j++) acc[j] = fma(base[j * p.lap_stride + r1], lv, acc[j]);

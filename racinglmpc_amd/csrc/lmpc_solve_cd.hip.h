@@ -88,7 +88,7 @@ __global__ __launch_bounds__(WAVE, 2) void lmpc_solve_kernel_cd(lmpc_dev_params 
         FOR_LANES_T(i, t, 12 * N) preB[t] = io.Bm[(size_t)b * 12 * N + i];
         FOR_LANES_T(i, t, 6 * N) preC[t] = io.C[(size_t)b * 6 * N + i];
     }
-    if constexpr (term) { k2_select<N, S, 1>(p, io, b, lane, 0, SS, Qsel, sel_start, &st_sh); __syncthreads(); }
+    if constexpr (term) { k2_select<N, S, 1>(p, io, b, lane, 0, SS, Qsel, sel_start, nullptr, &st_sh)       /* (never launched with io.ssTab: lmpc_capi.hip, launch_solve) */; __syncthreads(); }
     if (io.rstatus && lane < N) { const int rs_ = io.rstatus[(size_t)b * N + lane]; if (rs_) atomicOr(&st_sh, rs_); }
     TSTAMP(1);
     if (!(io.mode & 2)) { if (lane == 0) io.status[b] = st_sh; return; }

@@ -26,7 +26,7 @@
 #define TSMW(id) do { } while (0)
 #endif
 
-template <int N, int S, int NW>
+template <int N, int S, int NW, bool TAB = false>
 // (registers: four waves per QP = one wave per SIMD; two waves per QP = two waves per SIMD only where the LDS footprint lets three or more
 // QPs share a CU -- long horizons keep their sweep operands (3 N doubles per lane) in registers and need the full file: at N = 40 the
 // 256-register build spilled 221 VGPRs to scratch)
@@ -69,6 +69,7 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
     // the fourth QP of the two-wave kernel no longer fitted a CU (163 840 / 4 = 40 960) -- batch 1024 ran in two rounds, 2.85 -> 2.18 M steps/s.
     double *const dump_sh = gs0;
     __shared__ int sel_start[LMPC_MAX_USED_LAPS];
+    int *sel_lap = (int *)(sm + LL::tot);                    // (io.ssTab only: LMPC_SSTAB_LDS bytes behind the layout, see lmpc_kernels.hip.h)
     __shared__ double ss_rowsum[6];                          // sum over the selected safe-set points of each state (loop invariant)
     double *phi = phi_sh;
     if (tid == 0) { st_sh = 0; bad_sh = 0; }
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
 
     // K2: safe-set selection, one lap per wave (k2_select, lmpc_kernels.hip.h), then the regression status bits of this problem
     if constexpr (term) {
-        k2_select<N, S, NW>(p, io, b, lane, wave, SS, Qsel, sel_start, &st_sh); __syncthreads();
+        k2_select<N, S, NW, TAB>(p, io, b, lane, wave, SS, Qsel, sel_start, sel_lap, &st_sh); __syncthreads();
         if (tid < 6) { double v = 0.0; for (int c = 0; c < S; c++) v += SS[tid * S + c]; ss_rowsum[tid] = v; }
     }
     if (io.rstatus && tid < N) { const int rs_ = io.rstatus[(size_t)b * N + tid]; if (rs_) atomicOr(&st_sh, rs_); }
@@ -884,8 +885,10 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
             for (int j = 0; j < 8; j++) acc[j] = 0.0;
             for (int c = lane; c < S; c += WAVE) {
                 const int l = c / p.ppl, cc = c % p.ppl;
-                const double *base = p.sstore + (size_t)p.sslot[l] * LMPC_COLS * p.lap_stride;
-                int r1 = sel_start[l] + cc + 1; r1 = r1 > p.sslen[l] - 1 ? p.sslen[l] - 1 : r1;
+                int slot = p.sslot[l], T = p.sslen[l];
+                if constexpr (TAB) { slot = sel_lap[2 * l]; T = sel_lap[2 * l + 1]; }
+                const double *base = p.sstore + (size_t)slot * LMPC_COLS * p.lap_stride;
+                int r1 = sel_start[l] + cc + 1; r1 = r1 > T - 1 ? T - 1 : r1;
                 const double lv = lam[c];
 #pragma unroll
                 for (int j = 0; j < 8; j++) acc[j] = fma(base[j * p.lap_stride + r1], lv, acc[j]);

@@ -36,7 +36,7 @@ __host__ __device__ inline rt_lds rt_layout(int N, int S) {
 }
 
 // K2 with runtime N, S (one wave): the selection of k2_select, statement for statement
-__device__ inline void k2_select_rt(const lmpc_dev_params &p, const lmpc_solve_io &io, int b, int lane, int N, int S, double *SS, double *Qsel, int *sel_start, int *st_sh) {
+__device__ inline void k2_select_rt(const lmpc_dev_params &p, const lmpc_solve_io &io, int b, int lane, int N, int S, double *SS, double *Qsel, int *sel_start, int *sel_lap, int *st_sh) {
     if (io.mode & 1) {
         double ztv[6];
         for (int j = 0; j < 6; j++) ztv[j] = io.zt[(size_t)b * 6 + j];
@@ -55,8 +55,10 @@ __device__ inline void k2_select_rt(const lmpc_dev_params &p, const lmpc_solve_i
         const int tstep = io.timeStep ? io.timeStep[b] : 0;
         const int ppl = p.ppl, npw = ppl + 1;
         for (int l = 0; l < p.L; l++) {
-            const double *base = p.sstore + (size_t)p.sslot[l] * LMPC_COLS * p.lap_stride;
-            const int T = p.sslen[l], ls = p.lap_stride;
+            const k2_lap lp = io.ssTab ? k2_lap_of<true>(p, io, b, l) : k2_lap_of<false>(p, io, b, l);                           // (the problem's table row when io.ssTab is set)
+            const double *base = p.sstore + (size_t)lp.slot * LMPC_COLS * p.lap_stride;
+            const int T = lp.rows, ls = p.lap_stride;
+            if (io.ssTab && lane == 0) { sel_lap[2 * l] = lp.slot; sel_lap[2 * l + 1] = lp.rows; }
             double best = INFINITY; int bi = 0x7fffffff;
             for (int r = lane; r < T; r += WAVE) {
                 double nrm = fabs(base[r] - ztv[0]);                            // la.norm(x - zt, 1, axis=1)
@@ -76,7 +78,7 @@ __device__ inline void k2_select_rt(const lmpc_dev_params &p, const lmpc_solve_i
             if (lane == 0) { sel_start[l] = start; if (io.selStartOut) io.selStartOut[(size_t)b * p.L + l] = start; if (start + npw > T) atomicOr(st_sh, LMPC_ST_WINDOW); }
             double shift = 0.0;                                                 // :502-512
             if (hasPred && crossed > 0) {
-                if (p.sslapid[l] < p.cur_it - 1) shift = base[8 * ls];
+                if (!lp.latest) shift = base[8 * ls];
                 else shift = (double)tstep + (double)(N - crossed);
             }
             for (int cc = lane; cc < ppl; cc += WAVE) {
@@ -128,6 +130,7 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
                  *R2 = par + PAR_R2, *dR2 = par + PAR_DR2, *T2p = par + PAR_T2, *xRef = par + PAR_XREF;
     __shared__ int st_sh;
     __shared__ int sel_start[LMPC_MAX_USED_LAPS];
+    int *sel_lap = (int *)(sm + L.tot);                      // (io.ssTab only: LMPC_SSTAB_LDS bytes behind the layout, see lmpc_kernels.hip.h)
     if (lane == 0) st_sh = EQ ? (io.status[b] & (LMPC_ST_REG_SINGULAR | LMPC_ST_NO_SEGMENT)) : 0;
     if (lane < 12) par[PAR_FX + lane] = p.Fx[lane];
     if (lane < 8) par[PAR_FU + lane] = p.Fu[lane];
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
     if (lane == 0) { par[PAR_AS] = p.a_s; par[PAR_CS] = p.c_s; }
     RT_SYNC();
     const double a_s = par[PAR_AS], c_s = par[PAR_CS];
-    if (term) { k2_select_rt(p, io, b, lane, N, S, SS, Qsel, sel_start, &st_sh); RT_SYNC(); }
+    if (term) { k2_select_rt(p, io, b, lane, N, S, SS, Qsel, sel_start, sel_lap, &st_sh); RT_SYNC(); }
     if (!EQ && io.rstatus) { RT_FOR(i, N) { const int rs_ = io.rstatus[(size_t)b * N + i]; if (rs_) atomicOr(&st_sh, rs_); } }
     if (!(io.mode & 2)) { RT_SYNC(); if (lane == 0) io.status[b] = st_sh; return; }
 
@@ -524,8 +527,10 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
             for (int j = 0; j < 8; j++) acc[j] = 0.0;
             RT_FOR(c, S) {
                 const int l = c / p.ppl, cc = c % p.ppl;
-                const double *base = p.sstore + (size_t)p.sslot[l] * LMPC_COLS * p.lap_stride;
-                int r1 = sel_start[l] + cc + 1; r1 = r1 > p.sslen[l] - 1 ? p.sslen[l] - 1 : r1;
+                int slot = p.sslot[l], T = p.sslen[l];
+                if (io.ssTab) { slot = sel_lap[2 * l]; T = sel_lap[2 * l + 1]; }
+                const double *base = p.sstore + (size_t)slot * LMPC_COLS * p.lap_stride;
+                int r1 = sel_start[l] + cc + 1; r1 = r1 > T - 1 ? T - 1 : r1;
                 const double lv = lam[c];
                 for (int j = 0; j < 8; j++) acc[j] = fma(base[j * p.lap_stride + r1], lv, acc[j]);
             }
@@ -547,7 +552,7 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
 
 // launchers of the runtime kernel (the table of lmpc_variant.hip.h is filled by lmpc_variant_fill_rt there): one wave per QP on every route
 static int lmpc_rt_launch(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-    hipLaunchKernelGGL((lmpc_solve_kernel_rt<false>), dim3(B), dim3(WAVE), (size_t)rt_layout(p.N, p.S).tot * sizeof(double), st, p, B, io); return 0; }
+    hipLaunchKernelGGL((lmpc_solve_kernel_rt<false>), dim3(B), dim3(WAVE), (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0), st, p, B, io); return 0; }
 static int lmpc_rt_launch_retry(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-    hipLaunchKernelGGL((lmpc_solve_kernel_rt<true>), dim3(B), dim3(WAVE), (size_t)rt_layout(p.N, p.S).tot * sizeof(double), st, p, B, io); return 0; }
+    hipLaunchKernelGGL((lmpc_solve_kernel_rt<true>), dim3(B), dim3(WAVE), (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0), st, p, B, io); return 0; }
 static int lmpc_rt_launch_cd(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int) { return lmpc_rt_launch(st, p, B, io); }

@@ -41,9 +41,13 @@ template <int N, int S> struct lmpc_variant_launchers {
     // settings (4 laps x 7 points) and grows it a little beyond
     static size_t lds_for(const lmpc_dev_params &p, const lmpc_solve_io &io) {
         const size_t f = (io.mode & 4) ? (size_t)(54 * N + k1_fused_doubles(N, p.trToUse, p.maxNumPoint)) * sizeof(double) : 0;
-        return f > lds1 ? f : lds1;
+        return (f > lds1 ? f : lds1) + sstab(io);
     }
-    static constexpr size_t lds1_max() { const size_t f = (size_t)(54 * N + k1_fused_doubles(N, LMPC_MAX_USED_LAPS, 8)) * sizeof(double); return f > lds1 ? f : lds1; }
+    // per-problem safe-set laps (io.ssTab): the TAB instantiations of the kernels, which exist for S > 0 only (has_tab = false folds them onto the plain ones)
+    static constexpr bool has_tab = S > 0;
+    static bool tab(const lmpc_solve_io &io) { return has_tab && io.ssTab != nullptr; }
+    static size_t sstab(const lmpc_solve_io &io) { return io.ssTab ? LMPC_SSTAB_LDS : 0; }     // per-problem safe-set laps: (slot, rows) of the selected laps behind the layout
+    static constexpr size_t lds1_max() { const size_t f = (size_t)(54 * N + k1_fused_doubles(N, LMPC_MAX_USED_LAPS, 8)) * sizeof(double); return (f > lds1 ? f : lds1) + LMPC_SSTAB_LDS; }
     // long horizons: [A_k | B_k] in global memory where that lets more QPs share a CU than the 160 KB of LDS otherwise hold and fewer than four do (idle SIMDs)
     static constexpr size_t lds1g = (size_t)solve_lds1<N, S, true>::tot * sizeof(double);
     // (measured, solve kernel, ms at batch 1024 / 4096: N = 40 LDS 1.467 / 4.073, global 1.092 / 3.398 -- two -> four QPs per CU;  N = 20 LDS 0.655 / 1.571,
@@ -51,13 +55,25 @@ template <int N, int S> struct lmpc_variant_launchers {
     static constexpr bool use_abg = (160 * 1024 / lds1) < 4 && (160 * 1024 / lds1g) > (160 * 1024 / lds1) && solve_lds1<N, S>::CH == 1;
     static int l1(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
         if constexpr (use_abg) {
-            if (!(io.mode & 4) && io.abPack) { hipLaunchKernelGGL((lmpc_solve_kernel<N, S, false, true>), dim3(B), dim3(WAVE), lds1g, st, p, B, io); return 0; }
+            if (!(io.mode & 4) && io.abPack) {
+                if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel<N, S, false, true, has_tab>), dim3(B), dim3(WAVE), lds1g + sstab(io), st, p, B, io);
+                else hipLaunchKernelGGL((lmpc_solve_kernel<N, S, false, true>), dim3(B), dim3(WAVE), lds1g, st, p, B, io);
+                return 0;
+            }
         }
-        hipLaunchKernelGGL((lmpc_solve_kernel<N, S>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io); return 0; }
+        if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel<N, S, false, false, has_tab>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
+        else hipLaunchKernelGGL((lmpc_solve_kernel<N, S>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
+        return 0; }
     static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        hipLaunchKernelGGL((lmpc_solve_kernel<N, S, true>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io); return 0; }
+        if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel<N, S, true, false, has_tab>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
+        else hipLaunchKernelGGL((lmpc_solve_kernel<N, S, true>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
+        return 0; }
     static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        if constexpr (has_mw) { hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 4>), dim3(B), dim3(WAVE * 4), ldsm, st, p, B, io); return 0; } else return l1(st, p, B, io); }
+        if constexpr (has_mw) {
+            if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 4, has_tab>), dim3(B), dim3(WAVE * 4), ldsm + sstab(io), st, p, B, io);
+            else hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 4>), dim3(B), dim3(WAVE * 4), ldsm, st, p, B, io);
+            return 0;
+        } else return l1(st, p, B, io); }
 #ifdef LMPC_WITH_CD
     static constexpr bool has_cd = 2 * N <= 32 && S + 6 <= WAVE;          // condensed kernel: short horizons, one terminal-block column per lane
 #else
@@ -73,7 +89,11 @@ template <int N, int S> struct lmpc_variant_launchers {
         (void)hasQ; return l1(st, p, B, io);
     }
     static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        if constexpr (has_mw) { hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 2>), dim3(B), dim3(WAVE * 2), ldsm, st, p, B, io); return 0; } else return l1(st, p, B, io); }
+        if constexpr (has_mw) {
+            if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 2, has_tab>), dim3(B), dim3(WAVE * 2), ldsm + sstab(io), st, p, B, io);
+            else hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 2>), dim3(B), dim3(WAVE * 2), ldsm, st, p, B, io);
+            return 0;
+        } else return l1(st, p, B, io); }
 };
 
 // fills the table and raises the kernels' dynamic-LDS limit; false if the device refuses (footprint beyond 160 KB)
@@ -84,6 +104,17 @@ template <int N, int S> static bool lmpc_variant_fill(lmpc_variant_api *v) {
     v->lds_mw = L::ldsm; v->lds_1w = (size_t)solve_lds1<N, S>::tot * sizeof(double);      // lds_mw == 0: no multi-wave kernels for this S
     if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
     if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
+    if constexpr (L::has_tab) {
+        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
+        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
+        if constexpr (L::has_mw) {
+            if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(L::ldsm + LMPC_SSTAB_LDS)) != hipSuccess) return false;
+            if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(L::ldsm + LMPC_SSTAB_LDS)) != hipSuccess) return false;
+        }
+        if constexpr (L::use_abg) {
+            if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(L::lds1g + LMPC_SSTAB_LDS)) != hipSuccess) return false;
+        }
+    }
     if constexpr (L::has_mw) {
         if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds_mw) != hipSuccess) return false;
         if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds_mw) != hipSuccess) return false;
@@ -116,8 +147,8 @@ static bool lmpc_variant_fill_rt(lmpc_variant_api *v, int N, int S) {
     if (N < 2 || N > LMPC_MAX_N || S < 0 || S > LMPC_MAX_SS_POINTS) return false;
     const size_t lds = (size_t)rt_layout(N, S).tot * sizeof(double);
     if (lds + 1024 > (size_t)160 * 1024) return false;
-    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_rt<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_rt<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_rt<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + LMPC_SSTAB_LDS)) != hipSuccess) return false;
+    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_rt<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + LMPC_SSTAB_LDS)) != hipSuccess) return false;
     v->N = N; v->S = S; v->lds_mw = 0; v->lds_1w = lds; v->lds_1w_abg = 0; v->lds_cd = 0; v->lds_cd_q = 0; v->occ_mw2 = 0;
     v->launch_1w = &lmpc_rt_launch; v->launch_retry = &lmpc_rt_launch_retry; v->launch_mw4 = &lmpc_rt_launch; v->launch_mw2 = &lmpc_rt_launch; v->launch_cd = &lmpc_rt_launch_cd;
     return true;

@@ -17,13 +17,17 @@ from . import _capi, parallel
 
 
 class BatchedRollouts:
-    """B closed-loop LMPC laps against a shared safe set (one GPU context, one rank)."""
+    """B closed-loop LMPC laps against a shared safe set, or (ss_table) each car against its own (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None):
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None):
         """lap_table: per-car regression laps of the cars of THIS object, rows of trToUse insertion indices into the context's regression store -- one row for all cars
         or one per car (Context.model_set_lap_table); handed to the context before every begin and every LTV run_mpc_laps, as plant_params is.  None: the context's
         table is left as it is (no table unless the caller set one: every car regresses on the first trToUse laps of the store's sorted order).  On an LMPC context
-        the safe set stays shared whatever the table says.
+        the safe set does not follow this table: it has its own, ss_table.
+        ss_table / ss_last: per-car safe sets of the cars of THIS object, rows of numSS_it safe-set lap indices and each car's latest lap -- one row for all cars or one
+        per car (Context.ss_set_lap_table); handed to the context before every begin, as lap_table and plant_params are.  The context's table is live in a session:
+        a caller that changes it between two rollout_run calls reaches the next step.  None: the context's table is left as it is (the shared selection unless the
+        caller set one).
         plant_params: vehicle constants of the cars of THIS object (this rank's shard), rows of _capi.PLANT_PARAM_NAMES as _capi.plant_params builds them -- one row
         for all cars or one per car; handed to the context (Context.plant_set_params) before every begin, run_pid_laps and run_mpc_laps.  None: the context's
         parameters are left as they are (the reference's vehicle unless the caller set others).
@@ -44,6 +48,9 @@ class BatchedRollouts:
         self.last_done = None
         self.plant_params = None if plant_params is None else _capi.check_plant_params(plant_params)
         self.lap_table = None if lap_table is None else _capi.check_lap_table(lap_table, ctx.cfg.trToUse)
+        self.ss_table, self.ss_last = (None, None) if ss_table is None else _capi.check_ss_table(ss_table, ctx.cfg.numSS_it, ss_last)
+        if ss_table is None and ss_last is not None:
+            raise ValueError("ss_last: needs ss_table")
         self.device_noise = bool(device_noise)
         if self.device_noise:
             import operator
@@ -148,6 +155,15 @@ class BatchedRollouts:
             raise ValueError("lap_table: one row or one per car (%d) expected, got %d" % (B, tab.shape[0]))
         self.ctx.model_set_lap_table(tab)
 
+    def _apply_ss_table(self, B):
+        """The safe-set rows of this object's cars go to the context in front of an LMPC session."""
+        tab = getattr(self, "ss_table", None)          # (objects built without __init__ -- tests/test_host_checks.py -- have none)
+        if tab is None:
+            return
+        if tab.shape[0] not in (1, B):
+            raise ValueError("ss_table: one row or one per car (%d) expected, got %d" % (B, tab.shape[0]))
+        self.ctx.ss_set_lap_table(tab, getattr(self, "ss_last", None))
+
     @staticmethod
     def _per_rollout(a, B):
         a = np.asarray(a, float)
@@ -159,6 +175,7 @@ class BatchedRollouts:
         noise = self._draw_noise(max_steps, B)
         self._apply_plant_params(B)
         self._apply_lap_table(B)
+        self._apply_ss_table(B)
         if self._device_noise_session(B):
             self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, None, T_max=max_steps)
         else:
@@ -355,7 +372,8 @@ class LmpcGeneration:
 
     The rollouts may drive different vehicles (BatchedRollouts(plant_params=...): rows for the cars of the rank's shard).  The safe set and the regression store
     stay SHARED: a lap driven by one vehicle then serves as terminal set and as regression data for the others (BatchedRollouts(lap_table=...) can give each car
-    its own regression laps; the safe set has no such table).  Whether that is wanted -- robustness of a
+    its own regression laps and BatchedRollouts(ss_table=...) its own safe set, but this class hands out neither: PerCarLMPC below is the loop with nothing
+    shared).  Whether that is wanted -- robustness of a
     learned safe set against model mismatch -- or not is the caller's decision; nothing here keeps vehicles apart."""
 
     def __init__(self, rollouts, total_rollouts, K=4, T_max=400, ext=40, comm=None):
@@ -506,3 +524,142 @@ def lap_and_exchange(rollouts, x0_all, xLin0, uLin0, K, T_max, comm=None):
     """One generation over all ranks (first generation form: explicit start states), device-resident."""
     gen = LmpcGeneration(rollouts, x0_all.shape[0], K=K, T_max=T_max, ext=0, comm=comm)
     return gen.run(x0_all, xLin0, uLin0)
+
+
+class PerCarHistory:
+    """What one store holds of every car, as the reference's per-object lists do (LMPC.LapTime, PredictiveModel's sorted xStored): per car the (length, index)
+    entries in the order they were added, the same lap any number of times.  row(b): the `width` fastest entries of car b -- a stable argsort of the lengths over
+    the car's own list, multiplicities kept -- as store indices: a row of the lap tables."""
+
+    def __init__(self, B, width):
+        self.width = int(width)
+        self.entries = [[] for _ in range(int(B))]
+
+    def add(self, b, length, index, times=1):
+        self.entries[b].extend([(int(length), int(index))] * int(times))
+
+    def row(self, b):
+        e = self.entries[b]
+        if len(e) < self.width:
+            raise ValueError("car %d has %d history entries, %d are needed" % (b, len(e), self.width))
+        return [e[i][1] for i in sorted(range(len(e)), key=lambda i: e[i][0])[:self.width]]      # (sorted is stable)
+
+    def rows(self):
+        return np.array([self.row(b) for b in range(len(self.entries))], np.int32)
+
+
+class PerCarLMPC:
+    """main.py:100-121 once per car, with nothing shared: B independent learners in one batch.  Car b regresses on its own laps (Context.model_set_lap_table) and
+    takes its terminal set and terminal cost from its own laps (Context.ss_set_lap_table), with `last[b]` = its own most recent lap -- every controller object of
+    the reference owns both stores (PredictiveControllers.py:395-412, PredictiveModel.py:35-46).  With BatchedRollouts(plant_params=...) each car also drives its own
+    vehicle.  No collectives are needed: the cars are independent, and a rank runs its shard with `rollouts.noise_shard` set.
+
+    seed(laps_per_car): entry b is one lap tuple (x, u, x_glob, final12, ...) as run_pid_laps / bootstrap return them, or a list of them.  Every lap is stored ONCE in
+    both stores; the car's history starts as its laps, the fastest one repeated until numSS_it (safe set) and trToUse (regression) entries are there -- the
+    reference's four copies of the PID lap (main.py:103-110) without the copies.
+    run(): one generation.  Car b starts from its own finish state (xF, SysModel.py:50) and linearises about the first rows of its latest lap; the first `ext` steps
+    of car b extend car b's own latest lap past the finish line (the batched LMPC.addPoint, :466-474; ClosedLoop's rules: never rows of a flagged rollout, never
+    non-finite rows) unless that lap was stored with its rows past the line already (a multiLap PID lap); then the lap is finished, every valid lap is added to both
+    stores, and row b of both tables becomes the numSS_it / trToUse fastest entries of car b's history with last[b] = the lap just added.
+    A car whose lap is not valid -- not finished within T_max, flagged with anything but ST_INEXACT, or its extension skipped -- is RETIRED:
+    retired[b] = (generation, status).  It keeps its slot in the batch, so that indices, noise streams and rows of the others do not move; its later laps are ignored.
+    lap_times[b]: the steps of car b's laps, generation by generation."""
+
+    EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
+
+    def __init__(self, rollouts, T_max=400, ext=40):
+        self.ro, self.T_max, self.ext = rollouts, int(T_max), int(ext)
+        self.B = None
+        self.generation = 0
+        self.retired = {}
+        self.lap_times = []
+        self.last_status = self.last_done = None
+
+    def seed(self, laps_per_car):
+        ctx = self.ro.ctx
+        if ctx.ss_num_laps() != 0 or ctx.model_num_laps() != 0:      # (one counter below numbers the laps of both stores)
+            raise ValueError("PerCarLMPC.seed needs a context with empty lap stores")
+        laps_per_car = [list(l) if isinstance(l, list) else [l] for l in laps_per_car]
+        B = self.B = len(laps_per_car)
+        self.ss_hist, self.model_hist = PerCarHistory(B, ctx.cfg.numSS_it), PerCarHistory(B, ctx.cfg.trToUse)
+        self.last = np.full(B, -1, np.int32)
+        self.latest = [None] * B           # (x, u, final12, ends at the line) of each car's most recent lap
+        self.lap_times = [[] for _ in range(B)]
+        n = 0                              # laps stored so far: the next index in both stores (safe-set lap index, regression-store insertion index)
+        for b, laps in enumerate(laps_per_car):
+            if not laps:
+                raise ValueError("PerCarLMPC.seed: car %d has no lap" % b)
+            first = n
+            for lap in laps:
+                x, u = np.asarray(lap[0], float), np.asarray(lap[1], float)
+                ctx.model_add_trajectory(x, u); ctx.ss_add_trajectory(x, u)
+                self.ss_hist.add(b, x.shape[0], n); self.model_hist.add(b, x.shape[0], n)
+                n += 1
+            lens = [np.asarray(l[0]).shape[0] for l in laps]
+            k = int(np.argmin(lens))                       # (np.argmin: the first among equals)
+            for hist in (self.ss_hist, self.model_hist):
+                hist.add(b, lens[k], first + k, times=max(0, hist.width - len(laps)))
+            lap = laps[-1]
+            x = np.asarray(lap[0], float)
+            done = int(lap[4]) if len(lap) > 4 else x.shape[0]
+            self.latest[b] = (x, np.asarray(lap[1], float), np.asarray(lap[3], float), done >= x.shape[0])
+            self.last[b] = n - 1
+        self._hand_tables()
+
+    def _hand_tables(self):
+        """Rows of both tables and `last`, from the histories, to the rollouts object (it hands them to the context before the next begin)."""
+        self.ro.lap_table = _capi.check_lap_table(self.model_hist.rows(), self.model_hist.width)
+        self.ro.ss_table, self.ro.ss_last = _capi.check_ss_table(self.ss_hist.rows(), self.ss_hist.width, self.last.copy())
+
+    def close(self):
+        self.ro.close()
+
+    def run(self):
+        """One generation; returns the lap tuples (x, u, x_glob, final12, done_at, status) of every car, None for a retired one."""
+        if self.B is None:
+            raise RuntimeError("PerCarLMPC.run before seed")
+        ro, ctx, B, N = self.ro, self.ro.ctx, self.B, self.ro.ctx.N
+        gen = self.generation
+        fin = np.stack([self.latest[b][2] for b in range(B)])
+        x0 = fin[:, 0:6].copy(); x0[:, 4] -= ro.TL                              # xF = x_cl[-1] - [0,0,0,0,TrackLength,0]
+        xg0 = fin[:, 6:12].copy()
+        xl = np.stack([self.latest[b][0][1:N + 2] for b in range(B)]); ul = np.stack([self.latest[b][1][1:N + 1] for b in range(B)])
+        ro.begin(x0, xl, ul, xg0, self.T_max)
+        try:
+            if self.ext > 0 and any(self.latest[b][3] and b not in self.retired for b in range(B)):
+                t, _ = ctx.rollout_run(self.ext)
+                X, U, G, done, st, fx, fg = ctx.rollout_fetch(0, t)
+                n = min(t, self.ext)
+                for b in range(B):
+                    if b in self.retired or not self.latest[b][3]:
+                        continue
+                    clean = n > 0 and (int(st[b]) & ~_capi.ST_INEXACT) == 0 and bool(np.all(np.isfinite(X[:n, b]))) and bool(np.all(np.isfinite(U[:n, b])))
+                    if not clean:
+                        self.retired[b] = (gen, int(st[b]) | self.EXT_SKIPPED)
+                        continue
+                    ctx.ss_extend_lap(int(self.last[b]), X[:n, b], U[:n, b])     # (the table is live in the session: the next step selects from the longer lap)
+            t, _ = ctx.rollout_run(self.T_max)
+            X, U, G, done, st, fx, fg = ctx.rollout_fetch(0, t)
+        finally:
+            ctx.rollout_end()
+        self.last_status, self.last_done = st, done
+        out = [None] * B
+        for b in range(B):
+            if b in self.retired:
+                continue
+            if not (done[b] >= 0 and (int(st[b]) & ~_capi.ST_INEXACT) == 0):
+                self.retired[b] = (gen, int(st[b]))
+                continue
+            T = int(done[b])
+            x, u = X[:T, b].copy(), U[:T, b].copy()
+            idx = ctx.ss_num_laps()
+            ctx.ss_add_trajectory(x, u); ctx.model_add_trajectory(x, u)
+            self.ss_hist.add(b, T, idx); self.model_hist.add(b, T, idx)
+            self.last[b] = idx
+            f12 = np.concatenate([fx[b], fg[b]])
+            self.latest[b] = (x, u, f12, True)
+            self.lap_times[b].append(T)
+            out[b] = (x, u, G[:T, b].copy(), f12, T, int(st[b]))
+        self._hand_tables()
+        self.generation += 1
+        return out
