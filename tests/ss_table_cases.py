@@ -17,6 +17,11 @@ The reference of a table row is a context that holds ONLY that row's laps (with 
 force.  Its latest lap is the last one added, so: `last` in the row -- that lap is added last instead (it must then be listed once and tie with no other lap of
 the row, so that moving it does not change the stable argsort); `last` not in the row or -1 -- lap 5 is added behind the row's laps: it is the latest, it is no faster
 than any of them and added last, hence never selected, and every entry takes the Qfun[it][0] branch.
+
+Horizons.  problems(g, B, N) starts the six base problems at rows t = [100, 200, 308 - N, 311 - N, 150, 306] of the PID run (start_steps): the two problems whose
+previous prediction crosses the line keep their terminal targets zt = xP[309] and xP[312] at every N, problem 5 stays the one wrap problem, and the others end
+before the line at every built-in horizon (200 + 40 < 305).  tests/test_ss_table_host.py checks, for N in {8, 12, 14, 20, 40}, the crossing pattern, the single
+wrap and that none of the 36 (problem, row) pairs of either row set raises LMPC_ST_WINDOW in the oracle; no horizon needed other steps.  ppl is 12 at every horizon.
 """
 import numpy as np
 
@@ -42,6 +47,23 @@ def fixture_laps(g):
     return [(np.ascontiguousarray(x), np.ascontiguousarray(u)) for x, u in laps], ext
 
 
+def cpu_stored(g):
+    """[(x, u, qfun, LapTime)] of the six laps as a context stores them after fill_table_context (what read_laps returns), computed by the oracle on the CPU:
+    LMPC.computeCost per lap, and LMPC.addPoint for the rows that extend lap 2 (s + TrackLength, the Q-function counting down)."""
+    from oracle import lmpc_oracle as orc
+    TL = float(g["trackLength"])
+    laps, ext = fixture_laps(g)
+    stored = []
+    for i, (x, u) in enumerate(laps):
+        q = orc.compute_cost(x, TL); T0 = x.shape[0]
+        if i == EXTENDED:
+            assert x[-1, 4] <= TL
+            xe = ext[0].copy(); xe[:, 4] += TL
+            x = np.vstack([x, xe]); u = np.vstack([u, ext[1]]); q = np.concatenate([q, q[-1] - 1 - np.arange(xe.shape[0])])
+        stored.append((x, u, q, T0))
+    return stored
+
+
 def fill_table_context(ctx, g):
     """Regression store and the six safe-set laps, lap 2 extended."""
     laps, ext = fixture_laps(g)
@@ -52,11 +74,16 @@ def fill_table_context(ctx, g):
     ctx.ss_extend_lap(EXTENDED, ext[0], ext[1])
 
 
-def problems(g, B=6):
-    """B problems, the six base problems cycled: hasPred = 1 everywhere, timeStep != 0; xPredPrev crosses the line for problems 2, 3 and 5 and not for 0, 1 and 4;
-    problem 5 starts just behind the line with zt still counted in the lap before, the wrap branch (:392-394)."""
+def start_steps(N=N):
+    """Start rows of the six base problems in the golden PID run at horizon N."""
+    return [100, 200, 308 - N, 311 - N, 150, 306]
+
+
+def problems(g, B=6, N=N):
+    """B problems of horizon N (12: the arrays of the N = 12 tests), the six base problems cycled: hasPred = 1 everywhere, timeStep != 0; xPredPrev crosses the line
+    for problems 2, 3 and 5 and not for 0, 1 and 4; problem 5 starts just behind the line with zt still counted in the lap before, the wrap branch (:392-394)."""
     xP, uP = np.array(g["xPID"]), np.array(g["uPID"]); TL = float(g["trackLength"])
-    t = np.array([100, 200, 296, 299, 150, 306])[np.arange(B) % 6]
+    t = np.array(start_steps(N))[np.arange(B) % 6]
     x0 = xP[t].copy(); xLin = np.stack([xP[k + 1:k + N + 2] for k in t]); uLin = np.stack([uP[k + 1:k + N + 1] for k in t])
     zt = xP[t + N + 1].copy(); xPredPrev = np.stack([xP[k:k + N + 1] for k in t])
     wrap = t == 306
@@ -64,8 +91,8 @@ def problems(g, B=6):
     return dict(x0=x0, xLin=xLin, uLin=uLin, uOld=uP[t].copy(), zt=zt, xPredPrev=xPredPrev, hasPred=np.ones(B, np.int32), timeStep=(t % 97 + 3).astype(np.int32))
 
 
-def own_order(row, last, laptime):
-    """The laps of the reference context of (row, last), in the order they are added."""
+def own_order(row, last, laptime, extra=EXTRA):
+    """The laps of the reference context of (row, last), in the order they are added.  extra: the lap that is slower than all others (lap 5 of this fixture)."""
     row = [int(l) for l in row]; last = int(last)
     order = sorted(row)
     if last in row:
@@ -73,8 +100,8 @@ def own_order(row, last, laptime):
         order.remove(last); order.append(last)
     else:
         # (lap 5 may itself be in the row: the copy added behind it ties with it, and the stable argsort selects the copies added first)
-        assert all(laptime[l] <= laptime[EXTRA] for l in row), (row, last)
-        order.append(EXTRA)
+        assert all(laptime[l] <= laptime[extra] for l in row), (row, last)
+        order.append(extra)
     return order
 
 
@@ -93,16 +120,16 @@ def fill_own_context(own, g, stored, order):
         own.ss_replace_lap(i, x, u, q)
 
 
-def oracle_selection(stored, order, p, b, TL, numSS_it, ppl):
-    """oracle.terminal_components for problem b of `p` on the laps `order`, sortedLapTime and cur_it per car: (SSsel.T, Qsel, Succ.T, SuccU.T, window ok)."""
-    from oracle import lmpc_oracle as orc
-    SS = [stored[l][0] for l in order]; uSS = [stored[l][1] for l in order]; Qf = [stored[l][2] for l in order]; LapTime = [stored[l][3] for l in order]
+def window_ok(stored, order, p, b, TL, numSS_it, ppl):
+    """The oracle's window rule for problem b of `p` on the laps `order`: the ppl + 1 rows selected around zt lie inside every lap used (the reference's
+    IndexError, :497; LMPC_ST_WINDOW where it does not hold)."""
+    SS = [stored[l][0] for l in order]; LapTime = [stored[l][3] for l in order]
     z = p["zt"][b].copy()
     if z[4] - p["x0"][b][4] > TL / 2:
         z[4] = np.max([z[4] - TL, 0])
     srt = np.argsort(np.array(LapTime), kind="stable")
     ok = True
-    for jj in srt[0:numSS_it]:                 # the 13-row window must lie inside the lap (the reference's IndexError, :497; LMPC_ST_WINDOW)
+    for jj in srt[0:numSS_it]:
         d = SS[jj] - z[None, :]
         nrm = np.abs(d[:, 0])
         for j in range(1, 6):
@@ -110,6 +137,18 @@ def oracle_selection(stored, order, p, b, TL, numSS_it, ppl):
         m = int(np.argmin(nrm)); npw = ppl + 1
         start = m - npw // 2 if m - npw / 2 >= 0 else m
         ok = ok and start + npw <= SS[jj].shape[0]
+    return ok
+
+
+def oracle_selection(stored, order, p, b, TL, numSS_it, ppl, N=N):
+    """oracle.terminal_components for problem b of `p` on the laps `order`, sortedLapTime and cur_it per car: (SSsel.T, Qsel, Succ.T, SuccU.T, window ok)."""
+    from oracle import lmpc_oracle as orc
+    SS = [stored[l][0] for l in order]; uSS = [stored[l][1] for l in order]; Qf = [stored[l][2] for l in order]; LapTime = [stored[l][3] for l in order]
+    z = p["zt"][b].copy()
+    if z[4] - p["x0"][b][4] > TL / 2:
+        z[4] = np.max([z[4] - TL, 0])
+    srt = np.argsort(np.array(LapTime), kind="stable")
+    ok = window_ok(stored, order, p, b, TL, numSS_it, ppl)
     xPrev = p["xPredPrev"][b] if p["hasPred"][b] else None
     SSsel, Qsel, Succ, SuccU = orc.terminal_components(SS, uSS, Qf, LapTime, z, ppl * numSS_it, numSS_it, xPrev, len(order), int(p["timeStep"][b]), N, TL, sortedLapTime=srt)
     return SSsel.T, Qsel, Succ.T, SuccU.T, ok

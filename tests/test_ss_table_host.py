@@ -53,29 +53,31 @@ def test_row_check_of_the_python_layer():
             _capi.check_ss_table(bad, L, last)
 
 
-def test_fixture_of_the_gpu_tests_raises_no_window():
-    """The fixture of tests/test_gpu_ss_table.py on the CPU: at least 5 laps of at least 3 lengths, two equal LapTimes, one lap extended past the line; for every
-    (problem, row) pair of both row sets the 13-row window of every selected lap lies inside the lap (no LMPC_ST_WINDOW), so no case is left out of a comparison."""
-    from oracle import lmpc_oracle as orc
+@pytest.mark.parametrize("N", [8, 12, 14, 20, 40])
+def test_fixture_of_the_gpu_tests_raises_no_window(N):
+    """The fixture of tests/test_gpu_ss_table.py and tests/test_gpu_table_routes.py on the CPU, at every built-in horizon: at least 5 laps of at least 3 lengths, two
+    equal LapTimes, one lap extended past the line; problems 2, 3 and 5 cross the line and 0, 1 and 4 do not, one problem takes the wrap branch, the two crossing
+    problems keep zt = xP[309] and xP[312]; for every one of the 36 (problem, row) pairs of both row sets the 13-row window of every selected lap lies inside the
+    lap (no LMPC_ST_WINDOW), so no case is left out of a comparison."""
     from tests import ss_table_cases as c
     g = common.load_lmpc_golden(); TL = float(g["trackLength"])
-    laps, ext = c.fixture_laps(g)
-    stored = []
-    for i, (x, u) in enumerate(laps):
-        q = orc.compute_cost(x, TL); T0 = x.shape[0]
-        if i == c.EXTENDED:
-            assert x[-1, 4] <= TL
-            xe = ext[0].copy(); xe[:, 4] += TL
-            x = np.vstack([x, xe]); u = np.vstack([u, ext[1]]); q = np.concatenate([q, q[-1] - 1 - np.arange(xe.shape[0])])
-        stored.append((x, u, q, T0))
+    stored = c.cpu_stored(g)
+    assert stored[c.EXTENDED][0].shape[0] == stored[c.EXTENDED][3] + 30
     lt = [s[3] for s in stored]
     assert len(lt) >= 5 and len(set(lt)) >= 3 and len(set(lt)) < len(lt)
-    p = c.problems(g, 6)
+    p = c.problems(g, 6, N)
+    xP = np.array(g["xPID"])
+    assert c.start_steps(12) == [100, 200, 296, 299, 150, 306]
+    assert p["xLin"].shape == (6, N + 1, 6) and p["uLin"].shape == (6, N, 2) and p["xPredPrev"].shape == (6, N + 1, 6)
+    assert np.array_equal(p["zt"][2], xP[309]) and np.array_equal(p["zt"][3], xP[312])
+    crossed = (p["xPredPrev"][:, :, 4] > TL).any(1)
+    assert crossed.tolist() == [False, False, True, True, False, True] and (p["timeStep"] != 0).all() and p["hasPred"].all()
+    assert (p["zt"][:, 4] - p["x0"][:, 4] > TL / 2).tolist() == [False] * 5 + [True]
     for rows, last, L in ((c.ROWS4, c.LAST4, 4), (c.ROWS2, c.LAST2, 2)):
         for r in range(6):
             order = c.own_order(rows[r], last[r], lt)
             for b in range(6):
-                assert c.oracle_selection(stored, order, p, b, TL, L, 12)[4], (L, r, b)
+                assert c.oracle_selection(stored, order, p, b, TL, L, 12, N=N)[4], (N, L, r, b)
 
 
 class _Ctx(standin_capi.Context):
