@@ -338,6 +338,34 @@ int lmpc_ss_extend_lap(lmpc_ctx *, int lap, const double *x /*n x 6*/, const dou
  * generation back with it, so that a generation either completes or leaves the safe set as it found it.  No reference counterpart. */
 int lmpc_ss_truncate_lap(lmpc_ctx *, int lap, int T);
         /* LMPC.addPoint (:466-474) applied to any stored lap: n points appended with s + TrackLength, Qfun counting down */
+
+/* ---- laps of the active session committed to the lap stores ON THE DEVICE (version 107; kernels: racinglmpc_amd/csrc/lmpc_commit.hip.h).  The session logs lie in
+ * device memory next to the stores: no log is downloaded, no lap uploaded, one launch serves every listed car. */
+#define LMPC_COMMIT_SS 1u
+#define LMPC_COMMIT_MODEL 2u
+int lmpc_rollout_commit_laps(lmpc_ctx *, int n, const int *cars /*n*/, const int *rows /*n, or NULL: doneAt[car]*/,
+                             unsigned stores, int *first_ss /*or NULL*/, int *first_model /*or NULL*/);
+        /* For i = 0 .. n-1 in the order listed, the effect of fetching the logs and then lmpc_ss_add_trajectory(X[:T_i, car_i], U[:T_i, car_i], T_i) (bit LMPC_COMMIT_SS:
+         * LMPC.addTrajectory + computeCost, PredictiveControllers.py:418-464) followed by lmpc_model_add_trajectory of the same rows (bit LMPC_COMMIT_MODEL:
+         * PredictiveModel.addTrajectory, PredictiveModel.py:35-46; its prefilter image serves the scan of :180-197).  Afterwards store contents, Qfun, LapTime, the
+         * regression store's sorted order (ties append, in listed order), its prefilter image and the safe-set table's dirty mark are bit for bit what the host path
+         * leaves.  The new laps get consecutive indices; first_ss / first_model receive the first (-1 for a store not written).  A car may be listed more than
+         * once: every entry gets a lap (main.py:103-110 adds one lap four times).  Valid in an active session of any kind (lmpc_rollout_begin, _begin_mpc, _pid) with
+         * at least one step taken.  Everything is checked before anything changes: LMPC_E_ARG for n < 1, NULL cars, a car outside [0, B), stores 0 or with unknown
+         * bits, rows[i] < 1 (< 2 with the model bit, as lmpc_model_add_trajectory), rows[i] beyond what the session logged for that car (the steps taken; for a car of
+         * a stop_at_line PID session its crossing step); LMPC_E_STATE when rows == NULL and a listed car has doneAt < 0 (lmpc_last_error names the car).  One store
+         * growth, one table upload, one launch, one download of n doubles; the context's bookkeeping changes only after the launch has completed */
+int lmpc_rollout_extend_laps(lmpc_ctx *, int n, const int *cars /*n*/, const int *laps /*n distinct safe-set lap indices*/,
+                             int n_rows, int *extended /*n: 1 appended, 0 skipped (a non-finite value)*/);
+        /* lmpc_ss_extend_lap(laps[i], X[:n_rows, cars[i]], U[:n_rows, cars[i]], n_rows) -- the batched LMPC.addPoint, PredictiveControllers.py:466-474 -- for every entry
+         * whose n_rows x 8 logged values are all finite; the other entries are left untouched and reported in `extended`.  Qfun continues from the lap's last value by
+         * repeated subtraction of 1.0, as the host loop does.  The caller keeps deciding on status bits (it has them from lmpc_rollout_fetch with t0 = t1 = 0).
+         * LMPC_E_ARG, before anything changes, for n_rows < 1 or beyond the steps taken, a lap index that names no stored lap, the same lap twice, a car out of range.
+         * One store growth, one launch, one download of the flags; the live safe-set table sees the longer laps at the next step */
+int lmpc_debug_model_image(lmpc_ctx *, int lap /*insertion index*/, unsigned *q /*3 x (rows-1)*/, double *par /*chunks used x 6*/, int *chunks);
+        /* the prefilter image of one regression-store lap as the regression kernel reads it (the scan of PredictiveModel.py:180-197 on 16-bit fixed point): three planes
+         * of packed words (vx | vy << 16), (wz | delta << 16), (a) over rows 0 .. rows-2, and per 1024-row chunk the five minima and the common scale.  Available in every
+         * build; tests compare the image of a committed lap with that of an uploaded one.  Any output may be NULL.  No reference counterpart */
 int lmpc_lti_regression(int device, const double *x /*T x 6*/, const double *u /*T x 2*/, int T, double lamb,
                         double *A /*6 x 6*/, double *B /*6 x 2*/, double *Error /*2 x 6: max; min of the fit residual*/, int *status /*or NULL*/);
         /* Utilities.Regression, fnc/Utilities.py:5-28 (main.py:74-77: the LTI model of the path-following MPC); ridge least squares over one lap */

@@ -22,6 +22,7 @@ CREATE_RUNTIME_KERNEL, CREATE_FORCE_RUNTIME_KERNEL = 1, 2
 ST_MAXITER, ST_REG_SINGULAR, ST_NO_SEGMENT, ST_WINDOW, ST_NUMERIC, ST_NOT_INTERIOR, ST_INEXACT, ST_INFEASIBLE = 1, 2, 4, 8, 16, 32, 64, 128
 
 PLANT_NPAR = 10
+COMMIT_SS, COMMIT_MODEL = 1, 2         # LMPC_COMMIT_SS / LMPC_COMMIT_MODEL: the `stores` bits of lmpc_rollout_commit_laps
 PLANT_PARAM_NAMES = ("m", "lf", "lr", "Iz", "Df", "Cf", "Bf", "Dr", "Cr", "Br")       # one row of vehicle constants, the order of SysModel.py:60-70
 
 
@@ -82,6 +83,7 @@ EXPORTS = [
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
     "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
+    "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_debug_model_image",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -128,6 +130,11 @@ def load():
         lib.lmpc_ss_set_lap_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         lib.lmpc_ss_get_lap_table.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
         lib.lmpc_ss_set_lap_table.restype = lib.lmpc_ss_get_lap_table.restype = C.c_int
+        # (laps of a session committed on the device: int32 tables in, int32 / packed words out)
+        lib.lmpc_rollout_commit_laps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.lmpc_rollout_extend_laps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.lmpc_debug_model_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        lib.lmpc_rollout_commit_laps.restype = lib.lmpc_rollout_extend_laps.restype = lib.lmpc_debug_model_image.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
@@ -790,6 +797,42 @@ class Context:
     def ss_extend_lap(self, lap, x, u):
         x = _f64(x); u = _f64(u)
         _chk(self.lib.lmpc_ss_extend_lap(self._h, C.c_int(int(lap)), _d(x), _d(u), C.c_int(x.shape[0])))
+
+    def rollout_commit_laps(self, cars, rows=None, ss=True, model=True):
+        """Laps of the active session into the lap stores on the device (lmpc_rollout_commit_laps): entry i is rows [0, rows[i]) of car cars[i] as the session logged
+        them (rows=None: up to each car's crossing step), added to the safe set (ss) and / or the regression store (model) in the order listed -- what
+        ss_add_trajectory / model_add_trajectory make of the fetched rows, bit for bit, without the fetch.  Returns (first_ss, first_model): the index of the first new
+        lap in each store (None for a store not written); the others follow consecutively."""
+        cars = _i32(np.atleast_1d(cars))
+        if cars.ndim != 1:
+            raise ValueError("rollout_commit_laps: cars must be one-dimensional")
+        if rows is not None:
+            rows = _i32(np.atleast_1d(rows))
+            if rows.shape != cars.shape:
+                raise ValueError("rollout_commit_laps: one row count per listed car expected")
+        fs = C.c_int(-1); fm = C.c_int(-1)
+        stores = (COMMIT_SS if ss else 0) | (COMMIT_MODEL if model else 0)
+        _chk(self.lib.lmpc_rollout_commit_laps(self._h, cars.shape[0], cars.ctypes.data, None if rows is None else rows.ctypes.data, stores, C.byref(fs), C.byref(fm)))
+        return (fs.value if ss else None), (fm.value if model else None)
+
+    def rollout_extend_laps(self, cars, laps, n_rows):
+        """The first n_rows logged rows of car cars[i] appended to safe-set lap laps[i] on the device (lmpc_rollout_extend_laps: ss_extend_lap of the fetched rows
+        without the fetch).  Returns a bool array: False where a row held a non-finite value -- that lap is left as it was."""
+        cars = _i32(np.atleast_1d(cars)); laps = _i32(np.atleast_1d(laps))
+        if cars.ndim != 1 or laps.shape != cars.shape:
+            raise ValueError("rollout_extend_laps: one safe-set lap per listed car expected")
+        ext = np.zeros(cars.shape[0], np.int32)
+        _chk(self.lib.lmpc_rollout_extend_laps(self._h, cars.shape[0], cars.ctypes.data, laps.ctypes.data, int(n_rows), ext.ctypes.data))
+        return ext != 0
+
+    def debug_model_image(self, lap):
+        """(q (3, rows - 1) uint32, par (chunks, 6), chunks): the prefilter image of the regression-store lap with insertion index `lap` (lmpc_debug_model_image)."""
+        rows, _ = self.model_lap_info(lap)
+        n = C.c_int()
+        _chk(self.lib.lmpc_debug_model_image(self._h, int(lap), None, None, C.byref(n)))
+        q = np.zeros((3, rows - 1), np.uint32); par = np.zeros((n.value, 6))
+        _chk(self.lib.lmpc_debug_model_image(self._h, int(lap), q.ctypes.data, par.ctypes.data, C.byref(n)))
+        return q, par, n.value
 
     def ss_truncate_lap(self, lap, T):
         _chk(self.lib.lmpc_ss_truncate_lap(self._h, C.c_int(int(lap)), C.c_int(int(T))))

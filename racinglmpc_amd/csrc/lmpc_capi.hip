@@ -4,6 +4,7 @@
 #include "lmpc_variant.hip.h"
 #include "lmpc_noise.hip.h"
 #include "lmpc_track.hip.h"
+#include "lmpc_commit.hip.h"
 #include "lmpc_arrays.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -191,7 +192,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 106; }
+int lmpc_version(void) { return 107; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -1749,6 +1750,117 @@ int lmpc_ss_extend_lap(lmpc_ctx *c, int lap, const double *x, const double *u, i
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the pageable host rows must outlive the copy)
     if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_ss_extend_lap", hipGetErrorString(e));
     c->s_len[lap] += n; c->s_qlast[lap] = q; c->sst_dirty = true;
+    return LMPC_OK;
+}
+
+// ---- laps of the active session straight into the stores (lmpc_commit.hip.h): no log leaves the device
+static lmpc_commit_args commit_args(const lmpc_ctx *c) {
+    const lmpc_rollout_session *r = c->ro;
+    lmpc_commit_args a; a.logX = r->d_logX; a.logU = r->d_logU; a.B = r->B; a.sstore = c->sstore; a.mstore = c->mstore; a.mquant = c->mquant; a.mqpar = c->mqpar;
+    a.ls = c->cfg.max_lap_len; a.mq_chunks = c->mq_chunks; a.TL = c->cfg.trackLength; memcpy(a.scaling, c->cfg.scaling, sizeof(a.scaling));
+    return a;
+}
+// both streams of the session drained: the logs are complete up to step t and no launch reads the stores
+static int session_drain(lmpc_ctx *c) {
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
+    if (c->ro->pstream) HIPCHK(hipStreamSynchronize(c->ro->pstream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *rows, unsigned stores, int *first_ss, int *first_model) {
+    // For i = 0 .. n-1 in the order listed: lmpc_ss_add_trajectory (LMPC.addTrajectory + computeCost, PredictiveControllers.py:418-464) and lmpc_model_add_trajectory
+    // (PredictiveModel.addTrajectory, PredictiveModel.py:35-46) of rows [0, rows[i]) of car cars[i] as the session logged them -- one table upload, one launch, one
+    // download of n doubles.  Checked in full before anything changes; the host vectors are touched only after the launch has completed.
+    ARGCHK(c && c->ro && c->ro->active && c->ro->t >= 1 && n >= 1 && cars && stores != 0u && !(stores & ~(LMPC_COMMIT_SS | LMPC_COMMIT_MODEL)));
+    lmpc_rollout_session *r = c->ro; const int B = r->B;
+    const bool ss = (stores & LMPC_COMMIT_SS) != 0, model = (stores & LMPC_COMMIT_MODEL) != 0;
+    for (int i = 0; i < n; i++) ARGCHK(cars[i] >= 0 && cars[i] < B);
+    RCCHK(session_drain(c));
+    std::vector<int> done((size_t)B);
+    HIPCHK(hipMemcpy(done.data(), r->d_done, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    const int ns0 = (int)c->s_len.size(), nm0 = (int)c->m_len.size();
+    std::vector<lmpc_commit_entry> tab((size_t)n);
+    int max_rows = 0;
+    char msg[160];
+    for (int i = 0; i < n; i++) {
+        const int car = cars[i], T = rows ? rows[i] : done[car];
+        if (!rows && done[car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0) and no row count was given", car); return set_err(LMPC_E_STATE, "lmpc_rollout_commit_laps", msg); }
+        // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
+        const int logged = (r->kind == RO_PID && r->stop_at_line && done[car] >= 0) ? done[car] : r->t;
+        if (T < (model ? 2 : 1) || T > logged) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, %d are logged (at least %d needed)", i, T, car, logged, model ? 2 : 1); return set_err(LMPC_E_ARG, "lmpc_rollout_commit_laps", msg); }
+        tab[(size_t)i].car = car; tab[(size_t)i].rows = T; tab[(size_t)i].ss_slot = ss ? ns0 + i : -1; tab[(size_t)i].m_slot = model ? nm0 + i : -1;       // (regression store: insertion index == slot)
+        max_rows = std::max(max_rows, T);
+    }
+    RCCHK(grow_stores(c, std::max(ss ? ns0 + n : 0, model ? nm0 + n : 0), max_rows));
+    void *scr; RCCHK(pooled_scratch(c, (sizeof(double) + sizeof(lmpc_commit_entry)) * (size_t)n, &scr));
+    double *d_q0 = (double *)scr; lmpc_commit_entry *d_tab = (lmpc_commit_entry *)(d_q0 + n);
+    std::vector<double> q0((size_t)n, 0.0);
+    hipError_t e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_commit_entry) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { hipLaunchKernelGGL(lmpc_commit_laps_kernel, dim3(n), dim3(LMPC_COMMIT_NT), 0, c->stream, commit_args(c), (const lmpc_commit_entry *)d_tab, d_q0); e = hipGetLastError(); }
+    if (e == hipSuccess && ss) e = hipMemcpyAsync(q0.data(), d_q0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_rollout_commit_laps", hipGetErrorString(e));
+    for (int i = 0; i < n; i++) {
+        const int T = tab[(size_t)i].rows;
+        if (ss) { c->s_len.push_back(T); c->s_laptime.push_back(T); c->s_qlast.push_back(0.0); c->s_q0.push_back(q0[(size_t)i]); }      // (cost[T-1] = 0)
+        if (model) {
+            const int slot = nm0 + i;
+            c->m_len.push_back(T);
+            if (c->m_order.empty() || T >= c->m_len[c->m_order.back()]) c->m_order.push_back(slot);          // PredictiveModel.py:35-46, as lmpc_model_add_trajectory
+            else { size_t k = 0; while (k < c->m_order.size() && !(T < c->m_len[c->m_order[k]])) k++; c->m_order.insert(c->m_order.begin() + k, slot); }
+        }
+    }
+    if (ss) c->sst_dirty = true;
+    if (first_ss) *first_ss = ss ? ns0 : -1;
+    if (first_model) *first_model = model ? nm0 : -1;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_extend_laps(lmpc_ctx *c, int n, const int *cars, const int *laps, int n_rows, int *extended) {
+    // lmpc_ss_extend_lap (the batched LMPC.addPoint, PredictiveControllers.py:466-474) of rows [0, n_rows) of car cars[i] onto safe-set lap laps[i], for every entry
+    // whose rows are all finite; the others are left as they are and reported.  One growth, one launch, one download of the flags.
+    ARGCHK(c && c->ro && c->ro->active && n >= 1 && cars && laps && extended && n_rows >= 1 && n_rows <= c->ro->t);
+    lmpc_rollout_session *r = c->ro;
+    const int stored = (int)c->s_len.size();
+    std::vector<char> seen((size_t)stored, 0);
+    for (int i = 0; i < n; i++) {
+        ARGCHK(cars[i] >= 0 && cars[i] < r->B && laps[i] >= 0 && laps[i] < stored);
+        if (seen[(size_t)laps[i]]) { char msg[96]; snprintf(msg, sizeof(msg), "lap %d is listed twice", laps[i]); return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); }
+        seen[(size_t)laps[i]] = 1;
+    }
+    RCCHK(session_drain(c));
+    int longest = 0;
+    for (int i = 0; i < n; i++) longest = std::max(longest, c->s_len[laps[i]] + n_rows);
+    RCCHK(grow_stores(c, c->cfg.max_laps, longest));
+    std::vector<lmpc_extend_entry> tab((size_t)n); std::vector<double> ql((size_t)n);
+    for (int i = 0; i < n; i++) { tab[(size_t)i].car = cars[i]; tab[(size_t)i].lap = laps[i]; tab[(size_t)i].row0 = c->s_len[laps[i]]; tab[(size_t)i].pad = 0; ql[(size_t)i] = c->s_qlast[laps[i]]; }
+    void *scr; RCCHK(pooled_scratch(c, (sizeof(double) + sizeof(lmpc_extend_entry) + sizeof(int)) * (size_t)n, &scr));
+    double *d_ql = (double *)scr; lmpc_extend_entry *d_tab = (lmpc_extend_entry *)(d_ql + n); int *d_flag = (int *)(d_tab + n);
+    hipError_t e = hipMemcpyAsync(d_ql, ql.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_extend_entry) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { hipLaunchKernelGGL(lmpc_extend_laps_kernel, dim3(n), dim3(LMPC_COMMIT_NT), 0, c->stream, commit_args(c), n_rows, (const lmpc_extend_entry *)d_tab, (const double *)d_ql, d_flag); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(extended, d_flag, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_rollout_extend_laps", hipGetErrorString(e));
+    for (int i = 0; i < n; i++) {
+        if (!extended[i]) continue;
+        double q = c->s_qlast[laps[i]];
+        for (int k = 0; k < n_rows; k++) q -= 1.0;                     // :474, one subtraction per appended row
+        c->s_len[laps[i]] += n_rows; c->s_qlast[laps[i]] = q; c->sst_dirty = true;
+    }
+    return LMPC_OK;
+}
+
+int lmpc_debug_model_image(lmpc_ctx *c, int lap, unsigned *q, double *par, int *chunks) {
+    // the K1 prefilter image of the regression-store lap with insertion index `lap` (quantise_lap; the scan it serves: PredictiveModel.py:180-197): the three planes of
+    // packed words over rows 0 .. rows-2 (3 x (rows-1)), the six parameters of every chunk in use, and their number.  Any output may be NULL.
+    ARGCHK(c && lap >= 0 && lap < (int)c->m_len.size());
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    const int nrows = c->m_len[lap] - 1, used = (nrows + K1_CHUNK - 1) / K1_CHUNK; const size_t ls = (size_t)c->cfg.max_lap_len;
+    if (chunks) *chunks = used;
+    if (q) HIPCHK(hipMemcpy2D(q, (size_t)nrows * sizeof(unsigned), c->mquant + (size_t)lap * 3 * ls, ls * sizeof(unsigned), (size_t)nrows * sizeof(unsigned), 3, hipMemcpyDeviceToHost));
+    if (par && used) HIPCHK(hipMemcpy(par, c->mqpar + (size_t)lap * c->mq_chunks * 6, sizeof(double) * 6 * (size_t)used, hipMemcpyDeviceToHost));
     return LMPC_OK;
 }
 

@@ -563,12 +563,18 @@ class PerCarLMPC:
     stores, and row b of both tables becomes the numSS_it / trToUse fastest entries of car b's history with last[b] = the lap just added.
     A car whose lap is not valid -- not finished within T_max, flagged with anything but ST_INEXACT, or its extension skipped -- is RETIRED:
     retired[b] = (generation, status).  It keeps its slot in the batch, so that indices, noise streams and rows of the others do not move; its later laps are ignored.
-    lap_times[b]: the steps of car b's laps, generation by generation."""
+    lap_times[b]: the steps of car b's laps, generation by generation.
+    device_commit=True: the laps never leave the device.  The extension is one Context.rollout_extend_laps call and the adds one Context.rollout_commit_laps call
+    per generation, over the same cars in the same order, so store indices, histories, tables, `last`, lap_times and `retired` come out as without it (an entry
+    that comes back not extended -- a non-finite row -- retires its car with EXT_SKIPPED); only status words, crossing steps, final states and the first N + 2
+    logged rows are downloaded.  The tuples run() returns, and latest[b], then carry only the first min(T, N + 2) rows of x and u -- what the next generation
+    linearises about -- and None for x_glob; the full lap is in the stores (Context.store_read_lap)."""
 
     EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
 
-    def __init__(self, rollouts, T_max=400, ext=40):
+    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False):
         self.ro, self.T_max, self.ext = rollouts, int(T_max), int(ext)
+        self.device_commit = bool(device_commit)
         self.B = None
         self.generation = 0
         self.retired = {}
@@ -625,6 +631,8 @@ class PerCarLMPC:
         xg0 = fin[:, 6:12].copy()
         xl = np.stack([self.latest[b][0][1:N + 2] for b in range(B)]); ul = np.stack([self.latest[b][1][1:N + 1] for b in range(B)])
         ro.begin(x0, xl, ul, xg0, self.T_max)
+        if self.device_commit:
+            return self._finish_on_device(gen)
         try:
             if self.ext > 0 and any(self.latest[b][3] and b not in self.retired for b in range(B)):
                 t, _ = ctx.rollout_run(self.ext)
@@ -660,6 +668,56 @@ class PerCarLMPC:
             self.latest[b] = (x, u, f12, True)
             self.lap_times[b].append(T)
             out[b] = (x, u, G[:T, b].copy(), f12, T, int(st[b]))
+        self._hand_tables()
+        self.generation += 1
+        return out
+
+    def _finish_on_device(self, gen):
+        """The rest of run() after begin with device_commit: same decisions on the same status words, the rows themselves stay on the device."""
+        ro, ctx, B, N = self.ro, self.ro.ctx, self.B, self.ro.ctx.N
+        try:
+            if self.ext > 0 and any(self.latest[b][3] and b not in self.retired for b in range(B)):
+                t, _ = ctx.rollout_run(self.ext)
+                _, _, _, done, st, fx, fg = ctx.rollout_fetch(0, 0)
+                n = min(t, self.ext)
+                cars = []
+                for b in range(B):
+                    if b in self.retired or not self.latest[b][3]:
+                        continue
+                    if not (n > 0 and (int(st[b]) & ~_capi.ST_INEXACT) == 0):
+                        self.retired[b] = (gen, int(st[b]) | self.EXT_SKIPPED)
+                        continue
+                    cars.append(b)
+                if cars:                                    # (the table is live in the session: the next step selects from the longer laps)
+                    extended = ctx.rollout_extend_laps(cars, [int(self.last[b]) for b in cars], n)
+                    for b, ok in zip(cars, extended):
+                        if not ok:                          # (a non-finite row: the lap is as it was)
+                            self.retired[b] = (gen, int(st[b]) | self.EXT_SKIPPED)
+            t, _ = ctx.rollout_run(self.T_max)
+            _, _, _, done, st, fx, fg = ctx.rollout_fetch(0, 0)
+            Xh, Uh = ctx.rollout_fetch(0, min(t, N + 2))[:2]
+            valid = []
+            for b in range(B):
+                if b in self.retired:
+                    continue
+                if not (done[b] >= 0 and (int(st[b]) & ~_capi.ST_INEXACT) == 0):
+                    self.retired[b] = (gen, int(st[b]))
+                    continue
+                valid.append(b)
+            first = ctx.rollout_commit_laps(valid)[0] if valid else None
+        finally:
+            ctx.rollout_end()
+        self.last_status, self.last_done = st, done
+        out = [None] * B
+        for k, b in enumerate(valid):
+            T, idx = int(done[b]), first + k
+            x, u = Xh[:T, b].copy(), Uh[:T, b].copy()
+            self.ss_hist.add(b, T, idx); self.model_hist.add(b, T, idx)
+            self.last[b] = idx
+            f12 = np.concatenate([fx[b], fg[b]])
+            self.latest[b] = (x, u, f12, True)
+            self.lap_times[b].append(T)
+            out[b] = (x, u, None, f12, T, int(st[b]))
         self._hand_tables()
         self.generation += 1
         return out
