@@ -70,13 +70,7 @@ __global__ __launch_bounds__(WAVE, 2) void lmpc_solve_kernel_cd(lmpc_dev_params 
     int tcnt = 0; (void)tcnt;
     TSTAMP(0);
     if (lane == 0) st_sh = 0;
-    if (lane < 12) par[PAR_FX + lane] = p.Fx[lane];
-    if (lane < 8) par[PAR_FU + lane] = p.Fu[lane];
-    if (lane < 2) { par[PAR_BX + lane] = p.bx[lane]; par[PAR_DR2 + lane] = p.dR2[lane]; }
-    if (lane < 4) { par[PAR_BU + lane] = p.bu[lane]; par[PAR_R2 + lane] = p.R2[lane]; }
-    if (lane < 36) { par[PAR_Q2 + lane] = p.Q2[lane]; par[PAR_QF2 + lane] = p.Qf2[lane]; }
-    if (lane < 6) { par[PAR_T2 + lane] = p.T2[lane]; par[PAR_XREF + lane] = p.xRef[lane]; }
-    if (lane == 0) { par[PAR_AS] = p.a_s; par[PAR_CS] = p.c_s; }
+    stage_params(p, par, lane);
     __syncthreads();
     const double a_s = wave_uniform(par[PAR_AS]), c_s = wave_uniform(par[PAR_CS]);
 
@@ -89,9 +83,9 @@ __global__ __launch_bounds__(WAVE, 2) void lmpc_solve_kernel_cd(lmpc_dev_params 
         FOR_LANES_T(i, t, 6 * N) preC[t] = io.C[(size_t)b * 6 * N + i];
     }
     if constexpr (term) { k2_select<N, S, 1>(p, io, b, lane, 0, SS, Qsel, sel_start, nullptr, &st_sh)       /* (never launched with io.ssTab: lmpc_capi.hip, launch_solve) */; __syncthreads(); }
-    if (io.rstatus && lane < N) { const int rs_ = io.rstatus[(size_t)b * N + lane]; if (rs_) atomicOr(&st_sh, rs_); }
+    solve_regression_status(io, b, N, lane, &st_sh);
     TSTAMP(1);
-    if (!(io.mode & 2)) { if (lane == 0) io.status[b] = st_sh; return; }
+    if (solve_selection_only(io, b, lane, &st_sh)) return;
 
     FOR_LANES_T(i, t, 36 * N) { const int k = i / 36, r = (i % 36) / 6, c = i % 6; AB[k * 48 + r * 8 + c] = preA[t]; }
     FOR_LANES_T(i, t, 12 * N) { const int k = i / 12, r = (i % 12) >> 1, c = i & 1; AB[k * 48 + r * 8 + 6 + c] = preB[t]; }
@@ -201,18 +195,9 @@ __global__ __launch_bounds__(WAVE, 2) void lmpc_solve_kernel_cd(lmpc_dev_params 
     }
     __syncthreads();                                                                 // (AB is dead from here on: the scratch region is reused)
 
-    const double s_init = c_s > 1.0 ? 1.0 / c_s : 1.0;
-    if (lane < NV) {
-        const int k = lane >> 1, j = lane & 1; double f = 0.0;
-#pragma unroll
-        for (int c = 0; c < 6; c++) f = fma(Fx[j * 6 + c], x[k * 6 + c], f);
-        const double viol = f - bx[j];
-        s[lane] = viol > 0.0 ? viol + 1.0 : s_init;
-    }
-    double qmax = 0.0;
-    if constexpr (term) { if (lane < S) { lam[lane] = 1.0 / (double)S; qmax = fabs(qsel_r); } qmax = wmax(qmax); }
-    const double mu0 = fmax(1.0, 0.01 * (term ? qmax : 1.0));
-    if (lane < 4 && !(bu[lane] > 0.0)) atomicOr(&st_sh, LMPC_ST_NOT_INTERIOR);
+    double qmax = 0.0;                                                               // lane slacks, lambda = 1 / S, mu0 (solve_start)
+    if constexpr (term) { if (lane < S) qmax = fabs(qsel_r); }
+    const double mu0 = solve_start(N, S, lane, c_s, par, x, s, lam, qmax, &st_sh);
     double eta_m = 0.0;
     __syncthreads();
 
@@ -638,53 +623,8 @@ __global__ __launch_bounds__(WAVE, 2) void lmpc_solve_kernel_cd(lmpc_dev_params 
         step_pp = step_prev; step_prev = wave_uniform(wmax(smax));
     }
     TSTAMP(20);
-    if (!converged && lane == 0 && !(st_sh & (LMPC_ST_NUMERIC | LMPC_ST_INEXACT)))
-        atomicOr(&st_sh, (gap < 1e-9 && rdn < 1e-5 * qscale && ren < 1e-7) ? LMPC_ST_INEXACT : LMPC_ST_MAXITER);
-    if (!p.slacks) {
-        double smax = lane < NV ? s[lane] : 0.0;
-        smax = wmax(smax);
-        if (smax > 1e-8 && lane == 0) atomicOr(&st_sh, LMPC_ST_INFEASIBLE);
-    }
+    solve_exit_status(p, N, lane, converged, gap, rdn, ren, qscale, s, &st_sh);
     __syncthreads();
-
-    // ---- unpackSolution (:364-379) and feasibleStateInput (:382-384) -------------------------------------
-    FOR_LANES(i, 6 * (N + 1)) io.xPred[(size_t)b * 6 * (N + 1) + i] = x[i];
-    if (lane < NV) { io.uPred[(size_t)b * NV + lane] = u[lane]; if (io.slack) io.slack[(size_t)b * NV + lane] = s[lane]; }
-    if (io.mu) FOR_LANES(r, M) io.mu[(size_t)b * M + r] = m[r];
-    if constexpr (term) {
-        if (io.lambda && lane < S) io.lambda[(size_t)b * S + lane] = lam[lane];
-        if (lane < 6 && io.sTerm) {
-            double v = -x[N * 6 + lane];
-            for (int c = 0; c < S; c++) v = fma(SS[lane * S + c], lam[c], v);
-            io.sTerm[(size_t)b * 6 + lane] = v;
-        }
-        if ((io.mode & 1) && (io.ztNext || io.ztuNext)) {
-            double acc[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) acc[j] = 0.0;
-            if (lane < S) {
-                const int l = lane / p.ppl, cc = lane % p.ppl;
-                const double *base = p.sstore + (size_t)p.sslot[l] * LMPC_COLS * p.lap_stride;
-                int r1 = sel_start[l] + cc + 1; r1 = r1 > p.sslen[l] - 1 ? p.sslen[l] - 1 : r1;
-                const double lv = lam[lane];
-#pragma unroll
-                for (int j = 0; j < 8; j++) acc[j] = fma(base[j * p.lap_stride + r1], lv, acc[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) acc[j] = wsum(acc[j]);
-            if (lane < 6 && io.ztNext) { double v = acc[0];
-#pragma unroll
-                for (int j = 1; j < 6; j++) if (lane == j) v = acc[j];
-                io.ztNext[(size_t)b * 6 + lane] = v; }
-            if (lane < 2 && io.ztuNext) io.ztuNext[(size_t)b * 2 + lane] = lane == 0 ? acc[6] : acc[7];
-        }
-    } else {
-        if (lane < 6 && io.ztNext) io.ztNext[(size_t)b * 6 + lane] = x[N * 6 + lane];
-        if (lane < 2 && io.ztuNext) io.ztuNext[(size_t)b * 2 + lane] = u[(N - 1) * 2 + lane];
-    }
+    solve_epilogue(p, io, b, N, S, false, lane, x, u, s, lam, m, SS, sel_start, nullptr, &st_sh, it, gap, rdn, ren);
     TSTAMP(21);
-    if (lane == 0) {
-        io.status[b] = st_sh; io.iters[b] = it; flag_retry(io, st_sh);
-        if (io.resid) { io.resid[(size_t)b * 3] = gap; io.resid[(size_t)b * 3 + 1] = rdn; io.resid[(size_t)b * 3 + 2] = ren; }
-    }
 }

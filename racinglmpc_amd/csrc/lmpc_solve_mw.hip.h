@@ -89,7 +89,7 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
     auto red_max = [&](int slot) { double r = red[slot * 4]; for (int w = 1; w < NW; w++) r = fmax(r, red[slot * 4 + w]); return r; };
     auto red_min = [&](int slot) { double r = red[slot * 4]; for (int w = 1; w < NW; w++) r = fmin(r, red[slot * 4 + w]); return r; };
 
-    // K2: safe-set selection, one lap per wave (k2_select, lmpc_kernels.hip.h), then the regression status bits of this problem
+    // K2: safe-set selection, one lap per wave (k2_select, lmpc_solve_common.hip.h), then the regression status bits of this problem
     if constexpr (term) {
         k2_select<N, S, NW, TAB>(p, io, b, lane, wave, SS, Qsel, sel_start, sel_lap, &st_sh); __syncthreads();
         if (tid < 6) { double v = 0.0; for (int c = 0; c < S; c++) v += SS[tid * S + c]; ss_rowsum[tid] = v; }

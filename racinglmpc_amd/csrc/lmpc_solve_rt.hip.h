@@ -9,7 +9,7 @@
 //
 // Same QP, same interior-point method and the same rules as lmpc_solve_kernel (one-wave form: multipliers of the dynamics rows from the adjoint
 // recursion), written after tests/ipm_model.py (ipm_solve, kkt_factor, kkt_solve) line by line:
-//   K2  selection (k2_select_rt: LMPC.addTerminalComponents :386-416, selectPoints :478-514)
+//   K2  selection (k2_select, lmpc_solve_common.hip.h: LMPC.addTerminalComponents :386-416, selectPoints :478-514)
 //   K3  Mehrotra predictor-corrector on the block-banded KKT system: barrier weights capped (LMPC_TH_INV), lane slacks eliminated, terminal block
 //       (lambda, s_T) through a 7-column modified Gram-Schmidt QR (two passes), Riccati recursion on the augmented state (x_k, u_{k-1}),
 //       step rules and termination (step_bound_ok) of lmpc_kernels.hip.h
@@ -35,76 +35,6 @@ __host__ __device__ inline rt_lds rt_layout(int N, int S) {
     return L;
 }
 
-// K2 with runtime N, S (one wave): the selection of k2_select, statement for statement
-__device__ inline void k2_select_rt(const lmpc_dev_params &p, const lmpc_solve_io &io, int b, int lane, int N, int S, double *SS, double *Qsel, int *sel_start, int *sel_lap, int *st_sh) {
-    if (io.mode & 1) {
-        double ztv[6];
-        for (int j = 0; j < 6; j++) ztv[j] = io.zt[(size_t)b * 6 + j];
-        const double x04 = io.x0[(size_t)b * 6 + 4];
-        if (ztv[4] - x04 > p.TL / 2) ztv[4] = fmax(ztv[4] - p.TL, 0.0);        // :392-393
-        if (io.ztUsed && lane < 6) io.ztUsed[(size_t)b * 6 + lane] = ztv[lane < 6 ? lane : 0];
-        const int hasPred = io.hasPred ? io.hasPred[b] : 0;                     // Q-function shift bookkeeping (:502-512)
-        int crossed = 0;
-        if (hasPred) {
-            for (int r0 = 0; r0 <= N; r0 += WAVE) {
-                const int r = r0 + lane;
-                const int c_ = (r <= N && io.xPredPrev[((size_t)b * (N + 1) + (r <= N ? r : 0)) * 6 + 4] > p.TL) ? 1 : 0;
-                crossed += (int)__popcll(__ballot(c_));
-            }
-        }
-        const int tstep = io.timeStep ? io.timeStep[b] : 0;
-        const int ppl = p.ppl, npw = ppl + 1;
-        for (int l = 0; l < p.L; l++) {
-            const k2_lap lp = io.ssTab ? k2_lap_of<true>(p, io, b, l) : k2_lap_of<false>(p, io, b, l);                           // (the problem's table row when io.ssTab is set)
-            const double *base = p.sstore + (size_t)lp.slot * LMPC_COLS * p.lap_stride;
-            const int T = lp.rows, ls = p.lap_stride;
-            if (io.ssTab && lane == 0) { sel_lap[2 * l] = lp.slot; sel_lap[2 * l + 1] = lp.rows; }
-            double best = INFINITY; int bi = 0x7fffffff;
-            for (int r = lane; r < T; r += WAVE) {
-                double nrm = fabs(base[r] - ztv[0]);                            // la.norm(x - zt, 1, axis=1)
-                nrm = nrm + fabs(base[ls + r] - ztv[1]);
-                nrm = nrm + fabs(base[2 * ls + r] - ztv[2]);
-                nrm = nrm + fabs(base[3 * ls + r] - ztv[3]);
-                nrm = nrm + fabs(base[4 * ls + r] - ztv[4]);
-                nrm = nrm + fabs(base[5 * ls + r] - ztv[5]);
-                if (nrm < best) { best = nrm; bi = r; }
-            }
-            wave_argmin(best, bi);                                              // np.argmin: first minimum
-            if ((unsigned)bi >= (unsigned)T) {                                  // no row compares below +inf: zt or x0 is not finite (np.argmin would go on with row 0 or the first NaN).
-                bi = 0; if (lane == 0) atomicOr(st_sh, LMPC_ST_NUMERIC);        // The window arithmetic below must not see the sentinel (start + lane overflowed: a fault on the device)
-            }
-            const int MinNorm = bi;
-            const int start = ((double)MinNorm - (double)npw / 2.0 >= 0.0) ? MinNorm - npw / 2 : MinNorm;   // :492-495
-            if (lane == 0) { sel_start[l] = start; if (io.selStartOut) io.selStartOut[(size_t)b * p.L + l] = start; if (start + npw > T) atomicOr(st_sh, LMPC_ST_WINDOW); }
-            double shift = 0.0;                                                 // :502-512
-            if (hasPred && crossed > 0) {
-                if (!lp.latest) shift = base[8 * ls];
-                else shift = (double)tstep + (double)(N - crossed);
-            }
-            for (int cc = lane; cc < ppl; cc += WAVE) {
-                int r0 = start + cc; r0 = r0 > T - 1 ? T - 1 : r0;
-                int r1 = start + cc + 1; r1 = r1 > T - 1 ? T - 1 : r1;
-                const int col = l * ppl + cc;
-                for (int j = 0; j < 6; j++) {
-                    const double v = base[j * ls + r0];
-                    SS[j * S + col] = v;
-                    if (io.ssSelOut) io.ssSelOut[((size_t)b * S + col) * 6 + j] = v;
-                    if (io.succOut) io.succOut[((size_t)b * S + col) * 6 + j] = base[j * ls + r1];
-                }
-                if (io.succUOut) { io.succUOut[((size_t)b * S + col) * 2] = base[6 * ls + r1]; io.succUOut[((size_t)b * S + col) * 2 + 1] = base[7 * ls + r1]; }
-                const double qv = base[8 * ls + r0] + shift;
-                Qsel[col] = qv;
-                if (io.qSelOut) io.qSelOut[(size_t)b * S + col] = qv;
-            }
-        }
-    } else {
-        for (int c = lane; c < S; c += WAVE) {
-            for (int j = 0; j < 6; j++) SS[j * S + c] = io.ssSelIn[((size_t)b * S + c) * 6 + j];
-            Qsel[c] = io.qSelIn[(size_t)b * S + c];
-        }
-    }
-}
-
 #define RT_SYNC() __syncthreads()
 #define RT_FOR(i, n) for (int i = lane; i < (n); i += WAVE)
 
@@ -117,7 +47,7 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
     if constexpr (EQ) { if (!(io.status[b] & (LMPC_ST_MAXITER | LMPC_ST_NUMERIC))) return; }
     const int lane = threadIdx.x;
     const int N = p.N, S = p.S, M = 8 * N + S;
-    const bool term = S > 0;
+    const bool term = S > 0, tab = io.ssTab != nullptr;
     const rt_lds L = rt_layout(N, S);
     double *A = sm + L.A, *Bm = sm + L.B, *C = sm + L.C, *x = sm + L.x, *u = sm + L.u, *s = sm + L.s, *lam = sm + L.lam, *nu = sm + L.nu;
     double *t = sm + L.t, *m = sm + L.m, *th = sm + L.th, *rt = sm + L.rt, *h = sm + L.h, *dt = sm + L.dt, *dm = sm + L.dm, *tp = sm + L.tp;
@@ -132,18 +62,13 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
     __shared__ int sel_start[LMPC_MAX_USED_LAPS];
     int *sel_lap = (int *)(sm + L.tot);                      // (io.ssTab only: LMPC_SSTAB_LDS bytes behind the layout, see lmpc_kernels.hip.h)
     if (lane == 0) st_sh = EQ ? (io.status[b] & (LMPC_ST_REG_SINGULAR | LMPC_ST_NO_SEGMENT)) : 0;
-    if (lane < 12) par[PAR_FX + lane] = p.Fx[lane];
-    if (lane < 8) par[PAR_FU + lane] = p.Fu[lane];
-    if (lane < 2) { par[PAR_BX + lane] = p.bx[lane]; par[PAR_DR2 + lane] = p.dR2[lane]; }
-    if (lane < 4) { par[PAR_BU + lane] = p.bu[lane]; par[PAR_R2 + lane] = p.R2[lane]; }
-    if (lane < 36) { par[PAR_Q2 + lane] = p.Q2[lane]; par[PAR_QF2 + lane] = p.Qf2[lane]; }
-    if (lane < 6) { par[PAR_T2 + lane] = p.T2[lane]; par[PAR_XREF + lane] = p.xRef[lane]; }
-    if (lane == 0) { par[PAR_AS] = p.a_s; par[PAR_CS] = p.c_s; }
+    stage_params(p, par, lane);
     RT_SYNC();
     const double a_s = par[PAR_AS], c_s = par[PAR_CS];
-    if (term) { k2_select_rt(p, io, b, lane, N, S, SS, Qsel, sel_start, sel_lap, &st_sh); RT_SYNC(); }
-    if (!EQ && io.rstatus) { RT_FOR(i, N) { const int rs_ = io.rstatus[(size_t)b * N + i]; if (rs_) atomicOr(&st_sh, rs_); } }
-    if (!(io.mode & 2)) { RT_SYNC(); if (lane == 0) io.status[b] = st_sh; return; }
+    if (term) { k2_select<0, 0, 1, -1>(p, io, b, lane, 0, SS, Qsel, sel_start, sel_lap, &st_sh); RT_SYNC(); }
+    if constexpr (!EQ) solve_regression_status(io, b, N, lane, &st_sh);
+    if (!(io.mode & 2)) RT_SYNC();
+    if (solve_selection_only(io, b, lane, &st_sh)) return;
 
     // ---- K3 --------------------------------------------------------------------------------------------------------------------------
     RT_FOR(i, 36 * N) A[i] = io.A[(size_t)b * 36 * N + i];
@@ -161,18 +86,9 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
         }
         RT_SYNC();
     }
-    const double s_init = c_s > 1.0 ? 1.0 / c_s : 1.0;      // (see lmpc_solve_kernel)
-    RT_FOR(i, 2 * N) {
-        const int k = i >> 1, j = i & 1; double f = 0.0;
-        for (int c = 0; c < 6; c++) f = fma(Fx[j * 6 + c], x[k * 6 + c], f);
-        const double viol = f - bx[j];
-        s[i] = viol > 0.0 ? viol + 1.0 : s_init;
-    }
-    double qmax = 0.0;
-    if (term) { RT_FOR(c, S) { lam[c] = 1.0 / (double)S; qmax = fmax(qmax, fabs(Qsel[c])); } }
-    qmax = wmax(qmax);
-    const double mu0 = fmax(1.0, 0.01 * (term ? qmax : 1.0));
-    if (lane < 4 && !(bu[lane] > 0.0)) atomicOr(&st_sh, LMPC_ST_NOT_INTERIOR);
+    double qmax = 0.0;                                      // lane slacks, lambda = 1 / S, mu0 (solve_start)
+    if (term) { RT_FOR(c, S) qmax = fmax(qmax, fabs(Qsel[c])); }
+    const double mu0 = solve_start(N, S, lane, c_s, par, x, s, lam, qmax, &st_sh);
     double eta_m = 0.0;
     RT_SYNC();
     // inequality rows in the reference's order: lane rows (2N) | input rows (4N) | slack positivity (2N) | lambda >= 0 (S)
@@ -502,50 +418,9 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
         eta_m = fma(ald, deta, eta_m);
         RT_SYNC();
     }
-    if (!converged && lane == 0 && !(st_sh & (LMPC_ST_NUMERIC | LMPC_ST_INEXACT)))
-        atomicOr(&st_sh, (gap < 1e-9 && rdn < 1e-5 * qscale && ren < 1e-7) ? LMPC_ST_INEXACT : LMPC_ST_MAXITER);
-    if (!p.slacks) {                                        // hard lane rows exceeded: the hard problem is infeasible (see lmpc_solve_kernel)
-        double smax = 0.0;
-        RT_FOR(i, 2 * N) smax = fmax(smax, s[i]);
-        smax = wmax(smax);
-        if (smax > 1e-8 && lane == 0) atomicOr(&st_sh, LMPC_ST_INFEASIBLE);
-    }
+    solve_exit_status(p, N, lane, converged, gap, rdn, ren, qscale, s, &st_sh);
     RT_SYNC();
-    // ---- unpackSolution (:364-379) and feasibleStateInput (:382-384) -----------------------------------------------------------------------
-    RT_FOR(i, 6 * (N + 1)) io.xPred[(size_t)b * 6 * (N + 1) + i] = x[i];
-    RT_FOR(i, 2 * N) { io.uPred[(size_t)b * 2 * N + i] = u[i]; if (io.slack) io.slack[(size_t)b * 2 * N + i] = s[i]; }
-    if (io.mu) { RT_FOR(r, M) io.mu[(size_t)b * M + r] = m[r]; }
-    if (term) {
-        if (io.lambda) { RT_FOR(c, S) io.lambda[(size_t)b * S + c] = lam[c]; }
-        if (lane < 6 && io.sTerm) {
-            double v = -x[N * 6 + lane];
-            for (int c = 0; c < S; c++) v = fma(SS[lane * S + c], lam[c], v);
-            io.sTerm[(size_t)b * 6 + lane] = v;
-        }
-        if ((io.mode & 1) && (io.ztNext || io.ztuNext)) {   // zt = Succ_SS lambda, zt_u = Succ_uSS lambda
-            double acc[8];
-            for (int j = 0; j < 8; j++) acc[j] = 0.0;
-            RT_FOR(c, S) {
-                const int l = c / p.ppl, cc = c % p.ppl;
-                int slot = p.sslot[l], T = p.sslen[l];
-                if (io.ssTab) { slot = sel_lap[2 * l]; T = sel_lap[2 * l + 1]; }
-                const double *base = p.sstore + (size_t)slot * LMPC_COLS * p.lap_stride;
-                int r1 = sel_start[l] + cc + 1; r1 = r1 > T - 1 ? T - 1 : r1;
-                const double lv = lam[c];
-                for (int j = 0; j < 8; j++) acc[j] = fma(base[j * p.lap_stride + r1], lv, acc[j]);
-            }
-            for (int j = 0; j < 8; j++) acc[j] = wsum(acc[j]);
-            if (lane < 6 && io.ztNext) { double v = acc[0]; for (int j = 1; j < 6; j++) if (lane == j) v = acc[j]; io.ztNext[(size_t)b * 6 + lane] = v; }
-            if (lane < 2 && io.ztuNext) io.ztuNext[(size_t)b * 2 + lane] = lane == 0 ? acc[6] : acc[7];
-        }
-    } else {
-        if (lane < 6 && io.ztNext) io.ztNext[(size_t)b * 6 + lane] = x[N * 6 + lane];          // MPC.feasibleStateInput :157-159
-        if (lane < 2 && io.ztuNext) io.ztuNext[(size_t)b * 2 + lane] = u[(N - 1) * 2 + lane];
-    }
-    if (lane == 0) {
-        io.status[b] = st_sh; io.iters[b] = it; flag_retry(io, st_sh);
-        if (io.resid) { io.resid[(size_t)b * 3] = gap; io.resid[(size_t)b * 3 + 1] = rdn; io.resid[(size_t)b * 3 + 2] = ren; }
-    }
+    solve_epilogue(p, io, b, N, S, tab, lane, x, u, s, lam, m, SS, sel_start, sel_lap, &st_sh, it, gap, rdn, ren);
 }
 #undef RT_SYNC
 #undef RT_FOR

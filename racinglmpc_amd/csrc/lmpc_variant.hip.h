@@ -34,109 +34,97 @@ struct lmpc_variant_api {
 constexpr int LMPC_VARIANT_ABI = LMPC_VARIANT_ABI_REV * 0x1000000 + (int)((sizeof(lmpc_dev_params) * 31u + sizeof(lmpc_solve_io) * 7u + sizeof(lmpc_variant_api)) & 0xffffffu);
 static_assert(sizeof(lmpc_dev_params) < 4096 && sizeof(lmpc_solve_io) < 1024, "by-value kernel arguments: keep them inside the kernarg segment's preload range");
 
+// One kernel, its plain and its TAB instantiation: a launch with per-problem safe-set laps (io.ssTab) takes the second, with LMPC_SSTAB_LDS bytes behind `lds`
+// for the (slot, rows) of the selected laps.  (S = 0 has no TAB instantiations -- both names are the plain kernel there -- and no table: lmpc_capi.hip, ss_table_for.)
+template <class K> static int lmpc_launch_pair(K plain, K tab, int threads, size_t lds, hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
+    const bool t = io.ssTab != nullptr && tab != plain;
+    const K kernel = t ? tab : plain;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds + (t ? LMPC_SSTAB_LDS : 0), st, p, B, io);
+    return 0;
+}
+// An instantiation and the most dynamic LDS it is launched with; `built` = false: the name stands for another entry's kernel (no instantiation of its own)
+struct lmpc_kernel_lds { const void *fn; size_t lds; bool built; };
+template <int K> static bool lmpc_raise_lds_limits(const lmpc_kernel_lds (&k)[K]) {
+    for (const lmpc_kernel_lds &e : k)
+        if (e.built && hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.lds) != hipSuccess) return false;
+    return true;
+}
+
 template <int N, int S> struct lmpc_variant_launchers {
-    static constexpr bool has_mw = true;               // (every supported S: wave 0 of the multi-wave kernels carries ceil((S + 6) / 64) terminal-block columns per lane)
-    static constexpr size_t lds1 = (size_t)solve_lds1<N, S>::tot * sizeof(double), ldsm = has_mw ? (size_t)solve_lds<N, S>::tot * sizeof(double) : 0;
+    // (every supported S has the multi-wave kernels: wave 0 carries ceil((S + 6) / 64) terminal-block columns per lane)
+    static constexpr size_t lds1 = (size_t)solve_lds1<N, S>::tot * sizeof(double), ldsm = (size_t)solve_lds<N, S>::tot * sizeof(double);
     // fused step (io.mode & 4): the regression's work space sits behind [A_k | B_k], C_k; it fits the solve's footprint at the reference's
     // settings (4 laps x 7 points) and grows it a little beyond
     static size_t lds_for(const lmpc_dev_params &p, const lmpc_solve_io &io) {
         const size_t f = (io.mode & 4) ? (size_t)(54 * N + k1_fused_doubles(N, p.trToUse, p.maxNumPoint)) * sizeof(double) : 0;
-        return (f > lds1 ? f : lds1) + sstab(io);
+        return f > lds1 ? f : lds1;
     }
-    // per-problem safe-set laps (io.ssTab): the TAB instantiations of the kernels, which exist for S > 0 only (has_tab = false folds them onto the plain ones)
-    static constexpr bool has_tab = S > 0;
-    static bool tab(const lmpc_solve_io &io) { return has_tab && io.ssTab != nullptr; }
-    static size_t sstab(const lmpc_solve_io &io) { return io.ssTab ? LMPC_SSTAB_LDS : 0; }     // per-problem safe-set laps: (slot, rows) of the selected laps behind the layout
     static constexpr size_t lds1_max() { const size_t f = (size_t)(54 * N + k1_fused_doubles(N, LMPC_MAX_USED_LAPS, 8)) * sizeof(double); return (f > lds1 ? f : lds1) + LMPC_SSTAB_LDS; }
+    // per-problem safe-set laps (io.ssTab): the TAB instantiations of the kernels exist for S > 0 only
+    static constexpr bool has_tab = S > 0;
     // long horizons: [A_k | B_k] in global memory where that lets more QPs share a CU than the 160 KB of LDS otherwise hold and fewer than four do (idle SIMDs)
     static constexpr size_t lds1g = (size_t)solve_lds1<N, S, true>::tot * sizeof(double);
     // (measured, solve kernel, ms at batch 1024 / 4096: N = 40 LDS 1.467 / 4.073, global 1.092 / 3.398 -- two -> four QPs per CU;  N = 20 LDS 0.655 / 1.571,
     //  global 0.725 / 1.554 -- five -> seven per CU, but every SIMD was busy already and the variant spills: only where fewer than four QPs fit)
     static constexpr bool use_abg = (160 * 1024 / lds1) < 4 && (160 * 1024 / lds1g) > (160 * 1024 / lds1) && solve_lds1<N, S>::CH == 1;
-    static int l1(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        if constexpr (use_abg) {
-            if (!(io.mode & 4) && io.abPack) {
-                if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel<N, S, false, true, has_tab>), dim3(B), dim3(WAVE), lds1g + sstab(io), st, p, B, io);
-                else hipLaunchKernelGGL((lmpc_solve_kernel<N, S, false, true>), dim3(B), dim3(WAVE), lds1g, st, p, B, io);
-                return 0;
-            }
-        }
-        if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel<N, S, false, false, has_tab>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
-        else hipLaunchKernelGGL((lmpc_solve_kernel<N, S>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
-        return 0; }
-    static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel<N, S, true, false, has_tab>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
-        else hipLaunchKernelGGL((lmpc_solve_kernel<N, S, true>), dim3(B), dim3(WAVE), lds_for(p, io), st, p, B, io);
-        return 0; }
-    static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        if constexpr (has_mw) {
-            if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 4, has_tab>), dim3(B), dim3(WAVE * 4), ldsm + sstab(io), st, p, B, io);
-            else hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 4>), dim3(B), dim3(WAVE * 4), ldsm, st, p, B, io);
-            return 0;
-        } else return l1(st, p, B, io); }
 #ifdef LMPC_WITH_CD
     static constexpr bool has_cd = 2 * N <= 32 && S + 6 <= WAVE;          // condensed kernel: short horizons, one terminal-block column per lane
 #else
     static constexpr bool has_cd = false;
 #endif
+    static constexpr size_t lds_cd(bool hasQ) {
+#ifdef LMPC_WITH_CD
+        if constexpr (has_cd) return (size_t)(hasQ ? solve_ldsc<N, S>::tot_q : solve_ldsc<N, S>::tot) * sizeof(double);
+#endif
+        return 0; }
+    static const void *cd_kernel() {
+#ifdef LMPC_WITH_CD
+        if constexpr (has_cd) return (const void *)lmpc_solve_kernel_cd<N, S>;
+#endif
+        return nullptr; }
+
+    // Every instantiation of this (N, S) and its dynamic-LDS limit
+    static bool raise_limits() {
+        const lmpc_kernel_lds k[] = {
+            {(const void *)lmpc_solve_kernel<N, S>, lds1_max(), true},                       {(const void *)lmpc_solve_kernel<N, S, false, false, has_tab>, lds1_max(), has_tab},
+            {(const void *)lmpc_solve_kernel<N, S, true>, lds1_max(), true},                 {(const void *)lmpc_solve_kernel<N, S, true, false, has_tab>, lds1_max(), has_tab},
+            {(const void *)lmpc_solve_kernel<N, S, false, use_abg>, lds1g, use_abg},         {(const void *)lmpc_solve_kernel<N, S, false, use_abg, has_tab>, lds1g + LMPC_SSTAB_LDS, use_abg && has_tab},
+            {(const void *)lmpc_solve_kernel_mw<N, S, 4>, ldsm, true},                       {(const void *)lmpc_solve_kernel_mw<N, S, 4, has_tab>, ldsm + LMPC_SSTAB_LDS, has_tab},
+            {(const void *)lmpc_solve_kernel_mw<N, S, 2>, ldsm, true},                       {(const void *)lmpc_solve_kernel_mw<N, S, 2, has_tab>, ldsm + LMPC_SSTAB_LDS, has_tab},
+            {cd_kernel(), lds_cd(true), has_cd},
+        };
+        return lmpc_raise_lds_limits(k);
+    }
+
+    static int l1(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
+        if constexpr (use_abg) {
+            if (!(io.mode & 4) && io.abPack) return lmpc_launch_pair(lmpc_solve_kernel<N, S, false, true>, lmpc_solve_kernel<N, S, false, true, has_tab>, WAVE, lds1g, st, p, B, io);
+        }
+        return lmpc_launch_pair(lmpc_solve_kernel<N, S>, lmpc_solve_kernel<N, S, false, false, has_tab>, WAVE, lds_for(p, io), st, p, B, io); }
+    static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
+        return lmpc_launch_pair(lmpc_solve_kernel<N, S, true>, lmpc_solve_kernel<N, S, true, false, has_tab>, WAVE, lds_for(p, io), st, p, B, io); }
+    static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
+        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 4>, lmpc_solve_kernel_mw<N, S, 4, has_tab>, WAVE * 4, ldsm, st, p, B, io); }
+    static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
+        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 2>, lmpc_solve_kernel_mw<N, S, 2, has_tab>, WAVE * 2, ldsm, st, p, B, io); }
     static int lc(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int hasQ) {
 #ifdef LMPC_WITH_CD
-        if constexpr (has_cd) {
-            const size_t lds = (size_t)(hasQ ? solve_ldsc<N, S>::tot_q : solve_ldsc<N, S>::tot) * sizeof(double);
-            hipLaunchKernelGGL((lmpc_solve_kernel_cd<N, S>), dim3(B), dim3(WAVE), lds, st, p, B, io, hasQ); return 0;
-        }
+        if constexpr (has_cd) { hipLaunchKernelGGL((lmpc_solve_kernel_cd<N, S>), dim3(B), dim3(WAVE), lds_cd(hasQ), st, p, B, io, hasQ); return 0; }
 #endif
         (void)hasQ; return l1(st, p, B, io);
     }
-    static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        if constexpr (has_mw) {
-            if (tab(io)) hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 2, has_tab>), dim3(B), dim3(WAVE * 2), ldsm + sstab(io), st, p, B, io);
-            else hipLaunchKernelGGL((lmpc_solve_kernel_mw<N, S, 2>), dim3(B), dim3(WAVE * 2), ldsm, st, p, B, io);
-            return 0;
-        } else return l1(st, p, B, io); }
 };
 
 // fills the table and raises the kernels' dynamic-LDS limit; false if the device refuses (footprint beyond 160 KB)
 template <int N, int S> static bool lmpc_variant_fill(lmpc_variant_api *v) {
     static_assert(N >= 2 && N <= LMPC_MAX_N && S >= 0 && S <= LMPC_MAX_SS_POINTS, "unsupported variant");
     using L = lmpc_variant_launchers<N, S>;
+    if (!L::raise_limits()) return false;
     v->N = N; v->S = S;
-    v->lds_mw = L::ldsm; v->lds_1w = (size_t)solve_lds1<N, S>::tot * sizeof(double);      // lds_mw == 0: no multi-wave kernels for this S
-    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
-    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
-    if constexpr (L::has_tab) {
-        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
-        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1_max()) != hipSuccess) return false;
-        if constexpr (L::has_mw) {
-            if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(L::ldsm + LMPC_SSTAB_LDS)) != hipSuccess) return false;
-            if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(L::ldsm + LMPC_SSTAB_LDS)) != hipSuccess) return false;
-        }
-        if constexpr (L::use_abg) {
-            if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(L::lds1g + LMPC_SSTAB_LDS)) != hipSuccess) return false;
-        }
-    }
-    if constexpr (L::has_mw) {
-        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds_mw) != hipSuccess) return false;
-        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_mw<N, S, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds_mw) != hipSuccess) return false;
-    }
-    v->launch_1w = &L::l1; v->launch_retry = &L::lr; v->launch_mw4 = &L::l4; v->launch_mw2 = &L::l2;
-    v->occ_mw2 = 0;
-    if constexpr (L::has_mw) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)lmpc_solve_kernel_mw<N, S, 2>, 2 * WAVE, v->lds_mw) == hipSuccess) v->occ_mw2 = nb;
-    }
-    v->lds_1w_abg = 0;
-    if constexpr (L::use_abg) {
-        v->lds_1w_abg = L::lds1g;
-        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel<N, S, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::lds1g) != hipSuccess) return false;
-    }
-    v->lds_cd = 0; v->lds_cd_q = 0; v->launch_cd = &L::lc;
-#ifdef LMPC_WITH_CD
-    if constexpr (L::has_cd) {
-        v->lds_cd = (size_t)solve_ldsc<N, S>::tot * sizeof(double); v->lds_cd_q = (size_t)solve_ldsc<N, S>::tot_q * sizeof(double);
-        if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_cd<N, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds_cd_q) != hipSuccess) return false;
-    }
-#endif
+    v->lds_mw = L::ldsm; v->lds_1w = L::lds1; v->lds_1w_abg = L::use_abg ? L::lds1g : 0; v->lds_cd = L::lds_cd(false); v->lds_cd_q = L::lds_cd(true);
+    v->launch_1w = &L::l1; v->launch_retry = &L::lr; v->launch_mw4 = &L::l4; v->launch_mw2 = &L::l2; v->launch_cd = &L::lc;
+    int nb = 0;
+    v->occ_mw2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)lmpc_solve_kernel_mw<N, S, 2>, 2 * WAVE, v->lds_mw) == hipSuccess ? nb : 0;
     return true;
 }
 
@@ -147,8 +135,8 @@ static bool lmpc_variant_fill_rt(lmpc_variant_api *v, int N, int S) {
     if (N < 2 || N > LMPC_MAX_N || S < 0 || S > LMPC_MAX_SS_POINTS) return false;
     const size_t lds = (size_t)rt_layout(N, S).tot * sizeof(double);
     if (lds + 1024 > (size_t)160 * 1024) return false;
-    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_rt<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + LMPC_SSTAB_LDS)) != hipSuccess) return false;
-    if (hipFuncSetAttribute((const void *)lmpc_solve_kernel_rt<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + LMPC_SSTAB_LDS)) != hipSuccess) return false;
+    const lmpc_kernel_lds k[] = {{(const void *)lmpc_solve_kernel_rt<false>, lds + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_rt<true>, lds + LMPC_SSTAB_LDS, true}};
+    if (!lmpc_raise_lds_limits(k)) return false;
     v->N = N; v->S = S; v->lds_mw = 0; v->lds_1w = lds; v->lds_1w_abg = 0; v->lds_cd = 0; v->lds_cd_q = 0; v->occ_mw2 = 0;
     v->launch_1w = &lmpc_rt_launch; v->launch_retry = &lmpc_rt_launch_retry; v->launch_mw4 = &lmpc_rt_launch; v->launch_mw2 = &lmpc_rt_launch; v->launch_cd = &lmpc_rt_launch_cd;
     return true;

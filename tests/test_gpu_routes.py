@@ -11,6 +11,9 @@ Per horizon:
   * the fused step is bit-identical in EVERY output to the unfused step on the same one-wave kernel, the runtime kernel with LMPC_FUSE=1 to the runtime
     kernel without it, [A|B] in LDS (LMPC_NO_ABG) to [A|B] in global memory, the zero-copy single-problem path of a max_batch = 1 context (the drop-in
     classes) to the four-wave batch row;
+  * the selection's other outputs (selStart, succ, succU, ztUsed: select_batch on a context of the route, on P) are bit-identical to the four-wave route's too;
+  * the epilogue holds on the route's own outputs: ztNext = Succ lambda, ztuNext = SuccU lambda and sTerm = SS lambda - x_N to the rounding of a sum of that
+    many terms in any order, (n - 1) u sum |terms| with u = 2^-53 and a factor 2 to spare (_epilogue_fails); plain MPC: ztNext = x_N, ztuNext = u_{N-1} bit for bit;
   * xPred, uPred agree with the four-wave route to 2e-7 and ztNext to 2e-7 (1 + |zt|): the 1e-7 a-posteriori termination rule;
   * every route meets the oracle on P: A, B, C to TOL_ABC, selections identical, (x, u) at the certified optimum to TOL_XU (common.compare_with_oracle;
     plain MPC: the certified optimum of the reference-form MPC QP).
@@ -39,6 +42,7 @@ P_SIZE = 64
 SEED_P, SEED_FILL = 1234, 4321
 ALL_KEYS = ("A", "B", "C", "xPred", "uPred", "slack", "lambd", "sTerm", "ztNext", "ztuNext", "ssSel", "qSel", "mu", "status", "iters")
 SAME_KEYS = ("A", "B", "C", "ssSel", "qSel", "status")
+SAME_SELECT_KEYS = ("selStart", "succ", "succU", "ztUsed")
 TOL_ROUTE = 2e-7
 
 CASES = [(8, 48), (12, 48), (14, 48), (20, 48), (40, 48), (12, 0)]
@@ -130,6 +134,32 @@ def _step(ctx, inp):
     return ctx.step_batch(inp["x0"], inp["xLin"], inp["uLin"], inp["uOld"], zt=inp["zt"] if ctx.S else None, timeStep=inp["timeStep"] if ctx.S else None)
 
 
+def _epilogue_fails(out, sel, N, S):
+    """The epilogue's identities on one route's own outputs, rows of P.  S > 0: with t_c = succ[c, j] lambda_c, |ztNext[j] - sum_c t_c| <= S 2^-52 sum_c |t_c| (ztuNext
+    against succU likewise), and with t_c = ssSel[c, j] lambda_c, |sTerm[j] - (sum_c t_c - xPred[N, j])| <= (S + 1) 2^-52 (sum_c |t_c| + |xPred[N, j]|): the bound of an
+    n-term floating-point sum in any order, (n - 1) u sum |terms|, u = 2^-53, with a factor 2 to spare.  The sums are formed in extended precision, so that the
+    test's own rounding does not count.  S = 0: ztNext is x_N and ztuNext is u_{N-1}, bit for bit."""
+    R = slice(0, P_SIZE)
+    if not S:
+        return [k for k, want in (("ztNext", out["xPred"][R, N]), ("ztuNext", out["uPred"][R, N - 1])) if not np.array_equal(out[k][R], want)]
+    ld = np.longdouble
+    lam = out["lambd"][R].astype(ld)[:, :, None]
+    bad = []
+    for k, rows in (("ztNext", sel["succ"][R]), ("ztuNext", sel["succU"][R])):
+        t = rows.astype(ld) * lam
+        err, bound = np.abs(out[k][R].astype(ld) - t.sum(axis=1)), S * ld(2.0) ** -52 * np.abs(t).sum(axis=1)
+        print("    %-8s worst |error| / bound %.3f" % (k, float((err / bound).max())))
+        if not np.all(err <= bound):
+            bad.append(k)
+    t = out["ssSel"][R].astype(ld) * lam
+    xN = out["xPred"][R, N].astype(ld)
+    err, bound = np.abs(out["sTerm"][R].astype(ld) - (t.sum(axis=1) - xN)), (S + 1) * ld(2.0) ** -52 * (np.abs(t).sum(axis=1) + np.abs(xN))
+    print("    %-8s worst |error| / bound %.3f" % ("sTerm", float((err / bound).max())))
+    if not np.all(err <= bound):
+        bad.append("sTerm")
+    return bad
+
+
 @pytest.mark.parametrize("N,S", CASES, ids=["N%d_S%d" % c for c in CASES])
 def test_every_route_gives_one_answer(built, N, S):
     import bench
@@ -147,7 +177,7 @@ def test_every_route_gives_one_answer(built, N, S):
     else:
         res = _mpc_oracle(g, orc.QPParams.mpc_default(N, 0.8), N, P)
 
-    outs, fails, rows = {}, [], []
+    outs, sels, fails, rows = {}, {}, [], []
     for name, B, waves, knobs, rt, fused in routes:
         ctx = _context(g, N, S, B, knobs, rt)
         try:
@@ -155,10 +185,12 @@ def test_every_route_gives_one_answer(built, N, S):
             ctx.reset_stats()
             out = _step(ctx, _batch(P, F, B))
             n_regress = int(ctx.stats().n_regress)
+            sel = ctx.select_batch(P["x0"], P["zt"], timeStep=P["timeStep"]) if S else None
         finally:
             ctx.close()
-        outs[name] = out
+        outs[name] = out; sels[name] = sel
         what = "N = %d, S = %d, %s, batch %d" % (N, S, name, B)
+        print(what)
         if n_regress != (0 if fused else 1):                       # the fused step runs the regression inside the solve kernel; nothing else does
             fails.append("%s: %d regression launches" % (what, n_regress))
         if not np.all(out["status"][:P_SIZE] == 0):
@@ -167,6 +199,13 @@ def test_every_route_gives_one_answer(built, N, S):
         same = [k for k in SAME_KEYS if not np.array_equal(out[k][:P_SIZE], ref[k][:P_SIZE])]
         if same:
             fails.append("%s: %s not bit-identical to the four-wave route" % (what, ", ".join(same)))
+        if S:
+            same = [k for k in SAME_SELECT_KEYS if not np.array_equal(sel[k], sels["4 waves"][k])]
+            if same:
+                fails.append("%s: select_batch on P: %s not bit-identical to the four-wave route" % (what, ", ".join(same)))
+        bad = _epilogue_fails(out, sel, N, S)
+        if bad:
+            fails.append("%s: epilogue: %s beyond the rounding of its sum" % (what, ", ".join(bad)) if S else "%s: epilogue: %s not the last predicted row bit for bit" % (what, ", ".join(bad)))
         dxu = max(float(np.abs(out["xPred"][:P_SIZE] - ref["xPred"][:P_SIZE]).max()), float(np.abs(out["uPred"][:P_SIZE] - ref["uPred"][:P_SIZE]).max()))
         dzt = float((np.abs(out["ztNext"][:P_SIZE] - ref["ztNext"][:P_SIZE]) / (1 + np.abs(ref["ztNext"][:P_SIZE]))).max())
         if not (dxu < TOL_ROUTE and dzt < TOL_ROUTE):
