@@ -24,7 +24,7 @@ GENERATORS = {
     "lmpc_wide_n12.npz": "make_wide_golden.py", "lmpc_n14.npz": "make_wide_golden.py", "lmpc_n40.npz": "make_wide_golden.py", "lmpc_30laps_n12.npz": "make_wide_golden.py",
     "lmpc_30laps_stress_n12.npz": "make_wide_golden.py", "mpc_n14.npz": "make_wide_golden.py",
     "ltvmpc_noslack_n12.npz": "make_noslack_golden.py", "regression.npz": "make_regression_golden.py", "track_xy.npz": "make_track_golden.py",
-    "reference_flow_laps_n14.json": "make_flow_golden.py",
+    "reference_flow_laps_n14.json": "make_flow_golden.py", "lmpc_active.npz": "make_active_golden.py",
     "reg_singular_capture.npz": "tools/capture_reg_singular.py (GPU box: captured closed-loop events, not regenerable here)",
 }
 ORACLE_SOURCES = ("oracle/lmpc_oracle.py", "oracle/osqp_restated.c")

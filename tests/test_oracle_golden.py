@@ -304,6 +304,42 @@ def test_oracle_produced_fields_rederive_bit_for_bit(name, prefix, records):
         assert cert == g[prefix + "cert_opt"][r] and cert < 1e-9
 
 
+@pytest.mark.parametrize("N", [8, 12, 14, 20, 40])
+def test_active_fixture_rederives_bit_for_bit(N):
+    """tests/golden/lmpc_active.npz (make_active_golden.py; oracle-made throughout, no reference tree): of every horizon's directed problems the three whose A, B, C and
+    selection are stored (first, middle, last) and two more come out of TODAY's oracle bit for bit -- regression, selection with successors, the optimum of
+    osqp_solve_exact and both certificates -- and so do two closed-loop records per horizon from their stored A, B, C, SS, Qsel.  (The stores and the records' inputs
+    come from a 30-lap closed loop of 40 s per horizon, which is not run again here; the manifest holds their content hash.)"""
+    from tests import active_cases as ac
+    f = ac.load()
+    inp = ac.fixture_inputs(f, N)
+    p = "n%d_" % N
+    K = inp["x0"].shape[0]
+    k1 = [int(b) for b in f[p + "k1"]]
+    idx = sorted(set(k1) | {K // 4, (3 * K) // 4})
+    for r in ac.oracle_records(f, N, inp, idx, solve=True, procs=1):
+        b = r["b"]
+        assert ac.admitted(r, N), (N, b)
+        z = ac.split(r["opt"], N)
+        for j, k in enumerate(("x", "u", "slack", "lambd", "sTerm")):
+            assert np.array_equal(z[j], f[p + k][b]), (N, b, k)
+        assert r["cert"] == f[p + "cert"][b][0] and r["cert2"] == f[p + "cert"][b][1]
+        assert ac.active_counts(r["opt"], N) == (f[p + "nact_slack"][b], f[p + "nact_u"][b]) and ac.lambda_unique(r, N) == bool(f[p + "lam_unique"][b])
+        if b in k1:
+            for k in ("A", "B", "C", "SSsel", "Qsel", "Succ", "SuccU"):
+                assert np.array_equal(np.asarray(r[k]), f[p + k][k1.index(b)]), (N, b, k)
+    if N in ac.CL_HORIZONS:
+        p = "cl%d_" % N
+        par = orc.QPParams.lmpc_default(N)
+        for b in (0, 31):
+            P, q, A, l, u = orc.assemble_lmpc_qp(par, f[p + "A"][b], f[p + "B"][b], f[p + "C"][b], f[p + "x0"][b], f[p + "uOld"][b], f[p + "SS"][b], f[p + "Qsel"][b])
+            ex, cert = orc.osqp_solve_exact(P, q, A, l, u)
+            z = ac.split(ex.x, N)
+            for j, k in enumerate(("x", "u", "slack", "lambd", "sTerm")):
+                assert np.array_equal(z[j], f[p + k][b]), (N, b, k)
+            assert cert == f[p + "cert"][b][0] and cert <= 1e-8
+
+
 def test_dense_ipm_active_set_finish_reaches_the_optimum():
     """Round 6: the oracle's dense interior-point solver ends with an active-set finish (the reference's own polish idea, PredictiveControllers.py:275).  On flat /
     degenerate closed-loop QPs the interior iterate alone sat up to 7e-6 from the optimum with every residual test met -- found when the HIP kernels, with their
