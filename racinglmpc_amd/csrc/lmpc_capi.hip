@@ -93,7 +93,7 @@ struct lmpc_ctx {
     lmpc_dev_params dp;
     hipStream_t stream;
     double *mstore, *sstore;                 // device lap stores [lap][col][row]
-    unsigned *mquant; double *mqpar; int mq_chunks;   // K1 prefilter image of the model store, see quantise_lap
+    unsigned *mquant; double *mqpar; int mq_chunks;   // K1 prefilter image of the model store (lmpc_commit.hip.h: commit_quantise)
     std::vector<int> m_order, m_len;         // model: sorted position -> slot ; length per slot
     std::vector<int> s_len;                  // safe set: rows per lap (incl. addPoint extensions)
     std::vector<int> s_laptime;              // LMPC.LapTime (rows at addTrajectory time)
@@ -118,7 +118,7 @@ struct lmpc_ctx {
     struct pending_solve { lmpc_solve_io io; int B; int epoch; lmpc_dev_params dp; bool shared_abc; };   // dp: the parameter block (selected laps, store pointers) of the launch
     std::vector<pending_solve> pending; int *h_retry, *d_retry; int epoch;
     size_t ab_pack_cap;                      // problems ab_pack holds
-    void *scr_dev; size_t scr_bytes;         // pooled scratch of the small host-buffer entry points (plant step, global position)
+    void *scr_dev; size_t scr_bytes;         // pooled scratch of the host-buffer entry points (pooled_scratch: staged laps and launch tables of the stores, plant step, global position)
     std::vector<char *> gaps;                // guard builds: the 256-byte zones between the work-buffer ranges of the slabs
     unsigned create_flags; int solver_kind;  // lmpc_create_ex flags; which solve kernels serve this context: 0 built-in, 1 variant library, 2 the runtime-(N, S) kernel
     int dbg_capture;                         // lmpc_debug_rollout_capture: rollout sessions also keep the selected safe-set points of the last step (parity probes of the closed loop)
@@ -136,9 +136,28 @@ struct lmpc_ctx {
     // index).  The image names rows of laps, so every edit of the safe set marks it dirty and the next launch that reads it uploads it again (ss_table_for)
     std::vector<int> sst_idx, sst_last; int sst_n; bool sst_has_last, sst_dirty; int *d_sst; size_t d_sst_cap;
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
-    double *ext_rows; size_t ext_rows_bytes;   // staging buffer of lmpc_ss_extend_lap
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
 };
+
+// a device-resident rollout session (lmpc_rollout_*, below the stores section, which commits a session's logs and therefore sees the struct)
+struct lmpc_rollout_session {
+    bool active;                                                // between lmpc_rollout_begin and lmpc_rollout_end; the buffers outlive the session (see lmpc_rollout_begin)
+    int B, T_max, t;
+    int kind, stop_at_line;                                     // RO_LMPC / RO_LTV / RO_LTI / RO_PID (what one simulated step launches); 0: the run does not end when every car has crossed the line
+    double *d_noiseU, *d_vt;                                    // RO_PID only: controller noise T_max x B x 2, target speed per car
+    unsigned long long nz_seed, nz_lap; long long nz_car0;      // the session's snapshot of the noise source (lmpc_rollout_set_noise), taken when it begins
+    int *d_lt; bool has_lt, lt_small; int lt_stride;            // the session's snapshot of the lap table (resolved (slot, rows) pairs, B x trToUse x 2), taken when it begins; has_lt: the table builds of the regression kernel run
+    double *d_par; bool has_par;                                // the session's snapshot of the per-car vehicle constants (B x LMPC_PLANT_NPAR), taken when it begins; has_par: the PAR kernels run
+    hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
+    std::vector<void *> keep;
+    // what the session shares with a step, by the names and sizes of lmpc_arrays.h (x0: the cars' states).  Never allocated: mu, ztUsed, selStart; ssSel, qSel, succ,
+    // succU only with lmpc_debug_rollout_capture on (else null: the step does not write them)
+    lmpc_arrays a;
+    double *d_xg, *d_logX, *d_logU, *d_logG, *d_noise, *d_finX, *d_finG;
+    int *d_done, *d_nDone, *d_stAcc;
+};
+
+enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
 
 #ifdef LMPC_DEV_FAST
 // developer build (racinglmpc_amd.build.build_flavour("dev", ["LMPC_DEV_FAST"])): only the N = 12 variants, seconds to compile; LMPC_FORCE_NW=<1|2|4>
@@ -254,6 +273,17 @@ struct call_temps {
     ~call_temps() { for (void *q : held) (void)hipFree(q); }
     template <class T> hipError_t alloc(T **q, size_t bytes) { const hipError_t e = hipMalloc((void **)q, bytes); if (e == hipSuccess) held.push_back(*q); return e; }
 };
+// scratch of the host-buffer entry points (every one of them waits for its own work before it returns): one device allocation, grown on demand and kept (no hipMalloc / hipFree per call)
+static int pooled_scratch(lmpc_ctx *c, size_t bytes, void **out) {
+    if (bytes > c->scr_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->scr_dev) { (void)g_free(c->scr_dev); c->scr_dev = nullptr; c->scr_bytes = 0; }
+        const size_t want = std::max<size_t>((bytes + 4095) & ~(size_t)4095, (size_t)64 * 1024);
+        HIPCHK(g_malloc(&c->scr_dev, want)); c->scr_bytes = want;
+    }
+    *out = c->scr_dev;
+    return LMPC_OK;
+}
 // everything of lmpc_create that can fail; the caller destroys the context on any error (one failure path, no leaks)
 static int create_body(lmpc_ctx *c) {
     const lmpc_config *cfg = &c->cfg;
@@ -385,7 +415,6 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rollout_free(c);
     if (c->comm) { (void)ncclCommDestroy((ncclComm_t)c->comm); c->comm = nullptr; }
-    if (c->ext_rows) (void)g_free(c->ext_rows);
     if (c->scr_dev) (void)g_free(c->scr_dev);
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
@@ -485,50 +514,96 @@ static int grow_stores(lmpc_ctx *c, int need_laps, int need_len) {
     return resolve_lap_table(c);
 }
 
-static int upload_lap(lmpc_ctx *c, bool model, int slot, const double *x, const double *u, const double *qf, int T) {
-    { const int rc = grow_stores(c, slot + 1, T); if (rc) return rc; }
-    double *store = model ? c->mstore : c->sstore;
-    std::vector<double> col((size_t)T);
-    double *base = store + (size_t)slot * LMPC_COLS * c->cfg.max_lap_len;
-    for (int cI = 0; cI < LMPC_COLS; cI++) {
-        if (cI == 8 && !qf) continue;
-        for (int t = 0; t < T; t++) col[t] = cI < 6 ? x[(size_t)t * 6 + cI] : (cI < 8 ? u[(size_t)t * 2 + (cI - 6)] : qf[t]);
-        HIPCHK(hipMemcpy(base + (size_t)cI * c->cfg.max_lap_len, col.data(), sizeof(double) * T, hipMemcpyHostToDevice));
+// ---- the one writer of the stores (lmpc_commit.hip.h).  Its kernels read rows as log[(t * B + car) * width], the layout of a session's logs; a lap the host hands in
+// (x: T x 6, u: T x 2, row-major) is that layout with B = 1, car = 0, so it is staged at the head of the pooled scratch and written by the same launch.
+struct store_rows { const double *logX, *logU; int B; void *tail; };   // tail: pooled scratch behind the staged rows, for the launch's table and results
+static int staged_rows(lmpc_ctx *c, const double *x, const double *u, int T, size_t tail_bytes, store_rows *s) {
+    void *scr; RCCHK(pooled_scratch(c, sizeof(double) * 8 * (size_t)T + tail_bytes, &scr));
+    double *dx = (double *)scr, *du = dx + 6 * (size_t)T;
+    HIPCHK(hipMemcpyAsync(dx, x, sizeof(double) * 6 * (size_t)T, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(du, u, sizeof(double) * 2 * (size_t)T, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                          // (x and u are the caller's pageable memory: read before anything below can fail and return)
+    *s = {dx, du, 1, du + 2 * (size_t)T};
+    return LMPC_OK;
+}
+// both streams of the session drained (the logs are complete up to step t and no launch reads the stores), then its logs as the source
+static int session_rows(lmpc_ctx *c, size_t tail_bytes, store_rows *s) {
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
+    if (c->ro->pstream) HIPCHK(hipStreamSynchronize(c->ro->pstream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    void *scr; RCCHK(pooled_scratch(c, tail_bytes, &scr));
+    *s = {c->ro->d_logX, c->ro->d_logU, c->ro->B, scr};
+    return LMPC_OK;
+}
+static lmpc_commit_args commit_args(const lmpc_ctx *c, const store_rows &s) {
+    lmpc_commit_args a; a.logX = s.logX; a.logU = s.logU; a.B = s.B; a.sstore = c->sstore; a.mstore = c->mstore; a.mquant = c->mquant; a.mqpar = c->mqpar;
+    a.ls = c->cfg.max_lap_len; a.mq_chunks = c->mq_chunks; a.TL = c->cfg.trackLength; memcpy(a.scaling, c->cfg.scaling, sizeof(a.scaling));
+    return a;
+}
+#define LMPC_COMMIT_TAIL(n) ((sizeof(double) + sizeof(lmpc_commit_entry)) * (size_t)(n))
+#define LMPC_EXTEND_TAIL(n) ((sizeof(double) + sizeof(lmpc_extend_entry) + sizeof(int)) * (size_t)(n))
+
+// Whole laps: entry i of `tab` is rows [0, rows) of car `car` of the source, written to the slots it names.  One growth of the stores, one table upload, one launch, one
+// download of q0 (the Qfun of every entry's first row), then the stream is drained: on return the source has been read.  The context's vectors are not touched.
+static int commit_laps(lmpc_ctx *c, const store_rows &s, const std::vector<lmpc_commit_entry> &tab, std::vector<double> &q0) {
+    const size_t n = tab.size();
+    int laps = 0, rows = 0;
+    for (const lmpc_commit_entry &t : tab) { laps = std::max(laps, std::max(t.ss_slot, t.m_slot) + 1); rows = std::max(rows, t.rows); }
+    RCCHK(grow_stores(c, laps, rows));
+    double *d_q0 = (double *)s.tail; lmpc_commit_entry *d_tab = (lmpc_commit_entry *)(d_q0 + n);
+    q0.assign(n, 0.0);
+    hipError_t e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_commit_entry) * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { hipLaunchKernelGGL(lmpc_commit_laps_kernel, dim3((unsigned)n), dim3(LMPC_COMMIT_NT), 0, c->stream, commit_args(c, s), (const lmpc_commit_entry *)d_tab, d_q0); e = hipGetLastError(); }
+    if (e == hipSuccess && tab[0].ss_slot >= 0) e = hipMemcpyAsync(q0.data(), d_q0, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);      // (every entry of a call names the same stores)
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_commit_laps_kernel", hipGetErrorString(e));
+    return LMPC_OK;
+}
+// The context's vectors after commit_laps has written NEW laps (consecutive slots behind the stored ones): LMPC.addTrajectory's lists (PredictiveControllers.py:418-445;
+// the last row's cost is 0, :447-464) and PredictiveModel.addTrajectory's sorted insert (PredictiveModel.py:35-46: append if empty or T >= the longest, else in front
+// of the first longer lap -- a new lap goes behind the stored ones of its length).
+static void commit_book(lmpc_ctx *c, const std::vector<lmpc_commit_entry> &tab, const std::vector<double> &q0) {
+    for (size_t i = 0; i < tab.size(); i++) {
+        const int T = tab[i].rows;
+        if (tab[i].ss_slot >= 0) { c->s_len.push_back(T); c->s_laptime.push_back(T); c->s_qlast.push_back(0.0); c->s_q0.push_back(q0[i]); c->sst_dirty = true; }   // (last = NULL: which lap is the latest has changed)
+        if (tab[i].m_slot >= 0) {
+            c->m_len.push_back(T);                                   // (regression store: insertion index == slot)
+            if (c->m_order.empty() || T >= c->m_len[c->m_order.back()]) c->m_order.push_back(tab[i].m_slot);
+            else { size_t k = 0; while (k < c->m_order.size() && !(T < c->m_len[c->m_order[k]])) k++; c->m_order.insert(c->m_order.begin() + k, tab[i].m_slot); }
+        }
     }
+}
+// one lap handed in by the host: staged, written to the slots named (-1: that store is not written) and, a new lap, entered in the books.  Blocking: x and u are pageable memory
+static int commit_host_lap(lmpc_ctx *c, const double *x, const double *u, int T, int ss_slot, int m_slot, bool new_lap) {
+    store_rows s; RCCHK(staged_rows(c, x, u, T, LMPC_COMMIT_TAIL(1), &s));
+    const std::vector<lmpc_commit_entry> tab{{0, T, ss_slot, m_slot}}; std::vector<double> q0;
+    RCCHK(commit_laps(c, s, tab, q0));
+    if (new_lap) commit_book(c, tab, q0);
     return LMPC_OK;
 }
 
-// K1 prefilter image of one model-store lap (PredictiveModel.py:180-197 scans (vx, vy, wz, delta, a) . scaling of rows 0..T-2):
-// per 1024-row chunk, every scaled feature is mapped to 16-bit fixed point over the chunk's [min, max] with one common scale
-// 65535 / (widest range), packed as (vx | vy << 16), (wz | delta << 16), (a).  The regress kernel ranks rows by integer L1 distances on this image and re-evaluates the survivors
-// in FP64, so the image never decides anything by itself; it only has to be within a few units of the exact scaled values.
-static int quantise_lap(lmpc_ctx *c, int slot, const double *x, const double *u, int T) {
-    const int ls = c->cfg.max_lap_len, nrows = T - 1;
-    std::vector<unsigned> q((size_t)3 * ls, 0u);
-    std::vector<double> par((size_t)c->mq_chunks * 6, 0.0);
-    auto feat = [&](int t, int k) { return (k < 3 ? x[(size_t)t * 6 + k] : u[(size_t)t * 2 + (k - 3)]) * c->cfg.scaling[k]; };
-    for (int t0 = 0, ch = 0; t0 < nrows; t0 += K1_CHUNK, ch++) {
-        const int t1 = std::min(nrows, t0 + K1_CHUNK);
-        double lo[5], rmax = 0.0;
-        for (int k = 0; k < 5; k++) {
-            double l = INFINITY, h = -INFINITY;
-            for (int t = t0; t < t1; t++) { const double v = feat(t, k); if (std::isfinite(v)) { l = std::min(l, v); h = std::max(h, v); } }
-            if (!(l <= h)) { l = 0.0; h = 0.0; }
-            lo[k] = l; rmax = std::max(rmax, std::max(h - l, 1e-9 * std::max(std::fabs(l), std::fabs(h))));
-        }
-        const double sc = 65535.0 / std::max(rmax, 1e-300);
-        for (int k = 0; k < 5; k++) {
-            par[(size_t)ch * 6 + k] = lo[k];
-            for (int t = t0; t < t1; t++) {
-                const double v = (feat(t, k) - lo[k]) * sc;
-                const unsigned qq = std::isfinite(v) ? (unsigned)std::min(std::max(v, 0.0), 65535.0) : 0u;
-                q[(size_t)(k >> 1) * ls + t] |= (k & 1) ? qq << 16 : qq;
-            }
-        }
-        par[(size_t)ch * 6 + 5] = sc;
+// Appended rows, the batched LMPC.addPoint (PredictiveControllers.py:466-474): rows [0, n_rows) of car cars[i] of the source behind the rows of safe-set lap laps[i].  One
+// growth, one upload of the table and of every lap's last Qfun value, one launch, one download of the flags, a drained stream, then the books of every lap
+// extended.  extended == NULL: the rows are appended whatever they hold; else an entry with a non-finite value is left as it is and reported as 0.
+static int extend_laps(lmpc_ctx *c, const store_rows &s, int n, const int *cars, const int *laps, int n_rows, int *extended) {
+    int longest = 0;
+    for (int i = 0; i < n; i++) longest = std::max(longest, c->s_len[laps[i]] + n_rows);
+    RCCHK(grow_stores(c, c->cfg.max_laps, longest));
+    std::vector<lmpc_extend_entry> tab((size_t)n); std::vector<double> ql((size_t)n);
+    for (int i = 0; i < n; i++) { tab[(size_t)i] = {cars[i], laps[i], c->s_len[laps[i]], 0}; ql[(size_t)i] = c->s_qlast[laps[i]]; }
+    double *d_ql = (double *)s.tail; lmpc_extend_entry *d_tab = (lmpc_extend_entry *)(d_ql + n); int *d_flag = extended ? (int *)(d_tab + n) : nullptr;
+    hipError_t e = hipMemcpyAsync(d_ql, ql.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_extend_entry) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { hipLaunchKernelGGL(lmpc_extend_laps_kernel, dim3(n), dim3(LMPC_COMMIT_NT), 0, c->stream, commit_args(c, s), n_rows, (const lmpc_extend_entry *)d_tab, (const double *)d_ql, d_flag); e = hipGetLastError(); }
+    if (e == hipSuccess && extended) e = hipMemcpyAsync(extended, d_flag, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_extend_laps_kernel", hipGetErrorString(e));
+    for (int i = 0; i < n; i++) {
+        if (extended && !extended[i]) continue;
+        double q = c->s_qlast[laps[i]];
+        for (int k = 0; k < n_rows; k++) q -= 1.0;                     // :474, one subtraction per appended row, each rounded: what the kernel left in the last row
+        c->s_len[laps[i]] += n_rows; c->s_qlast[laps[i]] = q; c->sst_dirty = true;
     }
-    HIPCHK(hipMemcpy(c->mquant + (size_t)slot * 3 * ls, q.data(), q.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->mqpar + (size_t)slot * c->mq_chunks * 6, par.data(), par.size() * sizeof(double), hipMemcpyHostToDevice));
     return LMPC_OK;
 }
 
@@ -536,23 +611,15 @@ int lmpc_model_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int
     ARGCHK(c && x && u && T >= 2);
     HIPCHK(hipSetDevice(c->cfg.device));
     RESOLVE_PENDING();
-    const int slot = (int)c->m_len.size();
     HIPCHK(hipStreamSynchronize(c->stream));
-    int rc = upload_lap(c, true, slot, x, u, nullptr, T); if (rc) return rc;                 // (grows the stores when the lap does not fit)
-    rc = quantise_lap(c, slot, x, u, T); if (rc) return rc;
-    c->m_len.push_back(T);
-    // PredictiveModel.addTrajectory (PredictiveModel.py:35-46): append if empty or T >= last, else insert before first longer lap
-    if (c->m_order.empty() || T >= c->m_len[c->m_order.back()]) c->m_order.push_back(slot);
-    else { size_t i = 0; while (i < c->m_order.size() && !(T < c->m_len[c->m_order[i]])) i++; c->m_order.insert(c->m_order.begin() + i, slot); }
-    return LMPC_OK;
+    return commit_host_lap(c, x, u, T, -1, (int)c->m_len.size(), true);                       // PredictiveModel.addTrajectory (PredictiveModel.py:35-46)
 }
 int lmpc_model_num_laps(lmpc_ctx *c, int *n) { ARGCHK(c && n); *n = (int)c->m_order.size(); return LMPC_OK; }
 int lmpc_model_replace_lap(lmpc_ctx *c, int pos, const double *x, const double *u, int T) {
     ARGCHK(c && x && u && pos >= 0 && pos < (int)c->m_order.size());
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     ARGCHK(T == c->m_len[c->m_order[pos]]);
-    int rc = upload_lap(c, true, c->m_order[pos], x, u, nullptr, T); if (rc) return rc;
-    rc = quantise_lap(c, c->m_order[pos], x, u, T); if (rc) return rc;
+    RCCHK(commit_host_lap(c, x, u, T, -1, c->m_order[pos], false));
     return resolve_lap_table(c);
 }
 
@@ -591,20 +658,8 @@ int lmpc_ss_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int T)
     ARGCHK(c && x && u && T >= 1);
     HIPCHK(hipSetDevice(c->cfg.device));
     RESOLVE_PENDING();
-    const int lap = (int)c->s_len.size();
-    // LMPC.computeCost (PredictiveControllers.py:447-464)
-    std::vector<double> cost((size_t)T, 10000.0);
-    for (int i = 0; i < T; i++) {
-        const int r = T - 1 - i;
-        if (i == 0) cost[r] = 0;
-        else if (x[(size_t)r * 6 + 4] < c->cfg.trackLength) cost[r] = cost[r + 1] + 1;
-        else cost[r] = 0;
-    }
     HIPCHK(hipStreamSynchronize(c->stream));
-    int rc = upload_lap(c, false, lap, x, u, cost.data(), T); if (rc) return rc;
-    c->s_len.push_back(T); c->s_laptime.push_back(T); c->s_qlast.push_back(cost[T - 1]); c->s_q0.push_back(cost[0]);
-    c->sst_dirty = true;                                             // (last = NULL: which lap is the latest has changed)
-    return LMPC_OK;
+    return commit_host_lap(c, x, u, T, (int)c->s_len.size(), -1, true);                        // LMPC.addTrajectory + computeCost (PredictiveControllers.py:418-464)
 }
 
 __global__ void lmpc_store_row_kernel(double *base, int stride, int row, double v0, double v1, double v2, double v3, double v4, double v5, double v6, double v7, double v8) {
@@ -630,7 +685,9 @@ int lmpc_ss_add_point(lmpc_ctx *c, const double *x, const double *u) {
 int lmpc_ss_replace_lap(lmpc_ctx *c, int lap, const double *x, const double *u, const double *qfun, int T) {
     ARGCHK(c && x && u && qfun && lap >= 0 && lap < (int)c->s_len.size() && T >= 1);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
-    int rc = upload_lap(c, false, lap, x, u, qfun, T); if (rc) return rc;
+    RCCHK(commit_host_lap(c, x, u, T, lap, -1, false));
+    // the caller's Q-function over the cost the kernel wrote: column 8 of a lap is contiguous ([lap][column][row]; the stores may have moved above)
+    HIPCHK(hipMemcpy(c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len, qfun, sizeof(double) * (size_t)T, hipMemcpyHostToDevice));
     c->s_len[lap] = T; c->s_qlast[lap] = qfun[T - 1]; c->s_q0[lap] = qfun[0]; c->sst_dirty = true;
     return LMPC_OK;
 }
@@ -700,6 +757,86 @@ int lmpc_store_read_lap(lmpc_ctx *c, int store, int lap, double *x, double *u, d
 }
 
 int lmpc_ss_get_laptime(lmpc_ctx *c, int lap, int *T) { ARGCHK(c && T && lap >= 0 && lap < (int)c->s_laptime.size()); *T = c->s_laptime[lap]; return LMPC_OK; }
+
+int lmpc_ss_extend_lap(lmpc_ctx *c, int lap, const double *x, const double *u, int n) {
+    // batched-mode form of LMPC.addPoint (:466-474) for ANY stored lap: append n points shifted by TrackLength in s,
+    // Q-function continuing to count down.  (In the reference the points of lap j extend lap j-1 one by one.)  The rows are appended as given, finite or not.
+    ARGCHK(c && lap >= 0 && lap < (int)c->s_len.size() && n >= 0 && (n == 0 || (x && u)));
+    if (n == 0) return LMPC_OK;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    RESOLVE_PENDING();
+    store_rows s; RCCHK(staged_rows(c, x, u, n, LMPC_EXTEND_TAIL(1), &s));
+    const int car = 0;
+    return extend_laps(c, s, 1, &car, &lap, n, nullptr);
+}
+
+int lmpc_ss_truncate_lap(lmpc_ctx *c, int lap, int T) {
+    ARGCHK(c && lap >= 0 && lap < (int)c->s_len.size() && T >= c->s_laptime[lap] && T <= c->s_len[lap]);
+    if (T == c->s_len[lap]) return LMPC_OK;
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    double q = 0.0;                                                  // Qfun of the new last row (addPoint counts on from it, :474)
+    HIPCHK(hipMemcpy(&q, c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len + (T - 1), sizeof(double), hipMemcpyDeviceToHost));
+    c->s_len[lap] = T; c->s_qlast[lap] = q; c->sst_dirty = true;
+    return LMPC_OK;
+}
+
+int lmpc_debug_model_image(lmpc_ctx *c, int lap, unsigned *q, double *par, int *chunks) {
+    // the K1 prefilter image of the regression-store lap with insertion index `lap` (lmpc_commit.hip.h: commit_quantise; the scan it serves: PredictiveModel.py:180-197): the
+    // three planes of packed words over rows 0 .. rows-2 (3 x (rows-1)), the six parameters of every chunk in use, and their number.  Any output may be NULL.
+    ARGCHK(c && lap >= 0 && lap < (int)c->m_len.size());
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    const int nrows = c->m_len[lap] - 1, used = (nrows + K1_CHUNK - 1) / K1_CHUNK; const size_t ls = (size_t)c->cfg.max_lap_len;
+    if (chunks) *chunks = used;
+    if (q) HIPCHK(hipMemcpy2D(q, (size_t)nrows * sizeof(unsigned), c->mquant + (size_t)lap * 3 * ls, ls * sizeof(unsigned), (size_t)nrows * sizeof(unsigned), 3, hipMemcpyDeviceToHost));
+    if (par && used) HIPCHK(hipMemcpy(par, c->mqpar + (size_t)lap * c->mq_chunks * 6, sizeof(double) * 6 * (size_t)used, hipMemcpyDeviceToHost));
+    return LMPC_OK;
+}
+
+// ---- laps of the active session straight into the stores: no log leaves the device
+int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *rows, unsigned stores, int *first_ss, int *first_model) {
+    // For i = 0 .. n-1 in the order listed: lmpc_ss_add_trajectory (LMPC.addTrajectory + computeCost, PredictiveControllers.py:418-464) and lmpc_model_add_trajectory
+    // (PredictiveModel.addTrajectory, PredictiveModel.py:35-46) of rows [0, rows[i]) of car cars[i] as the session logged them, all in one commit_laps.
+    // Checked in full before anything changes; the host vectors are touched only after the launch has completed.
+    ARGCHK(c && c->ro && c->ro->active && c->ro->t >= 1 && n >= 1 && cars && stores != 0u && !(stores & ~(LMPC_COMMIT_SS | LMPC_COMMIT_MODEL)));
+    lmpc_rollout_session *r = c->ro; const int B = r->B;
+    const bool ss = (stores & LMPC_COMMIT_SS) != 0, model = (stores & LMPC_COMMIT_MODEL) != 0;
+    for (int i = 0; i < n; i++) ARGCHK(cars[i] >= 0 && cars[i] < B);
+    store_rows s; RCCHK(session_rows(c, LMPC_COMMIT_TAIL(n), &s));
+    std::vector<int> done((size_t)B);
+    HIPCHK(hipMemcpy(done.data(), r->d_done, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    const int ns0 = (int)c->s_len.size(), nm0 = (int)c->m_len.size();
+    std::vector<lmpc_commit_entry> tab((size_t)n);
+    char msg[160];
+    for (int i = 0; i < n; i++) {
+        const int car = cars[i], T = rows ? rows[i] : done[car];
+        if (!rows && done[car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0) and no row count was given", car); return set_err(LMPC_E_STATE, "lmpc_rollout_commit_laps", msg); }
+        // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
+        const int logged = (r->kind == RO_PID && r->stop_at_line && done[car] >= 0) ? done[car] : r->t;
+        if (T < (model ? 2 : 1) || T > logged) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, %d are logged (at least %d needed)", i, T, car, logged, model ? 2 : 1); return set_err(LMPC_E_ARG, "lmpc_rollout_commit_laps", msg); }
+        tab[(size_t)i] = {car, T, ss ? ns0 + i : -1, model ? nm0 + i : -1};
+    }
+    std::vector<double> q0;
+    RCCHK(commit_laps(c, s, tab, q0));
+    commit_book(c, tab, q0);
+    if (first_ss) *first_ss = ss ? ns0 : -1;
+    if (first_model) *first_model = model ? nm0 : -1;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_extend_laps(lmpc_ctx *c, int n, const int *cars, const int *laps, int n_rows, int *extended) {
+    // lmpc_ss_extend_lap of rows [0, n_rows) of car cars[i] onto safe-set lap laps[i], for every entry whose rows are all finite; the others are left as they are and
+    // reported, all in one extend_laps.
+    ARGCHK(c && c->ro && c->ro->active && n >= 1 && cars && laps && extended && n_rows >= 1 && n_rows <= c->ro->t);
+    const int stored = (int)c->s_len.size();
+    std::vector<char> seen((size_t)stored, 0);
+    for (int i = 0; i < n; i++) {
+        ARGCHK(cars[i] >= 0 && cars[i] < c->ro->B && laps[i] >= 0 && laps[i] < stored);
+        if (seen[(size_t)laps[i]]) { char msg[96]; snprintf(msg, sizeof(msg), "lap %d is listed twice", laps[i]); return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); }
+        seen[(size_t)laps[i]] = 1;
+    }
+    store_rows s; RCCHK(session_rows(c, LMPC_EXTEND_TAIL(n), &s));
+    return extend_laps(c, s, n, cars, laps, n_rows, extended);
+}
 
 // refresh the per-launch part of the device parameter block
 // model_from_table: the regression launch this refresh is for reads a lap table (the context's, or a session's snapshot), whose rows `set` has checked -- the
@@ -1208,17 +1345,6 @@ int lmpc_debug_k1_timing(lmpc_ctx *c, int B, const double *xLin, const double *u
 
 // ---------------------------------------------------------------------------------------------- plant / rollouts
 }  // extern "C"
-// scratch of the small host-buffer entry points below: one device allocation, grown on demand and kept (no hipMalloc / hipFree per call)
-static int pooled_scratch(lmpc_ctx *c, size_t bytes, void **out) {
-    if (bytes > c->scr_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->scr_dev) { (void)g_free(c->scr_dev); c->scr_dev = nullptr; c->scr_bytes = 0; }
-        const size_t want = std::max<size_t>((bytes + 4095) & ~(size_t)4095, (size_t)64 * 1024);
-        HIPCHK(g_malloc(&c->scr_dev, want)); c->scr_bytes = want;
-    }
-    *out = c->scr_dev;
-    return LMPC_OK;
-}
 // Per-car vehicle constants (lmpc_plant_set_params).  The rows in force for a call of B cars, one per car: the single row repeated, or the first B of the n rows.
 static int plant_rows_for(lmpc_ctx *c, int B, std::vector<double> &rows) {
     if (c->plant_n > 1 && B > c->plant_n) {
@@ -1395,24 +1521,6 @@ int lmpc_state_from_global_batch(lmpc_ctx *c, int T, int B, const double *xglob,
     return LMPC_OK;
 }
 
-struct lmpc_rollout_session {
-    bool active;                                                // between lmpc_rollout_begin and lmpc_rollout_end; the buffers outlive the session (see lmpc_rollout_begin)
-    int B, T_max, t;
-    int kind, stop_at_line;                                     // RO_LMPC / RO_LTV / RO_LTI / RO_PID (what one simulated step launches); 0: the run does not end when every car has crossed the line
-    double *d_noiseU, *d_vt;                                    // RO_PID only: controller noise T_max x B x 2, target speed per car
-    unsigned long long nz_seed, nz_lap; long long nz_car0;      // the session's snapshot of the noise source (lmpc_rollout_set_noise), taken when it begins
-    int *d_lt; bool has_lt, lt_small; int lt_stride;            // the session's snapshot of the lap table (resolved (slot, rows) pairs, B x trToUse x 2), taken when it begins; has_lt: the table builds of the regression kernel run
-    double *d_par; bool has_par;                                // the session's snapshot of the per-car vehicle constants (B x LMPC_PLANT_NPAR), taken when it begins; has_par: the PAR kernels run
-    hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
-    std::vector<void *> keep;
-    // what the session shares with a step, by the names and sizes of lmpc_arrays.h (x0: the cars' states).  Never allocated: mu, ztUsed, selStart; ssSel, qSel, succ,
-    // succU only with lmpc_debug_rollout_capture on (else null: the step does not write them)
-    lmpc_arrays a;
-    double *d_xg, *d_logX, *d_logU, *d_logG, *d_noise, *d_finX, *d_finG;
-    int *d_done, *d_nDone, *d_stAcc;
-};
-
-enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
 #define LMPC_PID_MAX_STEPS 100000                             // host bound on the one launch that holds a whole lap (the reference simulates 1000 steps, main.py:57): ~seconds of kernel at most
 
 static void rollout_free(lmpc_ctx *c) {
@@ -1710,167 +1818,6 @@ int lmpc_rollout_release(lmpc_ctx *c) {
     ARGCHK(c && !(c->ro && c->ro->active));
     HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(c->stream));
     rollout_free(c);
-    return LMPC_OK;
-}
-
-__global__ void lmpc_store_rows_kernel(double *base, int stride, int row0, int n, const double *rows /* n x 9: x (6, s already shifted) | u (2) | Qfun */) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n * LMPC_COLS) { const int i = e / LMPC_COLS, col = e % LMPC_COLS; base[(size_t)col * stride + row0 + i] = rows[e]; }
-}
-
-int lmpc_ss_extend_lap(lmpc_ctx *c, int lap, const double *x, const double *u, int n) {
-    // batched-mode form of LMPC.addPoint (:466-474) for ANY stored lap: append n points shifted by TrackLength in s,
-    // Q-function continuing to count down.  (In the reference the points of lap j extend lap j-1 one by one.)  One upload, one launch.
-    ARGCHK(c && lap >= 0 && lap < (int)c->s_len.size() && n >= 0 && (n == 0 || (x && u)));
-    if (n == 0) return LMPC_OK;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    RESOLVE_PENDING();
-    if (c->s_len[lap] + n > c->cfg.max_lap_len) { const int rc = grow_stores(c, c->cfg.max_laps, c->s_len[lap] + n); if (rc) return rc; }
-    std::vector<double> rows((size_t)n * LMPC_COLS);
-    double q = c->s_qlast[lap];
-    for (int i = 0; i < n; i++) {
-        q -= 1.0;
-        double *r = &rows[(size_t)i * LMPC_COLS];
-        for (int j = 0; j < 6; j++) r[j] = x[(size_t)i * 6 + j];
-        r[4] += c->cfg.trackLength; r[6] = u[(size_t)i * 2]; r[7] = u[(size_t)i * 2 + 1]; r[8] = q;
-    }
-    if (rows.size() * sizeof(double) > c->ext_rows_bytes) {       // staging buffer of the batched addPoint: grown once, kept
-        if (c->ext_rows) (void)g_free(c->ext_rows);
-        c->ext_rows = nullptr; c->ext_rows_bytes = 0;
-        const size_t want = std::max<size_t>(rows.size() * sizeof(double), (size_t)64 * LMPC_COLS * sizeof(double));
-        HIPCHK(g_malloc(&c->ext_rows, want)); c->ext_rows_bytes = want;
-    }
-    double *d_rows = c->ext_rows;
-    hipError_t e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        double *base = c->sstore + (size_t)lap * LMPC_COLS * c->cfg.max_lap_len;
-        hipLaunchKernelGGL(lmpc_store_rows_kernel, dim3((n * LMPC_COLS + 255) / 256), dim3(256), 0, c->stream, base, c->cfg.max_lap_len, c->s_len[lap], n, (const double *)d_rows);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the pageable host rows must outlive the copy)
-    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_ss_extend_lap", hipGetErrorString(e));
-    c->s_len[lap] += n; c->s_qlast[lap] = q; c->sst_dirty = true;
-    return LMPC_OK;
-}
-
-// ---- laps of the active session straight into the stores (lmpc_commit.hip.h): no log leaves the device
-static lmpc_commit_args commit_args(const lmpc_ctx *c) {
-    const lmpc_rollout_session *r = c->ro;
-    lmpc_commit_args a; a.logX = r->d_logX; a.logU = r->d_logU; a.B = r->B; a.sstore = c->sstore; a.mstore = c->mstore; a.mquant = c->mquant; a.mqpar = c->mqpar;
-    a.ls = c->cfg.max_lap_len; a.mq_chunks = c->mq_chunks; a.TL = c->cfg.trackLength; memcpy(a.scaling, c->cfg.scaling, sizeof(a.scaling));
-    return a;
-}
-// both streams of the session drained: the logs are complete up to step t and no launch reads the stores
-static int session_drain(lmpc_ctx *c) {
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
-    if (c->ro->pstream) HIPCHK(hipStreamSynchronize(c->ro->pstream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return LMPC_OK;
-}
-
-int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *rows, unsigned stores, int *first_ss, int *first_model) {
-    // For i = 0 .. n-1 in the order listed: lmpc_ss_add_trajectory (LMPC.addTrajectory + computeCost, PredictiveControllers.py:418-464) and lmpc_model_add_trajectory
-    // (PredictiveModel.addTrajectory, PredictiveModel.py:35-46) of rows [0, rows[i]) of car cars[i] as the session logged them -- one table upload, one launch, one
-    // download of n doubles.  Checked in full before anything changes; the host vectors are touched only after the launch has completed.
-    ARGCHK(c && c->ro && c->ro->active && c->ro->t >= 1 && n >= 1 && cars && stores != 0u && !(stores & ~(LMPC_COMMIT_SS | LMPC_COMMIT_MODEL)));
-    lmpc_rollout_session *r = c->ro; const int B = r->B;
-    const bool ss = (stores & LMPC_COMMIT_SS) != 0, model = (stores & LMPC_COMMIT_MODEL) != 0;
-    for (int i = 0; i < n; i++) ARGCHK(cars[i] >= 0 && cars[i] < B);
-    RCCHK(session_drain(c));
-    std::vector<int> done((size_t)B);
-    HIPCHK(hipMemcpy(done.data(), r->d_done, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
-    const int ns0 = (int)c->s_len.size(), nm0 = (int)c->m_len.size();
-    std::vector<lmpc_commit_entry> tab((size_t)n);
-    int max_rows = 0;
-    char msg[160];
-    for (int i = 0; i < n; i++) {
-        const int car = cars[i], T = rows ? rows[i] : done[car];
-        if (!rows && done[car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0) and no row count was given", car); return set_err(LMPC_E_STATE, "lmpc_rollout_commit_laps", msg); }
-        // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
-        const int logged = (r->kind == RO_PID && r->stop_at_line && done[car] >= 0) ? done[car] : r->t;
-        if (T < (model ? 2 : 1) || T > logged) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, %d are logged (at least %d needed)", i, T, car, logged, model ? 2 : 1); return set_err(LMPC_E_ARG, "lmpc_rollout_commit_laps", msg); }
-        tab[(size_t)i].car = car; tab[(size_t)i].rows = T; tab[(size_t)i].ss_slot = ss ? ns0 + i : -1; tab[(size_t)i].m_slot = model ? nm0 + i : -1;       // (regression store: insertion index == slot)
-        max_rows = std::max(max_rows, T);
-    }
-    RCCHK(grow_stores(c, std::max(ss ? ns0 + n : 0, model ? nm0 + n : 0), max_rows));
-    void *scr; RCCHK(pooled_scratch(c, (sizeof(double) + sizeof(lmpc_commit_entry)) * (size_t)n, &scr));
-    double *d_q0 = (double *)scr; lmpc_commit_entry *d_tab = (lmpc_commit_entry *)(d_q0 + n);
-    std::vector<double> q0((size_t)n, 0.0);
-    hipError_t e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_commit_entry) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { hipLaunchKernelGGL(lmpc_commit_laps_kernel, dim3(n), dim3(LMPC_COMMIT_NT), 0, c->stream, commit_args(c), (const lmpc_commit_entry *)d_tab, d_q0); e = hipGetLastError(); }
-    if (e == hipSuccess && ss) e = hipMemcpyAsync(q0.data(), d_q0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_rollout_commit_laps", hipGetErrorString(e));
-    for (int i = 0; i < n; i++) {
-        const int T = tab[(size_t)i].rows;
-        if (ss) { c->s_len.push_back(T); c->s_laptime.push_back(T); c->s_qlast.push_back(0.0); c->s_q0.push_back(q0[(size_t)i]); }      // (cost[T-1] = 0)
-        if (model) {
-            const int slot = nm0 + i;
-            c->m_len.push_back(T);
-            if (c->m_order.empty() || T >= c->m_len[c->m_order.back()]) c->m_order.push_back(slot);          // PredictiveModel.py:35-46, as lmpc_model_add_trajectory
-            else { size_t k = 0; while (k < c->m_order.size() && !(T < c->m_len[c->m_order[k]])) k++; c->m_order.insert(c->m_order.begin() + k, slot); }
-        }
-    }
-    if (ss) c->sst_dirty = true;
-    if (first_ss) *first_ss = ss ? ns0 : -1;
-    if (first_model) *first_model = model ? nm0 : -1;
-    return LMPC_OK;
-}
-
-int lmpc_rollout_extend_laps(lmpc_ctx *c, int n, const int *cars, const int *laps, int n_rows, int *extended) {
-    // lmpc_ss_extend_lap (the batched LMPC.addPoint, PredictiveControllers.py:466-474) of rows [0, n_rows) of car cars[i] onto safe-set lap laps[i], for every entry
-    // whose rows are all finite; the others are left as they are and reported.  One growth, one launch, one download of the flags.
-    ARGCHK(c && c->ro && c->ro->active && n >= 1 && cars && laps && extended && n_rows >= 1 && n_rows <= c->ro->t);
-    lmpc_rollout_session *r = c->ro;
-    const int stored = (int)c->s_len.size();
-    std::vector<char> seen((size_t)stored, 0);
-    for (int i = 0; i < n; i++) {
-        ARGCHK(cars[i] >= 0 && cars[i] < r->B && laps[i] >= 0 && laps[i] < stored);
-        if (seen[(size_t)laps[i]]) { char msg[96]; snprintf(msg, sizeof(msg), "lap %d is listed twice", laps[i]); return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); }
-        seen[(size_t)laps[i]] = 1;
-    }
-    RCCHK(session_drain(c));
-    int longest = 0;
-    for (int i = 0; i < n; i++) longest = std::max(longest, c->s_len[laps[i]] + n_rows);
-    RCCHK(grow_stores(c, c->cfg.max_laps, longest));
-    std::vector<lmpc_extend_entry> tab((size_t)n); std::vector<double> ql((size_t)n);
-    for (int i = 0; i < n; i++) { tab[(size_t)i].car = cars[i]; tab[(size_t)i].lap = laps[i]; tab[(size_t)i].row0 = c->s_len[laps[i]]; tab[(size_t)i].pad = 0; ql[(size_t)i] = c->s_qlast[laps[i]]; }
-    void *scr; RCCHK(pooled_scratch(c, (sizeof(double) + sizeof(lmpc_extend_entry) + sizeof(int)) * (size_t)n, &scr));
-    double *d_ql = (double *)scr; lmpc_extend_entry *d_tab = (lmpc_extend_entry *)(d_ql + n); int *d_flag = (int *)(d_tab + n);
-    hipError_t e = hipMemcpyAsync(d_ql, ql.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_extend_entry) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { hipLaunchKernelGGL(lmpc_extend_laps_kernel, dim3(n), dim3(LMPC_COMMIT_NT), 0, c->stream, commit_args(c), n_rows, (const lmpc_extend_entry *)d_tab, (const double *)d_ql, d_flag); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(extended, d_flag, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_rollout_extend_laps", hipGetErrorString(e));
-    for (int i = 0; i < n; i++) {
-        if (!extended[i]) continue;
-        double q = c->s_qlast[laps[i]];
-        for (int k = 0; k < n_rows; k++) q -= 1.0;                     // :474, one subtraction per appended row
-        c->s_len[laps[i]] += n_rows; c->s_qlast[laps[i]] = q; c->sst_dirty = true;
-    }
-    return LMPC_OK;
-}
-
-int lmpc_debug_model_image(lmpc_ctx *c, int lap, unsigned *q, double *par, int *chunks) {
-    // the K1 prefilter image of the regression-store lap with insertion index `lap` (quantise_lap; the scan it serves: PredictiveModel.py:180-197): the three planes of
-    // packed words over rows 0 .. rows-2 (3 x (rows-1)), the six parameters of every chunk in use, and their number.  Any output may be NULL.
-    ARGCHK(c && lap >= 0 && lap < (int)c->m_len.size());
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
-    const int nrows = c->m_len[lap] - 1, used = (nrows + K1_CHUNK - 1) / K1_CHUNK; const size_t ls = (size_t)c->cfg.max_lap_len;
-    if (chunks) *chunks = used;
-    if (q) HIPCHK(hipMemcpy2D(q, (size_t)nrows * sizeof(unsigned), c->mquant + (size_t)lap * 3 * ls, ls * sizeof(unsigned), (size_t)nrows * sizeof(unsigned), 3, hipMemcpyDeviceToHost));
-    if (par && used) HIPCHK(hipMemcpy(par, c->mqpar + (size_t)lap * c->mq_chunks * 6, sizeof(double) * 6 * (size_t)used, hipMemcpyDeviceToHost));
-    return LMPC_OK;
-}
-
-int lmpc_ss_truncate_lap(lmpc_ctx *c, int lap, int T) {
-    ARGCHK(c && lap >= 0 && lap < (int)c->s_len.size() && T >= c->s_laptime[lap] && T <= c->s_len[lap]);
-    if (T == c->s_len[lap]) return LMPC_OK;
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
-    double q = 0.0;                                                  // Qfun of the new last row (addPoint counts on from it, :474)
-    HIPCHK(hipMemcpy(&q, c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len + (T - 1), sizeof(double), hipMemcpyDeviceToHost));
-    c->s_len[lap] = T; c->s_qlast[lap] = q; c->sst_dirty = true;
     return LMPC_OK;
 }
 

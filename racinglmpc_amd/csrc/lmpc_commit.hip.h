@@ -1,10 +1,12 @@
-// racinglmpc_amd/csrc/lmpc_commit.hip.h -- the end-of-lap bookkeeping of a rollout session on the device: rows of the session logs (logX: T x B x 6, logU: T x B x 2)
-// become laps of the two stores ([lap][column][row], row stride max_lap_len) without passing through the host.
-//   lmpc_commit_laps_kernel   what lmpc_ss_add_trajectory + lmpc_model_add_trajectory do with a fetched lap: the transposed copy, LMPC.computeCost
-//                             (PredictiveControllers.py:447-464) and the K1 prefilter image of the regression store (quantise_lap in lmpc_capi.hip; the scan it
-//                             serves is PredictiveModel.py:180-197).
-//   lmpc_extend_laps_kernel   what lmpc_ss_extend_lap does with the fetched first rows: the batched LMPC.addPoint (PredictiveControllers.py:466-474).
-// Both are one 256-thread work-group per lap: nothing here is compute-heavy, what is saved are the ~20 blocking copies per car of the host path.
+// racinglmpc_amd/csrc/lmpc_commit.hip.h -- the writer of the two lap stores ([lap][column][row], row stride max_lap_len): every lap and every batch of appended rows, from
+// a rollout session's logs or from the host, enters the stores through the two kernels below, and the rules of what a stored lap holds are stated here only.
+// A source is a log: logX (T x B x 6) and logU (T x B x 2), row t of car b at log[(t * B + b) * width] -- a session's logs as they are, or one lap handed in by the
+// host (T x 6, T x 2, row-major: B = 1, car 0) staged on the device.
+//   lmpc_commit_laps_kernel   whole laps: the transposed copy of rows [0, T) into the safe set and / or the regression store, the Q-function of the safe-set lap
+//                             (LMPC.computeCost, PredictiveControllers.py:447-464) and the K1 prefilter image of the regression-store lap (the scan it serves:
+//                             PredictiveModel.py:180-197).
+//   lmpc_extend_laps_kernel   rows appended to safe-set laps: the batched LMPC.addPoint (PredictiveControllers.py:466-474).
+// Both are one 256-thread work-group per lap: nothing here is compute-heavy, what counts is that a lap costs one launch and no per-column copy.
 // Included by lmpc_capi.hip only, after the kernels' header (K1_CHUNK, LMPC_COLS).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,15 +17,16 @@ static_assert(K1_CHUNK % LMPC_COMMIT_NT == 0 && LMPC_COMMIT_NT % 64 == 0, "one p
 
 struct lmpc_commit_entry { int car, rows, ss_slot, m_slot; };          // slots: -1 = that store is not written
 struct lmpc_commit_args {
-    const double *logX, *logU; int B;                                   // the session's logs
+    const double *logX, *logU; int B;                                   // the source
     double *sstore, *mstore; unsigned *mquant; double *mqpar;           // the stores and the prefilter image (lmpc_ctx)
     int ls, mq_chunks;                                                  // row stride of every column (max_lap_len); chunks the image holds per lap
     double TL, scaling[5];
 };
 struct lmpc_extend_entry { int car, lap, row0, pad; };                 // row0: rows the lap holds now (the first appended row)
 
-// std::min / std::max as quantise_lap applies them, operand order kept: among equals (+0.0 and -0.0 compare equal) the value met FIRST stays.  "Keep the left one
-// on a tie" is associative, so a reduction that combines neighbours in row order gives the bits of the host's sequential scan.
+// The minimum / maximum of a feature over a chunk is the one a scan in row order finds when it replaces its value only by a strictly smaller / larger one: among equals
+// (+0.0 and -0.0 compare equal) the value met FIRST stays, which defines the sign of a zero minimum.  "Keep the left one on a tie" is associative, so a reduction
+// that combines neighbours in row order gives the bits of that sequential scan.
 __device__ __forceinline__ double commit_first_min(double left, double right) { return right < left ? right : left; }
 __device__ __forceinline__ double commit_first_max(double left, double right) { return left < right ? right : left; }
 
@@ -50,7 +53,12 @@ __device__ __forceinline__ void commit_reduce_minmax(double (&lo)[5], double (&h
     }
 }
 
-// The prefilter image of rows 0 .. T-2 of one lap, chunk by chunk: quantise_lap's arithmetic, every operation rounded on its own.
+// The prefilter image of rows 0 .. T-2 of one lap (the regression reads row t with row t + 1, so the last row is no candidate), per chunk of K1_CHUNK rows.  Feature k of
+// (vx, vy, wz, delta, a) is scaled by scaling[k]; lo_k / hi_k are its extremes over the chunk's finite values (0 / 0 when there is none); the chunk's one scale is
+// sc = 65535 / W, W the widest hi_k - lo_k, each range taken no smaller than 1e-9 max(|lo_k|, |hi_k|) (a constant feature) and W no smaller than 1e-300 (all zero).
+// A row's 16-bit word is (feature - lo_k) * sc clamped to [0, 65535] and truncated, 0 when not finite; words are packed (vx | vy << 16), (wz | delta << 16), (a), and
+// the chunk's parameters are (lo_0 .. lo_4, sc).  The regression kernel ranks rows by integer L1 distances on this image and re-evaluates the survivors in FP64, so the
+// image decides nothing by itself -- but it is part of what a context computes bit for bit, hence every operation is rounded on its own (no contraction).
 __device__ __forceinline__ void commit_quantise(const lmpc_commit_args &a, int car, int T, int slot, double (*red)[10]) {
 #pragma clang fp contract(off)
     const int nrows = T - 1, tid = threadIdx.x;
@@ -104,14 +112,15 @@ __device__ __forceinline__ void commit_quantise(const lmpc_commit_args &a, int c
             q[t] = w[0]; q[(size_t)a.ls + t] = w[1]; q[2 * (size_t)a.ls + t] = w[2];
         }
     }
-    // what quantise_lap uploads beside the rows in use: zeros behind row T-2 of the three planes and in the parameters of the chunks not used
+    // a lap's image is written whole: zeros behind row T-2 of the three planes and in the parameters of the chunks not used (a replaced lap leaves nothing behind)
     for (int e = tid; e < 3 * (a.ls - nrows); e += LMPC_COMMIT_NT) { const int pl = e / (a.ls - nrows), t = nrows + e % (a.ls - nrows); q[(size_t)pl * a.ls + t] = 0u; }
     const int used = (nrows + K1_CHUNK - 1) / K1_CHUNK;
     for (int e = used * 6 + tid; e < a.mq_chunks * 6; e += LMPC_COMMIT_NT) par[e] = 0.0;
 }
 
-// LMPC.computeCost as lmpc_ss_add_trajectory restates it: cost[T-1] = 0, backwards cost[r] = cost[r+1] + 1 where s[r] < trackLength, else 0 -- the distance from r
-// to the nearest row r' >= r that is the last one or has !(s < trackLength).  Small integers: exact in any order.  256 rows per pass, from the end of the lap.
+// LMPC.computeCost (PredictiveControllers.py:447-464): cost[T-1] = 0, backwards cost[r] = cost[r+1] + 1 where s[r] < trackLength, else 0 (a NaN s is not below) -- the
+// distance from r to the nearest row r' >= r that is the last one or has !(s < trackLength).  Small integers: exact in any order.  256 rows per pass, from the end of
+// the lap; *q0 = cost[0].
 __device__ __forceinline__ void commit_cost(const lmpc_commit_args &a, int car, int T, double *qcol, double *q0, int *nearw) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int carry = T - 1;                                                  // the nearest such row at or behind the end of the pass
@@ -152,23 +161,27 @@ __global__ void __launch_bounds__(LMPC_COMMIT_NT) lmpc_commit_laps_kernel(lmpc_c
     if (mb) commit_quantise(a, e.car, T, e.m_slot, red);
 }
 
-// One work-group per (car, safe-set lap): flag = every value of rows [0, n_rows) of the car is finite; only then the rows are appended at row0 -- s + trackLength,
-// Qfun counting down from qlast by REPEATED subtraction of 1.0 (row i: i + 1 subtractions, each rounded, as the host loop of lmpc_ss_extend_lap; a closed form
-// qlast - (i + 1) is another number when qlast is not an integer).  Thread k owns rows [k c, (k + 1) c), c = ceil(n_rows / 256): O(n_rows) subtractions per thread.
+// One work-group per (car, safe-set lap): rows [0, n_rows) of the car appended at row0 -- s + trackLength (:472), Qfun counting down from qlast by REPEATED subtraction
+// of 1.0 (:474 once per row; row i: i + 1 subtractions, each rounded -- a closed form qlast - (i + 1) is another number when qlast is not an integer).  Thread k owns
+// rows [k c, (k + 1) c), c = ceil(n_rows / 256): O(n_rows) subtractions per thread.
+// flag != NULL (a session's logs, which may hold a diverged car): flag[entry] = every value of the rows is finite, and only then they are appended.
+// flag == NULL (rows the host hands in): appended whatever they hold, as LMPC.addPoint does.
 __global__ void __launch_bounds__(LMPC_COMMIT_NT) lmpc_extend_laps_kernel(lmpc_commit_args a, int n_rows, const lmpc_extend_entry *__restrict__ table, const double *__restrict__ qlast,
                                                                           int *__restrict__ flag) {
 #pragma clang fp contract(off)
     const lmpc_extend_entry e = table[blockIdx.x];
     const int tid = threadIdx.x, ls = a.ls;
-    int ok = 1;
-    for (int i = tid; i < n_rows * 8; i += LMPC_COMMIT_NT) {
-        const int t = i >> 3, j = i & 7;
-        const double v = j < 6 ? a.logX[((size_t)t * a.B + e.car) * 6 + j] : a.logU[((size_t)t * a.B + e.car) * 2 + (j - 6)];
-        if (!__builtin_isfinite(v)) ok = 0;
+    if (flag) {                                                         // (uniform over the grid)
+        int ok = 1;
+        for (int i = tid; i < n_rows * 8; i += LMPC_COMMIT_NT) {
+            const int t = i >> 3, j = i & 7;
+            const double v = j < 6 ? a.logX[((size_t)t * a.B + e.car) * 6 + j] : a.logU[((size_t)t * a.B + e.car) * 2 + (j - 6)];
+            if (!__builtin_isfinite(v)) ok = 0;
+        }
+        ok = __syncthreads_and(ok);
+        if (tid == 0) flag[blockIdx.x] = ok ? 1 : 0;
+        if (!ok) return;
     }
-    ok = __syncthreads_and(ok);
-    if (tid == 0) flag[blockIdx.x] = ok ? 1 : 0;
-    if (!ok) return;
     double *base = a.sstore + (size_t)e.lap * LMPC_COLS * ls + e.row0;
     for (int i = tid; i < n_rows * 8; i += LMPC_COMMIT_NT) {
         const int j = i / n_rows, t = i - j * n_rows;                  // column-major: neighbouring lanes, neighbouring rows

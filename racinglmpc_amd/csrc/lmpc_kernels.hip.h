@@ -371,7 +371,7 @@ __device__ __forceinline__ void k1_scan_lap(const lmpc_dev_params &p, const k1_s
     const int nrows = k1_lap_len<TAB>(p, lt, c) - 1;
     for (int t0 = 0; t0 < nrows; t0 += RPL * WAVE) {
         // Prefilter image of this lane's rows: the scaled features in 16-bit fixed point, packed (vx, vy | wz, delta | a, flag),
-        // quantised by the host when the lap was stored (lmpc_capi.hip: quantise_lap), per 1024-row chunk over the chunk's own
+        // quantised on the device when the lap was stored (lmpc_commit.hip.h: commit_quantise), per 1024-row chunk over the chunk's own
         // [min, max] with ONE scale for the five features (the L1 norm weighs them equally).  Three v_sad_u16 per row give the
         // integer L1 distance; every decision is re-made in FP64 below.  A query outside [min, max] is clamped: that shifts all
         // of a feature's |differences| by the same amount, so the order of the rows is untouched.  Rows beyond the lap carry

@@ -44,7 +44,7 @@ def slack_case(E0=40, eps=1e-3, T=400, seed=11):
 
 
 def emulate_prefilter(case, maxp=7):
-    """Host emulation of quantise_lap (lmpc_capi.hip) + step A of lmpc_regress_kernel for a single-chunk lap with scaling = 1:
+    """Host emulation of the prefilter image (csrc/lmpc_commit.hip.h: commit_quantise; tests/store_ref.py restates it in full) + step A of lmpc_regress_kernel for a single-chunk lap with scaling = 1:
     returns the integer distances e, the threshold T, and the exact top-maxp rows (stable argsort of the FP64 distances)."""
     x, u = case["x"], case["u"]
     nrows = x.shape[0] - 1

@@ -3,11 +3,13 @@
 The reference of every case is the host path on a second context: rollout_fetch of the same session's logs, then ss_add_trajectory / model_add_trajectory /
 ss_extend_lap of those rows.  Everything is compared bit for bit (as int64 words, so that NaN rows and the sign of a zero count): the rows of both stores, Qfun,
 LapTime, the regression store's sorted order, the prefilter image (lmpc_debug_model_image), and what a regression and a safe-set selection compute from them.
+Both contexts' laps go through the same store-writing kernels (the second one's from staged host rows, one lap per launch), so every snapshot of the stores is
+also compared, bit for bit, with tests/store_ref.py: the same edits restated on the host from the fetched rows.
 N = 12; what needs no device is in tests/test_device_commit_host.py."""
 import numpy as np
 import pytest
 
-from tests import common
+from tests import common, store_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -88,10 +90,13 @@ def test_commit_equals_the_host_path_at_every_boundary(built, g):
         A.rollout_end()
         assert first == (0, 0) and A.ss_num_laps() == 6 and A.model_num_laps() == 6               # no entry skipped
         assert (done[:3] >= 0).all() and (done[:3] < 1024).all(), done                             # (rows past the first crossing are part of the long laps)
+        ref = store_ref.RefStores.like(cfg)
         for c, T in zip(cars, rows):
             x, u = X[:T, c].copy(), U[:T, c].copy()
-            Bc.ss_add_trajectory(x, u); Bc.model_add_trajectory(x, u)
+            for dst in (Bc, ref):
+                dst.ss_add_trajectory(x, u); dst.model_add_trajectory(x, u)
         sa, sb = _stores(A), _stores(Bc)
+        _same_stores(sa, ref.snapshot(), "commit against the restatement"); _same_stores(sb, ref.snapshot(), "host laps against the restatement")
         assert [s[3] for s in sa["ss"]] == rows and [i[0] for i in sa["info"]] == rows
         assert [i[1] for i in sa["info"]] == [3, 4, 5, 0, 1, 2]                                    # ascending rows, the two 300s in listed order
         assert [im[2] for im in sa["image"]] == [1, 1, 2, 1, 1, 1]                                 # 1023 and 1024 image rows: one chunk; 1025: two
@@ -122,8 +127,11 @@ def test_rows_none_refusals_and_nothing_half_done(built, g):
     cfg, _ = common.lmpc_config(g, N, max_batch=4, max_laps=4, max_lap_len=512)
     with _capi.Context(cfg) as A:
         xs, us = np.array(g["xPID"])[:100], np.array(g["uPID"])[:100]
-        A.ss_add_trajectory(xs, us); A.model_add_trajectory(xs, us)
+        ref = store_ref.RefStores.like(cfg)
+        for dst in (A, ref):
+            dst.ss_add_trajectory(xs, us); dst.model_add_trajectory(xs, us)
         before = _stores(A)
+        _same_stores(before, ref.snapshot(), "one lap from the host against the restatement")
         t = _pid(A, [0.9, 0.8, 0.45], 400, True)
         X, U, _, done, st, _, _ = A.rollout_fetch(0, t)
         assert t == 400 and done[0] >= 0 and done[1] >= 0 and done[2] < 0 and done[0] != done[1], done
@@ -148,6 +156,9 @@ def test_rows_none_refusals_and_nothing_half_done(built, g):
             assert A.ss_lap_time(1 + k) == done[b] and A.model_lap_info(1 + k)[0] == done[b]
         x0, u0, q0 = A.store_read_lap(1, 0)
         _same(x0, before["ss"][0][0], "the lap stored before")
+        for b in (0, 1):
+            ref.ss_add_trajectory(X[:done[b], b], U[:done[b], b]); ref.model_add_trajectory(X[:done[b], b], U[:done[b], b])
+        _same_stores(_stores(A), ref.snapshot(), "rows=None against the restatement")
 
 
 def _seeded(ctx, g):
@@ -165,9 +176,11 @@ def test_extension_equals_the_host_path(built, g):
     cars, laps, n = [0, 1, 2], [2, 0, 1], 40
     vt = [0.7, 0.8, 0.9]
     with _capi.Context(cfg) as A, _capi.Context(cfg) as Bc:
-        for c in (A, Bc):
+        ref = store_ref.RefStores.like(cfg)
+        for c in (A, Bc, ref):
             _seeded(c, g)
         before = _stores(A)
+        _same_stores(before, ref.snapshot(), "seed laps against the restatement")
         t = _pid(A, vt, 60, False)
         _refused(E_ARG, lambda: A.rollout_extend_laps([0, 1, 2], [2, 0, 2], n))                    # the same lap twice
         _refused(E_ARG, lambda: A.rollout_extend_laps(cars, laps, t + 1))
@@ -181,18 +194,20 @@ def test_extension_equals_the_host_path(built, g):
         X, U = Bc.rollout_fetch(0, t)[:2]
         Bc.rollout_end()
         for c, l in zip(cars, laps):
-            Bc.ss_extend_lap(l, X[:n, c], U[:n, c])
+            Bc.ss_extend_lap(l, X[:n, c], U[:n, c]); ref.ss_extend_lap(l, X[:n, c], U[:n, c])
         assert [A.ss_lap_rows(l) for l in range(3)] == [140, 150, 160] == [Bc.ss_lap_rows(l) for l in range(3)]
         _same_stores(_stores(A), _stores(Bc), "extension")
+        _same_stores(_stores(A), ref.snapshot(), "extension against the restatement")
         q = A.store_read_lap(1, 2)[2]
         want = 1.0 / 3.0
         for i in range(n):
             want -= 1.0
             assert q[120 + i] == want, i
         assert any(q[120 + i] != 1.0 / 3.0 - (i + 1) for i in range(n))                            # (the closed form is another number)
-        for c in (A, Bc):                                                                          # one more row on the last lap: it continues from the Qfun value the call left on the host side
+        for c in (A, Bc, ref):                                                                     # one more row on the last lap: it continues from the Qfun value the call left on the host side
             c.ss_add_point(X[0, 0], U[0, 0])
         _same_stores(_stores(A), _stores(Bc), "addPoint after the extension")
+        _same_stores(_stores(A), ref.snapshot(), "addPoint after the extension against the restatement")
 
 
 def test_extension_skips_a_car_with_non_finite_rows(built, g):
@@ -203,7 +218,8 @@ def test_extension_skips_a_car_with_non_finite_rows(built, g):
     vt = [0.7, 0.8, 0.9]
     x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (3, 1)); x0[1, 0] = np.nan
     with _capi.Context(cfg) as A, _capi.Context(cfg) as Bc:
-        for c in (A, Bc):
+        ref = store_ref.RefStores.like(cfg)
+        for c in (A, Bc, ref):
             _seeded(c, g)
         t = _pid(A, vt, 60, False, x0=x0)
         ext = A.rollout_extend_laps(cars, laps, n)
@@ -212,9 +228,10 @@ def test_extension_skips_a_car_with_non_finite_rows(built, g):
         assert not np.isfinite(X[:n, 1]).all() and np.isfinite(X[:n, [0, 2]]).all() and np.isfinite(U[:n, [0, 2]]).all()
         assert ext.tolist() == [True, False, True]
         for c, l in ((0, 2), (2, 1)):
-            Bc.ss_extend_lap(l, X[:n, c], U[:n, c])
+            Bc.ss_extend_lap(l, X[:n, c], U[:n, c]); ref.ss_extend_lap(l, X[:n, c], U[:n, c])
         assert [A.ss_lap_rows(l) for l in range(3)] == [100, 150, 160]
         _same_stores(_stores(A), _stores(Bc), "extension with a skipped car")
+        _same_stores(_stores(A), ref.snapshot(), "extension with a skipped car against the restatement")
 
 
 def test_per_car_lmpc_with_device_commit_equals_the_host_loop(built, g):
@@ -228,7 +245,13 @@ def test_per_car_lmpc_with_device_commit_equals_the_host_loop(built, g):
     vt = np.array([0.75, 0.8, 0.85])
     runs = []
     ctxs = [_capi.Context(cfg), _capi.Context(cfg)]
+    ref = store_ref.RefStores.like(cfg)
     try:
+        for name in ("ss_add_trajectory", "model_add_trajectory", "ss_extend_lap"):                # what the host loop hands to its context goes to the restatement as well
+            def both(*args, _real=getattr(ctxs[0], name), _ref=getattr(ref, name)):
+                _ref(*args)
+                return _real(*args)
+            setattr(ctxs[0], name, both)
         for ctx, dev in zip(ctxs, (False, True)):
             ro = rollout.BatchedRollouts(ctx, track, seed=SEED, device_noise=True)
             ro.noise_shard = (0, 3, 3)
@@ -253,6 +276,7 @@ def test_per_car_lmpc_with_device_commit_equals_the_host_loop(built, g):
         sh, sd = _stores(ctxs[0]), _stores(ctxs[1])
         assert len(sh["ss"]) == 9 and any(s[4] > s[3] for s in sh["ss"])                            # 3 seeds + 2 x 3 laps; generation 2 has extended laps
         _same_stores(sd, sh, "after generation 2")
+        _same_stores(sh, ref.snapshot(), "after generation 2 against the restatement")
     finally:
         for c in ctxs:
             c.close()

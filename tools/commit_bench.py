@@ -1,5 +1,5 @@
-"""What happens between two laps of rollout.PerCarLMPC, timed both ways on the GPU: the host path (the whole session log downloaded, every car's lap uploaded again
-column by column, one extension call per car) against the device path (Context.rollout_extend_laps / rollout_commit_laps: the laps never leave the device).
+"""What happens between two laps of rollout.PerCarLMPC, timed both ways on the GPU: the host path (the whole session log downloaded, every car's lap handed in again
+through the host entry points, one add and one extension call per car per store) against the device path (Context.rollout_extend_laps / rollout_commit_laps: the laps never leave the device).
 
     python tools/commit_bench.py [--batches 256 1024] [--repeats 5] [--horizon 12] [--out profiles/device_commit.json]
 
