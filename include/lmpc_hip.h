@@ -174,6 +174,34 @@ int lmpc_ss_set_lap_table(lmpc_ctx *, int n, const int *laps /* n x numSS_it saf
 int lmpc_ss_get_lap_table(lmpc_ctx *, int *n, int *laps /* capacity x numSS_it, or NULL */, int *last /* capacity, or NULL */, int capacity);
         /* the rows in force as lmpc_ss_set_lap_table received them (n = 0: the shared selection); laps / last receive min(n, capacity) rows / entries, every entry of
          * last LMPC_SS_LAST_SHARED where `set` was given last = NULL */
+
+/* Per-problem controller tuning: the cost weights and bounds of each problem of a batch from its own row -- every controller object of the reference owns its MPCParams
+ * (PredictiveControllers.py:24-51, initControllerParameters.py).  A row is LMPC_TUNING_NPAR doubles in this order: Q[36], R[4], Qf[36], dR[2], Qslack[2],
+ * QtermSlack[6] (the diagonal), xRef[6], bx[2], bu[4] -- the values of lmpc_config, not the doubled ones of the device block.  Fx and Fu, the shape of the
+ * constraint rows, stay context-wide. */
+#define LMPC_TUNING_NPAR 98
+int lmpc_tuning_from_config(const lmpc_config *, double *row /*98*/);
+        /* the row a context created from that config uses by default (MPCParams, PredictiveControllers.py:24-51).  Needs no device */
+int lmpc_tuning_set(lmpc_ctx *, int n, const double *rows /*n x 98, or NULL with n = 0*/);
+        /* The tuning (MPCParams, PredictiveControllers.py:24-51) of every later solve on this context.  n = 0: back to the config's weights, bit for bit (the kernels
+         * that read the parameter block).  n = 1: that row serves every problem.  n > 1: problem b of a call uses row b, and a launch whose batch B != n returns
+         * LMPC_E_ARG and says so in lmpc_last_error (the context stays usable) -- the lap tables' rule.  LMPC_E_ARG, with the rows in force kept, for a non-finite
+         * entry, Q, R or Qf not exactly symmetric, a negative dR or Qslack entry, a QtermSlack entry <= 0 on a context with numSS_it > 0, n < 0, n > max_batch, NULL
+         * rows with n > 0.  (n <= max_batch also bounds what a rollout session can use: lmpc_rollout_begin accepts more cars than max_batch, but such a session
+         * cannot have one row per car -- `set` refuses the rows, and rows of another count refuse every step; it runs on n = 0 or n = 1.  Create the context with
+         * max_batch >= the cars of a per-car tuned session.)  A row with bu[j] <= 0 is NOT an argument error: the kernels' own rule gives that problem LMPC_ST_NOT_INTERIOR and leaves its neighbours
+         * alone.  On a context with slacks = 0 the rows' Qslack is ignored (the internal weight 1e12 and no linear term, as for the config).  The rows apply to
+         * lmpc_qp_solve_batch, lmpc_step_batch, lmpc_step_batch_dev, every step of lmpc_rollout_begin and lmpc_rollout_begin_mpc sessions (LTI and LTV form) and
+         * lmpc_assemble_batch (the explicit matrices of problem b from row b); lmpc_select_batch and the regression read no weights.  The rows are LIVE, as the
+         * safe-set table is: a `set` between two lmpc_rollout_run calls reaches the next step, and B is checked against n before the first launch of a step, so a
+         * refused step leaves nothing half done.  The device image (doubled values in the layout of the kernels' parameter block in LDS, ready for their staging copy)
+         * is uploaded by `set`, not per launch; launches still waiting for their deferred retry pass are resolved and the stream is drained before it is overwritten,
+         * so a retry pass reads the rows of its own launch.  All solve kernels (one, two, four waves per QP, the runtime-(N, S) kernel, their retry passes) serve rows
+         * -- the fixed-(N, S) ones in the per-problem-rows instantiations that also serve the safe-set table, so that a launch without rows or table runs the kernels
+         * it ran before.  While rows are in force NEITHER the fused one-wave step (LMPC_FUSE=1) NOR the condensed kernel (LMPC_CD=1, which takes Q pre-digested by
+         * the host) is taken: the two-kernel step / the ordinary kernels run */
+int lmpc_tuning_get(lmpc_ctx *, int *n, double *rows /*capacity x 98, or NULL*/, int capacity);
+        /* the rows in force as lmpc_tuning_set received them (n = 0: the config's weights; MPCParams, PredictiveControllers.py:24-51); rows receives min(n, capacity) rows */
 int lmpc_ss_num_laps(lmpc_ctx *, int *n);
 int lmpc_ss_get_qfun(lmpc_ctx *, int lap, double *qfun /*T*/, int *T);
 int lmpc_store_read_lap(lmpc_ctx *, int store /*0: regression store (sorted position), 1: safe set*/, int lap, double *x /*T x 6*/, double *u /*T x 2*/, double *qfun /*T, safe set only*/, int *T);

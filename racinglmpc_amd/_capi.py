@@ -83,7 +83,7 @@ EXPORTS = [
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
     "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
-    "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_debug_model_image",
+    "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_debug_model_image", "lmpc_tuning_from_config", "lmpc_tuning_set", "lmpc_tuning_get",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -135,6 +135,11 @@ def load():
         lib.lmpc_rollout_extend_laps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         lib.lmpc_debug_model_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         lib.lmpc_rollout_commit_laps.restype = lib.lmpc_rollout_extend_laps.restype = lib.lmpc_debug_model_image.restype = C.c_int
+        # (per-problem controller tuning: rows of TUNING_NPAR doubles)
+        lib.lmpc_tuning_from_config.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lmpc_tuning_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.lmpc_tuning_get.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]
+        lib.lmpc_tuning_from_config.restype = lib.lmpc_tuning_set.restype = lib.lmpc_tuning_get.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
@@ -268,6 +273,73 @@ def plant_params(B, m=1.98, lf=0.125, lr=0.125, Iz=0.024, mu_f=0.8, mu_r=0.8, Cf
     Dr = col("mu_r", mu_r) * m * 9.81 / 2.0 if Dr is None else col("Dr", Dr)
     cols = [m, col("lf", lf), col("lr", lr), col("Iz", Iz), Df, col("Cf", Cf), col("Bf", Bf), Dr, col("Cr", Cr), col("Br", Br)]
     return check_plant_params(np.stack(cols, axis=1))
+
+
+# One row of controller tuning (lmpc_tuning_set): name -> slice of the row, in the order of include/lmpc_hip.h.  The values of LmpcConfig; QtermSlack is the diagonal.
+TUNING_NPAR = 98
+TUNING_FIELDS = {"Q": slice(0, 36), "R": slice(36, 40), "Qf": slice(40, 76), "dR": slice(76, 78), "Qslack": slice(78, 80), "QtermSlack": slice(80, 86),
+                 "xRef": slice(86, 92), "bx": slice(92, 94), "bu": slice(94, 98)}
+_TUNING_SHAPES = {"Q": (6, 6), "R": (2, 2), "Qf": (6, 6), "dR": (2,), "Qslack": (2,), "QtermSlack": (6,), "xRef": (6,), "bx": (2,), "bu": (4,)}
+
+
+def check_tuning(rows, numSS_it=0):
+    """(n, 98) float64 rows, or None for "no rows" (None or empty); ValueError for what lmpc_tuning_set refuses in a row: a wrong shape, a non-finite entry, Q, R or
+    Qf not exactly symmetric, a negative dR or Qslack entry, and (numSS_it > 0) a QtermSlack entry <= 0.  bu <= 0 is no error here either (LMPC_ST_NOT_INTERIOR)."""
+    if rows is None or np.size(rows) == 0:
+        return None
+    r = np.array(rows, dtype=np.float64, ndmin=2)
+    if r.ndim != 2 or r.shape[1] != TUNING_NPAR:
+        raise ValueError("tuning: rows of %d values expected, got shape %s" % (TUNING_NPAR, r.shape))
+    if not np.all(np.isfinite(r)):
+        raise ValueError("tuning: non-finite entry in row(s) %s" % np.where(~np.isfinite(r).all(1))[0].tolist())
+    for name in ("Q", "R", "Qf"):
+        m = r[:, TUNING_FIELDS[name]].reshape((-1,) + _TUNING_SHAPES[name])
+        if not np.array_equal(m, m.transpose(0, 2, 1)):
+            raise ValueError("tuning: %s must be exactly symmetric" % name)
+    for name in ("dR", "Qslack"):
+        if (r[:, TUNING_FIELDS[name]] < 0).any():
+            raise ValueError("tuning: negative %s entry" % name)
+    if int(numSS_it) > 0 and not (r[:, TUNING_FIELDS["QtermSlack"]] > 0).all():
+        raise ValueError("tuning: QtermSlack entries must be positive on a context with a terminal set")
+    return np.ascontiguousarray(r)
+
+
+def tuning_rows(cfg, B, **fields):
+    """(B, 98) rows of controller tuning for Context.tuning_set, columns TUNING_FIELDS: the weights and bounds of `cfg` (an LmpcConfig) with the named fields replaced.
+    Each keyword -- Q, R, Qf, dR, Qslack, QtermSlack (or QterminalSlack), xRef, bx, bu -- is a scalar, an array for every car (the field's own shape: Q (6, 6),
+    dR (2,), ...), or an array with a leading B axis, one entry per car.  The terminal-slack weight has two keywords, so that a (6, 6) array is never ambiguous at
+    B = 6: QtermSlack takes DIAGONALS -- (6,) for every car or (B, 6), one per car; QterminalSlack takes full MATRICES, the reference's name and form -- (6, 6) or
+    (B, 6, 6), which must be diagonal.
+    Needs neither the library nor a device.  Raises ValueError on what lmpc_tuning_set would refuse."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("tuning_rows: B must be at least 1")
+    row = np.zeros(TUNING_NPAR)
+    for name, sl in TUNING_FIELDS.items():
+        v = np.array(getattr(cfg, name), dtype=np.float64)
+        row[sl] = v.reshape(6, 6).diagonal() if name == "QtermSlack" else v
+    rows = np.tile(row, (B, 1))
+    for key, v in fields.items():
+        name = "QtermSlack" if key == "QterminalSlack" else key
+        if name not in TUNING_FIELDS:
+            raise ValueError("tuning_rows: unknown field %r (one of %s)" % (key, ", ".join(TUNING_FIELDS)))
+        shp = _TUNING_SHAPES[name]
+        v = np.asarray(v, dtype=np.float64)
+        if key == "QterminalSlack":
+            if v.ndim not in (2, 3) or v.shape[-2:] != (6, 6):
+                raise ValueError("tuning_rows: QterminalSlack must be a (6, 6) or a (%d, 6, 6) array of matrices, got shape %s (diagonals go by the name QtermSlack)" % (B, v.shape))
+            off = v - v * np.eye(6)
+            if np.any(off != 0):
+                raise ValueError("tuning_rows: QterminalSlack must be diagonal")
+            v = np.diagonal(v, axis1=-2, axis2=-1)
+        if v.ndim == 0:
+            v = np.broadcast_to(v, shp)
+        if v.shape == shp:
+            v = np.broadcast_to(v, (B,) + shp)
+        elif v.shape != (B,) + shp:
+            raise ValueError("tuning_rows: %s must be a scalar, a %s array or a (%d,) + %s array, got shape %s" % (key, shp, B, shp, v.shape))
+        rows[:, TUNING_FIELDS[name]] = v.reshape(B, -1)
+    return check_tuning(rows, cfg.numSS_it)
 
 
 def _chk(rc):
@@ -609,6 +681,26 @@ class Context:
         par = _f64(par).reshape(-1, PLANT_NPAR)
         _chk(self.lib.lmpc_plant_set_params(self._h, C.c_int(par.shape[0]), _d(par)))
 
+    def tuning_set(self, rows):
+        """Per-problem controller tuning (lmpc_tuning_set): None or no rows -- the config's weights and bounds; one row of TUNING_FIELDS -- every problem; (n, 98) --
+        problem b uses row b, and a launch of another batch size is refused (LmpcError, the context stays usable).  The rows are live: a call between two rollout_run
+        calls reaches the next step.  They apply to qp_solve_batch, step_batch, step_batch_dev, every step of a rollout session and assemble_batch.  tuning_rows()
+        builds the rows."""
+        rows = check_tuning(rows, int(self.cfg.numSS_it))
+        if rows is None:
+            _chk(self.lib.lmpc_tuning_set(self._h, 0, None))
+            return
+        _chk(self.lib.lmpc_tuning_set(self._h, rows.shape[0], rows.ctypes.data))
+
+    def tuning(self):
+        """The rows in force, (n, 98), as tuning_set received them; n = 0: the config's weights (lmpc_tuning_get)."""
+        n = C.c_int()
+        _chk(self.lib.lmpc_tuning_get(self._h, C.byref(n), None, 0))
+        rows = np.zeros((n.value, TUNING_NPAR))
+        if n.value:
+            _chk(self.lib.lmpc_tuning_get(self._h, C.byref(n), rows.ctypes.data, rows.shape[0]))
+        return rows
+
     def plant_params(self):
         """The rows in force, (n, 10); n = 0: the reference's vehicle (lmpc_plant_get_params)."""
         n = C.c_int()
@@ -730,7 +822,8 @@ class Context:
         return x, u, q
 
     def save_stores(self, path):
-        """Both lap stores (and the explicit safe-set selection, if one is set by the caller: not stored -- it is per-step state of the controller) as one .npz."""
+        """Both lap stores (and the explicit safe-set selection, if one is set by the caller: not stored -- it is per-step state of the controller) as one .npz.
+        Tuning rows (tuning_set) are not saved either: they are controller parameters, not store content -- set them again on the restored context."""
         out = {}
         nm = C.c_int(); _chk(self.lib.lmpc_model_num_laps(self._h, C.byref(nm)))
         for i in range(nm.value):
@@ -1027,7 +1120,7 @@ class ContextPool:
     def __getattr__(self, name):                       # lap-store edits (model_add_trajectory, ss_add_trajectory, ss_add_point, ss_set_selected, ...): the same call on every member
         if name in ("members", "_next"):               # (not set yet: a failed __init__ must not recurse through this hook)
             raise AttributeError(name)
-        if name == "plant_set_params" or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num", "model_lap"))):   # (the vehicle too: the same on every member; model_set_lap_table and ss_set_lap_table go with the store edits, the queries model_lap_table / model_lap_info / ss_lap_table to the first)
+        if name in ("plant_set_params", "tuning_set") or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num", "model_lap"))):   # (the vehicle too: the same on every member; model_set_lap_table and ss_set_lap_table go with the store edits, the queries model_lap_table / model_lap_info / ss_lap_table to the first)
             def forward(*a, **kw):
                 out = None
                 for m in self.members:

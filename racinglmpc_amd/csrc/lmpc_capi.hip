@@ -135,6 +135,10 @@ struct lmpc_ctx {
     // on the device as the solve kernels read them (LMPC_SSTAB_ENTRY ints per entry: slot, current rows, latest flag, pad; each row in ascending LapTime, ties by
     // index).  The image names rows of laps, so every edit of the safe set marks it dirty and the next launch that reads it uploads it again (ss_table_for)
     std::vector<int> sst_idx, sst_last; int sst_n; bool sst_has_last, sst_dirty; int *d_sst; size_t d_sst_cap;
+    // lmpc_tuning_set: tune_n rows of LMPC_TUNING_NPAR doubles as the caller gave them (0 rows: the config's weights serve every problem).  d_tune: the device image the
+    // per-problem-rows instantiations of the solve kernels and the assemble kernel stage from -- PAR_TOT doubles per row in the PAR_* layout, doubled weights, Fx / Fu of
+    // the config; with no rows in force it holds the config's own row (what a launch with a safe-set table alone reads).  Uploaded by `set`, never per launch
+    std::vector<double> tune_rows; int tune_n; double *d_tune; size_t d_tune_cap;
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
 };
@@ -211,7 +215,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 107; }
+int lmpc_version(void) { return 108; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -261,7 +265,32 @@ static void fill_params(lmpc_ctx *c) {
     p.mquant = c->mquant; p.mqpar = c->mqpar; p.mq_chunks = c->mq_chunks;
 }
 
+
+// ---- controller tuning rows (lmpc_tuning_set): Q[36] R[4] Qf[36] dR[2] Qslack[2] QtermSlack[6] xRef[6] bx[2] bu[4], the values of lmpc_config
+enum { TN_Q = 0, TN_R = 36, TN_QF = 40, TN_DR = 76, TN_QS = 78, TN_T = 80, TN_XREF = 86, TN_BX = 92, TN_BU = 94 };
+static_assert(TN_BU + 4 == LMPC_TUNING_NPAR, "layout of a tuning row");
+int lmpc_tuning_from_config(const lmpc_config *f, double *row) {
+    if (!f || !row) return set_err(LMPC_E_ARG, "lmpc_tuning_from_config", "NULL argument");
+    memcpy(row + TN_Q, f->Q, sizeof(f->Q)); memcpy(row + TN_R, f->R, sizeof(f->R)); memcpy(row + TN_QF, f->Qf, sizeof(f->Qf));
+    memcpy(row + TN_DR, f->dR, sizeof(f->dR)); memcpy(row + TN_QS, f->Qslack, sizeof(f->Qslack));
+    for (int i = 0; i < 6; i++) row[TN_T + i] = f->QtermSlack[i * 7];
+    memcpy(row + TN_XREF, f->xRef, sizeof(f->xRef)); memcpy(row + TN_BX, f->bx, sizeof(f->bx)); memcpy(row + TN_BU, f->bu, sizeof(f->bu));
+    return LMPC_OK;
+}
+
 }  // extern "C" (helpers)
+
+// one row as the kernels stage it: the PAR_* layout of the parameter block in LDS, the values fill_params derives from a config holding this row
+static void tuning_image_row(const lmpc_config &f, const double *row, double *img) {
+    memcpy(img + PAR_FX, f.Fx, sizeof(f.Fx)); memcpy(img + PAR_FU, f.Fu, sizeof(f.Fu));
+    memcpy(img + PAR_BX, row + TN_BX, 2 * sizeof(double)); memcpy(img + PAR_BU, row + TN_BU, 4 * sizeof(double));
+    for (int i = 0; i < 36; i++) { img[PAR_Q2 + i] = 2 * row[TN_Q + i]; img[PAR_QF2 + i] = 2 * row[TN_QF + i]; }
+    for (int i = 0; i < 4; i++) img[PAR_R2 + i] = 2 * row[TN_R + i];
+    img[PAR_DR2] = 2 * row[TN_DR]; img[PAR_DR2 + 1] = 2 * row[TN_DR + 1];
+    for (int i = 0; i < 6; i++) { img[PAR_T2 + i] = 2 * row[TN_T + i]; img[PAR_XREF + i] = row[TN_XREF + i]; }
+    img[PAR_AS] = f.slacks ? 2 * row[TN_QS] : 2.0e12; img[PAR_CS] = f.slacks ? row[TN_QS + 1] : 0.0;      // (hard lane rows: the rows' Qslack is ignored, see fill_params)
+}
+static int tuning_upload(lmpc_ctx *c, int n, const double *rows);
 
 #define LMPC_RETRY_RING 64
 #define LMPC_SLAB_COPY_MAX ((size_t)256 * 1024)     // contexts whose output slab has at most this many bytes (batch 1 .. ~16) own host-mapped mirrors of their slabs
@@ -395,6 +424,8 @@ int lmpc_create_ex(const lmpc_config *cfg, unsigned flags, lmpc_ctx **out) {
     int rc = create_body(c);
     if (rc != LMPC_OK) { const std::string keep = g_err; lmpc_destroy(c); g_err = keep; return rc; }
     fill_params(c);
+    rc = tuning_upload(c, 0, nullptr);                 // (the config's own row: what a launch with a safe-set table and no tuning rows stages from)
+    if (rc != LMPC_OK) { const std::string keep = g_err; lmpc_destroy(c); g_err = keep; return rc; }
     *out = c;
     return LMPC_OK;
 }
@@ -419,7 +450,7 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt, c->d_sst};      // (the work buffers are ranges of the two slabs)
+    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt, c->d_sst, c->d_tune};      // (the work buffers are ranges of the two slabs)
     check_slab_gaps(c);
     for (void *q : ptrs) if (q) (void)g_free(q);
     if (c->h_retry) (void)hipHostFree(c->h_retry);
@@ -996,9 +1027,40 @@ static int ss_table_for(lmpc_ctx *c, int B, lmpc_solve_io *io) {
     io->ssTab = c->d_sst; io->ssTabStride = c->sst_n == 1 ? 0 : L * LMPC_SSTAB_ENTRY;
     return LMPC_OK;
 }
+// Per-problem controller tuning (lmpc_tuning_set) for a launch of B problems that solves: B against the rows, io.tune / io.tuneStride set.  No rows in force, or a
+// launch that only selects (the selection reads no weights): io stays as it is.  Called where ss_table_for is, before the first launch of a step.
+static int tuning_for(lmpc_ctx *c, int B, lmpc_solve_io *io) {
+    if (c->tune_n == 0 || !(io->mode & 2)) return LMPC_OK;
+    if (c->tune_n > 1 && B != c->tune_n) {
+        char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_tuning_set holds %d rows", B, c->tune_n);
+        return set_err(LMPC_E_ARG, "tuning rows", msg);
+    }
+    io->tune = c->d_tune; io->tuneStride = c->tune_n == 1 ? 0 : PAR_TOT;
+    return LMPC_OK;
+}
+// The device image of n rows (n = 0: the config's own row).  Launches still pending their retry pass read the image of THEIR launch: they are resolved, and the stream
+// is drained, before it is overwritten (as ss_table_for does for the safe-set table).
+static int tuning_upload(lmpc_ctx *c, int n, const double *rows) {
+    double own[LMPC_TUNING_NPAR];
+    if (n == 0) { lmpc_tuning_from_config(&c->cfg, own); rows = own; }
+    const int nr = n == 0 ? 1 : n;
+    std::vector<double> img((size_t)nr * PAR_TOT);
+    for (int r = 0; r < nr; r++) tuning_image_row(c->cfg, rows + (size_t)r * LMPC_TUNING_NPAR, &img[(size_t)r * PAR_TOT]);
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    // (a larger image goes into a new allocation that replaces the old one only once it is filled: a HIP failure on the way leaves the image in force as it was)
+    const bool grow = img.size() > c->d_tune_cap;
+    double *buf = c->d_tune;
+    if (grow) HIPCHK(g_malloc(&buf, img.size() * sizeof(double)));
+    const hipError_t e = hipMemcpy(buf, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { if (grow) (void)g_free(buf); return set_err(LMPC_E_HIP, "hipMemcpy (tuning image)", hipGetErrorString(e)); }
+    if (grow) { if (c->d_tune) (void)g_free(c->d_tune); c->d_tune = buf; c->d_tune_cap = img.size(); }
+    return LMPC_OK;
+}
 static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false) {
     lmpc_solve_io io = io_in;
     if (!io.ssTab) { const int rc = ss_table_for(c, B, &io); if (rc) return rc; }
+    if (!io.tune) { const int rc = tuning_for(c, B, &io); if (rc) return rc; }
+    if (io.ssTab && !io.tune) { io.tune = c->d_tune; io.tuneStride = 0; }      // (a table alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
     // [A_k | B_k] from global memory only when the batch does not fit the CUs with it in LDS (N = 40: more than two QPs per CU); a batch that
     // fits runs 3 % faster from LDS (measured at N = 40, batch 512: 0.997 vs 1.030 ms)
     io.abPack = nullptr;
@@ -1031,8 +1093,8 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
         rc = nw == 4 ? c->var.launch_mw4(c->stream, c->dp, B, io) : nw == 2 ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
     } else
 #endif
-    // (a safe-set lap table: the condensed kernel has no per-problem lookup and is not taken -- the kernels below have it)
-    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.ssTab) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
+    // (a safe-set lap table, tuning rows: the condensed kernel has no per-problem lookup -- it takes Q pre-digested by the host, cd_hasq -- and is not taken: the kernels below serve them)
+    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
        : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, B, io)        // fused step: the one-wave kernel runs the regression itself
        : (B <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, B, io)
        : (lmpc_solver_waves(c, B) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
@@ -1203,7 +1265,8 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows: refused before anything is queued)
     // (a lap table in force: the fused form reads the laps of the parameter block -- it lives in the variant libraries -- so the two-kernel step runs)
     // (likewise a safe-set lap table, lmpc_ss_set_lap_table: the fused form's LDS layout has no room behind it for the selected laps)
-    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0 && !(term && c->sst_n);
+    // (likewise tuning rows, lmpc_tuning_set: the fused form has no per-problem-rows instantiation)
+    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0 && !(term && c->sst_n) && c->tune_n == 0;
     double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
     // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
     // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
@@ -1211,6 +1274,7 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     if (dA == c->w.A || dB == c->w.Bm || dC == c->w.C) for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
     lmpc_solve_io io = solve_io((fused ? 4 : 0) | (term ? 3 : 2), a);
     RCCHK(ss_table_for(c, B, &io));                       // (B against the safe-set lap table's rows: refused before the regression is queued)
+    RCCHK(tuning_for(c, B, &io));                         // (and against the tuning rows)
     io.A = dA; io.Bm = dB; io.C = dC;
     // (io.rstatus / the fused regression: a singular regression or an off-track linearisation point marks status[b]; the reference raises there)
     if (fused) { io.xLin = a.xLin; io.uLin = a.uLin; io.Aout = a.A; io.Bout = a.Bm; io.Cout = a.C; RCCHK(refresh_params(c, true, false)); }
@@ -1284,15 +1348,43 @@ int lmpc_assemble_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     ARGCHK(c && A && Bm && C && x0 && uOld && Pdense && q && Adense && l && u && B >= 1 && B <= c->cfg.max_batch);
     int nz, mi, me; lmpc_qp_dims(c, &nz, &mi, &me); const int mm = mi + me;
     if (c->dims.S > 0) ARGCHK(ssSel && qSel);
+    if (c->tune_n > 1 && B != c->tune_n) { char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_tuning_set holds %d rows", B, c->tune_n); return set_err(LMPC_E_ARG, "tuning rows", msg); }
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
     call_temps tmp; double *dP, *dq, *dA, *dl, *du;
     HIPCHK(tmp.alloc(&dP, sizeof(double) * (size_t)B * nz * nz)); HIPCHK(tmp.alloc(&dq, sizeof(double) * (size_t)B * nz));
     HIPCHK(tmp.alloc(&dA, sizeof(double) * (size_t)B * mm * nz)); HIPCHK(tmp.alloc(&dl, sizeof(double) * (size_t)B * mm)); HIPCHK(tmp.alloc(&du, sizeof(double) * (size_t)B * mm));
     RCCHK(upload_qp(c, B, A, Bm, C, x0, uOld, ssSel, qSel));
-    hipLaunchKernelGGL(lmpc_assemble_kernel, dim3(B), dim3(256), 0, c->stream, c->dp, B, c->w.A, c->w.Bm, c->w.C, c->w.x0, c->w.uOld, c->w.ssSel, c->w.qSel, dP, dq, dA, dl, du);
+    // (the matrices of problem b from tuning row b; no rows in force: the image holds the config's own row)
+    hipLaunchKernelGGL(lmpc_assemble_kernel, dim3(B), dim3(256), 0, c->stream, c->dp, B, c->w.A, c->w.Bm, c->w.C, c->w.x0, c->w.uOld, c->w.ssSel, c->w.qSel, dP, dq, dA, dl, du,
+                       (const double *)c->d_tune, c->tune_n > 1 ? (int)PAR_TOT : 0);
     HIPCHK(hipGetLastError());
     D2H(Pdense, dP, (size_t)B * nz * nz); D2H(q, dq, (size_t)B * nz); D2H(Adense, dA, (size_t)B * mm * nz); D2H(l, dl, (size_t)B * mm); D2H(u, du, (size_t)B * mm);
     HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- controller tuning rows
+int lmpc_tuning_set(lmpc_ctx *c, int n, const double *rows) {
+    ARGCHK(c && n >= 0 && n <= c->cfg.max_batch && (rows || n == 0));
+    char msg[160];
+    for (int r = 0; r < n; r++) {
+        const double *w = rows + (size_t)r * LMPC_TUNING_NPAR; const char *bad = nullptr;
+        for (int i = 0; i < LMPC_TUNING_NPAR && !bad; i++) if (!std::isfinite(w[i])) bad = "a non-finite entry";
+        for (int i = 0; i < 6 && !bad; i++) for (int j = 0; j < i; j++) if (w[TN_Q + i * 6 + j] != w[TN_Q + j * 6 + i] || w[TN_QF + i * 6 + j] != w[TN_QF + j * 6 + i]) bad = "Q or Qf not symmetric";
+        if (!bad && w[TN_R + 1] != w[TN_R + 2]) bad = "R not symmetric";
+        if (!bad && (w[TN_DR] < 0.0 || w[TN_DR + 1] < 0.0)) bad = "a negative dR entry";
+        if (!bad && (w[TN_QS] < 0.0 || w[TN_QS + 1] < 0.0)) bad = "a negative Qslack entry";
+        if (!bad && c->cfg.numSS_it > 0) for (int i = 0; i < 6; i++) if (!(w[TN_T + i] > 0.0)) bad = "a QtermSlack entry <= 0";
+        if (bad) { snprintf(msg, sizeof(msg), "row %d: %s (the rows in force stay)", r, bad); return set_err(LMPC_E_ARG, "lmpc_tuning_set", msg); }
+    }
+    RCCHK(tuning_upload(c, n, rows));
+    c->tune_rows.assign(rows, rows + (size_t)n * LMPC_TUNING_NPAR); c->tune_n = n;
+    return LMPC_OK;
+}
+int lmpc_tuning_get(lmpc_ctx *c, int *n, double *rows, int capacity) {
+    ARGCHK(c && n && capacity >= 0);
+    *n = c->tune_n;
+    if (rows) memcpy(rows, c->tune_rows.data(), sizeof(double) * LMPC_TUNING_NPAR * (size_t)std::min(c->tune_n, capacity));
     return LMPC_OK;
 }
 
@@ -1718,6 +1810,7 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         lmpc_solve_io io = solve_io(lmpc ? 3 : 2, r->a);
         // the safe-set lap table is live in a session (as lmpc_ss_set_selected is): B against its rows before the first launch of the step
         if (lmpc) { rc = ss_table_for(c, B, &io); if (rc) return rc; }
+        rc = tuning_for(c, B, &io); if (rc) return rc;       // (the tuning rows are live in the same way: a lmpc_tuning_set between two runs reaches the next step)
         if (!lti) {
         rc = refresh_params(c, true, lmpc, r->has_lt, io.ssTab != nullptr); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
         ev_begin(c, 0);

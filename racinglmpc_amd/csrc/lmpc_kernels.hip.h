@@ -17,7 +17,7 @@
 #include "../../include/lmpc_hip.h"
 
 #define WAVE 64
-#define LMPC_VARIANT_ABI_REV 8          // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
+#define LMPC_VARIANT_ABI_REV 9          // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
                                         // (LMPC_VARIANT_ABI, lmpc_variant.hip.h) also folds in the three struct sizes, so that layout drift cannot pass on the number alone
 #define LMPC_COLS 9                 // lap-store columns: x0..x5, u0, u1, Qfun
 
@@ -1382,7 +1382,9 @@ __global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 
         FOR_LANES_T(i, t, 6 * N) c_r[t] = sm[LL::oCk1 + i];
         __syncthreads();
     }
-    // stage the parameter block
+    // stage the parameter block: from the block every problem shares, or (TAB: per-problem rows) from this problem's row of the tuning image, which lies in the PAR_* layout
+    // (the TAB = false branch is the text it was, left at its indentation: the default instantiations compile from unchanged lines)
+    if constexpr (TAB) { const double *row = io.tune + (size_t)b * io.tuneStride; for (int i = lane; i < PAR_TOT; i += WAVE) par[i] = row[i]; } else {
     if (lane < 12) par[PAR_FX + lane] = p.Fx[lane];
     if (lane < 8) par[PAR_FU + lane] = p.Fu[lane];
     if (lane < 2) { par[PAR_BX + lane] = p.bx[lane]; par[PAR_DR2 + lane] = p.dR2[lane]; }
@@ -1390,6 +1392,7 @@ __global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 
     if (lane < 36) { par[PAR_Q2 + lane] = p.Q2[lane]; par[PAR_QF2 + lane] = p.Qf2[lane]; }
     if (lane < 6) { par[PAR_T2 + lane] = p.T2[lane]; par[PAR_XREF + lane] = p.xRef[lane]; }
     if (lane == 0) { par[PAR_AS] = p.a_s; par[PAR_CS] = p.c_s; }
+    }
     __syncthreads();
     const double a_s = wave_uniform(par[PAR_AS]), c_s = wave_uniform(par[PAR_CS]);
 
@@ -2509,9 +2512,13 @@ __global__ __launch_bounds__(256) void lmpc_assemble_kernel(lmpc_dev_params p, i
                                                             const double *__restrict__ C, const double *__restrict__ x0, const double *__restrict__ uOld,
                                                             const double *__restrict__ ssSel, const double *__restrict__ qSel,
                                                             double *__restrict__ Pd, double *__restrict__ q, double *__restrict__ Ad,
-                                                            double *__restrict__ l, double *__restrict__ u) {
+                                                            double *__restrict__ l, double *__restrict__ u, const double *__restrict__ tune, int tuneStride) {
     const int b = blockIdx.x; if (b >= B) return;
     const int N = p.N, S = p.S, n = 6, d = 2;
+    // the weights and bounds of problem b: its row of the tuning image (lmpc_tuning_set; without rows in force the context's default row, stride 0), PAR_* layout
+    const double *par = tune + (size_t)b * tuneStride;
+    const double *Fx = par + PAR_FX, *Fu = par + PAR_FU, *bx = par + PAR_BX, *bu = par + PAR_BU, *Q2 = par + PAR_Q2, *Qf2 = par + PAR_QF2,
+                 *R2 = par + PAR_R2, *dR2 = par + PAR_DR2, *T2p = par + PAR_T2, *xRef = par + PAR_XREF;
     const int ns = p.slacks ? 2 * N : 0;                 // slack variables and their positivity rows (MPCParams.slacks, :184-198)
     const int ox = 0, ou = n * (N + 1), os = ou + d * N, ol = os + ns, ot = ol + S, nz = S > 0 ? ot + n : ol;
     const int mi = 6 * N + ns + S, me = n * (N + 1) + (S > 0 ? n + 1 : 0), mm = mi + me;
@@ -2522,27 +2529,27 @@ __global__ __launch_bounds__(256) void lmpc_assemble_kernel(lmpc_dev_params p, i
     __syncthreads();
     for (int i = threadIdx.x; i < nz; i += blockDim.x) {
         double v = 0.0;
-        if (i < ou) { const int k = i / n, c = i % n; const double *Qk = k < N ? p.Q2 : p.Qf2; for (int j = 0; j < n; j++) v -= p.xRef[j] * Qk[j * 6 + c]; }
-        else if (i < os) { const int k = (i - ou) / d, c = (i - ou) % d; v = k == 0 ? -p.dR2[c] * uOld[(size_t)b * 2 + c] : 0.0; }
-        else if (i < ol) v = p.c_s;
+        if (i < ou) { const int k = i / n, c = i % n; const double *Qk = k < N ? Q2 : Qf2; for (int j = 0; j < n; j++) v -= xRef[j] * Qk[j * 6 + c]; }
+        else if (i < os) { const int k = (i - ou) / d, c = (i - ou) % d; v = k == 0 ? -dR2[c] * uOld[(size_t)b * 2 + c] : 0.0; }
+        else if (i < ol) v = par[PAR_CS];
         else if (i < ot) v = qSel[(size_t)b * S + (i - ol)];
         qb[i] = v;
     }
     // P
-    for (int i = threadIdx.x; i < (N + 1) * 36; i += blockDim.x) { const int k = i / 36, r = (i % 36) / 6, c = i % 6; Pb[(size_t)(k * 6 + r) * nz + k * 6 + c] = k < N ? p.Q2[r * 6 + c] : p.Qf2[r * 6 + c]; }
+    for (int i = threadIdx.x; i < (N + 1) * 36; i += blockDim.x) { const int k = i / 36, r = (i % 36) / 6, c = i % 6; Pb[(size_t)(k * 6 + r) * nz + k * 6 + c] = k < N ? Q2[r * 6 + c] : Qf2[r * 6 + c]; }
     for (int i = threadIdx.x; i < N * 4; i += blockDim.x) {
         const int k = i / 4, r = (i % 4) / 2, c = i % 2;
-        double v = p.R2[r * 2 + c]; if (r == c) v += (k < N - 1 ? 2.0 : 1.0) * p.dR2[r];
+        double v = R2[r * 2 + c]; if (r == c) v += (k < N - 1 ? 2.0 : 1.0) * dR2[r];
         Pb[(size_t)(ou + k * 2 + r) * nz + ou + k * 2 + c] = v;
-        if (r == c && k < N - 1) { Pb[(size_t)(ou + k * 2 + r) * nz + ou + (k + 1) * 2 + r] = -p.dR2[r]; Pb[(size_t)(ou + (k + 1) * 2 + r) * nz + ou + k * 2 + r] = -p.dR2[r]; }
+        if (r == c && k < N - 1) { Pb[(size_t)(ou + k * 2 + r) * nz + ou + (k + 1) * 2 + r] = -dR2[r]; Pb[(size_t)(ou + (k + 1) * 2 + r) * nz + ou + k * 2 + r] = -dR2[r]; }
     }
-    for (int i = threadIdx.x; i < ns; i += blockDim.x) Pb[(size_t)(os + i) * nz + os + i] = p.a_s;
-    if (S > 0) for (int i = threadIdx.x; i < 6; i += blockDim.x) Pb[(size_t)(ot + i) * nz + ot + i] = p.T2[i];
+    for (int i = threadIdx.x; i < ns; i += blockDim.x) Pb[(size_t)(os + i) * nz + os + i] = par[PAR_AS];
+    if (S > 0) for (int i = threadIdx.x; i < 6; i += blockDim.x) Pb[(size_t)(ot + i) * nz + ot + i] = T2p[i];
     // inequality rows
     for (int r = threadIdx.x; r < mi; r += blockDim.x) {
         double *row = Ab + (size_t)r * nz; double bb = 0.0;
-        if (r < 2 * N) { const int k = r >> 1, j = r & 1; for (int c = 0; c < 6; c++) row[ox + k * 6 + c] = p.Fx[j * 6 + c]; if (ns) row[os + r] = -1.0; bb = p.bx[j]; }
-        else if (r < 6 * N) { const int qd = r - 2 * N, k = qd >> 2, j = qd & 3; row[ou + k * 2] = p.Fu[j * 2]; row[ou + k * 2 + 1] = p.Fu[j * 2 + 1]; bb = p.bu[j]; }
+        if (r < 2 * N) { const int k = r >> 1, j = r & 1; for (int c = 0; c < 6; c++) row[ox + k * 6 + c] = Fx[j * 6 + c]; if (ns) row[os + r] = -1.0; bb = bx[j]; }
+        else if (r < 6 * N) { const int qd = r - 2 * N, k = qd >> 2, j = qd & 3; row[ou + k * 2] = Fu[j * 2]; row[ou + k * 2 + 1] = Fu[j * 2 + 1]; bb = bu[j]; }
         else if (r < 6 * N + ns) row[os + (r - 6 * N)] = -1.0;
         else row[ol + (r - 6 * N - ns)] = -1.0;
         lb[r] = -INFINITY; ub[r] = bb;

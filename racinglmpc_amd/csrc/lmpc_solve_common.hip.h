@@ -41,19 +41,24 @@ struct lmpc_solve_io {
     int retry_epoch;          // scope), so that the host launches the retry pass only when one is needed (lmpc_capi.hip: resolve_retries)
     const int *ssTab;         // optional: per-problem safe-set laps (lmpc_ss_set_lap_table), resolved on the host: numSS_it entries of LMPC_SSTAB_ENTRY ints per row --
     int ssTabStride;          // (slot, rows, is the car's latest lap, pad), 16 bytes -- in the row's sorted order; ints between rows (0: one row serves every problem)
+    const double *tune;       // optional: per-problem controller tuning (lmpc_tuning_set), the device image of the rows: PAR_TOT doubles per row in the PAR_* layout (doubled
+    int tuneStride;           // weights, Fx / Fu of the context) -- what the staging copy of the parameter block reads instead of `p`; doubles between rows (0: one row serves every problem)
 };
 #define LMPC_SSTAB_ENTRY 4
 // With a table the selection keeps (slot, rows) of every selected lap for the successor rows of feasibleStateInput, beside sel_start: in LMPC_SSTAB_LDS bytes of
 // dynamic LDS behind the kernel's layout, which the launchers add only when io.ssTab is set -- a launch without a table has the footprint it always had.
 // The fixed-(N, S) solve kernels are templates on TAB, as the regression kernel is: the TAB = false instantiations, which serve every launch without a table, carry
 // none of this; the runtime-(N, S) kernel branches at run time.
+// TAB is the ONE "per-problem rows" instantiation: it serves the safe-set table and the tuning rows (io.tune) alike.  Its staging copy always reads io.tune (a launch
+// with a table and no rows in force hands in the context's default row, stride 0); its selection reads io.ssTab where there is one and the parameter block's
+// selection where there is none (a tuned launch without a table: k2_lap_of) -- a wave-uniform test in that instantiation only.
 #define LMPC_SSTAB_LDS (2 * LMPC_MAX_USED_LAPS * sizeof(int))
 // The lap K2 reads as entry l of problem b: from the table row (b and l are uniform over the wave: one 16-byte scalar load), else from the parameter block.
 // latest: the entry takes the "current lap" branch of the Q-function shift (:502-512)
 struct k2_lap { int slot, rows, latest; };
 template <bool TAB>
 __device__ __forceinline__ k2_lap k2_lap_of(const lmpc_dev_params &p, const lmpc_solve_io &io, int b, int l) {
-    if (TAB) { const int4 e = *(const int4 *)(io.ssTab + (size_t)b * io.ssTabStride + LMPC_SSTAB_ENTRY * l); return {e.x, e.y, e.z}; }
+    if (TAB && io.ssTab) { const int4 e = *(const int4 *)(io.ssTab + (size_t)b * io.ssTabStride + LMPC_SSTAB_ENTRY * l); return {e.x, e.y, e.z}; }
     return {p.sslot[l], p.sslen[l], p.sslapid[l] < p.cur_it - 1 ? 0 : 1};
 }
 __device__ __forceinline__ void flag_retry(const lmpc_solve_io &io, int st) {
@@ -116,7 +121,9 @@ __device__ __forceinline__ double centring_sigma(double r) { const double r2 = r
 // ------------------------------------------------------------------------------------------------
 // The parameter block in LDS (PAR_*).  Visible behind the caller's barrier.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void stage_params(const lmpc_dev_params &p, double *par, int lane) {
+// tune: the problem's row of the tuning image (io.tune + b * io.tuneStride), or null: the block every problem shares
+__device__ __forceinline__ void stage_params(const lmpc_dev_params &p, double *par, int lane, const double *tune = nullptr) {
+    if (tune) { for (int i = lane; i < PAR_TOT; i += WAVE) par[i] = tune[i]; return; }
     if (lane < 12) par[PAR_FX + lane] = p.Fx[lane];
     if (lane < 8) par[PAR_FU + lane] = p.Fu[lane];
     if (lane < 2) { par[PAR_BX + lane] = p.bx[lane]; par[PAR_DR2 + lane] = p.dR2[lane]; }

@@ -73,7 +73,8 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
     __shared__ double ss_rowsum[6];                          // sum over the selected safe-set points of each state (loop invariant)
     double *phi = phi_sh;
     if (tid == 0) { st_sh = 0; bad_sh = 0; }
-    // stage the parameter block
+    // stage the parameter block (TAB: this problem's row of the tuning image, see lmpc_solve_kernel)
+    if constexpr (TAB) { const double *row = io.tune + (size_t)b * io.tuneStride; for (int i = tid; i < PAR_TOT; i += NT) par[i] = row[i]; } else {
     if (tid < 12) par[PAR_FX + tid] = p.Fx[tid];
     if (tid < 8) par[PAR_FU + tid] = p.Fu[tid];
     if (tid < 2) { par[PAR_BX + tid] = p.bx[tid]; par[PAR_DR2 + tid] = p.dR2[tid]; }
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
     if (tid < 36) { par[PAR_Q2 + tid] = p.Q2[tid]; par[PAR_QF2 + tid] = p.Qf2[tid]; }
     if (tid < 6) { par[PAR_T2 + tid] = p.T2[tid]; par[PAR_XREF + tid] = p.xRef[tid]; }
     if (tid == 0) { par[PAR_AS] = p.a_s; par[PAR_CS] = p.c_s; }
+    }
     __syncthreads();
     const double a_s = par[PAR_AS], c_s = par[PAR_CS];
 

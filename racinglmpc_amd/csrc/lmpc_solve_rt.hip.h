@@ -62,7 +62,7 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
     __shared__ int sel_start[LMPC_MAX_USED_LAPS];
     int *sel_lap = (int *)(sm + L.tot);                      // (io.ssTab only: LMPC_SSTAB_LDS bytes behind the layout, see lmpc_kernels.hip.h)
     if (lane == 0) st_sh = EQ ? (io.status[b] & (LMPC_ST_REG_SINGULAR | LMPC_ST_NO_SEGMENT)) : 0;
-    stage_params(p, par, lane);
+    stage_params(p, par, lane, io.tune ? io.tune + (size_t)b * io.tuneStride : nullptr);       // (tuning rows: found out at run time, as the table is)
     RT_SYNC();
     const double a_s = par[PAR_AS], c_s = par[PAR_CS];
     if (term) { k2_select<0, 0, 1, -1>(p, io, b, lane, 0, SS, Qsel, sel_start, sel_lap, &st_sh); RT_SYNC(); }

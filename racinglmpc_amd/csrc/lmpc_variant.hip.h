@@ -34,10 +34,11 @@ struct lmpc_variant_api {
 constexpr int LMPC_VARIANT_ABI = LMPC_VARIANT_ABI_REV * 0x1000000 + (int)((sizeof(lmpc_dev_params) * 31u + sizeof(lmpc_solve_io) * 7u + sizeof(lmpc_variant_api)) & 0xffffffu);
 static_assert(sizeof(lmpc_dev_params) < 4096 && sizeof(lmpc_solve_io) < 1024, "by-value kernel arguments: keep them inside the kernarg segment's preload range");
 
-// One kernel, its plain and its TAB instantiation: a launch with per-problem safe-set laps (io.ssTab) takes the second, with LMPC_SSTAB_LDS bytes behind `lds`
-// for the (slot, rows) of the selected laps.  (S = 0 has no TAB instantiations -- both names are the plain kernel there -- and no table: lmpc_capi.hip, ss_table_for.)
+// One kernel, its plain and its TAB instantiation: a launch with per-problem rows -- safe-set laps (io.ssTab), controller tuning (lmpc_tuning_set), or both; the
+// host sets io.tune for every such launch (lmpc_capi.hip, launch_solve) -- takes the second, with LMPC_SSTAB_LDS bytes behind `lds` for the (slot, rows) of the
+// selected laps.  (S = 0 has the TAB instantiations for the tuning rows alone: no table there, lmpc_capi.hip, ss_table_for.)
 template <class K> static int lmpc_launch_pair(K plain, K tab, int threads, size_t lds, hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-    const bool t = io.ssTab != nullptr && tab != plain;
+    const bool t = io.tune != nullptr;
     const K kernel = t ? tab : plain;
     hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds + (t ? LMPC_SSTAB_LDS : 0), st, p, B, io);
     return 0;
@@ -60,8 +61,8 @@ template <int N, int S> struct lmpc_variant_launchers {
         return f > lds1 ? f : lds1;
     }
     static constexpr size_t lds1_max() { const size_t f = (size_t)(54 * N + k1_fused_doubles(N, LMPC_MAX_USED_LAPS, 8)) * sizeof(double); return (f > lds1 ? f : lds1) + LMPC_SSTAB_LDS; }
-    // per-problem safe-set laps (io.ssTab): the TAB instantiations of the kernels exist for S > 0 only
-    static constexpr bool has_tab = S > 0;
+    // per-problem rows (io.ssTab, io.tune): every (N, S) has the TAB instantiations of its kernels -- S = 0 for the tuning rows
+    static constexpr bool has_tab = true;
     // long horizons: [A_k | B_k] in global memory where that lets more QPs share a CU than the 160 KB of LDS otherwise hold and fewer than four do (idle SIMDs)
     static constexpr size_t lds1g = (size_t)solve_lds1<N, S, true>::tot * sizeof(double);
     // (measured, solve kernel, ms at batch 1024 / 4096: N = 40 LDS 1.467 / 4.073, global 1.092 / 3.398 -- two -> four QPs per CU;  N = 20 LDS 0.655 / 1.571,

@@ -19,8 +19,11 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set, or (ss_table) each car against its own (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None):
-        """lap_table: per-car regression laps of the cars of THIS object, rows of trToUse insertion indices into the context's regression store -- one row for all cars
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None):
+        """tuning: controller tuning of the cars of THIS object (this rank's shard), rows of _capi.TUNING_FIELDS as _capi.tuning_rows builds them -- one row for all cars
+        or one per car (Context.tuning_set); handed to the context before every begin and run_mpc_laps, beside lap_table / ss_table.  The context's rows are live in a
+        session, as the safe-set table is.  None: the context's rows are left as they are (the config's weights unless the caller set others).
+        lap_table: per-car regression laps of the cars of THIS object, rows of trToUse insertion indices into the context's regression store -- one row for all cars
         or one per car (Context.model_set_lap_table); handed to the context before every begin and every LTV run_mpc_laps, as plant_params is.  None: the context's
         table is left as it is (no table unless the caller set one: every car regresses on the first trToUse laps of the store's sorted order).  On an LMPC context
         the safe set does not follow this table: it has its own, ss_table.
@@ -51,6 +54,7 @@ class BatchedRollouts:
         self.ss_table, self.ss_last = (None, None) if ss_table is None else _capi.check_ss_table(ss_table, ctx.cfg.numSS_it, ss_last)
         if ss_table is None and ss_last is not None:
             raise ValueError("ss_last: needs ss_table")
+        self.tuning = None if tuning is None else _capi.check_tuning(tuning, ctx.cfg.numSS_it)
         self.device_noise = bool(device_noise)
         if self.device_noise:
             import operator
@@ -164,6 +168,15 @@ class BatchedRollouts:
             raise ValueError("ss_table: one row or one per car (%d) expected, got %d" % (B, tab.shape[0]))
         self.ctx.ss_set_lap_table(tab, getattr(self, "ss_last", None))
 
+    def _apply_tuning(self, B):
+        """The tuning rows of this object's cars go to the context in front of a session that solves."""
+        rows = getattr(self, "tuning", None)           # (objects built without __init__ -- tests/test_host_checks.py -- have none)
+        if rows is None:
+            return
+        if rows.shape[0] not in (1, B):
+            raise ValueError("tuning: one row or one per car (%d) expected, got %d" % (B, rows.shape[0]))
+        self.ctx.tuning_set(rows)
+
     @staticmethod
     def _per_rollout(a, B):
         a = np.asarray(a, float)
@@ -176,6 +189,7 @@ class BatchedRollouts:
         self._apply_plant_params(B)
         self._apply_lap_table(B)
         self._apply_ss_table(B)
+        self._apply_tuning(B)
         if self._device_noise_session(B):
             self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, None, T_max=max_steps)
         else:
@@ -247,6 +261,7 @@ class BatchedRollouts:
         self._apply_plant_params(nb)
         if A is None:
             self._apply_lap_table(nb)              # (the LTI form runs no regression)
+        self._apply_tuning(nb)
         kw = dict(T_max=max_steps) if self._device_noise_session(nb) else {}       # (noise is None then: the session's buffer is filled on the device)
         if A is not None:
             self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line, **kw)
@@ -272,7 +287,7 @@ def mpc_stage_config(track, N, vt, max_batch, trToUse=1, device=0):
                              trackLength=float(track[-1, 3] + track[-1, 4]), max_batch=int(max_batch), device=int(device))
 
 
-def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None, device_noise=False, per_car_store=False):
+def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None, device_noise=False, per_car_store=False, tuning=None):
     """main.py:61-95 for B cars without a host round trip inside a lap: PID laps -> one LTI model per car (batched Utilities.Regression, lamb = 1e-7) -> LTI-MPC laps,
     car b on its own (A_b, B_b) -> LTV-MPC laps.  vt: the PID target speed, one value (main.py:50) or one per car; the MPC stages track vt_mpc (default: vt, or the
     mean of the per-car values).  Every stage runs max_steps steps from x0 = [0.5, 0, 0, 0, 0, 0] like the reference's multiLap simulator (main.py:45, 57).
@@ -290,6 +305,9 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     plant_params: vehicle constants (one row, or one per car; _capi.plant_params) of all three stages -- car b drives the same vehicle in its PID, LTI-MPC and LTV-MPC
     lap; None: the reference's vehicle.
 
+    tuning: controller tuning of the two MPC stages (one row, or one per car; _capi.tuning_rows on mpc_stage_config) -- e.g. a target speed xRef[0] per car; None: the
+    values of mpc_stage_config for every car.
+
     One generator seeded with `seed` feeds all stages in the order PID control-law noise, PID plant noise, LTI-MPC plant noise, LTV-MPC plant noise.
     device_noise: the disturbances are generated on the device instead (BatchedRollouts(device_noise=True)): the three stages are sessions 0, 1 and 2 of `seed`.
     Returns dict(pid=, mpc=, ltvmpc= lists of lap tuples (x, u, x_glob, final12, done_at, status) with every car in it, flagged or not -- check `status` and
@@ -301,7 +319,7 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     n_store = B if per_car_store else min(B, BOOTSTRAP_STORE_LAPS)
     ctx = _capi.Context(mpc_stage_config(track, N, vt_mpc, B, trToUse=1 if per_car_store else n_store, device=device))
     try:
-        ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params, device_noise=device_noise)
+        ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params, device_noise=device_noise, tuning=tuning)
     except Exception:
         ctx.close()
         raise
@@ -568,13 +586,16 @@ class PerCarLMPC:
     per generation, over the same cars in the same order, so store indices, histories, tables, `last`, lap_times and `retired` come out as without it (an entry
     that comes back not extended -- a non-finite row -- retires its car with EXT_SKIPPED); only status words, crossing steps, final states and the first N + 2
     logged rows are downloaded.  The tuples run() returns, and latest[b], then carry only the first min(T, N + 2) rows of x and u -- what the next generation
-    linearises about -- and None for x_glob; the full lap is in the stores (Context.store_read_lap)."""
+    linearises about -- and None for x_glob; the full lap is in the stores (Context.store_read_lap).
+    tuning: rows of _capi.tuning_rows, one for all cars or one per car -- what BatchedRollouts(tuning=) takes; car b then also runs its own controller tuning."""
 
     EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
 
-    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False):
+    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None):
         self.ro, self.T_max, self.ext = rollouts, int(T_max), int(ext)
         self.device_commit = bool(device_commit)
+        if tuning is not None:             # (one row, or one per car: each learner its own cost weights and bounds; the rollouts object hands them to the context before every begin)
+            self.ro.tuning = _capi.check_tuning(tuning, self.ro.ctx.cfg.numSS_it)
         self.B = None
         self.generation = 0
         self.retired = {}
