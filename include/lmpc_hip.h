@@ -202,6 +202,34 @@ int lmpc_tuning_set(lmpc_ctx *, int n, const double *rows /*n x 98, or NULL with
          * the host) is taken: the two-kernel step / the ordinary kernels run */
 int lmpc_tuning_get(lmpc_ctx *, int *n, double *rows /*capacity x 98, or NULL*/, int capacity);
         /* the rows in force as lmpc_tuning_set received them (n = 0: the config's weights; MPCParams, PredictiveControllers.py:24-51); rows receives min(n, capacity) rows */
+
+/* Per-car tracks: the track table and length of each element of a batch from its own row -- the reference builds one Map per spec (Track.py:13 "Modify the vector spec
+ * to change the geometry of the track").  A row is LMPC_TRACK_NPAR doubles: [0] the number of table rows (an integer 1..16 as a double), [1] trackLength, [2..97]
+ * PointAndTangent, 16 x 6 row-major (x, y, psi, cumulative s, segment length, curvature), unused rows zero. */
+#define LMPC_TRACK_NPAR 98
+int lmpc_track_row_from_config(const lmpc_config *, double *row /*98*/);
+        /* the row a context created from that config uses by default (track, track_rows, trackLength).  Needs no device */
+int lmpc_track_set(lmpc_ctx *, int n, const double *rows /*n x 98, or NULL with n = 0*/);
+        /* n = 0: the config's track; every path returns the bits it returned before there were rows (the kernels that read the parameter block run).  n = 1: that row
+         * serves every car.  n > 1: element b of a batched call uses row b, and a call whose count differs from n returns LMPC_E_ARG and says so in lmpc_last_error
+         * (the context stays usable).  LMPC_E_ARG, with the rows in force kept, for a non-finite entry, a row count that is not an integer in 1..16, trackLength <= 0, a
+         * negative segment length (a zero or rounding-sized one is a row no s lies on, e.g. the closing row of an oval: accepted), n < 0, n > max_batch, NULL rows with
+         * n > 0.  LMPC_E_STATE while a rollout session is active: a lap on a track that changes under it means nothing, so rows are NOT live (unlike tuning rows).
+         * Launches still waiting for their deferred retry pass are resolved and the stream is drained before the device image is overwritten, so a retry pass reads
+         * the rows of its own launch.
+         * "Element b": problem b of lmpc_regress_batch, lmpc_step_batch, lmpc_step_batch_dev, lmpc_select_batch, lmpc_qp_solve_batch (where it selects); point e of
+         * lmpc_regress_points, lmpc_global_position_batch, lmpc_local_position_batch, lmpc_track_angle_batch; car b of lmpc_plant_step_batch, of lmpc_rollout_begin /
+         * _begin_mpc / _pid sessions and every step of them, of lmpc_rollout_commit_laps / _extend_laps (computeCost and addPoint with the car's own TrackLength) and of
+         * the T x B log of lmpc_state_from_global_batch.  max_ey stays one scalar per call.
+         * The host-side lap writers name no car: lmpc_ss_add_trajectory, lmpc_ss_add_point and lmpc_ss_extend_lap use the config's TrackLength at n = 0 and row 0 at
+         * n = 1, and return LMPC_E_STATE at n > 1 -- the _on forms below take the row.  lmpc_ss_replace_lap takes its own Qfun; lmpc_model_* reads no track.
+         * While rows are in force neither the fused one-wave step (LMPC_FUSE=1) nor the condensed kernel (LMPC_CD=1) is taken, as with tuning rows; the selection reads
+         * the problem's TrackLength in the per-problem-rows instantiations of the solve kernels and in the runtime-(N, S) kernel */
+int lmpc_track_get(lmpc_ctx *, int *n, double *rows /*capacity x 98, or NULL*/, int capacity);
+        /* the rows in force as lmpc_track_set received them (n = 0: the config's track); rows receives min(n, capacity) rows */
+int lmpc_ss_add_trajectory_on(lmpc_ctx *, int track_row, const double *x, const double *u, int T);
+int lmpc_ss_extend_lap_on(lmpc_ctx *, int track_row, int lap, const double *x /*n x 6*/, const double *u /*n x 2*/, int n);
+        /* lmpc_ss_add_trajectory / lmpc_ss_extend_lap with the TrackLength of track row `track_row` (0 <= track_row < max(n, 1) of lmpc_track_set) in computeCost / addPoint */
 int lmpc_ss_num_laps(lmpc_ctx *, int *n);
 int lmpc_ss_get_qfun(lmpc_ctx *, int lap, double *qfun /*T*/, int *T);
 int lmpc_store_read_lap(lmpc_ctx *, int store /*0: regression store (sorted position), 1: safe set*/, int lap, double *x /*T x 6*/, double *u /*T x 2*/, double *qfun /*T, safe set only*/, int *T);

@@ -84,6 +84,7 @@ EXPORTS = [
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
     "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
     "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_debug_model_image", "lmpc_tuning_from_config", "lmpc_tuning_set", "lmpc_tuning_get",
+    "lmpc_track_row_from_config", "lmpc_track_set", "lmpc_track_get", "lmpc_ss_add_trajectory_on", "lmpc_ss_extend_lap_on",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -140,6 +141,14 @@ def load():
         lib.lmpc_tuning_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.lmpc_tuning_get.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]
         lib.lmpc_tuning_from_config.restype = lib.lmpc_tuning_set.restype = lib.lmpc_tuning_get.restype = C.c_int
+        # (per-car tracks: rows of TRACK_NPAR doubles)
+        lib.lmpc_track_row_from_config.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lmpc_track_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.lmpc_track_get.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]
+        lib.lmpc_ss_add_trajectory_on.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        lib.lmpc_ss_extend_lap_on.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        for f in (lib.lmpc_track_row_from_config, lib.lmpc_track_set, lib.lmpc_track_get, lib.lmpc_ss_add_trajectory_on, lib.lmpc_ss_extend_lap_on):
+            f.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
@@ -342,6 +351,57 @@ def tuning_rows(cfg, B, **fields):
     return check_tuning(rows, cfg.numSS_it)
 
 
+# One track row (lmpc_track_set): [0] the number of table rows, [1] trackLength, [2:98] PointAndTangent, 16 x 6 row-major, unused rows zero.
+TRACK_NPAR = 2 + MAX_TRACK_ROWS * 6
+
+
+def track_row(table, trackLength=None):
+    """One row of TRACK_NPAR doubles from a PointAndTangent table ((rows, 6), rows <= 16) and its length (default: cumulative s + length of the last row, as
+    Map.__init__ computes TrackLength, Track.py:133).  Needs neither the library nor a device."""
+    t = np.asarray(table, dtype=np.float64)
+    if t.ndim != 2 or t.shape[1] != 6 or not 1 <= t.shape[0] <= MAX_TRACK_ROWS:
+        raise ValueError("track_row: a (rows, 6) table with 1 <= rows <= %d expected, got shape %s" % (MAX_TRACK_ROWS, t.shape))
+    row = np.zeros(TRACK_NPAR)
+    row[0] = t.shape[0]
+    row[1] = float(t[-1, 3] + t[-1, 4]) if trackLength is None else float(trackLength)
+    row[2:2 + t.size] = t.reshape(-1)
+    return row
+
+
+def track_rows(tables):
+    """(n, 98) rows for Context.track_set from a sequence of PointAndTangent tables, or of (table, trackLength) pairs; checked as check_tracks does."""
+    rows = [track_row(*t) if isinstance(t, tuple) else track_row(t) for t in tables]
+    return check_tracks(np.stack(rows)) if rows else None
+
+
+def track_table(row):
+    """(PointAndTangent, trackLength) of one track row: the inverse of track_row."""
+    row = np.asarray(row, dtype=np.float64)
+    n = int(row[0])
+    return row[2:2 + 6 * n].reshape(n, 6).copy(), float(row[1])
+
+
+def check_tracks(rows):
+    """(n, 98) float64 rows, or None for "no rows" (None or empty); ValueError for what lmpc_track_set refuses in a row: a wrong shape, a non-finite entry, a row count
+    that is not an integer in 1..16, trackLength <= 0, a negative segment length."""
+    if rows is None or np.size(rows) == 0:
+        return None
+    r = np.array(rows, dtype=np.float64, ndmin=2)
+    if r.ndim != 2 or r.shape[1] != TRACK_NPAR:
+        raise ValueError("tracks: rows of %d values expected, got shape %s" % (TRACK_NPAR, r.shape))
+    if not np.all(np.isfinite(r)):
+        raise ValueError("tracks: non-finite entry in row(s) %s" % np.where(~np.isfinite(r).all(1))[0].tolist())
+    n = r[:, 0]
+    if not np.all((n >= 1) & (n <= MAX_TRACK_ROWS) & (n == np.floor(n))):
+        raise ValueError("tracks: the row count must be an integer in 1..%d" % MAX_TRACK_ROWS)
+    if not np.all(r[:, 1] > 0):
+        raise ValueError("tracks: trackLength must be positive")
+    for k in range(r.shape[0]):
+        if (r[k, 2:].reshape(MAX_TRACK_ROWS, 6)[:int(n[k]), 4] < 0).any():
+            raise ValueError("tracks: negative segment length in row %d" % k)
+    return np.ascontiguousarray(r)
+
+
 def _chk(rc):
     if rc != 0:
         raise LmpcError("liblmpc_hip error %d: %s" % (rc, load().lmpc_last_error().decode()))
@@ -481,9 +541,14 @@ class Context:
             _chk(self.lib.lmpc_model_get_lap_table(self._h, C.byref(n), rows.ctypes.data, rows.shape[0]))
         return rows
 
-    def ss_add_trajectory(self, x, u):
+    def ss_add_trajectory(self, x, u, track_row=None):
+        """LMPC.addTrajectory.  track_row: the row of track_set whose TrackLength computeCost uses (lmpc_ss_add_trajectory_on) -- needed when one row per car is in
+        force, since a lap handed in by the host names no car; None: the config's TrackLength, or the one row's."""
         x = _f64(x); u = _f64(u)
-        _chk(self.lib.lmpc_ss_add_trajectory(self._h, _d(x), _d(u), C.c_int(x.shape[0])))
+        if track_row is None:
+            _chk(self.lib.lmpc_ss_add_trajectory(self._h, _d(x), _d(u), C.c_int(x.shape[0])))
+        else:
+            _chk(self.lib.lmpc_ss_add_trajectory_on(self._h, C.c_int(int(track_row)), _d(x), _d(u), C.c_int(x.shape[0])))
 
     def ss_add_point(self, x, u):
         x = _f64(x); u = _f64(u)
@@ -692,6 +757,25 @@ class Context:
             return
         _chk(self.lib.lmpc_tuning_set(self._h, rows.shape[0], rows.ctypes.data))
 
+    def track_set(self, rows):
+        """Per-car tracks (lmpc_track_set): None or no rows -- the config's track; one row of TRACK_NPAR doubles (track_row) -- every car; (n, 98) -- element b of a
+        batched call uses row b, and a call of another count is refused (LmpcError, the context stays usable).  Refused while a rollout session is active.
+        track_rows() builds the rows from PointAndTangent tables."""
+        rows = check_tracks(rows)
+        if rows is None:
+            _chk(self.lib.lmpc_track_set(self._h, 0, None))
+            return
+        _chk(self.lib.lmpc_track_set(self._h, rows.shape[0], rows.ctypes.data))
+
+    def tracks(self):
+        """The rows in force, (n, 98), as track_set received them; n = 0: the config's track (lmpc_track_get)."""
+        n = C.c_int()
+        _chk(self.lib.lmpc_track_get(self._h, C.byref(n), None, 0))
+        rows = np.zeros((n.value, TRACK_NPAR))
+        if n.value:
+            _chk(self.lib.lmpc_track_get(self._h, C.byref(n), rows.ctypes.data, rows.shape[0]))
+        return rows
+
     def tuning(self):
         """The rows in force, (n, 98), as tuning_set received them; n = 0: the config's weights (lmpc_tuning_get)."""
         n = C.c_int()
@@ -823,7 +907,8 @@ class Context:
 
     def save_stores(self, path):
         """Both lap stores (and the explicit safe-set selection, if one is set by the caller: not stored -- it is per-step state of the controller) as one .npz.
-        Tuning rows (tuning_set) are not saved either: they are controller parameters, not store content -- set them again on the restored context."""
+        Tuning rows (tuning_set) are not saved either: they are controller parameters, not store content -- set them again on the restored context.
+        Neither are track rows (track_set): the stores carry laps, not tracks -- a stored lap's Qfun and extension rows already hold what its TrackLength made of them."""
         out = {}
         nm = C.c_int(); _chk(self.lib.lmpc_model_num_laps(self._h, C.byref(nm)))
         for i in range(nm.value):
@@ -887,9 +972,13 @@ class Context:
                                             g("lam"), g("ztNext"), g("ztuNext"), g("iters"), g("status")))
         return o
 
-    def ss_extend_lap(self, lap, x, u):
+    def ss_extend_lap(self, lap, x, u, track_row=None):
+        """track_row: the row of track_set whose TrackLength is added to s (lmpc_ss_extend_lap_on); None: the config's, or the one row's."""
         x = _f64(x); u = _f64(u)
-        _chk(self.lib.lmpc_ss_extend_lap(self._h, C.c_int(int(lap)), _d(x), _d(u), C.c_int(x.shape[0])))
+        if track_row is None:
+            _chk(self.lib.lmpc_ss_extend_lap(self._h, C.c_int(int(lap)), _d(x), _d(u), C.c_int(x.shape[0])))
+        else:
+            _chk(self.lib.lmpc_ss_extend_lap_on(self._h, C.c_int(int(track_row)), C.c_int(int(lap)), _d(x), _d(u), C.c_int(x.shape[0])))
 
     def rollout_commit_laps(self, cars, rows=None, ss=True, model=True):
         """Laps of the active session into the lap stores on the device (lmpc_rollout_commit_laps): entry i is rows [0, rows[i]) of car cars[i] as the session logged
@@ -1120,7 +1209,7 @@ class ContextPool:
     def __getattr__(self, name):                       # lap-store edits (model_add_trajectory, ss_add_trajectory, ss_add_point, ss_set_selected, ...): the same call on every member
         if name in ("members", "_next"):               # (not set yet: a failed __init__ must not recurse through this hook)
             raise AttributeError(name)
-        if name in ("plant_set_params", "tuning_set") or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num", "model_lap"))):   # (the vehicle too: the same on every member; model_set_lap_table and ss_set_lap_table go with the store edits, the queries model_lap_table / model_lap_info / ss_lap_table to the first)
+        if name in ("plant_set_params", "tuning_set", "track_set") or (name.startswith(("model_", "ss_")) and not name.startswith(("ss_get", "ss_num", "ss_lap", "model_num", "model_lap"))):   # (the vehicle too: the same on every member; model_set_lap_table and ss_set_lap_table go with the store edits, the queries model_lap_table / model_lap_info / ss_lap_table to the first)
             def forward(*a, **kw):
                 out = None
                 for m in self.members:

@@ -139,6 +139,9 @@ struct lmpc_ctx {
     // per-problem-rows instantiations of the solve kernels and the assemble kernel stage from -- PAR_TOT doubles per row in the PAR_* layout, doubled weights, Fx / Fu of
     // the config; with no rows in force it holds the config's own row (what a launch with a safe-set table alone reads).  Uploaded by `set`, never per launch
     std::vector<double> tune_rows; int tune_n; double *d_tune; size_t d_tune_cap;
+    // lmpc_track_set: trk_n rows of LMPC_TRACK_NPAR doubles as the caller gave them (0 rows: the config's track, read from the parameter block by the kernels that ran
+    // before there were rows); d_trk: the same rows on the device, uploaded by `set` (allocated with the first rows)
+    std::vector<double> trk_rows; int trk_n; double *d_trk; size_t d_trk_cap;
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
 };
@@ -151,6 +154,7 @@ struct lmpc_rollout_session {
     double *d_noiseU, *d_vt;                                    // RO_PID only: controller noise T_max x B x 2, target speed per car
     unsigned long long nz_seed, nz_lap; long long nz_car0;      // the session's snapshot of the noise source (lmpc_rollout_set_noise), taken when it begins
     int *d_lt; bool has_lt, lt_small; int lt_stride;            // the session's snapshot of the lap table (resolved (slot, rows) pairs, B x trToUse x 2), taken when it begins; has_lt: the table builds of the regression kernel run
+    const double *trk; int trk_stride;                          // the context's track image for this session's cars (null: the config's track); lmpc_track_set is refused while the session is active
     double *d_par; bool has_par;                                // the session's snapshot of the per-car vehicle constants (B x LMPC_PLANT_NPAR), taken when it begins; has_par: the PAR kernels run
     hipStream_t pstream; hipEvent_t e_solved, e_plant;          // plant integration runs beside the next regression (lmpc_rollout_plant_kernel)
     std::vector<void *> keep;
@@ -215,7 +219,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 108; }
+int lmpc_version(void) { return 109; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -278,7 +282,48 @@ int lmpc_tuning_from_config(const lmpc_config *f, double *row) {
     return LMPC_OK;
 }
 
+
+// ---- track rows (lmpc_track_set): [0] rows, [1] trackLength, [2..97] PointAndTangent 16 x 6 row-major, unused rows zero
+static_assert(2 + LMPC_MAX_TRACK_ROWS * 6 == LMPC_TRACK_NPAR, "layout of a track row");
+int lmpc_track_row_from_config(const lmpc_config *f, double *row) {
+    if (!f || !row) return set_err(LMPC_E_ARG, "lmpc_track_row_from_config", "NULL argument");
+    if (f->track_rows < 0 || f->track_rows > LMPC_MAX_TRACK_ROWS) return set_err(LMPC_E_ARG, "lmpc_track_row_from_config", "track_rows out of range");
+    memset(row, 0, sizeof(double) * LMPC_TRACK_NPAR);
+    row[0] = (double)f->track_rows; row[1] = f->trackLength;
+    memcpy(row + 2, f->track, sizeof(double) * 6 * (size_t)f->track_rows);
+    return LMPC_OK;
+}
+
 }  // extern "C" (helpers)
+
+// The track of element b of a batched call with rows in force: the device image and its stride (0: one row serves all).  No rows: dev stays null -- the kernels
+// that read the parameter block run.  B against the rows is checked by track_for before anything is queued.
+struct trk_src { const double *dev; int stride; };
+static int track_for(lmpc_ctx *c, long long B, trk_src *t) {
+    t->dev = nullptr; t->stride = 0;
+    if (c->trk_n == 0) return LMPC_OK;
+    if (c->trk_n > 1 && B != c->trk_n) {
+        char msg[128]; snprintf(msg, sizeof(msg), "B = %lld elements but lmpc_track_set holds %d rows", B, c->trk_n);
+        return set_err(LMPC_E_ARG, "track rows", msg);
+    }
+    t->dev = c->d_trk; t->stride = c->trk_n == 1 ? 0 : LMPC_TRACK_NPAR;
+    return LMPC_OK;
+}
+// TrackLength of track row `row` (computeCost, addPoint): the config's without rows, the one row's with one
+static double track_length_of(const lmpc_ctx *c, int row) {
+    return c->trk_n == 0 ? c->cfg.trackLength : c->trk_rows[(size_t)(c->trk_n == 1 ? 0 : row) * LMPC_TRACK_NPAR + 1];
+}
+// the host-side lap writers have no car: the config's TrackLength, or row 0 of one; with one row per car the caller must say which (the _on forms)
+static int track_length_host(lmpc_ctx *c, const char *who, const char *on_form, double *TL) {
+    if (c->trk_n > 1) { char msg[160]; snprintf(msg, sizeof(msg), "lmpc_track_set holds %d rows and this call names no car: use %s", c->trk_n, on_form); return set_err(LMPC_E_STATE, who, msg); }
+    *TL = track_length_of(c, 0);
+    return LMPC_OK;
+}
+static int track_length_on(lmpc_ctx *c, const char *who, int row, double *TL) {
+    if (row < 0 || row >= std::max(c->trk_n, 1)) { char msg[128]; snprintf(msg, sizeof(msg), "track_row %d, %d rows in force", row, c->trk_n); return set_err(LMPC_E_ARG, who, msg); }
+    *TL = track_length_of(c, row);
+    return LMPC_OK;
+}
 
 // one row as the kernels stage it: the PAR_* layout of the parameter block in LDS, the values fill_params derives from a config holding this row
 static void tuning_image_row(const lmpc_config &f, const double *row, double *img) {
@@ -450,7 +495,7 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt, c->d_sst, c->d_tune};      // (the work buffers are ranges of the two slabs)
+    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt, c->d_sst, c->d_tune, c->d_trk};      // (the work buffers are ranges of the two slabs)
     check_slab_gaps(c);
     for (void *q : ptrs) if (q) (void)g_free(q);
     if (c->h_retry) (void)hipHostFree(c->h_retry);
@@ -568,7 +613,7 @@ static int session_rows(lmpc_ctx *c, size_t tail_bytes, store_rows *s) {
 }
 static lmpc_commit_args commit_args(const lmpc_ctx *c, const store_rows &s) {
     lmpc_commit_args a; a.logX = s.logX; a.logU = s.logU; a.B = s.B; a.sstore = c->sstore; a.mstore = c->mstore; a.mquant = c->mquant; a.mqpar = c->mqpar;
-    a.ls = c->cfg.max_lap_len; a.mq_chunks = c->mq_chunks; a.TL = c->cfg.trackLength; memcpy(a.scaling, c->cfg.scaling, sizeof(a.scaling));
+    a.ls = c->cfg.max_lap_len; a.mq_chunks = c->mq_chunks; memcpy(a.scaling, c->cfg.scaling, sizeof(a.scaling));
     return a;
 }
 #define LMPC_COMMIT_TAIL(n) ((sizeof(double) + sizeof(lmpc_commit_entry)) * (size_t)(n))
@@ -605,9 +650,9 @@ static void commit_book(lmpc_ctx *c, const std::vector<lmpc_commit_entry> &tab, 
     }
 }
 // one lap handed in by the host: staged, written to the slots named (-1: that store is not written) and, a new lap, entered in the books.  Blocking: x and u are pageable memory
-static int commit_host_lap(lmpc_ctx *c, const double *x, const double *u, int T, int ss_slot, int m_slot, bool new_lap) {
+static int commit_host_lap(lmpc_ctx *c, const double *x, const double *u, int T, int ss_slot, int m_slot, bool new_lap, double TL) {
     store_rows s; RCCHK(staged_rows(c, x, u, T, LMPC_COMMIT_TAIL(1), &s));
-    const std::vector<lmpc_commit_entry> tab{{0, T, ss_slot, m_slot}}; std::vector<double> q0;
+    const std::vector<lmpc_commit_entry> tab{{0, T, ss_slot, m_slot, TL}}; std::vector<double> q0;
     RCCHK(commit_laps(c, s, tab, q0));
     if (new_lap) commit_book(c, tab, q0);
     return LMPC_OK;
@@ -616,12 +661,13 @@ static int commit_host_lap(lmpc_ctx *c, const double *x, const double *u, int T,
 // Appended rows, the batched LMPC.addPoint (PredictiveControllers.py:466-474): rows [0, n_rows) of car cars[i] of the source behind the rows of safe-set lap laps[i].  One
 // growth, one upload of the table and of every lap's last Qfun value, one launch, one download of the flags, a drained stream, then the books of every lap
 // extended.  extended == NULL: the rows are appended whatever they hold; else an entry with a non-finite value is left as it is and reported as 0.
-static int extend_laps(lmpc_ctx *c, const store_rows &s, int n, const int *cars, const int *laps, int n_rows, int *extended) {
+// track_row < 0: entry i adds the TrackLength of car cars[i]'s track (a session); else that of the row named (a host lap)
+static int extend_laps(lmpc_ctx *c, const store_rows &s, int n, const int *cars, const int *laps, int n_rows, int *extended, int track_row = -1) {
     int longest = 0;
     for (int i = 0; i < n; i++) longest = std::max(longest, c->s_len[laps[i]] + n_rows);
     RCCHK(grow_stores(c, c->cfg.max_laps, longest));
     std::vector<lmpc_extend_entry> tab((size_t)n); std::vector<double> ql((size_t)n);
-    for (int i = 0; i < n; i++) { tab[(size_t)i] = {cars[i], laps[i], c->s_len[laps[i]], 0}; ql[(size_t)i] = c->s_qlast[laps[i]]; }
+    for (int i = 0; i < n; i++) { tab[(size_t)i] = {cars[i], laps[i], c->s_len[laps[i]], 0, track_length_of(c, track_row < 0 ? cars[i] : track_row)}; ql[(size_t)i] = c->s_qlast[laps[i]]; }
     double *d_ql = (double *)s.tail; lmpc_extend_entry *d_tab = (lmpc_extend_entry *)(d_ql + n); int *d_flag = extended ? (int *)(d_tab + n) : nullptr;
     hipError_t e = hipMemcpyAsync(d_ql, ql.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_extend_entry) * (size_t)n, hipMemcpyHostToDevice, c->stream);
@@ -643,14 +689,14 @@ int lmpc_model_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int
     HIPCHK(hipSetDevice(c->cfg.device));
     RESOLVE_PENDING();
     HIPCHK(hipStreamSynchronize(c->stream));
-    return commit_host_lap(c, x, u, T, -1, (int)c->m_len.size(), true);                       // PredictiveModel.addTrajectory (PredictiveModel.py:35-46)
+    return commit_host_lap(c, x, u, T, -1, (int)c->m_len.size(), true, 0.0);                  // PredictiveModel.addTrajectory (PredictiveModel.py:35-46); the regression store holds no cost: no TrackLength is read
 }
 int lmpc_model_num_laps(lmpc_ctx *c, int *n) { ARGCHK(c && n); *n = (int)c->m_order.size(); return LMPC_OK; }
 int lmpc_model_replace_lap(lmpc_ctx *c, int pos, const double *x, const double *u, int T) {
     ARGCHK(c && x && u && pos >= 0 && pos < (int)c->m_order.size());
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     ARGCHK(T == c->m_len[c->m_order[pos]]);
-    RCCHK(commit_host_lap(c, x, u, T, -1, c->m_order[pos], false));
+    RCCHK(commit_host_lap(c, x, u, T, -1, c->m_order[pos], false, 0.0));
     return resolve_lap_table(c);
 }
 
@@ -685,12 +731,21 @@ int lmpc_model_get_lap_table(lmpc_ctx *c, int *n, int *laps, int capacity) {
     return LMPC_OK;
 }
 
-int lmpc_ss_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int T) {
-    ARGCHK(c && x && u && T >= 1);
+static int ss_add_trajectory_tl(lmpc_ctx *c, const double *x, const double *u, int T, double TL) {
     HIPCHK(hipSetDevice(c->cfg.device));
     RESOLVE_PENDING();
     HIPCHK(hipStreamSynchronize(c->stream));
-    return commit_host_lap(c, x, u, T, (int)c->s_len.size(), -1, true);                        // LMPC.addTrajectory + computeCost (PredictiveControllers.py:418-464)
+    return commit_host_lap(c, x, u, T, (int)c->s_len.size(), -1, true, TL);
+}
+int lmpc_ss_add_trajectory_on(lmpc_ctx *c, int track_row, const double *x, const double *u, int T) {
+    ARGCHK(c && x && u && T >= 1);
+    double TL; RCCHK(track_length_on(c, "lmpc_ss_add_trajectory_on", track_row, &TL));
+    return ss_add_trajectory_tl(c, x, u, T, TL);
+}
+int lmpc_ss_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int T) {
+    ARGCHK(c && x && u && T >= 1);
+    double TL; RCCHK(track_length_host(c, "lmpc_ss_add_trajectory", "lmpc_ss_add_trajectory_on", &TL));
+    return ss_add_trajectory_tl(c, x, u, T, TL);                        // LMPC.addTrajectory + computeCost (PredictiveControllers.py:418-464)
 }
 
 __global__ void lmpc_store_row_kernel(double *base, int stride, int row, double v0, double v1, double v2, double v3, double v4, double v5, double v6, double v7, double v8) {
@@ -701,6 +756,7 @@ __global__ void lmpc_store_row_kernel(double *base, int stride, int row, double 
 int lmpc_ss_add_point(lmpc_ctx *c, const double *x, const double *u) {
     ARGCHK(c && x && u);
     if (c->s_len.empty()) return set_err(LMPC_E_STATE, "addPoint before any addTrajectory", "");
+    double TL; RCCHK(track_length_host(c, "lmpc_ss_add_point", "lmpc_ss_extend_lap_on", &TL));
     HIPCHK(hipSetDevice(c->cfg.device));
     RESOLVE_PENDING();
     const int lap = (int)c->s_len.size() - 1, row = c->s_len[lap];
@@ -708,7 +764,7 @@ int lmpc_ss_add_point(lmpc_ctx *c, const double *x, const double *u) {
     const double q = c->s_qlast[lap] - 1.0;                        // :474
     double *base = c->sstore + (size_t)lap * LMPC_COLS * c->cfg.max_lap_len;
     hipLaunchKernelGGL(lmpc_store_row_kernel, dim3(1), dim3(64), 0, c->stream, base, c->cfg.max_lap_len, row,
-                       x[0], x[1], x[2], x[3], x[4] + c->cfg.trackLength, x[5], u[0], u[1], q);   // :472-473
+                       x[0], x[1], x[2], x[3], x[4] + TL, x[5], u[0], u[1], q);   // :472-473
     HIPCHK(hipGetLastError());
     c->s_len[lap] = row + 1; c->s_qlast[lap] = q; c->sst_dirty = true;
     return LMPC_OK;
@@ -716,7 +772,7 @@ int lmpc_ss_add_point(lmpc_ctx *c, const double *x, const double *u) {
 int lmpc_ss_replace_lap(lmpc_ctx *c, int lap, const double *x, const double *u, const double *qfun, int T) {
     ARGCHK(c && x && u && qfun && lap >= 0 && lap < (int)c->s_len.size() && T >= 1);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
-    RCCHK(commit_host_lap(c, x, u, T, lap, -1, false));
+    RCCHK(commit_host_lap(c, x, u, T, lap, -1, false, track_length_of(c, 0)));     // (the cost the kernel writes is replaced below: the caller's Qfun stands)
     // the caller's Q-function over the cost the kernel wrote: column 8 of a lap is contiguous ([lap][column][row]; the stores may have moved above)
     HIPCHK(hipMemcpy(c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len, qfun, sizeof(double) * (size_t)T, hipMemcpyHostToDevice));
     c->s_len[lap] = T; c->s_qlast[lap] = qfun[T - 1]; c->s_q0[lap] = qfun[0]; c->sst_dirty = true;
@@ -789,16 +845,26 @@ int lmpc_store_read_lap(lmpc_ctx *c, int store, int lap, double *x, double *u, d
 
 int lmpc_ss_get_laptime(lmpc_ctx *c, int lap, int *T) { ARGCHK(c && T && lap >= 0 && lap < (int)c->s_laptime.size()); *T = c->s_laptime[lap]; return LMPC_OK; }
 
+static int ss_extend_lap_row(lmpc_ctx *c, int track_row, int lap, const double *x, const double *u, int n);
+int lmpc_ss_extend_lap_on(lmpc_ctx *c, int track_row, int lap, const double *x, const double *u, int n) {
+    ARGCHK(c && lap >= 0 && lap < (int)c->s_len.size() && n >= 0 && (n == 0 || (x && u)));
+    double TL; RCCHK(track_length_on(c, "lmpc_ss_extend_lap_on", track_row, &TL));
+    return ss_extend_lap_row(c, track_row, lap, x, u, n);
+}
 int lmpc_ss_extend_lap(lmpc_ctx *c, int lap, const double *x, const double *u, int n) {
     // batched-mode form of LMPC.addPoint (:466-474) for ANY stored lap: append n points shifted by TrackLength in s,
     // Q-function continuing to count down.  (In the reference the points of lap j extend lap j-1 one by one.)  The rows are appended as given, finite or not.
     ARGCHK(c && lap >= 0 && lap < (int)c->s_len.size() && n >= 0 && (n == 0 || (x && u)));
+    double TL; RCCHK(track_length_host(c, "lmpc_ss_extend_lap", "lmpc_ss_extend_lap_on", &TL));
+    return ss_extend_lap_row(c, 0, lap, x, u, n);
+}
+static int ss_extend_lap_row(lmpc_ctx *c, int track_row, int lap, const double *x, const double *u, int n) {
     if (n == 0) return LMPC_OK;
     HIPCHK(hipSetDevice(c->cfg.device));
     RESOLVE_PENDING();
     store_rows s; RCCHK(staged_rows(c, x, u, n, LMPC_EXTEND_TAIL(1), &s));
     const int car = 0;
-    return extend_laps(c, s, 1, &car, &lap, n, nullptr);
+    return extend_laps(c, s, 1, &car, &lap, n, nullptr, track_row);
 }
 
 int lmpc_ss_truncate_lap(lmpc_ctx *c, int lap, int T) {
@@ -844,7 +910,7 @@ int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *row
         // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
         const int logged = (r->kind == RO_PID && r->stop_at_line && done[car] >= 0) ? done[car] : r->t;
         if (T < (model ? 2 : 1) || T > logged) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, %d are logged (at least %d needed)", i, T, car, logged, model ? 2 : 1); return set_err(LMPC_E_ARG, "lmpc_rollout_commit_laps", msg); }
-        tab[(size_t)i] = {car, T, ss ? ns0 + i : -1, model ? nm0 + i : -1};
+        tab[(size_t)i] = {car, T, ss ? ns0 + i : -1, model ? nm0 + i : -1, track_length_of(c, car)};
     }
     std::vector<double> q0;
     RCCHK(commit_laps(c, s, tab, q0));
@@ -923,10 +989,12 @@ static void k1_grid(lmpc_ctx *c, int B, int *qg, int *nblk) {
 // The regression kernel in the build that fits the launch: the occupancy build when the grid exceeds one work-group per CU, and the
 // 8-rows-per-lane scan when every lap in use lies inside its first quantisation chunk half (<= 512 rows; k1_scan_lap).
 // The lap table a regression launch reads: the context's (k1_table_for) or a rollout session's snapshot.  dev == nullptr: none, the laps of the parameter block.
-struct k1_table { const int *dev; int stride; bool small; };
+// trk / trkStride: the per-problem tracks of the same launch (lmpc_track_set; null: the parameter block's track)
+struct k1_table { const int *dev; int stride; bool small; const double *trk; int trkStride; };
 // the context's table for a call of B problems (B points for lmpc_regress_points): one row serves all, else row b belongs to problem b and the counts must agree
 static int k1_table_for(lmpc_ctx *c, int B, k1_table *t) {
     t->dev = nullptr; t->stride = 0; t->small = true;
+    { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; t->trk = ts.dev; t->trkStride = ts.stride; }
     if (c->lt_n == 0) return LMPC_OK;
     if (c->lt_n > 1 && B != c->lt_n) {
         char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_model_set_lap_table holds %d rows", B, c->lt_n);
@@ -943,7 +1011,7 @@ static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, 
     const bool occ = nblk > c->n_cu;
     auto k = occ ? (small ? lmpc_regress_kernel<true, 8> : lmpc_regress_kernel<true, K1_RPL>) : (small ? lmpc_regress_kernel<false, 8> : lmpc_regress_kernel<false, K1_RPL>);
     if (t.dev) k = occ ? (small ? lmpc_regress_kernel<true, 8, true> : lmpc_regress_kernel<true, K1_RPL, true>) : (small ? lmpc_regress_kernel<false, 8, true> : lmpc_regress_kernel<false, K1_RPL, true>);
-    hipLaunchKernelGGL(k, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride);
+    hipLaunchKernelGGL(k, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride);
 }
 static int launch_regress(lmpc_ctx *c, int B, const double *d_xLin, int xstride, const double *d_uLin, double *dA, double *dB, double *dC, int *dst) {
     int rc = refresh_params(c, true, false, c->lt_n != 0); if (rc) return rc;
@@ -1060,7 +1128,9 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
     lmpc_solve_io io = io_in;
     if (!io.ssTab) { const int rc = ss_table_for(c, B, &io); if (rc) return rc; }
     if (!io.tune) { const int rc = tuning_for(c, B, &io); if (rc) return rc; }
-    if (io.ssTab && !io.tune) { io.tune = c->d_tune; io.tuneStride = 0; }      // (a table alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
+    // (per-problem tracks, lmpc_track_set: the selection reads the problem's TrackLength; B against the rows)
+    if (!io.trk && (io.mode & 1)) { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; io.trk = ts.dev; io.trkStride = ts.stride; }
+    if ((io.ssTab || io.trk) && !io.tune) { io.tune = c->d_tune; io.tuneStride = 0; }      // (a table or tracks alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
     // [A_k | B_k] from global memory only when the batch does not fit the CUs with it in LDS (N = 40: more than two QPs per CU); a batch that
     // fits runs 3 % faster from LDS (measured at N = 40, batch 512: 0.997 vs 1.030 ms)
     io.abPack = nullptr;
@@ -1094,7 +1164,7 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
     } else
 #endif
     // (a safe-set lap table, tuning rows: the condensed kernel has no per-problem lookup -- it takes Q pre-digested by the host, cd_hasq -- and is not taken: the kernels below serve them)
-    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
+    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune && c->trk_n == 0) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
        : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, B, io)        // fused step: the one-wave kernel runs the regression itself
        : (B <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, B, io)
        : (lmpc_solver_waves(c, B) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
@@ -1266,7 +1336,7 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     // (a lap table in force: the fused form reads the laps of the parameter block -- it lives in the variant libraries -- so the two-kernel step runs)
     // (likewise a safe-set lap table, lmpc_ss_set_lap_table: the fused form's LDS layout has no room behind it for the selected laps)
     // (likewise tuning rows, lmpc_tuning_set: the fused form has no per-problem-rows instantiation)
-    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0 && !(term && c->sst_n) && c->tune_n == 0;
+    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0 && !(term && c->sst_n) && c->tune_n == 0 && c->trk_n == 0;      // (likewise track rows, lmpc_track_set)
     double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
     // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
     // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
@@ -1385,6 +1455,41 @@ int lmpc_tuning_get(lmpc_ctx *c, int *n, double *rows, int capacity) {
     ARGCHK(c && n && capacity >= 0);
     *n = c->tune_n;
     if (rows) memcpy(rows, c->tune_rows.data(), sizeof(double) * LMPC_TUNING_NPAR * (size_t)std::min(c->tune_n, capacity));
+    return LMPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- track rows
+int lmpc_track_set(lmpc_ctx *c, int n, const double *rows) {
+    ARGCHK(c && n >= 0 && n <= c->cfg.max_batch && (rows || n == 0));
+    if (c->ro && c->ro->active) return set_err(LMPC_E_STATE, "lmpc_track_set", "a rollout session is active: a lap on a track that changes under it means nothing (lmpc_rollout_end first)");
+    char msg[160];
+    for (int r = 0; r < n; r++) {
+        const double *w = rows + (size_t)r * LMPC_TRACK_NPAR; const char *bad = nullptr;
+        for (int i = 0; i < LMPC_TRACK_NPAR && !bad; i++) if (!std::isfinite(w[i])) bad = "a non-finite entry";
+        if (!bad && !(w[0] >= 1.0 && w[0] <= (double)LMPC_MAX_TRACK_ROWS && w[0] == std::floor(w[0]))) bad = "the row count is not an integer in 1..16";
+        if (!bad && !(w[1] > 0.0)) bad = "trackLength <= 0";
+        for (int i = 0; !bad && i < (int)w[0]; i++) if (w[2 + i * 6 + 4] < 0.0) bad = "a negative segment length";
+        if (bad) { snprintf(msg, sizeof(msg), "row %d: %s (the rows in force stay)", r, bad); return set_err(LMPC_E_ARG, "lmpc_track_set", msg); }
+    }
+    // launches still pending their retry pass read the image of THEIR launch: they are resolved, and the stream is drained, before it is overwritten (as for tuning)
+    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    if (n > 0) {
+        const size_t len = (size_t)n * LMPC_TRACK_NPAR;
+        // (a larger image goes into a new allocation that replaces the old one only once it is filled: a HIP failure on the way leaves the image in force as it was)
+        const bool grow = len > c->d_trk_cap;
+        double *buf = c->d_trk;
+        if (grow) HIPCHK(g_malloc(&buf, len * sizeof(double)));
+        const hipError_t e = hipMemcpy(buf, rows, len * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { if (grow) (void)g_free(buf); return set_err(LMPC_E_HIP, "hipMemcpy (track image)", hipGetErrorString(e)); }
+        if (grow) { if (c->d_trk) (void)g_free(c->d_trk); c->d_trk = buf; c->d_trk_cap = len; }
+    }
+    c->trk_rows.assign(rows, rows + (size_t)n * LMPC_TRACK_NPAR); c->trk_n = n;
+    return LMPC_OK;
+}
+int lmpc_track_get(lmpc_ctx *c, int *n, double *rows, int capacity) {
+    ARGCHK(c && n && capacity >= 0);
+    *n = c->trk_n;
+    if (rows) memcpy(rows, c->trk_rows.data(), sizeof(double) * LMPC_TRACK_NPAR * (size_t)std::min(c->trk_n, capacity));
     return LMPC_OK;
 }
 
@@ -1531,6 +1636,7 @@ int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg,
     const bool par = c->plant_n > 0;
     std::vector<double> rows;
     if (par) { const int rc = plant_rows_for(c, B, rows); if (rc) return rc; }
+    trk_src ts; { const int rc = track_for(c, B, &ts); if (rc) return rc; }      // (car b on track row b)
     double *d; { void *q; const int rc = pooled_scratch(c, sizeof(double) * (size_t)B * (29 + LMPC_PLANT_NPAR) + sizeof(int) * (size_t)B, &q); if (rc) return rc; d = (double *)q; }
     double *dp = d + (size_t)B * 29;
     int *ds = (int *)(d + (size_t)B * (29 + LMPC_PLANT_NPAR));
@@ -1539,8 +1645,11 @@ int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg,
     const dim3 grid((B + PLANT_CARS - 1) / PLANT_CARS);
     if (par) {
         H2D(dp, rows.data(), rows.size());                            // (`rows` lives until the stream is drained below)
-        hipLaunchKernelGGL(lmpc_plant_kernel<true>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds, (const double *)dp);
-    } else hipLaunchKernelGGL(lmpc_plant_kernel<false>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds, (const double *)nullptr);
+    }
+    const double *kp = par ? dp : nullptr;
+    auto k = par ? lmpc_plant_kernel<true> : lmpc_plant_kernel<false>;
+    if (ts.dev) k = par ? lmpc_plant_kernel<true, true> : lmpc_plant_kernel<false, true>;
+    hipLaunchKernelGGL(k, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds, kp, ts.dev, ts.stride);
     HIPCHK(hipGetLastError());
     D2H(xn, dxn, (size_t)B * 6); D2H(xgn, dgn, (size_t)B * 6); D2H(status, ds, B);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1551,10 +1660,12 @@ int lmpc_global_position_batch(lmpc_ctx *c, int n, const double *s, const double
     ARGCHK(c && s && ey && xy && status && n >= 1);
     HIPCHK(hipSetDevice(c->cfg.device));
     int rc = refresh_params(c, false, false); if (rc) return rc;
+    trk_src ts; rc = track_for(c, n, &ts); if (rc) return rc;         // (point e on track row e)
     double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * (size_t)n * 4 + sizeof(int) * (size_t)n, &q); if (rc2) return rc2; d = (double *)q; }
     int *ds = (int *)(d + (size_t)n * 4);
     H2D(d, s, (size_t)n); H2D(d + n, ey, (size_t)n);
-    hipLaunchKernelGGL(lmpc_global_position_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->dp, n, d, d + n, d + 2 * (size_t)n, ds);
+    hipLaunchKernelGGL(ts.dev ? lmpc_global_position_kernel<true> : lmpc_global_position_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->dp, n,
+                       (const double *)d, (const double *)(d + n), d + 2 * (size_t)n, ds, ts.dev, ts.stride);
     HIPCHK(hipGetLastError());
     D2H(xy, d + 2 * (size_t)n, (size_t)n * 2); D2H(status, ds, (size_t)n);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1567,12 +1678,14 @@ int lmpc_local_position_batch(lmpc_ctx *c, int n, const double *x, const double 
     ARGCHK(c && x && y && psi && s && ey && epsi && status && n >= 1 && std::isfinite(max_ey) && max_ey >= 0.0);
     HIPCHK(hipSetDevice(c->cfg.device));
     int rc = refresh_params(c, false, false); if (rc) return rc;
+    trk_src ts; rc = track_for(c, n, &ts); if (rc) return rc;         // (point e on track row e)
     const size_t m = (size_t)n;
     double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * m * 6 + sizeof(int) * m, &q); if (rc2) return rc2; d = (double *)q; }
     int *ds = (int *)(d + m * 6);
     H2D(d, x, m); H2D(d + m, y, m); H2D(d + 2 * m, psi, m);
-    hipLaunchKernelGGL(lmpc_local_position_kernel, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m, (const double *)d, (const double *)(d + m),
-                       (const double *)(d + 2 * m), (size_t)1, max_ey, d + 3 * m, d + 4 * m, d + 5 * m, (size_t)1, ds, (const double *)nullptr, (double *)nullptr);
+    hipLaunchKernelGGL(ts.dev ? lmpc_local_position_kernel<true> : lmpc_local_position_kernel<false>, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m,
+                       (const double *)d, (const double *)(d + m), (const double *)(d + 2 * m), (size_t)1, max_ey, d + 3 * m, d + 4 * m, d + 5 * m, (size_t)1, ds,
+                       (const double *)nullptr, (double *)nullptr, ts.dev, ts.stride, (size_t)0);
     HIPCHK(hipGetLastError());
     D2H(s, d + 3 * m, m); D2H(ey, d + 4 * m, m); D2H(epsi, d + 5 * m, m); D2H(status, ds, m);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1583,11 +1696,13 @@ int lmpc_track_angle_batch(lmpc_ctx *c, int n, const double *s, const double *ep
     ARGCHK(c && s && epsi && psi && status && n >= 1);
     HIPCHK(hipSetDevice(c->cfg.device));
     int rc = refresh_params(c, false, false); if (rc) return rc;
+    trk_src ts; rc = track_for(c, n, &ts); if (rc) return rc;         // (point e on track row e)
     const size_t m = (size_t)n;
     double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * m * 3 + sizeof(int) * m, &q); if (rc2) return rc2; d = (double *)q; }
     int *ds = (int *)(d + m * 3);
     H2D(d, s, m); H2D(d + m, epsi, m);
-    hipLaunchKernelGGL(lmpc_track_angle_kernel, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m, (const double *)d, (const double *)(d + m), d + 2 * m, ds);
+    hipLaunchKernelGGL(ts.dev ? lmpc_track_angle_kernel<true> : lmpc_track_angle_kernel<false>, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m,
+                       (const double *)d, (const double *)(d + m), d + 2 * m, ds, ts.dev, ts.stride);
     HIPCHK(hipGetLastError());
     D2H(psi, d + 2 * m, m); D2H(status, ds, m);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1601,12 +1716,14 @@ int lmpc_state_from_global_batch(lmpc_ctx *c, int T, int B, const double *xglob,
     ARGCHK(((unsigned long long)T * (unsigned long long)B + LMPC_TRACK_NT - 1) / LMPC_TRACK_NT <= 0x7fffffffull);
     HIPCHK(hipSetDevice(c->cfg.device));
     int rc = refresh_params(c, false, false); if (rc) return rc;
+    trk_src ts; rc = track_for(c, B, &ts); if (rc) return rc;         // (car b of the T x B log on track row b)
     const size_t m = (size_t)T * (size_t)B;
     double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * m * 12 + sizeof(int) * m, &q); if (rc2) return rc2; d = (double *)q; }
     double *dx = d + m * 6; int *ds = (int *)(d + m * 12);
     H2D(d, xglob, m * 6);
-    hipLaunchKernelGGL(lmpc_local_position_kernel, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m, (const double *)(d + 4), (const double *)(d + 5),
-                       (const double *)(d + 3), (size_t)6, max_ey, dx + 4, dx + 5, dx + 3, (size_t)6, ds, (const double *)d, dx);
+    hipLaunchKernelGGL(ts.dev ? lmpc_local_position_kernel<true> : lmpc_local_position_kernel<false>, dim3(lmpc_track_grid(m)), dim3(LMPC_TRACK_NT), 0, c->stream, c->dp, m,
+                       (const double *)(d + 4), (const double *)(d + 5), (const double *)(d + 3), (size_t)6, max_ey, dx + 4, dx + 5, dx + 3, (size_t)6, ds, (const double *)d, dx,
+                       ts.dev, ts.stride, (size_t)B);
     HIPCHK(hipGetLastError());
     D2H(x, dx, m * 6); D2H(status, ds, m);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1628,6 +1745,7 @@ static void rollout_free(lmpc_ctx *c) {
 static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
     HIPCHK(hipSetDevice(c->cfg.device));
     const size_t S = c->dims.S, Bz = B;
+    trk_src trk; { const int rc = track_for(c, B, &trk); if (rc) return rc; }      // (car b on track row b: refused before any session state changes)
     std::vector<double> par_rows;                               // refused before any session state changes (B beyond the per-car rows)
     if (c->plant_n > 0) { const int rc = plant_rows_for(c, B, par_rows); if (rc) return rc; }
     std::vector<int> lt_rows; bool lt_small = true;             // sessions that run the regression: the lap table in force, one resolved row per car (refused here as well when B is not its row count)
@@ -1688,6 +1806,7 @@ init_state:
     r->nz_seed = c->noise_seed; r->nz_lap = c->noise_lap; r->nz_car0 = c->noise_car0;
     if (noise) H2D(r->d_noise, noise, (size_t)T_max * Bz * 3);
     else { lmpc_noise_fill_launch(c->stream, r->nz_seed, 0ull, r->nz_lap, 0, T_max, r->nz_car0, B, 3, r->d_noise); HIPCHK(hipGetLastError()); }
+    r->trk = trk.dev; r->trk_stride = trk.stride;
     r->has_par = !par_rows.empty();                             // the snapshot: lmpc_plant_set_params during the session reaches the next one only
     if (r->has_par) H2D(r->d_par, par_rows.data(), par_rows.size());
     r->has_lt = !lt_rows.empty(); r->lt_small = lt_small; r->lt_stride = 2 * c->cfg.trToUse;   // the snapshot: lmpc_model_set_lap_table during the session reaches the next one only
@@ -1701,7 +1820,7 @@ static void rollout_state(lmpc_rollout_session *r, lmpc_rollout_state &st) {
     const lmpc_arrays &a = r->a; st.x = a.x0; st.xg = r->d_xg; st.xLin = a.xLin; st.uLin = a.uLin; st.uOld = a.uOld; st.zt = a.zt; st.xPP = a.xPredPrev;
     st.hasPred = a.hasPred; st.timeStep = a.timeStep; st.doneAt = r->d_done; st.xPred = a.xPred; st.uPred = a.uPred; st.ztNext = a.ztNext; st.ztuNext = a.ztuNext;
     st.status = a.status; st.logX = r->d_logX; st.logU = r->d_logU; st.logG = r->d_logG; st.noise = r->d_noise; st.nDone = r->d_nDone; st.statusAcc = r->d_stAcc;
-    st.finX = r->d_finX; st.finG = r->d_finG; st.plantPar = r->d_par;
+    st.finX = r->d_finX; st.finG = r->d_finG; st.plantPar = r->d_par; st.trk = r->trk; st.trkStride = r->trk_stride;
 }
 extern "C" {
 int lmpc_rollout_begin(lmpc_ctx *c, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
@@ -1777,8 +1896,11 @@ int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const doub
     if (e != hipSuccess) return fail(set_err(LMPC_E_HIP, "lmpc_rollout_pid", hipGetErrorString(e)));
     lmpc_rollout_state st; rollout_state(r, st);
     const dim3 grid((B + PLANT_CARS - 1) / PLANT_CARS);
-    if (r->has_par) hipLaunchKernelGGL(lmpc_pid_rollout_kernel<true>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0, (const double *)r->d_vt, (const double *)r->d_noiseU, st);
-    else hipLaunchKernelGGL(lmpc_pid_rollout_kernel<false>, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0, (const double *)r->d_vt, (const double *)r->d_noiseU, st);
+    {
+        auto k = r->has_par ? lmpc_pid_rollout_kernel<true> : lmpc_pid_rollout_kernel<false>;
+        if (r->trk) k = r->has_par ? lmpc_pid_rollout_kernel<true, true> : lmpc_pid_rollout_kernel<false, true>;
+        hipLaunchKernelGGL(k, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0, (const double *)r->d_vt, (const double *)r->d_noiseU, st);
+    }
     e = hipGetLastError();
     std::vector<int> done(Bz);
     if (e == hipSuccess) e = hipMemcpyAsync(done.data(), r->d_done, sizeof(int) * Bz, hipMemcpyDeviceToHost, c->stream);
@@ -1815,7 +1937,7 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         rc = refresh_params(c, true, lmpc, r->has_lt, io.ssTab != nullptr); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
         ev_begin(c, 0);
         { int qg, nblk; k1_grid(c, B, &qg, &nblk);
-          const k1_table tab = {r->has_lt ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small};
+          const k1_table tab = {r->has_lt ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small, r->trk, r->trk_stride};
           launch_k1(c, nblk, B, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
         ev_end(c); c->stats.n_regress++;
         }
@@ -1824,8 +1946,11 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         rc = launch_solve(c, B, io, true); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
         HIPCHK(hipEventRecord(r->e_solved, c->stream));
         HIPCHK(hipStreamWaitEvent(r->pstream, r->e_solved, 0));
-        if (r->has_par) hipLaunchKernelGGL(lmpc_rollout_plant_kernel<true>, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
-        else hipLaunchKernelGGL(lmpc_rollout_plant_kernel<false>, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
+        {
+            auto k = r->has_par ? lmpc_rollout_plant_kernel<true> : lmpc_rollout_plant_kernel<false>;
+            if (r->trk) k = r->has_par ? lmpc_rollout_plant_kernel<true, true> : lmpc_rollout_plant_kernel<false, true>;
+            hipLaunchKernelGGL(k, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
+        }
         HIPCHK(hipEventRecord(r->e_plant, r->pstream));
         if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->a.uPred, r->a.uOld);
         else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression

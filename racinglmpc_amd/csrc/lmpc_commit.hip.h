@@ -15,14 +15,15 @@
 #define LMPC_COMMIT_RPT (K1_CHUNK / LMPC_COMMIT_NT)      // rows of one prefilter chunk per thread, CONSECUTIVE ones (see commit_first_min)
 static_assert(K1_CHUNK % LMPC_COMMIT_NT == 0 && LMPC_COMMIT_NT % 64 == 0, "one prefilter chunk is a whole number of rows per thread");
 
-struct lmpc_commit_entry { int car, rows, ss_slot, m_slot; };          // slots: -1 = that store is not written
+struct lmpc_commit_entry { int car, rows, ss_slot, m_slot; double TL; };   // slots: -1 = that store is not written; TL: the trackLength computeCost compares s with -- the
+                                                                        // entry's own, since cars may be on different tracks (lmpc_track_set) and a host lap is "car 0" of a one-car source
 struct lmpc_commit_args {
     const double *logX, *logU; int B;                                   // the source
     double *sstore, *mstore; unsigned *mquant; double *mqpar;           // the stores and the prefilter image (lmpc_ctx)
     int ls, mq_chunks;                                                  // row stride of every column (max_lap_len); chunks the image holds per lap
-    double TL, scaling[5];
+    double scaling[5];
 };
-struct lmpc_extend_entry { int car, lap, row0, pad; };                 // row0: rows the lap holds now (the first appended row)
+struct lmpc_extend_entry { int car, lap, row0, pad; double TL; };      // row0: rows the lap holds now (the first appended row); TL: the trackLength added to s (:472), the entry's own
 
 // The minimum / maximum of a feature over a chunk is the one a scan in row order finds when it replaces its value only by a strictly smaller / larger one: among equals
 // (+0.0 and -0.0 compare equal) the value met FIRST stays, which defines the sign of a zero minimum.  "Keep the left one on a tie" is associative, so a reduction
@@ -121,13 +122,13 @@ __device__ __forceinline__ void commit_quantise(const lmpc_commit_args &a, int c
 // LMPC.computeCost (PredictiveControllers.py:447-464): cost[T-1] = 0, backwards cost[r] = cost[r+1] + 1 where s[r] < trackLength, else 0 (a NaN s is not below) -- the
 // distance from r to the nearest row r' >= r that is the last one or has !(s < trackLength).  Small integers: exact in any order.  256 rows per pass, from the end of
 // the lap; *q0 = cost[0].
-__device__ __forceinline__ void commit_cost(const lmpc_commit_args &a, int car, int T, double *qcol, double *q0, int *nearw) {
+__device__ __forceinline__ void commit_cost(const lmpc_commit_args &a, int car, int T, double TL, double *qcol, double *q0, int *nearw) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int carry = T - 1;                                                  // the nearest such row at or behind the end of the pass
     for (int base = ((T - 1) / LMPC_COMMIT_NT) * LMPC_COMMIT_NT; base >= 0; base -= LMPC_COMMIT_NT) {
         const int r = base + tid;
         int idx = 0x7fffffff;
-        if (r < T && (r == T - 1 || !(a.logX[((size_t)r * a.B + car) * 6 + 4] < a.TL))) idx = r;
+        if (r < T && (r == T - 1 || !(a.logX[((size_t)r * a.B + car) * 6 + 4] < TL))) idx = r;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_down(idx, off, 64); if (lane + off < 64) idx = min(idx, o); }     // suffix minimum within the wave
         __syncthreads();
@@ -157,7 +158,7 @@ __global__ void __launch_bounds__(LMPC_COMMIT_NT) lmpc_commit_laps_kernel(lmpc_c
 #pragma unroll
         for (int j = 0; j < 8; j++) { if (sb) sb[(size_t)j * ls + t] = v[j]; if (mb) mb[(size_t)j * ls + t] = v[j]; }
     }
-    if (sb) commit_cost(a, e.car, T, sb + (size_t)8 * ls, q0 + blockIdx.x, nearw);
+    if (sb) commit_cost(a, e.car, T, e.TL, sb + (size_t)8 * ls, q0 + blockIdx.x, nearw);
     if (mb) commit_quantise(a, e.car, T, e.m_slot, red);
 }
 
@@ -186,7 +187,7 @@ __global__ void __launch_bounds__(LMPC_COMMIT_NT) lmpc_extend_laps_kernel(lmpc_c
     for (int i = tid; i < n_rows * 8; i += LMPC_COMMIT_NT) {
         const int j = i / n_rows, t = i - j * n_rows;                  // column-major: neighbouring lanes, neighbouring rows
         double v = j < 6 ? a.logX[((size_t)t * a.B + e.car) * 6 + j] : a.logU[((size_t)t * a.B + e.car) * 2 + (j - 6)];
-        if (j == 4) v = v + a.TL;
+        if (j == 4) v = v + e.TL;
         base[(size_t)j * ls + t] = v;
     }
     const int per = (n_rows + LMPC_COMMIT_NT - 1) / LMPC_COMMIT_NT, t_lo = tid * per, t_hi = min(n_rows, t_lo + per);

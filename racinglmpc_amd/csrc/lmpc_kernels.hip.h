@@ -17,7 +17,7 @@
 #include "../../include/lmpc_hip.h"
 
 #define WAVE 64
-#define LMPC_VARIANT_ABI_REV 9          // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
+#define LMPC_VARIANT_ABI_REV 10         // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
                                         // (LMPC_VARIANT_ABI, lmpc_variant.hip.h) also folds in the three struct sizes, so that layout drift cannot pass on the number alone
 #define LMPC_COLS 9                 // lap-store columns: x0..x5, u0, u1, Qfun
 
@@ -85,8 +85,20 @@ __device__ __forceinline__ void wave_argmin(double &v, int &i) {
     }
 }
 
+// Per-element tracks (lmpc_track_set): an element's own row of the track image -- LMPC_TRACK_NPAR doubles: rows, trackLength, PointAndTangent 16 x 6 -- under the
+// member names of lmpc_dev_params.  The functions that read a track are templates on the source (TK: lmpc_dev_params or lmpc_track_row): with the parameter block
+// they are the text they were, so a launch without rows runs the code it ran before.
+struct lmpc_track_row { const double *track; int track_rows; double TL; };
+__device__ __forceinline__ lmpc_track_row track_row_at(const double *trk, size_t stride, size_t b) {
+    const double *r = trk + b * stride;
+    return {r + 2, (int)r[0], r[1]};
+}
+// the track source of an instantiation: the element's row (TRK) or the parameter block
+template <bool TRK> __device__ __forceinline__ decltype(auto) track_src(const lmpc_dev_params &p, const lmpc_track_row &t) { if constexpr (TRK) return (t); else return (p); }
+
 // Map.curvature, Track.py:292-310.  Returns 0 and sets *bad when s lies on no segment (the reference raises).
-__device__ __forceinline__ double track_curvature(const lmpc_dev_params &p, double s, int *bad) {
+template <class TK>
+__device__ __forceinline__ double track_curvature(const TK &p, double s, int *bad) {
     const double TL = p.TL;
     // `while s > TrackLength: s = s - TrackLength` of the reference, bounded: an infinite or absurd s (a diverged rollout) must not hang the
     // GPU -- beyond 64 laps it is reported as "on no segment", which is what the reference's own loop could never return from either
@@ -212,10 +224,14 @@ __device__ __forceinline__ double frsqrt(double x) {
 // Map.getGlobalPosition, Track.py:135-189: curvilinear (s, ey) -> inertial (X, Y), one thread per point (batched plotting /
 // logging export of predicted trajectories and safe-set points).  Row i - 1 of the table wraps to the last
 // row for i = 0, as the reference's negative index does.
-__global__ void lmpc_global_position_kernel(lmpc_dev_params p, int n, const double *__restrict__ s_in, const double *__restrict__ ey_in,
-                                            double *__restrict__ xy, int *__restrict__ status) {
+// TRK: point e reads row e of trk (stride doubles between rows; 0: one row serves every point) instead of the parameter block's track (lmpc_track_set).
+template <bool TRK>
+__global__ void lmpc_global_position_kernel(lmpc_dev_params p_, int n, const double *__restrict__ s_in, const double *__restrict__ ey_in,
+                                            double *__restrict__ xy, int *__restrict__ status, const double *__restrict__ trk, int trkStride) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
+    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(trk, (size_t)trkStride, (size_t)e);
+    const auto &p = track_src<TRK>(p_, tr_);
     const double PI = 3.141592653589793;
     double s = s_in[e]; const double ey = ey_in[e];
     for (int lap = 0; lap < 4096 && s > p.TL; lap++) s = s - p.TL;                          // (`while s > TrackLength`, bounded: an infinite s must not hang the GPU)
@@ -523,7 +539,8 @@ __device__ __forceinline__ void k1_scan_lap(const lmpc_dev_params &p, const k1_s
 // pass (selection in sm.seld / seli / nsel), by the nt threads of the work-group: A_i | B_i | C_i end up in sm.outv[0 .. nf), status bits in
 // sm.st_s[q0 ..].  xq: the problem's xLin rows (6 doubles each, row i0 = first query of the pass).  Work-group barriers inside.  TAB / lt: see k1_lap_slot.
 template <bool TAB = false>
-__device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &sm, int q0, int nf, int tid, int nt, const double *xq_pass, int MAXP, const int *lt = nullptr) {
+__device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &sm, int q0, int nf, int tid, int nt, const double *xq_pass, int MAXP, const int *lt = nullptr,
+                                       const double *trk = nullptr) {
     const int L = p.trToUse, PP = L * MAXP;
     const double h = p.h;
     // ---- assemble A_i, B_i, C_i (:70-135), one thread per query.  The kinematic rows (epsi, s, ey) depend on the query state only: they are
@@ -538,7 +555,8 @@ __device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &
         for (int j = 0; j < 6; j++) sm.outv[ql][36 + 6 + j] = 0.0;
         const double vx = xq[0], vy = xq[1], wz = xq[2], epsi = xq[3], s = xq[4], ey = xq[5], dt = p.dt;
         int bad = 0;
-        const double cur = track_curvature(p, s, &bad);
+        // (trk: the problem's own track row, lmpc_track_set -- one test per query; null: the parameter block's track)
+        const double cur = trk ? track_curvature(track_row_at(trk, 0, 0), s, &bad) : track_curvature(p, s, &bad);
         if (bad) atomicOr(&sm.st_s[qi], LMPC_ST_NO_SEGMENT);
         const double den = 1 - cur * ey, ce = cos(epsi), se = sin(epsi);
         const double xv[6] = {vx, vy, wz, epsi, s, ey};
@@ -659,7 +677,8 @@ template <bool OCC, int RPL, bool TAB = false>
 __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 : 6) : 4) : 2) void lmpc_regress_kernel(lmpc_dev_params p, int B, int qg, const double *__restrict__ xLin, int xstride,
                                                              const double *__restrict__ uLin, double *__restrict__ Aout,
                                                              double *__restrict__ Bout, double *__restrict__ Cout, int *__restrict__ status,
-                                                             const int *__restrict__ lapTab, int tabStride) {
+                                                             const int *__restrict__ lapTab, int tabStride,
+                                                             const double *__restrict__ trk, int trkStride) {      // trk: per-problem tracks (lmpc_track_set), or null: the parameter block's; see k1_fit
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);             // wave-uniform by construction: lap pointers, row counts and loop bounds stay in SGPRs
     __shared__ double qf[K1_QG][5];
@@ -703,7 +722,7 @@ __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 
         k1_scan_lap<!OCC, RPL, TAB>(p, sm, c, wave * K1_QG, sgi, nsub, nq, lane, MAXP, lt);
     __syncthreads();
     K1STAMP(2);
-    k1_fit<TAB>(p, sm, 0, nq, tid, K1_NT, xLin + (size_t)b * xstride + (size_t)i0 * 6, MAXP, lt);
+    k1_fit<TAB>(p, sm, 0, nq, tid, K1_NT, xLin + (size_t)b * xstride + (size_t)i0 * 6, MAXP, lt, trk ? trk + (size_t)b * trkStride : nullptr);
     for (int e = tid; e < nq * 54; e += K1_NT) {
         const int qi = e / 54, le = e % 54; const size_t item = (size_t)b * N + i0 + qi;
         if (le < 36) Aout[item * 36 + le] = outv[qi][le];
@@ -2147,7 +2166,8 @@ __device__ __forceinline__ void plant_sincos_fast(const plant_coeffs &k_, double
 // 7 here) runs a few times per simulated step instead of 100 times.  Same arithmetic and the same comparisons as track_curvature on the segment found -- the
 // wrap `while s > TrackLength` is repeated every call, the segments are disjoint, the reference takes the first that matches -- hence the same value.
 struct plant_seg { double c0, c1, cur; int nw; };
-__device__ __forceinline__ double plant_curvature(const lmpc_dev_params &p, double s, plant_seg &g, int *bad) {
+template <class TK>
+__device__ __forceinline__ double plant_curvature(const TK &p, double s, plant_seg &g, int *bad) {
     const double TL = p.TL;
     // the cached number of wraps first, branch-free: the same sequential subtractions the reference's loop makes (bit-identical s), up to three of them.
     // It is the loop's result iff the value before the last subtraction was > TL (s_w > 0 here, or no subtraction) and the result is not (> TL) -- implied by
@@ -2186,8 +2206,9 @@ struct plant_lds { double v[2][PLANT_CARS][3]; };
 // right: (1 / m) is a value of its own there, so dividing once in front of the loop gives the same bits (IEEE division: the build has no fast-math flag).  The rear
 // slip angle uses lf, as the reference does (SysModel.py:97); lr enters the yaw equation only (:106).  The guards test the computed arguments, so a car whose B or C
 // pushes one out of the fast range takes the ocml routines like a sliding car.
-template <bool PAR>
-__device__ __forceinline__ void plant_step_duo(const lmpc_dev_params &p, plant_lds &L, const double *x, const double *xg, const double *u, const double *nz,
+// TK: the car's track -- the parameter block, or the lane's own lmpc_track_row (pointer, row count and TL in registers; only the table walk reads the row).
+template <bool PAR, class TK>
+__device__ __forceinline__ void plant_step_duo(const TK &p, plant_lds &L, const double *x, const double *xg, const double *u, const double *nz,
                                                double *xn, double *xgn, int *bad, const int wave, const int role, const int cl, const double *par = nullptr) {
     constexpr double m0 = 1.98, lf0 = 0.125, lr0 = 0.125, Iz0 = 0.024;
     constexpr double Df0 = 0.8 * m0 * 9.81 / 2.0, Cf0 = 1.25, Bf0 = 1.0;             // rear tyre: same D, C, B (SysModel.py:68-76)
@@ -2264,15 +2285,19 @@ __device__ __forceinline__ void plant_step_duo(const lmpc_dev_params &p, plant_l
 }
 
 // PAR (here and in the two rollout kernels below): car b integrates with row b of par (B x LMPC_PLANT_NPAR) instead of the reference's vehicle; see plant_step_duo.
-template <bool PAR>
+// TRK (likewise): car b drives on row b of trk (lmpc_track_set; trkStride doubles between rows, 0: one row for every car) -- the table walk of plant_curvature reads
+// the car's row, and the finish line is the row's trackLength, kept in the lane's registers.  The 32 cars of a work-group may be on 32 tracks.
+template <bool PAR, bool TRK = false>
 __global__ __launch_bounds__(PLANT_NT) void lmpc_plant_kernel(lmpc_dev_params p, int B, const double *__restrict__ x, const double *__restrict__ xg, const double *__restrict__ u,
-                                  const double *__restrict__ nz, double *__restrict__ xn, double *__restrict__ xgn, int *__restrict__ status, const double *__restrict__ par) {
+                                  const double *__restrict__ nz, double *__restrict__ xn, double *__restrict__ xgn, int *__restrict__ status, const double *__restrict__ par,
+                                  const double *__restrict__ trk, int trkStride) {
     __shared__ plant_lds L;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, cl = lane >> 1, role = lane & 1;
     const int b0 = blockIdx.x * PLANT_CARS + cl; const bool on = b0 < B; const int b = on ? b0 : B - 1;      // (a lane without a car repeats the last one: barriers inside)
     int bad = 0;
     double xo[6], go[6];
-    plant_step_duo<PAR>(p, L, x + (size_t)b * 6, xg + (size_t)b * 6, u + (size_t)b * 2, nz + (size_t)b * 3, xo, go, &bad, wave, role, cl, PAR ? par + (size_t)b * LMPC_PLANT_NPAR : nullptr);
+    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(trk, (size_t)trkStride, (size_t)b);
+    plant_step_duo<PAR>(track_src<TRK>(p, tr_), L, x + (size_t)b * 6, xg + (size_t)b * 6, u + (size_t)b * 2, nz + (size_t)b * 3, xo, go, &bad, wave, role, cl, PAR ? par + (size_t)b * LMPC_PLANT_NPAR : nullptr);
     if (wave == 1 && role == 0 && on) {
         for (int j = 0; j < 6; j++) { xn[(size_t)b * 6 + j] = xo[j]; xgn[(size_t)b * 6 + j] = go[j]; }
         if (status) status[b] = bad ? LMPC_ST_NO_SEGMENT : 0;
@@ -2287,6 +2312,7 @@ struct lmpc_rollout_state {
     double *logX, *logU, *logG; const double *noise; int *nDone, *statusAcc;                   // logs [T][B][..], noise [T][B][3]
     double *finX, *finG;                                                                       // state right after the crossing step
     const double *plantPar;                                                                    // B x LMPC_PLANT_NPAR, the session's snapshot of the per-car vehicle constants (PAR kernels only)
+    const double *trk; int trkStride;                                                          // the context's track image (TRK kernels only; lmpc_track_set is refused while a session is active)
 };
 // The step's bookkeeping and its plant integration are two kernels on two streams: the shift of the linearisation trajectory
 // feeds the NEXT step's regression kernel, which does not need the plant's result and runs concurrently with it; only the next
@@ -2314,7 +2340,7 @@ __global__ __launch_bounds__(256) void lmpc_rollout_shift_kernel(lmpc_dev_params
     }
     if (e == 0) { r.hasPred[b] = 1; r.timeStep[b] = t + 1; }
 }
-template <bool PAR>
+template <bool PAR, bool TRK = false>
 __global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_params p, int B, int t, lmpc_rollout_state r) {
     __shared__ plant_lds L;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, cl = lane >> 1, role = lane & 1;     // two waves per 32 cars, see plant_step_duo
@@ -2329,13 +2355,15 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_p
         r.logU[((size_t)t * B + b) * 2] = u0[0]; r.logU[((size_t)t * B + b) * 2 + 1] = u0[1];
     }
     int bad = 0; double xo[6], go[6];
-    plant_step_duo<PAR>(p, L, x, xg, u0, r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl, PAR ? r.plantPar + (size_t)b * LMPC_PLANT_NPAR : nullptr);
+    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(r.trk, (size_t)r.trkStride, (size_t)b);
+    const auto &tk = track_src<TRK>(p, tr_);
+    plant_step_duo<PAR>(tk, L, x, xg, u0, r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl, PAR ? r.plantPar + (size_t)b * LMPC_PLANT_NPAR : nullptr);
     if (writer) {
         for (int j = 0; j < 6; j++) { x[j] = xo[j]; xg[j] = go[j]; }
         // status bits count only up to and including the step that crosses the line: a finished car keeps being simulated until
         // the slowest rollout ends, and whatever happens to it there (window past the lap end, ...) does not belong to its lap
         if (r.doneAt[b] < 0) r.statusAcc[b] |= r.status[b] | (bad ? LMPC_ST_NO_SEGMENT : 0);
-        if (r.doneAt[b] < 0 && xo[4] > p.TL) {                                                 // lap completed, SysModel.py:45
+        if (r.doneAt[b] < 0 && xo[4] > tk.TL) {                                                 // lap completed, SysModel.py:45
             r.doneAt[b] = t + 1; atomicAdd(r.nDone, 1);
             for (int j = 0; j < 6; j++) { r.finX[(size_t)b * 6 + j] = xo[j]; r.finG[(size_t)b * 6 + j] = go[j]; }
         }
@@ -2363,7 +2391,7 @@ __device__ __forceinline__ void pid_control_law(const double *x, double vt, cons
     u0 = -0.6 * x[5] - 0.9 * x[3] + c0;
     u1 = 1.5 * (vt - x[0]) + c1;
 }
-template <bool PAR>
+template <bool PAR, bool TRK = false>
 __global__ __launch_bounds__(PLANT_NT) void lmpc_pid_rollout_kernel(lmpc_dev_params p, int B, int T_max, int stop_at_line, const double *__restrict__ vt,
                                                                     const double *__restrict__ noise_u /* T_max x B x 2 */, lmpc_rollout_state r) {
     __shared__ plant_lds L;
@@ -2372,6 +2400,8 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_pid_rollout_kernel(lmpc_dev_par
     const int b0 = blockIdx.x * PLANT_CARS + cl; const bool on = b0 < B; const int b = on ? b0 : B - 1;      // (a lane without a car repeats the last one: barriers inside)
     const bool keeper = wave == 1 && role == 0;                        // the lane that owns car cl's LDS rows; it writes to global memory only if `on`
     const double vtb = vt[b];
+    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(r.trk, (size_t)r.trkStride, (size_t)b);
+    const auto &tk = track_src<TRK>(p, tr_);
     int done = -1, acc = 0;
     if (keeper) for (int j = 0; j < 6; j++) { sx[cl][j] = r.x[(size_t)b * 6 + j]; sg[cl][j] = r.xg[(size_t)b * 6 + j]; }
     for (int t = 0; t < T_max; t++) {
@@ -2386,12 +2416,12 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_pid_rollout_kernel(lmpc_dev_par
         }
         __syncthreads();
         int bad = 0; double xo[6], go[6];
-        plant_step_duo<PAR>(p, L, sx[cl], sg[cl], su[cl], r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl, PAR ? r.plantPar + (size_t)b * LMPC_PLANT_NPAR : nullptr);
+        plant_step_duo<PAR>(tk, L, sx[cl], sg[cl], su[cl], r.noise + ((size_t)t * B + b) * 3, xo, go, &bad, wave, role, cl, PAR ? r.plantPar + (size_t)b * LMPC_PLANT_NPAR : nullptr);
         if (keeper) {
             for (int j = 0; j < 6; j++) { sx[cl][j] = xo[j]; sg[cl][j] = go[j]; }
             if (done < 0) {
                 acc |= bad ? LMPC_ST_NO_SEGMENT : 0;
-                if (xo[4] > p.TL) {                                                             // lap completed, SysModel.py:45
+                if (xo[4] > tk.TL) {                                                            // lap completed, SysModel.py:45
                     done = t + 1;
                     if (on) for (int j = 0; j < 6; j++) { r.finX[(size_t)b * 6 + j] = xo[j]; r.finG[(size_t)b * 6 + j] = go[j]; }
                 }

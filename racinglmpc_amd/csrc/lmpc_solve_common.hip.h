@@ -43,6 +43,8 @@ struct lmpc_solve_io {
     int ssTabStride;          // (slot, rows, is the car's latest lap, pad), 16 bytes -- in the row's sorted order; ints between rows (0: one row serves every problem)
     const double *tune;       // optional: per-problem controller tuning (lmpc_tuning_set), the device image of the rows: PAR_TOT doubles per row in the PAR_* layout (doubled
     int tuneStride;           // weights, Fx / Fu of the context) -- what the staging copy of the parameter block reads instead of `p`; doubles between rows (0: one row serves every problem)
+    const double *trk;        // optional: per-problem tracks (lmpc_track_set), the device image of the rows (LMPC_TRACK_NPAR doubles each; [1] is the trackLength the selection reads).
+    int trkStride;            // Served by the per-problem-rows instantiations (the host sets io.tune with it); doubles between rows (0: one row serves every problem)
 };
 #define LMPC_SSTAB_ENTRY 4
 // With a table the selection keeps (slot, rows) of every selected lap for the successor rows of feasibleStateInput, beside sel_start: in LMPC_SSTAB_LDS bytes of
@@ -147,11 +149,15 @@ __device__ __forceinline__ void k2_select(const lmpc_dev_params &p, const lmpc_s
     const int N = N_ ? N_ : p.N, S = N_ ? S_ : p.S;
     const bool tab = TAB_ < 0 ? io.ssTab != nullptr : TAB_ != 0;
     if (io.mode & 1) {
+        // TrackLength of THIS problem: its track row (lmpc_track_set) in the per-problem-rows instantiations and the runtime kernel -- one double per problem, uniform
+        // over the wave -- else the parameter block's.  A retry pass gets the io of its own launch, hence the rows of its own launch.
+        double TL = p.TL;
+        if (TAB_ != 0) { if (io.trk) TL = io.trk[(size_t)b * io.trkStride + 1]; }
         double ztv[6];
 #pragma unroll
         for (int j = 0; j < 6; j++) ztv[j] = io.zt[(size_t)b * 6 + j];
         const double x04 = io.x0[(size_t)b * 6 + 4];
-        if (ztv[4] - x04 > p.TL / 2) ztv[4] = fmax(ztv[4] - p.TL, 0.0);        // :392-393
+        if (ztv[4] - x04 > TL / 2) ztv[4] = fmax(ztv[4] - TL, 0.0);        // :392-393
         if (io.ztUsed && wave == 0 && lane < 6) { double v = ztv[0];
 #pragma unroll
             for (int j = 1; j < 6; j++) if (lane == j) v = ztv[j];
@@ -162,7 +168,7 @@ __device__ __forceinline__ void k2_select(const lmpc_dev_params &p, const lmpc_s
 #pragma unroll
             for (int r0 = 0; r0 <= N; r0 += WAVE) {                               // N + 1 predicted rows: 65 at the largest horizon, one more than a wave has lanes
                 const int r = r0 + lane;
-                const int c_ = (r <= N && io.xPredPrev[((size_t)b * (N + 1) + (r <= N ? r : 0)) * 6 + 4] > p.TL) ? 1 : 0;
+                const int c_ = (r <= N && io.xPredPrev[((size_t)b * (N + 1) + (r <= N ? r : 0)) * 6 + 4] > TL) ? 1 : 0;
                 crossed += (int)__popcll(__ballot(c_));
             }
         }

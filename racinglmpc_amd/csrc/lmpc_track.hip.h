@@ -3,7 +3,8 @@
 // lmpc_global_position_kernel in lmpc_kernels.hip.h.  Included by lmpc_capi.hip only (the variant libraries carry no track kernel).
 //
 // Both kernels run one thread per point, LMPC_TRACK_NT threads per work-group, size_t indexing, the track table read from the lmpc_dev_params kernel argument as
-// lmpc_global_position_kernel reads it; no LDS, no scratch.  The only loops are the walk over the track rows (bounded by track_rows) and the bounded lap wrap of s.
+// lmpc_global_position_kernel reads it -- or, in the TRK instantiations, from the point's own row of the track image (lmpc_track_set; lmpc_kernels.hip.h:
+// lmpc_track_row) --; no LDS, no scratch.  The only loops are the walk over the track rows (bounded by track_rows) and the bounded lap wrap of s.
 //
 // getLocalPosition is a chain of branch tests on doubles (exact equality with a segment end point, |angle| <= pi / 2, sign(arc1) == sign(arc2), |arc1| >= |arc2|,
 // |ey| <= max_ey).  Every function below switches contraction into FMAs off, as pid_control_law does, and evaluates products and sums in the order NumPy
@@ -48,7 +49,8 @@ __device__ __forceinline__ double lmpc_sign(double a) { return (double)((a > 0.0
 
 // Map.getLocalPosition(x, y, psi) with halfWidth + slack = max_ey, branch for branch; the first completing row wins.  Returns the status word (0, or
 // LMPC_ST_NO_SEGMENT with s = ey = epsi = 10000: no row completes, or an input is not finite).  Row i - 1 of row 0 is the last row (the reference's index -1).
-__device__ __forceinline__ int lmpc_local_position(const lmpc_dev_params &p, double x, double y, double psi, double max_ey, double &s_out, double &ey_out, double &epsi_out) {
+template <class TK>
+__device__ __forceinline__ int lmpc_local_position(const TK &p, double x, double y, double psi, double max_ey, double &s_out, double &ey_out, double &epsi_out) {
 #pragma clang fp contract(off)
     const double PI = 3.141592653589793;
     s_out = LMPC_TRACK_OFF; ey_out = LMPC_TRACK_OFF; epsi_out = LMPC_TRACK_OFF;
@@ -89,14 +91,19 @@ __device__ __forceinline__ int lmpc_local_position(const lmpc_dev_params &p, dou
 // Point e reads x[e in_stride], y[e in_stride], psi[e in_stride] and writes s[e out_stride], ey[e out_stride], epsi[e out_stride], status[e].  Stride 1: the three
 // input and three output arrays of lmpc_local_position_batch.  Stride 6 with the pointers offset into T x B x 6 session logs: lmpc_state_from_global_batch, which
 // also hands over copy_src / copy_dst -- the first three doubles of row e (vx, vy, wz) are then copied through unchanged.
+// TRK (per-element tracks, lmpc_track_set): point e reads row (trkMod ? e % trkMod : e) of trk, trkStride doubles between rows (0: one row for all) -- trkMod = B for a
+// T x B log, whose car b is on row b.
+template <bool TRK>
 __global__ void __launch_bounds__(LMPC_TRACK_NT) lmpc_local_position_kernel(lmpc_dev_params p, size_t n, const double *__restrict__ x, const double *__restrict__ y,
                                                                             const double *__restrict__ psi, size_t in_stride, double max_ey, double *__restrict__ s,
                                                                             double *__restrict__ ey, double *__restrict__ epsi, size_t out_stride, int *__restrict__ status,
-                                                                            const double *__restrict__ copy_src, double *__restrict__ copy_dst) {
+                                                                            const double *__restrict__ copy_src, double *__restrict__ copy_dst,
+                                                                            const double *__restrict__ trk, int trkStride, size_t trkMod) {
     const size_t e = (size_t)blockIdx.x * LMPC_TRACK_NT + threadIdx.x;
     if (e >= n) return;
     double so, eyo, epo;
-    const int st = lmpc_local_position(p, x[e * in_stride], y[e * in_stride], psi[e * in_stride], max_ey, so, eyo, epo);
+    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(trk, (size_t)trkStride, trkMod ? e % trkMod : e);
+    const int st = lmpc_local_position(track_src<TRK>(p, tr_), x[e * in_stride], y[e * in_stride], psi[e * in_stride], max_ey, so, eyo, epo);
     if (copy_dst) { const double *cs = copy_src + e * in_stride; double *cd = copy_dst + e * out_stride; cd[0] = cs[0]; cd[1] = cs[1]; cd[2] = cs[2]; }
     s[e * out_stride] = so; ey[e * out_stride] = eyo; epsi[e * out_stride] = epo; status[e] = st;
 }
@@ -104,11 +111,14 @@ __global__ void __launch_bounds__(LMPC_TRACK_NT) lmpc_local_position_kernel(lmpc
 // Map.getAngle(s, epsi), Track.py:312-349: the heading of a car at (s, epsi).  s is wrapped with the bounded loop of lmpc_global_position_kernel.  ang is 0 on
 // row 0 (NOT the last row's psi: the reference's `if i > 0` here, against its index -1 in getLocalPosition).  status = LMPC_ST_NO_SEGMENT and psi = 0 where the
 // reference raises (s on no row).
-__global__ void __launch_bounds__(LMPC_TRACK_NT) lmpc_track_angle_kernel(lmpc_dev_params p, size_t n, const double *__restrict__ s_in, const double *__restrict__ epsi_in,
-                                                                         double *__restrict__ psi_out, int *__restrict__ status) {
+template <bool TRK>
+__global__ void __launch_bounds__(LMPC_TRACK_NT) lmpc_track_angle_kernel(lmpc_dev_params p_, size_t n, const double *__restrict__ s_in, const double *__restrict__ epsi_in,
+                                                                         double *__restrict__ psi_out, int *__restrict__ status, const double *__restrict__ trk, int trkStride) {
 #pragma clang fp contract(off)
     const size_t e = (size_t)blockIdx.x * LMPC_TRACK_NT + threadIdx.x;
     if (e >= n) return;
+    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(trk, (size_t)trkStride, e);
+    const auto &p = track_src<TRK>(p_, tr_);
     const double PI = 3.141592653589793;
     double s = s_in[e]; const double epsi = epsi_in[e];
     for (int lap = 0; lap < 4096 && s > p.TL; lap++) s = s - p.TL;                          // (`while s > TrackLength`, bounded: an infinite s must not hang the GPU)

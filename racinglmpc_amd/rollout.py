@@ -19,8 +19,12 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set, or (ss_table) each car against its own (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None):
-        """tuning: controller tuning of the cars of THIS object (this rank's shard), rows of _capi.TUNING_FIELDS as _capi.tuning_rows builds them -- one row for all cars
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None, tracks=None):
+        """tracks: the tracks of the cars of THIS object (this rank's shard) -- one PointAndTangent table for all cars or a sequence of them, one per car (tables, or
+        (table, trackLength) pairs, or (n, 98) rows as _capi.track_rows builds them); handed to the context (Context.track_set) before every begin, run_pid_laps and
+        run_mpc_laps, beside plant_params.  `TL` is then an array, one length per row (track_lengths(B): one per car).  None: the context's rows are left as they
+        are and `TL` is the length of `track`, the table of the context's configuration.
+        tuning: controller tuning of the cars of THIS object (this rank's shard), rows of _capi.TUNING_FIELDS as _capi.tuning_rows builds them -- one row for all cars
         or one per car (Context.tuning_set); handed to the context before every begin and run_mpc_laps, beside lap_table / ss_table.  The context's rows are live in a
         session, as the safe-set table is.  None: the context's rows are left as they are (the config's weights unless the caller set others).
         lap_table: per-car regression laps of the cars of THIS object, rows of trToUse insertion indices into the context's regression store -- one row for all cars
@@ -45,6 +49,9 @@ class BatchedRollouts:
         counter.  The stream is the device generator's own: it does not reproduce the draws of `rng`."""
         self.ctx, self.track = ctx, np.asarray(track, float)
         self.TL = float(self.track[-1, 3] + self.track[-1, 4])
+        self.tracks = None
+        if tracks is not None:
+            self.set_tracks(tracks)
         self.rng = np.random.default_rng(seed)
         self.global_noise, self.noise_shard = bool(global_noise), None
         self.last_status = None
@@ -141,6 +148,41 @@ class BatchedRollouts:
         self.lap += 1
         return True
 
+    def set_tracks(self, tracks):
+        """tracks as __init__ takes them; TL becomes the array of their lengths."""
+        arr = tracks if isinstance(tracks, np.ndarray) else None
+        if arr is not None and arr.ndim == 2 and arr.shape[1] == _capi.TRACK_NPAR:
+            rows = _capi.check_tracks(arr)
+        elif arr is not None and arr.ndim == 2:                       # one table for every car
+            rows = _capi.track_rows([arr])
+        else:
+            rows = _capi.track_rows(list(tracks))
+        if rows is None:
+            raise ValueError("tracks: at least one track expected")
+        self.tracks = rows
+        self.TL = rows[:, 1].copy()
+
+    def track_lengths(self, B):
+        """TrackLength of each of B cars, (B,): the cars' own rows, or the one length every car shares."""
+        TL = np.atleast_1d(np.asarray(self.TL, float))
+        if TL.shape[0] not in (1, B):
+            raise ValueError("tracks: one row or one per car (%d) expected, got %d" % (B, TL.shape[0]))
+        return np.broadcast_to(TL, (B,)).copy()
+
+    def track_row_of(self, b):
+        """The track_row argument of the host-side lap writers for car b: b with one row per car in force, else None (the config's track, or the one row)."""
+        rows = getattr(self, "tracks", None)
+        return int(b) if rows is not None and rows.shape[0] > 1 else None
+
+    def _apply_tracks(self, B):
+        """The track rows of this object's cars go to the context in front of a session (the context refuses a change while one is active)."""
+        rows = getattr(self, "tracks", None)           # (objects built without __init__ -- tests/test_host_checks.py -- have none)
+        if rows is None:
+            return
+        if rows.shape[0] not in (1, B):
+            raise ValueError("tracks: one row or one per car (%d) expected, got %d" % (B, rows.shape[0]))
+        self.ctx.track_set(rows)
+
     def _apply_plant_params(self, B):
         """The vehicle rows of this object's cars go to the context in front of a session (the session takes its snapshot when it begins)."""
         par = getattr(self, "plant_params", None)      # (objects built without __init__ -- tests/test_host_checks.py -- have none)
@@ -186,6 +228,7 @@ class BatchedRollouts:
         B = x0.shape[0]
         xl = self._per_rollout(xLin0, B); ul = self._per_rollout(uLin0, B)
         noise = self._draw_noise(max_steps, B)
+        self._apply_tracks(B)
         self._apply_plant_params(B)
         self._apply_lap_table(B)
         self._apply_ss_table(B)
@@ -243,6 +286,7 @@ class BatchedRollouts:
         x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1)) if x0 is None else np.asarray(x0, float)
         noise_u = self._draw_noise(max_steps, B, width=2)
         noise = self._draw_noise(max_steps, B)
+        self._apply_tracks(B)
         self._apply_plant_params(B)
         if self._device_noise_session(B):
             t, _ = self.ctx.rollout_pid(x0, x0, vt, None, None, stop_at_line=stop_at_line, T_max=max_steps)
@@ -258,6 +302,7 @@ class BatchedRollouts:
         context's regression store.  Generator consumption: one plant-noise draw (max_steps, nb, 3) (device_noise: none, one session of the device generator).  Returns lap tuples as run_pid_laps does."""
         x0 = np.asarray(x0, float); nb = x0.shape[0]
         noise = self._draw_noise(max_steps, nb)
+        self._apply_tracks(nb)
         self._apply_plant_params(nb)
         if A is None:
             self._apply_lap_table(nb)              # (the LTI form runs no regression)
@@ -287,7 +332,7 @@ def mpc_stage_config(track, N, vt, max_batch, trToUse=1, device=0):
                              trackLength=float(track[-1, 3] + track[-1, 4]), max_batch=int(max_batch), device=int(device))
 
 
-def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None, device_noise=False, per_car_store=False, tuning=None):
+def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plant_params=None, device_noise=False, per_car_store=False, tuning=None, tracks=None):
     """main.py:61-95 for B cars without a host round trip inside a lap: PID laps -> one LTI model per car (batched Utilities.Regression, lamb = 1e-7) -> LTI-MPC laps,
     car b on its own (A_b, B_b) -> LTV-MPC laps.  vt: the PID target speed, one value (main.py:50) or one per car; the MPC stages track vt_mpc (default: vt, or the
     mean of the per-car values).  Every stage runs max_steps steps from x0 = [0.5, 0, 0, 0, 0, 0] like the reference's multiLap simulator (main.py:45, 57).
@@ -305,6 +350,9 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     plant_params: vehicle constants (one row, or one per car; _capi.plant_params) of all three stages -- car b drives the same vehicle in its PID, LTI-MPC and LTV-MPC
     lap; None: the reference's vehicle.
 
+    tracks: the cars' tracks in all three stages (BatchedRollouts(tracks=): one table, or one per car); None: every car on `track`.  `track` stays the table of the
+    context's configuration.  With cars on different tracks use per_car_store: a lap of another track is no regression data for a car.
+
     tuning: controller tuning of the two MPC stages (one row, or one per car; _capi.tuning_rows on mpc_stage_config) -- e.g. a target speed xRef[0] per car; None: the
     values of mpc_stage_config for every car.
 
@@ -319,7 +367,7 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
     n_store = B if per_car_store else min(B, BOOTSTRAP_STORE_LAPS)
     ctx = _capi.Context(mpc_stage_config(track, N, vt_mpc, B, trToUse=1 if per_car_store else n_store, device=device))
     try:
-        ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params, device_noise=device_noise, tuning=tuning)
+        ro = BatchedRollouts(ctx, track, seed=seed, plant_params=plant_params, device_noise=device_noise, tuning=tuning, tracks=tracks)
     except Exception:
         ctx.close()
         raise
@@ -344,40 +392,68 @@ def bootstrap(track, B, N, vt, seed, device=0, max_steps=1000, vt_mpc=None, plan
 
 
 def lap_from_global(ctx, xglob, max_ey, TL=None):
-    """One lap recorded in the inertial frame -- (T, 6) rows [vx, vy, wz, psi, X, Y], the reference's x_glob -- as the (T, 6) curvilinear rows [vx, vy, wz, epsi, s, ey]
+    """xglob (T, B, 6): the logs of B cars at once, car b of the log on track row b of the context (Context.track_set) and s made continuous with car b's own
+    TrackLength -- TL: one length or (B,), default: the rows in force on the context, else its configuration's.  Returns (T, B, 6).  xglob (T, 6):
+    One lap recorded in the inertial frame -- (T, 6) rows [vx, vy, wz, psi, X, Y], the reference's x_glob -- as the (T, 6) curvilinear rows [vx, vy, wz, epsi, s, ey]
     the lap stores take (Context.state_from_global: Map.getLocalPosition per row, Track.py:191-290).  The map returns s on the first lap; here s is made continuous
     across finish-line crossings: from every row whose s drops by more than TrackLength / 2 against the row before, one more TrackLength is added, so a multi-lap
     PID lap comes back with s running past TrackLength, as seed_lmpc expects.  TL: the track length (default: the context's).  max_ey: the reference's
     halfWidth + slack.  Raises LmpcError naming the first row the map places on no segment (ST_NO_SEGMENT)."""
     xg = np.asarray(xglob, float)
-    if xg.ndim != 2 or xg.shape[1] != 6 or xg.shape[0] < 1:
-        raise ValueError("lap_from_global: (T, 6) rows [vx, vy, wz, psi, X, Y] expected, got shape %s" % (xg.shape,))
-    TL = float(ctx.cfg.trackLength if TL is None else TL)
+    if xg.ndim not in (2, 3) or xg.shape[-1] != 6 or xg.shape[0] < 1:
+        raise ValueError("lap_from_global: (T, 6) or (T, B, 6) rows [vx, vy, wz, psi, X, Y] expected, got shape %s" % (xg.shape,))
+    if TL is None:
+        rows = ctx.tracks() if hasattr(ctx, "tracks") else np.zeros((0, 0))
+        TL = rows[:, 1] if rows.shape[0] else ctx.cfg.trackLength
+    TL = np.asarray(TL, float)
     x, st = ctx.state_from_global(xg, max_ey)
-    x = np.array(x, float).reshape(xg.shape); st = np.asarray(st).reshape(-1)
-    bad = np.nonzero(st & _capi.ST_NO_SEGMENT)[0]
+    x = np.array(x, float).reshape(xg.shape); st = np.asarray(st).reshape(xg.shape[:-1])
+    bad = np.argwhere(st & _capi.ST_NO_SEGMENT)
     if bad.size:
-        r = int(bad[0])
-        raise _capi.LmpcError("lap_from_global: row %d (X = %r, Y = %r, psi = %r) lies on no track segment within max_ey = %r (LMPC_ST_NO_SEGMENT)"
-                              % (r, xg[r, 4], xg[r, 5], xg[r, 3], float(max_ey)))
-    laps = np.concatenate([[0], np.cumsum(np.diff(x[:, 4]) < -TL / 2)])
-    x[:, 4] = x[:, 4] + laps * TL
+        r = tuple(int(i) for i in bad[0])
+        raise _capi.LmpcError("lap_from_global: row %s (X = %r, Y = %r, psi = %r) lies on no track segment within max_ey = %r (LMPC_ST_NO_SEGMENT)"
+                              % (r[0] if len(r) == 1 else r, xg[r + (4,)], xg[r + (5,)], xg[r + (3,)], float(max_ey)))
+    if xg.ndim == 2:
+        if TL.size != 1:
+            raise ValueError("lap_from_global: one (T, 6) lap takes one TrackLength, got %d (per-car tracks: pass the (T, B, 6) log)" % TL.size)
+        TL = float(TL.reshape(-1)[0])
+        laps = np.concatenate([[0], np.cumsum(np.diff(x[:, 4]) < -TL / 2)])
+        x[:, 4] = x[:, 4] + laps * TL
+        return x
+    if TL.size not in (1, xg.shape[1]):
+        raise ValueError("lap_from_global: one TrackLength or one per car (%d) expected, got %d" % (xg.shape[1], TL.size))
+    TLb = np.broadcast_to(TL.reshape(-1), (xg.shape[1],))
+    laps = np.concatenate([np.zeros((1, xg.shape[1]), int), np.cumsum(np.diff(x[:, :, 4], axis=0) < -TLb[None] / 2, axis=0)])
+    x[:, :, 4] = x[:, :, 4] + laps * TLb[None]
     return x
 
 
-def seed_lmpc(ctx, laps, from_global=False, max_ey=None):
+def seed_lmpc(ctx, laps, from_global=False, max_ey=None, track_rows=None):
     """main.py:102-110 with laps of bootstrap(): every (x, u, ...) tuple goes into the regression store (PredictiveModel.addTrajectory) and into the safe set
     (LMPC.addTrajectory) of the LMPC context `ctx`, in the order given; an LMPC context needs numSS_it / trToUse of them.  The reference passes its one PID lap four
     times; bootstrap()'s "pid" laps are such laps -- max_steps rows of a multiLap run, s running past TrackLength -- one per car.
     from_global: each lap is (x_glob, u, ...) recorded in the inertial frame (motion capture, another simulator, the reference's x_glob log) and is converted with
-    lap_from_global(ctx, x_glob, max_ey) first; max_ey (the reference's halfWidth + slack) must then be given."""
+    lap_from_global(ctx, x_glob, max_ey) first; max_ey (the reference's halfWidth + slack) must then be given.
+    track_rows: with one track row per car in force on the context (Context.track_set), the row of each lap -- the TrackLength of its Q-function; from_global then
+    needs one lap per row, lap i recorded on track i (the laps, cut or padded to one length, are converted as one (T, n, 6) log)."""
     if from_global:
         if max_ey is None:
             raise ValueError("seed_lmpc(from_global=True) needs max_ey (the reference's halfWidth + slack)")
-        laps = [(lap_from_global(ctx, lap[0], max_ey), lap[1]) for lap in laps]
-    for lap in laps:
+        if track_rows is None:
+            laps = [(lap_from_global(ctx, lap[0], max_ey), lap[1]) for lap in laps]
+        else:
+            if [int(r) for r in track_rows] != list(range(len(laps))):
+                raise ValueError("seed_lmpc(from_global=True, track_rows=...): lap i must be the lap of track row i")
+            T = max(np.asarray(lap[0]).shape[0] for lap in laps)
+            log = np.stack([np.concatenate([np.asarray(lap[0], float), np.tile(np.asarray(lap[0], float)[-1:], (T - np.asarray(lap[0]).shape[0], 1))]) for lap in laps], axis=1)
+            x = lap_from_global(ctx, log, max_ey)
+            laps = [(x[:np.asarray(lap[0]).shape[0], i], lap[1]) for i, lap in enumerate(laps)]
+    for i, lap in enumerate(laps):
         ctx.model_add_trajectory(lap[0], lap[1])
-        ctx.ss_add_trajectory(lap[0], lap[1])
+        if track_rows is None:
+            ctx.ss_add_trajectory(lap[0], lap[1])
+        else:
+            ctx.ss_add_trajectory(lap[0], lap[1], track_row=int(track_rows[i]))
 
 
 class LmpcGeneration:
@@ -396,6 +472,9 @@ class LmpcGeneration:
 
     def __init__(self, rollouts, total_rollouts, K=4, T_max=400, ext=40, comm=None):
         self.ro, self.total, self.K, self.T_max, self.ext = rollouts, total_rollouts, K, T_max, ext
+        trk = getattr(rollouts, "tracks", None)
+        if trk is not None and np.unique(trk, axis=0).shape[0] > 1:      # (one safe set for all cars: a lap of one track is no terminal set on another)
+            raise ValueError("LmpcGeneration shares one safe set among its cars: they must be on one track (PerCarLMPC is the loop for cars on different tracks)")
         self.comm = comm or parallel.LocalComm()
         self.rank, self.world = self.comm.rank, self.comm.world
         self.lo, self.hi = parallel.shard(total_rollouts, self.rank, self.world)
@@ -442,7 +521,7 @@ class LmpcGeneration:
         else:
             par = gb % K
             fin = np.stack([self.parents[k][3] for k in range(K)])
-            x0 = fin[par, 0:6].copy(); x0[:, 4] -= ro.TL                           # xF = x_cl[-1] - [0,0,0,0,TrackLength,0]
+            x0 = fin[par, 0:6].copy(); x0[:, 4] -= ro.track_lengths(x0.shape[0]) if getattr(ro, "tracks", None) is not None else ro.TL   # xF = x_cl[-1] - [0,0,0,0,TrackLength,0]
             xg0 = fin[par, 6:12].copy()
             xl = np.stack([self.parents[k][0][1:N + 2] for k in par]); ul = np.stack([self.parents[k][1][1:N + 1] for k in par])
             ext = self.ext
@@ -587,7 +666,10 @@ class PerCarLMPC:
     that comes back not extended -- a non-finite row -- retires its car with EXT_SKIPPED); only status words, crossing steps, final states and the first N + 2
     logged rows are downloaded.  The tuples run() returns, and latest[b], then carry only the first min(T, N + 2) rows of x and u -- what the next generation
     linearises about -- and None for x_glob; the full lap is in the stores (Context.store_read_lap).
-    tuning: rows of _capi.tuning_rows, one for all cars or one per car -- what BatchedRollouts(tuning=) takes; car b then also runs its own controller tuning."""
+    tuning: rows of _capi.tuning_rows, one for all cars or one per car -- what BatchedRollouts(tuning=) takes; car b then also runs its own controller tuning.
+    Tracks: with BatchedRollouts(tracks=) holding one track per car, car b drives, regresses and selects on its own track; its start state is its crossing state
+    shifted by its OWN TrackLength, and its laps and extensions are stored with track_row = b (Context.ss_add_trajectory / ss_extend_lap, or the device commit, which
+    takes the car's row by itself)."""
 
     EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
 
@@ -608,6 +690,7 @@ class PerCarLMPC:
             raise ValueError("PerCarLMPC.seed needs a context with empty lap stores")
         laps_per_car = [list(l) if isinstance(l, list) else [l] for l in laps_per_car]
         B = self.B = len(laps_per_car)
+        self.ro._apply_tracks(B)           # (per-car tracks: car b's laps are stored with the TrackLength of row b)
         self.ss_hist, self.model_hist = PerCarHistory(B, ctx.cfg.numSS_it), PerCarHistory(B, ctx.cfg.trToUse)
         self.last = np.full(B, -1, np.int32)
         self.latest = [None] * B           # (x, u, final12, ends at the line) of each car's most recent lap
@@ -619,7 +702,7 @@ class PerCarLMPC:
             first = n
             for lap in laps:
                 x, u = np.asarray(lap[0], float), np.asarray(lap[1], float)
-                ctx.model_add_trajectory(x, u); ctx.ss_add_trajectory(x, u)
+                ctx.model_add_trajectory(x, u); self._ss_add(b, x, u)
                 self.ss_hist.add(b, x.shape[0], n); self.model_hist.add(b, x.shape[0], n)
                 n += 1
             lens = [np.asarray(l[0]).shape[0] for l in laps]
@@ -632,6 +715,14 @@ class PerCarLMPC:
             self.latest[b] = (x, np.asarray(lap[1], float), np.asarray(lap[3], float), done >= x.shape[0])
             self.last[b] = n - 1
         self._hand_tables()
+
+    def _ss_add(self, b, x, u):
+        """Car b's lap into the safe set, its Q-function counted with car b's own TrackLength."""
+        row = self.ro.track_row_of(b)
+        if row is None:
+            self.ro.ctx.ss_add_trajectory(x, u)
+        else:
+            self.ro.ctx.ss_add_trajectory(x, u, track_row=row)
 
     def _hand_tables(self):
         """Rows of both tables and `last`, from the histories, to the rollouts object (it hands them to the context before the next begin)."""
@@ -648,7 +739,7 @@ class PerCarLMPC:
         ro, ctx, B, N = self.ro, self.ro.ctx, self.B, self.ro.ctx.N
         gen = self.generation
         fin = np.stack([self.latest[b][2] for b in range(B)])
-        x0 = fin[:, 0:6].copy(); x0[:, 4] -= ro.TL                              # xF = x_cl[-1] - [0,0,0,0,TrackLength,0]
+        x0 = fin[:, 0:6].copy(); x0[:, 4] -= ro.track_lengths(B) if getattr(ro, "tracks", None) is not None else ro.TL   # xF = x_cl[-1] - [0,0,0,0,TrackLength_b,0]: each car's own track
         xg0 = fin[:, 6:12].copy()
         xl = np.stack([self.latest[b][0][1:N + 2] for b in range(B)]); ul = np.stack([self.latest[b][1][1:N + 1] for b in range(B)])
         ro.begin(x0, xl, ul, xg0, self.T_max)
@@ -666,7 +757,10 @@ class PerCarLMPC:
                     if not clean:
                         self.retired[b] = (gen, int(st[b]) | self.EXT_SKIPPED)
                         continue
-                    ctx.ss_extend_lap(int(self.last[b]), X[:n, b], U[:n, b])     # (the table is live in the session: the next step selects from the longer lap)
+                    if ro.track_row_of(b) is None:
+                        ctx.ss_extend_lap(int(self.last[b]), X[:n, b], U[:n, b])     # (the table is live in the session: the next step selects from the longer lap)
+                    else:
+                        ctx.ss_extend_lap(int(self.last[b]), X[:n, b], U[:n, b], track_row=b)     # (the table is live in the session: the next step selects from the longer lap)
             t, _ = ctx.rollout_run(self.T_max)
             X, U, G, done, st, fx, fg = ctx.rollout_fetch(0, t)
         finally:
@@ -682,7 +776,7 @@ class PerCarLMPC:
             T = int(done[b])
             x, u = X[:T, b].copy(), U[:T, b].copy()
             idx = ctx.ss_num_laps()
-            ctx.ss_add_trajectory(x, u); ctx.model_add_trajectory(x, u)
+            self._ss_add(b, x, u); ctx.model_add_trajectory(x, u)
             self.ss_hist.add(b, T, idx); self.model_hist.add(b, T, idx)
             self.last[b] = idx
             f12 = np.concatenate([fx[b], fg[b]])

@@ -12,6 +12,10 @@ are fed the same draws, and the tool checks that their logs are equal bit for bi
 --plant-params: every batch size is measured a second time with per-car vehicle constants in force (Context.plant_set_params: all ten constants of every car scaled
 by U(0.9, 1.1), generator seeded with 7) -- the per-car instantiations of the plant kernels beside the nominal ones; those rows carry "plant_params": true.
 
+--tracks: every batch size is also measured with track rows in force (Context.track_set): once with ONE row, the L track's own -- the per-car-track kernels on the
+geometry of the configuration, the price of reading a row at all --, and once with the cars dealt round-robin over the reference's three tracks (racinglmpc_amd.track:
+L, oval, goggle); those rows carry "tracks": "one" / "three" (else "none").  Both ways of a row run with the same rows, so the bit-for-bit check holds there too.
+
     python tools/stage_bench.py --device-noise   # host wall clock of a session's begin: host draw + upload  vs  the noise generated on the device
 
 --device-noise (no --stage): BatchedRollouts.begin of an LMPC session at B = 1024, T_max = 400 on the golden N = 12 stores, timed three ways in one run, alternating:
@@ -36,10 +40,21 @@ def pid_u(x, vt, nu):
     return np.stack([-0.6 * x[:, 5] - 0.9 * x[:, 3] + np.clip(nu[:, 0] * 0.25, -0.9, 0.9), 1.5 * (vt - x[:, 0]) + np.clip(nu[:, 1] * 0.10, -0.2, 0.2)], axis=1)
 
 
-def run_stage(stage, g, B, T, plant_params=False):
+def track_rows_for(B, tracks):
+    """Rows for Context.track_set: "one" -- the L track for every car; "three" -- car b on track b mod 3 of (L, oval, goggle); "none" -- no rows."""
+    from racinglmpc_amd import _capi, track
+    if tracks == "none":
+        return None
+    names = ("L",) if tracks == "one" else tuple("L oval goggle".split()[b % 3] for b in range(B))
+    tabs = {n: track.table_from_spec(track.REFERENCE_SPECS[n]) for n in set(names)}
+    return _capi.track_rows([tabs[n] for n in names])
+
+
+def run_stage(stage, g, B, T, plant_params=False, tracks="none"):
     from racinglmpc_amd import _capi, rollout
     N = 12
     ctx = _capi.Context(rollout.mpc_stage_config(g["track"], N, 0.8, B, trToUse=1))
+    ctx.track_set(track_rows_for(B, tracks))
     if plant_params:
         ctx.plant_set_params(_capi.plant_params_default()[None] * np.random.default_rng(7).uniform(0.9, 1.1, (B, _capi.PLANT_NPAR)))
     rng = np.random.default_rng(7)
@@ -127,6 +142,7 @@ def main():
     ap.add_argument("--steps", type=int, default=0, help="simulated steps per lap (default: 400 for pid, 100 for the MPC stages)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--plant-params", action="store_true", help="also measure every batch size with per-car vehicle constants (+-10 % around the reference's, seed 7)")
+    ap.add_argument("--tracks", action="store_true", help="also measure every batch size with one track row (the L track's) and with the cars over the three reference tracks")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if not args.device_noise and not args.stage:
@@ -143,8 +159,8 @@ def main():
         return
     T = args.steps or (400 if args.stage == "pid" else 100)
     rows = []
-    for B, par in [(B, par) for B in args.batches for par in ([False, True] if args.plant_params else [False])]:
-        ctx, device, host = run_stage(args.stage, g, B, T, plant_params=par)
+    for B, par, trk in [(B, par, trk) for B in args.batches for par in ([False, True] if args.plant_params else [False]) for trk in (("none", "one", "three") if args.tracks else ("none",))]:
+        ctx, device, host = run_stage(args.stage, g, B, T, plant_params=par, tracks=trk)
         d, h = device(), host()                                        # untimed: code objects, session buffers, pooled scratch
         same = all(np.array_equal(a, b) for a, b in zip(d, h))
         td, th = [], []
@@ -153,7 +169,7 @@ def main():
             t0 = time.perf_counter(); host(); th.append(time.perf_counter() - t0)
         ctx.close()
         sd, sh = float(np.median(td)), float(np.median(th))
-        rows.append(dict(B=B, steps=T, plant_params=par, device_s=sd, host_stepped_s=sh, device_steps_per_s=B * T / sd, host_stepped_steps_per_s=B * T / sh,
+        rows.append(dict(B=B, steps=T, plant_params=par, tracks=trk, device_s=sd, host_stepped_s=sh, device_steps_per_s=B * T / sd, host_stepped_steps_per_s=B * T / sh,
                          device_s_all=td, host_stepped_s_all=th, logs_bit_identical=bool(same)))
     line = dict(tool="stage_bench", stage=args.stage, N=12, unit="car-steps per second of wall time" + ("" if args.stage == "pid" else " = closed-loop QP solves per second"),
                 results=rows)
