@@ -99,8 +99,9 @@ int lmpc_solver_kind(lmpc_ctx *);                                /* 0: built-in 
 int lmpc_destroy(lmpc_ctx *ctx);
 const char *lmpc_last_error(void);
 const char *lmpc_active_knobs(void);                             /* developer environment variables this process has acted on ("NAME=value;..."; "" = none): LMPC_K1_QG,
-                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG -- route / grid choices,
-                                                                    each announced once on stderr; no reference counterpart.  Bit-identical results: LMPC_K1_QG, LMPC_K1_RPL16
+                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG, LMPC_TRACE_OWN_STREAM -- route / grid
+                                                                    choices, each announced once on stderr; no reference counterpart.  Bit-identical results: LMPC_TRACE_OWN_STREAM
+                                                                    (traced sessions: the trace kernel on a stream of its own instead of the plant stream), LMPC_K1_QG, LMPC_K1_RPL16
                                                                     (regression grid / scan build: A, B, C do not depend on either), LMPC_FUSE (fused one-wave step against the
                                                                     two-kernel one-wave step; ignored by the runtime-(N, S) kernel, which has no fused form), LMPC_NO_ABG
                                                                     ([A_k | B_k] in LDS instead of global memory).  LMPC_MW_MAX_BATCH and LMPC_MW2_MAX_BATCH move a batch to
@@ -389,6 +390,41 @@ int lmpc_rollout_end(lmpc_ctx *);
          * lap of the same shape (a generation loop begins one per lap); lmpc_rollout_release or lmpc_destroy frees them */
 int lmpc_rollout_release(lmpc_ctx *);
         /* give the kept session buffers back (55 MB at 1024 rollouts x 400 steps) without destroying the context; not valid between begin and end.  No reference counterpart */
+
+/* ---- session traces (version 110; kernel: racinglmpc_amd/csrc/lmpc_trace.hip.h).  What the controller of a listed car computed at every step of a session, kept on
+ * the device beside the plant's logs: the three per-step logs LMPC.unpackSolution appends (PredictiveControllers.py:364-379: xStoredPredTraj, uStoredPredTraj,
+ * SSStoredPredTraj), the Q-values of the selected points, the solver's words of the step and the inertial positions of the predicted and selected points
+ * (Map.getGlobalPosition, Track.py:135-189; plot.py:106-175 draws them). */
+enum { LMPC_TRACE_XPRED = 1,   /* (N+1) x 6                      xStoredPredTraj[it][i]            */
+       LMPC_TRACE_UPRED = 2,   /* N x 2                          uStoredPredTraj[it][i]            */
+       LMPC_TRACE_SS    = 4,   /* S x 6 selected points          SSStoredPredTraj[it][i] (= SS_PointSelectedTot.T) */
+       LMPC_TRACE_QSEL  = 8,   /* S  Qfun_SelectedTot                                              */
+       LMPC_TRACE_SOLVER= 16,  /* int iters, int status of the step (status: the step's own word, not the accumulated one) */
+       LMPC_TRACE_XY    = 32 };/* (N+1) x 2 inertial (X, Y) of the xPred rows; on a context with a safe set also S x 2 of the
+                                  selected points; one int mapStatus per (step, car) */
+#define LMPC_TRACE_ALL 63u
+int lmpc_rollout_set_trace(lmpc_ctx *, int n, const int *cars /*n distinct car indices, any order; NULL with n = 0: off*/, unsigned what);
+        /* the cars and planes later sessions of lmpc_rollout_begin and lmpc_rollout_begin_mpc (LTV and LTI form) record at every step (LMPC.unpackSolution,
+         * PredictiveControllers.py:364-379).  A session takes (cars, what) as a snapshot when it begins, like the vehicle rows and the noise source: a `set` during a
+         * session reaches the next session only.  Off after lmpc_create; with the trace off every path allocates, launches and returns what it did before this entry
+         * point existed.  lmpc_rollout_pid ignores it (no predictions).  LMPC_E_ARG, with the trace in force kept, for n < 0, n > 0 with NULL cars, what == 0 or
+         * unknown bits, a negative or repeated car, LMPC_TRACE_SS or LMPC_TRACE_QSEL on a context with numSS_it == 0.  A car >= B is refused by the `begin` that meets
+         * it, before any session state changes.  Needs no device */
+int lmpc_rollout_get_trace(lmpc_ctx *, int *n, int *cars /*capacity, or NULL*/, unsigned *what, int capacity);
+        /* what lmpc_rollout_set_trace left in force (n = 0, what = 0: off); cars receives min(n, capacity) entries.  No reference counterpart (the reference's
+         * logs are Python lists, PredictiveControllers.py:364-379) */
+int lmpc_rollout_trace_bytes(lmpc_ctx *, int n, unsigned what, int T_max, long long *bytes);
+        /* device memory a session of that shape allocates for its trace planes: T_max x n x the bytes of the planes per (step, car) -- XPRED (N+1) x 6 doubles, UPRED
+         * N x 2, SS S x 6, QSEL S, SOLVER two ints, XY ((N+1) + S) x 2 doubles and one int; S = numSS_points on a context with a safe set, else 0.  On an LMPC context
+         * SS, QSEL and XY also make the session keep the selection outputs of the last step for all B cars (B x S x 15 doubles, the buffers of
+         * lmpc_debug_rollout_capture), not counted here.  No reference counterpart (Python lists, PredictiveControllers.py:364-379).  Needs no device */
+typedef struct { double *xPred, *uPred, *ssSel, *qSel, *xyPred, *xySS; int *iters, *status, *mapStatus; } lmpc_trace_out;   /* any may be NULL */
+int lmpc_rollout_fetch_trace(lmpc_ctx *, int t0, int t1, const lmpc_trace_out *out);   /* plane layout [t - t0][k][...], k = position in `cars` */
+        /* the trace rows of steps [t0, t1) of the active session (xStoredPredTraj / uStoredPredTraj / SSStoredPredTraj of PredictiveControllers.py:364-379, per listed
+         * car).  Every row t < steps taken has been written for every listed car, also for a car that has crossed the line (its lane keeps solving): cut at doneAt.
+         * mapStatus[t][k]: LMPC_ST_NO_SEGMENT if a point of that row lies on no segment of the car's track (written as (0, 0), the rule of
+         * lmpc_global_position_batch), else 0.  LMPC_E_STATE with no session active, on a session begun without a trace and on a lmpc_rollout_pid session;
+         * LMPC_E_ARG for a non-NULL pointer of a plane the session does not record, t0 < 0, t1 < t0, t1 beyond the steps taken */
 int lmpc_ss_extend_lap(lmpc_ctx *, int lap, const double *x /*n x 6*/, const double *u /*n x 2*/, int n);
 /* Undo extensions: keep the first T rows of stored lap `lap` (LapTime <= T <= current rows).  rollout.LmpcGeneration rolls a failed
  * generation back with it, so that a generation either completes or leaves the safe set as it found it.  No reference counterpart. */

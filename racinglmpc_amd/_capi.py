@@ -23,6 +23,10 @@ ST_MAXITER, ST_REG_SINGULAR, ST_NO_SEGMENT, ST_WINDOW, ST_NUMERIC, ST_NOT_INTERI
 
 PLANT_NPAR = 10
 COMMIT_SS, COMMIT_MODEL = 1, 2         # LMPC_COMMIT_SS / LMPC_COMMIT_MODEL: the `stores` bits of lmpc_rollout_commit_laps
+# LMPC_TRACE_*: the planes of a session trace (lmpc_rollout_set_trace), the per-step logs of LMPC.unpackSolution (PredictiveControllers.py:364-379) among them
+TRACE_XPRED, TRACE_UPRED, TRACE_SS, TRACE_QSEL, TRACE_SOLVER, TRACE_XY = 1, 2, 4, 8, 16, 32
+TRACE_ALL = 63
+TRACE_DEFAULT = None                   # rollout_set_trace(what=TRACE_DEFAULT): every plane the context can record (no SS / QSEL without a safe set)
 PLANT_PARAM_NAMES = ("m", "lf", "lr", "Iz", "Df", "Cf", "Bf", "Dr", "Cr", "Br")       # one row of vehicle constants, the order of SysModel.py:60-70
 
 
@@ -74,6 +78,50 @@ class StepDevArgs(C.Structure):
     _fields_ = [(f, C.c_void_p) for k, f, dt, role, shp in ARRAYS if f is not None]
 
 
+class TraceOut(C.Structure):
+    """lmpc_trace_out: one pointer per plane, NULL = not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in ("xPred", "uPred", "ssSel", "qSel", "xyPred", "xySS", "iters", "status", "mapStatus")]
+
+
+def trace_planes(N, S, what):
+    """The planes a session trace of `what` records at horizon N with S safe-set points in use (0 without a safe set), in the order of lmpc_trace_out:
+    [(key, bit, shape per (step, car), dtype)].  XY records xyPred, mapStatus and -- with a safe set -- xySS."""
+    table = (("xPred", TRACE_XPRED, (N + 1, 6), _f8), ("uPred", TRACE_UPRED, (N, 2), _f8), ("ssSel", TRACE_SS, (S, 6), _f8), ("qSel", TRACE_QSEL, (S,), _f8),
+             ("xyPred", TRACE_XY, (N + 1, 2), _f8), ("xySS", TRACE_XY, (S, 2), _f8), ("iters", TRACE_SOLVER, (), _i4), ("status", TRACE_SOLVER, (), _i4),
+             ("mapStatus", TRACE_XY, (), _i4))
+    return [(k, bit, shp, dt) for k, bit, shp, dt in table if (what & bit) and int(np.prod(shp)) > 0]
+
+
+def trace_bytes(N, S, n, what, T_max):
+    """What lmpc_rollout_trace_bytes returns: T_max x n x the bytes of the recorded planes per (step, car)."""
+    return int(T_max) * int(n) * sum(int(np.prod(shp)) * np.dtype(dt).itemsize for k, bit, shp, dt in trace_planes(N, S, what))
+
+
+def check_trace(cars, what, numSS_it):
+    """(cars as int32, what) of a rollout_set_trace call, or ValueError for what the library refuses with LMPC_E_ARG: no planes or unknown bits, a negative or repeated
+    car, SS / QSEL without a safe set.  what=None: every plane the context can record.  No cars: (empty, 0), the trace is off."""
+    cars = np.zeros(0, np.int32) if cars is None else np.asarray(cars)
+    if cars.ndim != 1:
+        raise ValueError("trace: cars must be one-dimensional")
+    if cars.size and not np.issubdtype(cars.dtype, np.integer):
+        raise ValueError("trace: cars must be integers")
+    cars = _i32(cars)
+    if cars.size == 0:
+        return cars, 0
+    if what is None:
+        what = TRACE_ALL if numSS_it > 0 else TRACE_ALL & ~(TRACE_SS | TRACE_QSEL)
+    what = int(what)
+    if what <= 0 or what & ~TRACE_ALL:
+        raise ValueError("trace: what = %d names no plane or an unknown one" % what)
+    if (cars < 0).any():
+        raise ValueError("trace: negative car index")
+    if np.unique(cars).size != cars.size:
+        raise ValueError("trace: a car is listed twice")
+    if numSS_it == 0 and what & (TRACE_SS | TRACE_QSEL):
+        raise ValueError("trace: SS / QSEL planes need a context with a safe set (numSS_it > 0)")
+    return cars, what
+
+
 EXPORTS = [
     "lmpc_config_default", "lmpc_create", "lmpc_create_ex", "lmpc_solver_kind", "lmpc_destroy", "lmpc_last_error", "lmpc_active_knobs", "lmpc_version", "lmpc_device_memory",
     "lmpc_model_add_trajectory", "lmpc_model_num_laps", "lmpc_model_replace_lap", "lmpc_model_set_lap_table", "lmpc_model_get_lap_table", "lmpc_model_lap_info",
@@ -85,6 +133,7 @@ EXPORTS = [
     "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
     "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_debug_model_image", "lmpc_tuning_from_config", "lmpc_tuning_set", "lmpc_tuning_get",
     "lmpc_track_row_from_config", "lmpc_track_set", "lmpc_track_get", "lmpc_ss_add_trajectory_on", "lmpc_ss_extend_lap_on",
+    "lmpc_rollout_set_trace", "lmpc_rollout_get_trace", "lmpc_rollout_trace_bytes", "lmpc_rollout_fetch_trace",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -148,6 +197,13 @@ def load():
         lib.lmpc_ss_add_trajectory_on.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         lib.lmpc_ss_extend_lap_on.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         for f in (lib.lmpc_track_row_from_config, lib.lmpc_track_set, lib.lmpc_track_get, lib.lmpc_ss_add_trajectory_on, lib.lmpc_ss_extend_lap_on):
+            f.restype = C.c_int
+        # (session traces: an int32 car list, plane bits, a struct of plane pointers)
+        lib.lmpc_rollout_set_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+        lib.lmpc_rollout_get_trace.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_uint), C.c_int]
+        lib.lmpc_rollout_trace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_longlong)]
+        lib.lmpc_rollout_fetch_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(TraceOut)]
+        for f in (lib.lmpc_rollout_set_trace, lib.lmpc_rollout_get_trace, lib.lmpc_rollout_trace_bytes, lib.lmpc_rollout_fetch_trace):
             f.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
@@ -460,6 +516,7 @@ class Context:
         self.S = cfg.numSS_points if cfg.numSS_it > 0 else 0
         self.M = 8 * self.N + self.S
         self._step_plan = {}
+        self._ro_trace = None
         self._h = C.c_void_p()
         self._pid = os.getpid()         # the process that owns the device context (see close)
         if runtime_kernel:              # (tests: the runtime-(N, S) kernel even where a fast one exists)
@@ -841,8 +898,9 @@ class Context:
         B = x0.shape[0]
         nz, T = self._session_noise(noise, B, 3, T_max)
         assert xl.shape == (B, self.N + 1, 6) and ul.shape == (B, self.N, 2)
+        tr = self.rollout_trace()                 # (what the session is about to take as its snapshot of the trace)
         _chk(self.lib.lmpc_rollout_begin(self._h, C.c_int(B), C.c_int(T), _d(x0), _d(xg), _d(xl), _d(ul), _d(nz)))
-        self._ro = (B, T); self._ro_t = 0
+        self._ro = (B, T); self._ro_t = 0; self._ro_trace = tr
 
     def rollout_begin_mpc(self, x0, xglob0, noise, xLin0=None, uLin0=None, A=None, B=None, stop_at_line=False, T_max=None):
         """Session of B plain-MPC laps on a numSS_it == 0 context (lmpc_rollout_begin_mpc).  A (B, 6, 6) and B (B, 6, 2) given: the LTI MPC on those models;
@@ -859,8 +917,9 @@ class Context:
             xl = _f64(xLin0); ul = _f64(uLin0); A = B = None
             assert xl.shape == (nb, self.N + 1, 6) and ul.shape == (nb, self.N, 2), (xl.shape, ul.shape)
         pa = lambda a: None if a is None else a.ctypes.data
+        tr = self.rollout_trace()
         _chk(self.lib.lmpc_rollout_begin_mpc(self._h, nb, T, pa(x0), pa(xg), pa(xl), pa(ul), pa(A), pa(B), pa(nz), 1 if stop_at_line else 0))
-        self._ro = (nb, T); self._ro_t = 0
+        self._ro = (nb, T); self._ro_t = 0; self._ro_trace = tr
 
     def rollout_pid(self, x0, xglob0, vt, noise_u, noise, stop_at_line=False, T_max=None):
         """B whole PID laps in one launch (lmpc_rollout_pid): vt (B,) target speeds, noise_u (T_max, B, 2) and noise (T_max, B, 3) N(0, 1) draws of the control law and
@@ -877,7 +936,7 @@ class Context:
         t = C.c_int(); nd = C.c_int()
         _chk(self.lib.lmpc_rollout_pid(self._h, nb, T, x0.ctypes.data, xg.ctypes.data, vt.ctypes.data, pa(nu), pa(nz),
                                        1 if stop_at_line else 0, C.byref(t), C.byref(nd)))
-        self._ro = (nb, T); self._ro_t = t.value
+        self._ro = (nb, T); self._ro_t = t.value; self._ro_trace = None              # (a PID session records no trace)
         return t.value, nd.value
 
     def rollout_run(self, max_steps):
@@ -895,6 +954,48 @@ class Context:
 
     def rollout_end(self):
         _chk(self.lib.lmpc_rollout_end(self._h))
+
+    # ---- session traces (lmpc_rollout_set_trace; csrc/lmpc_trace.hip.h)
+    def rollout_set_trace(self, cars, what=TRACE_DEFAULT):
+        """The cars whose controller output the sessions begun after this call record at every step, and the planes (TRACE_* bits; TRACE_DEFAULT: every plane this
+        context can record) -- xStoredPredTraj / uStoredPredTraj / SSStoredPredTraj of the reference (PredictiveControllers.py:364-379), Qfun_SelectedTot, the
+        solver's words and the inertial positions.  None or no cars: off.  A session keeps the list it began with; rollout_pid ignores it."""
+        cars, what = check_trace(cars, what, self.cfg.numSS_it)
+        _chk(self.lib.lmpc_rollout_set_trace(self._h, cars.shape[0], cars.ctypes.data if cars.size else None, what))
+
+    def rollout_trace(self):
+        """(cars (n,) int32, what) in force (lmpc_rollout_get_trace); no cars and 0: off."""
+        n = C.c_int(); what = C.c_uint()
+        _chk(self.lib.lmpc_rollout_get_trace(self._h, C.byref(n), None, C.byref(what), 0))
+        cars = np.zeros(n.value, np.int32)
+        _chk(self.lib.lmpc_rollout_get_trace(self._h, C.byref(n), cars.ctypes.data, C.byref(what), cars.shape[0]))
+        return cars, int(what.value)
+
+    def rollout_trace_bytes(self, n, what, T_max):
+        """Device memory the trace planes of a session of that shape take (lmpc_rollout_trace_bytes)."""
+        b = C.c_longlong()
+        _chk(self.lib.lmpc_rollout_trace_bytes(self._h, int(n), int(what), int(T_max), C.byref(b)))
+        return int(b.value)
+
+    def rollout_fetch_trace(self, t0, t1, keys=None):
+        """The recorded planes of steps [t0, t1) of the active session (lmpc_rollout_fetch_trace): dict key -> array (t1 - t0, n, ...) with n the listed cars in the
+        order given to rollout_set_trace -- xPred (.., N + 1, 6), uPred (.., N, 2), ssSel (.., S, 6), qSel (.., S), iters, status, xyPred (.., N + 1, 2), xySS (.., S, 2),
+        mapStatus.  keys: only those planes (one the session does not record is refused by the library)."""
+        if self._ro_trace is None:
+            cars, what = np.zeros(0, np.int32), 0
+        else:
+            cars, what = self._ro_trace
+        n = int(t1) - int(t0)
+        if n < 0:
+            raise ValueError("rollout_fetch_trace: t1 < t0")
+        planes = {k: (shp, dt) for k, bit, shp, dt in trace_planes(self.N, self.S, what)}
+        if keys is not None:
+            full = {k: (shp, dt) for k, bit, shp, dt in trace_planes(self.N, max(self.S, 1), TRACE_ALL)}
+            planes = {k: full[k] for k in keys}
+        out = {k: np.zeros((n, cars.shape[0]) + tuple(shp), dt) for k, (shp, dt) in planes.items()}
+        arg = TraceOut(**{k: v.ctypes.data for k, v in out.items()})
+        _chk(self.lib.lmpc_rollout_fetch_trace(self._h, int(t0), int(t1), C.byref(arg)))
+        return out
 
     # ---- checkpoint / resume of the lap stores (SURVEY 5: optional .npz dump; no reference counterpart beyond an unused `import pickle`, main.py:36) ----
     def store_read_lap(self, store, lap):

@@ -5,6 +5,7 @@
 #include "lmpc_noise.hip.h"
 #include "lmpc_track.hip.h"
 #include "lmpc_commit.hip.h"
+#include "lmpc_trace.hip.h"
 #include "lmpc_arrays.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -126,6 +127,7 @@ struct lmpc_ctx {
     double tr_s[4]; long long tr_n;          // developer trace of lmpc_step_batch's one-QP path (lmpc_debug_step_trace): seconds spent staging / launching / waiting / unstaging
     struct lmpc_rollout_session *ro;
     int noise_on; unsigned long long noise_seed, noise_lap; long long noise_car0;   // lmpc_rollout_set_noise: sessions begun with noise = NULL fill their buffer on the device (lmpc_noise.hip.h); 0 after lmpc_create
+    std::vector<int> trace_cars; unsigned trace_what;   // lmpc_rollout_set_trace: the cars and planes later sessions record at every step (lmpc_trace.hip.h); empty / 0 after lmpc_create
     std::vector<double> plant_par; int plant_n;   // lmpc_plant_set_params: plant_n rows of LMPC_PLANT_NPAR vehicle constants (0: the reference's vehicle, the kernels with the literals)
     // lmpc_model_set_lap_table: lt_n rows of trToUse insertion indices as the caller gave them (0 rows: the first trToUse laps of the sorted order serve every problem);
     // d_lt: the same rows on the device as resolved (slot, rows) pairs in each row's sorted order, uploaded by `set` and rebuilt when the stores move or a lap is
@@ -163,6 +165,13 @@ struct lmpc_rollout_session {
     lmpc_arrays a;
     double *d_xg, *d_logX, *d_logU, *d_logG, *d_noise, *d_finX, *d_finG;
     int *d_done, *d_nDone, *d_stAcc;
+    // the session's snapshot of the trace (lmpc_rollout_set_trace), taken when it begins: tr_n listed cars (0: no trace, nothing below exists), the planes recorded;
+    // d_trCars: the list on the device, uploaded per begin; the planes [T_max][tr_n][...] belong to the kept set and are reused while B, T_max, tr_n, tr_what stay;
+    // the trace kernel runs on the plant stream behind the plant kernel (lmpc_rollout_run); tstream / e_trace serve the measured alternative, tr_own_stream
+    int tr_n; unsigned tr_what; int *d_trCars;
+    double *tr_x, *tr_u, *tr_ss, *tr_q, *tr_xy, *tr_xys; int *tr_it, *tr_st, *tr_map;
+    hipStream_t tstream; hipEvent_t e_trace;
+    bool tr_own_stream;                                         // (developer knob LMPC_TRACE_OWN_STREAM=1, read when a traced session begins: the trace kernel on a stream of its own beside the plant, the next solve waiting for a second event -- the A / B of tools/trace_bench.py, measured slower; same bits)
 };
 
 enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
@@ -219,7 +228,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 109; }
+int lmpc_version(void) { return 110; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -1736,10 +1745,20 @@ static void rollout_free(lmpc_ctx *c) {
     if (!c->ro) return;
     for (void *q : c->ro->keep) (void)g_free(q);
     if (c->ro->pstream) { (void)hipStreamDestroy(c->ro->pstream); (void)hipEventDestroy(c->ro->e_solved); (void)hipEventDestroy(c->ro->e_plant); }
+    if (c->ro->tstream) { (void)hipStreamDestroy(c->ro->tstream); (void)hipEventDestroy(c->ro->e_trace); }
     delete c->ro; c->ro = nullptr;
 }
 
 }  // extern "C"
+// Session traces (lmpc_rollout_set_trace): bytes per (step, car) of each plane in the order xPred, uPred, ssSel, qSel, iters, status, xyPred, xySS, mapStatus; 0: not recorded.
+#define LMPC_TRACE_PLANES 9
+static void trace_plane_bytes(const lmpc_ctx *c, unsigned what, size_t pb[LMPC_TRACE_PLANES]) {
+    const size_t N = c->dims.N, S = c->dims.S, d = sizeof(double);
+    pb[0] = (what & LMPC_TRACE_XPRED) ? (N + 1) * 6 * d : 0; pb[1] = (what & LMPC_TRACE_UPRED) ? N * 2 * d : 0;
+    pb[2] = (what & LMPC_TRACE_SS) ? S * 6 * d : 0; pb[3] = (what & LMPC_TRACE_QSEL) ? S * d : 0;
+    pb[4] = pb[5] = (what & LMPC_TRACE_SOLVER) ? sizeof(int) : 0;
+    pb[6] = (what & LMPC_TRACE_XY) ? (N + 1) * 2 * d : 0; pb[7] = (what & LMPC_TRACE_XY) ? S * 2 * d : 0; pb[8] = (what & LMPC_TRACE_XY) ? sizeof(int) : 0;
+}
 // Session set-up shared by lmpc_rollout_begin (kind RO_LMPC), lmpc_rollout_begin_mpc (RO_LTV / RO_LTI) and lmpc_rollout_pid (RO_PID): buffers, initial state, noise.
 // xLin0 / uLin0 may be NULL (RO_LTI, RO_PID: no linearisation trajectory; the buffers are zeroed).
 static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
@@ -1748,6 +1767,14 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     trk_src trk; { const int rc = track_for(c, B, &trk); if (rc) return rc; }      // (car b on track row b: refused before any session state changes)
     std::vector<double> par_rows;                               // refused before any session state changes (B beyond the per-car rows)
     if (c->plant_n > 0) { const int rc = plant_rows_for(c, B, par_rows); if (rc) return rc; }
+    // the trace in force (lmpc_rollout_set_trace; a PID session has no predictions and records none): a listed car the session does not have is refused here
+    const int tn = kind == RO_PID ? 0 : (int)c->trace_cars.size(); const unsigned tw = tn ? c->trace_what : 0u;
+    for (int k = 0; k < tn; k++) if (c->trace_cars[(size_t)k] >= B) {
+        char msg[128]; snprintf(msg, sizeof(msg), "traced car %d (entry %d of lmpc_rollout_set_trace) but the session has B = %d cars", c->trace_cars[(size_t)k], k, B);
+        return set_err(LMPC_E_ARG, "session trace", msg);
+    }
+    // SS, QSEL and XY of an LMPC session read the selection outputs the step writes only into the capture buffers: a traced session has them, capture or not
+    const bool need_sel = c->dbg_capture != 0 || (tn > 0 && S > 0 && (tw & (LMPC_TRACE_SS | LMPC_TRACE_QSEL | LMPC_TRACE_XY)) != 0);
     std::vector<int> lt_rows; bool lt_small = true;             // sessions that run the regression: the lap table in force, one resolved row per car (refused here as well when B is not its row count)
     if ((kind == RO_LMPC || kind == RO_LTV) && c->lt_n > 0) {
         k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc;
@@ -1759,13 +1786,15 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     // A generation loop begins a session of the same shape every lap: its ~35 device buffers (55 MB of logs at 1024 rollouts x 400 steps), the plant stream and
     // the two events are kept from one session to the next (round 5: allocating and freeing them was ~5 ms of every generation) and released by
     // lmpc_destroy or by a session of another shape.
-    if (c->ro && !c->ro->active && c->ro->B == B && c->ro->T_max == T_max && (c->ro->a.ssSel != nullptr) == (c->dbg_capture != 0)) {
+    if (c->ro && !c->ro->active && c->ro->B == B && c->ro->T_max == T_max && (c->ro->a.ssSel != nullptr) == need_sel && c->ro->tr_n == tn && c->ro->tr_what == tw) {
         lmpc_rollout_session *r = c->ro; r->t = 0; r->active = true; r->kind = kind; r->stop_at_line = stop_at_line;
         goto init_state;
     }
     rollout_free(c);
     {
     lmpc_rollout_session *r = new lmpc_rollout_session(); c->ro = r; r->B = B; r->T_max = T_max; r->t = 0; r->pstream = nullptr; r->active = true; r->kind = kind; r->stop_at_line = stop_at_line;
+    r->tr_n = tn; r->tr_what = tw; r->tstream = nullptr;
+    if (tn) { HIPCHK(hipStreamCreate(&r->tstream)); HIPCHK(hipEventCreateWithFlags(&r->e_trace, hipEventDisableTiming)); }
     HIPCHK(hipStreamCreate(&r->pstream)); HIPCHK(hipEventCreateWithFlags(&r->e_solved, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&r->e_plant, hipEventDisableTiming));
     bool ok = true;
     auto dalloc = [&](size_t bytes) -> void * { void *q = nullptr; if (g_malloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) { ok = false; return nullptr; } r->keep.push_back(q); return q; };
@@ -1779,8 +1808,15 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     });
     DA(double, d_xg, Bz * 6) DA(int, d_done, Bz) DA(int, d_nDone, 1) DA(int, d_stAcc, Bz) DA(double, d_finX, Bz * 6) DA(double, d_finG, Bz * 6)
     DA(double, d_par, Bz * LMPC_PLANT_NPAR) DA(int, d_lt, Bz * (size_t)std::max(c->cfg.trToUse, 1) * 2)
-    if (c->dbg_capture) { DA(double, a.ssSel, Bz * S * 6) DA(double, a.qSel, Bz * S) DA(double, a.succ, Bz * S * 6) DA(double, a.succU, Bz * S * 2) }
+    if (need_sel) { DA(double, a.ssSel, Bz * S * 6) DA(double, a.qSel, Bz * S) DA(double, a.succ, Bz * S * 6) DA(double, a.succU, Bz * S * 2) }
     DA(double, d_logX, (size_t)T_max * Bz * 6) DA(double, d_logU, (size_t)T_max * Bz * 2) DA(double, d_logG, (size_t)T_max * Bz * 6) DA(double, d_noise, (size_t)T_max * Bz * 3)
+    if (tn) {                                                   // only the planes asked for (trace_plane_bytes: bytes per step and car)
+        size_t pb[LMPC_TRACE_PLANES]; trace_plane_bytes(c, tw, pb);
+        const size_t rows = (size_t)T_max * (size_t)tn;
+        DA(int, d_trCars, tn)
+        void **pl[LMPC_TRACE_PLANES] = {(void **)&r->tr_x, (void **)&r->tr_u, (void **)&r->tr_ss, (void **)&r->tr_q, (void **)&r->tr_it, (void **)&r->tr_st, (void **)&r->tr_xy, (void **)&r->tr_xys, (void **)&r->tr_map};
+        for (int i = 0; i < LMPC_TRACE_PLANES; i++) *pl[i] = pb[i] ? dalloc(rows * pb[i]) : nullptr;
+    }
     r->d_noiseU = nullptr; r->d_vt = nullptr;                   // (allocated by the first lmpc_rollout_pid on the session's buffers, kept with them)
 #undef DA
     if (!ok) { rollout_free(c); return set_err(LMPC_E_HIP, "hipMalloc", "rollout buffers"); }
@@ -1807,10 +1843,15 @@ init_state:
     if (noise) H2D(r->d_noise, noise, (size_t)T_max * Bz * 3);
     else { lmpc_noise_fill_launch(c->stream, r->nz_seed, 0ull, r->nz_lap, 0, T_max, r->nz_car0, B, 3, r->d_noise); HIPCHK(hipGetLastError()); }
     r->trk = trk.dev; r->trk_stride = trk.stride;
+    if (r->tr_n) { const char *e = dev_knob("LMPC_TRACE_OWN_STREAM"); r->tr_own_stream = e && atoi(e) != 0; }
     r->has_par = !par_rows.empty();                             // the snapshot: lmpc_plant_set_params during the session reaches the next one only
     if (r->has_par) H2D(r->d_par, par_rows.data(), par_rows.size());
     r->has_lt = !lt_rows.empty(); r->lt_small = lt_small; r->lt_stride = 2 * c->cfg.trToUse;   // the snapshot: lmpc_model_set_lap_table during the session reaches the next one only
     if (r->has_lt) H2D(r->d_lt, lt_rows.data(), lt_rows.size());
+    if (r->tr_n) {                                              // the car list may differ from the kept session's; mapStatus is ORed into, so it starts at zero
+        H2D(r->d_trCars, c->trace_cars.data(), (size_t)r->tr_n);
+        if (r->tr_map) HIPCHK(hipMemsetAsync(r->tr_map, 0, sizeof(int) * (size_t)T_max * (size_t)r->tr_n, c->stream));
+    }
     HIPCHK(hipMemsetAsync(r->d_nDone, 0, sizeof(int), c->stream)); HIPCHK(hipMemsetAsync(r->d_stAcc, 0, sizeof(int) * Bz, c->stream));
     HIPCHK(hipMemsetAsync(r->d_finX, 0, sizeof(double) * Bz * 6, c->stream)); HIPCHK(hipMemsetAsync(r->d_finG, 0, sizeof(double) * Bz * 6, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1943,14 +1984,29 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         }
         io.rstatus = lti ? nullptr : r->a.rstatus;
         if (r->t > 0) HIPCHK(hipStreamWaitEvent(c->stream, r->e_plant, 0));          // the solve needs the plant's new state
+        if (r->t > 0 && r->tr_n && r->tr_own_stream) HIPCHK(hipStreamWaitEvent(c->stream, r->e_trace, 0));   // (traced sessions: and must not overwrite outputs the trace kernel of the last step still reads)
         rc = launch_solve(c, B, io, true); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
         HIPCHK(hipEventRecord(r->e_solved, c->stream));
         HIPCHK(hipStreamWaitEvent(r->pstream, r->e_solved, 0));
+        // the trace of this step: behind the plant kernel on the plant stream, in front of e_plant -- off the solve -> shift -> regression chain of the context's
+        // stream, and the one event the next solve waits for anyway covers it.  (LMPC_TRACE_OWN_STREAM=1: on a stream of its own beside the plant, with an event of its
+        // own for the next solve -- measured slower, DESIGN.md "Session traces")
+        auto launch_trace = [&](hipStream_t on) {
+            lmpc_trace_args ta = {r->d_trCars, r->tr_n, (int)N, (int)c->dims.S, r->a.xPred, r->a.uPred, r->a.ssSel, r->a.qSel, r->a.iters, r->a.status,
+                                  r->tr_x, r->tr_u, r->tr_ss, r->tr_q, r->tr_xy, r->tr_xys, r->tr_it, r->tr_st, r->tr_map, r->trk, r->trk_stride};
+            hipLaunchKernelGGL(r->trk ? lmpc_rollout_trace_kernel<true> : lmpc_rollout_trace_kernel<false>, dim3(r->tr_n), dim3(LMPC_TRACE_NT), 0, on, c->dp, r->t, ta);
+        };
+        if (r->tr_n && r->tr_own_stream) {
+            HIPCHK(hipStreamWaitEvent(r->tstream, r->e_solved, 0));
+            launch_trace(r->tstream);
+            HIPCHK(hipEventRecord(r->e_trace, r->tstream));
+        }
         {
             auto k = r->has_par ? lmpc_rollout_plant_kernel<true> : lmpc_rollout_plant_kernel<false>;
             if (r->trk) k = r->has_par ? lmpc_rollout_plant_kernel<true, true> : lmpc_rollout_plant_kernel<false, true>;
             hipLaunchKernelGGL(k, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
         }
+        if (r->tr_n && !r->tr_own_stream) launch_trace(r->pstream);
         HIPCHK(hipEventRecord(r->e_plant, r->pstream));
         if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->a.uPred, r->a.uOld);
         else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression
@@ -1958,6 +2014,7 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         r->t++;
         if ((r->t & 7) == 0 || r->t == t_end) {
             HIPCHK(hipStreamSynchronize(r->pstream));
+            if (r->tr_n) HIPCHK(hipStreamSynchronize(r->tstream));
             HIPCHK(hipMemcpyAsync(&nd, r->d_nDone, sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
             if (nd >= B && r->stop_at_line) break;
         }
@@ -1975,6 +2032,58 @@ int lmpc_rollout_fetch(lmpc_ctx *c, int t0, int t1, double *X, double *U, double
     HIPCHK(hipSetDevice(c->cfg.device));
     if (n) { D2H(X, r->d_logX + (size_t)t0 * Bz * 6, n * Bz * 6); D2H(U, r->d_logU + (size_t)t0 * Bz * 2, n * Bz * 2); D2H(G, r->d_logG + (size_t)t0 * Bz * 6, n * Bz * 6); }
     D2H(doneAt, r->d_done, Bz); D2H(status, r->d_stAcc, Bz); D2H(finalX, r->d_finX, Bz * 6); D2H(finalG, r->d_finG, Bz * 6);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LMPC_OK;
+}
+
+int lmpc_rollout_set_trace(lmpc_ctx *c, int n, const int *cars, unsigned what) {
+    // the cars and planes of the sessions begun after this call (an active session keeps its snapshot); checked in full before anything changes; needs no device.
+    // A car >= B can only be judged by the begin that meets it (rollout_setup)
+    ARGCHK(c && n >= 0 && (n == 0 || cars));
+    if (n > 0) {
+        ARGCHK(what != 0 && (what & ~LMPC_TRACE_ALL) == 0);
+        if (c->cfg.numSS_it == 0 && (what & (LMPC_TRACE_SS | LMPC_TRACE_QSEL)))
+            return set_err(LMPC_E_ARG, "lmpc_rollout_set_trace", "LMPC_TRACE_SS / LMPC_TRACE_QSEL on a context without a safe set (numSS_it == 0)");
+        std::vector<int> sorted(cars, cars + n); std::sort(sorted.begin(), sorted.end());
+        if (sorted[0] < 0) { char msg[64]; snprintf(msg, sizeof(msg), "car %d is negative", sorted[0]); return set_err(LMPC_E_ARG, "lmpc_rollout_set_trace", msg); }
+        for (int k = 1; k < n; k++) if (sorted[(size_t)k] == sorted[(size_t)k - 1]) { char msg[64]; snprintf(msg, sizeof(msg), "car %d is listed twice", sorted[(size_t)k]); return set_err(LMPC_E_ARG, "lmpc_rollout_set_trace", msg); }
+    }
+    c->trace_cars.assign(cars, cars + n); c->trace_what = n ? what : 0u;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_get_trace(lmpc_ctx *c, int *n, int *cars, unsigned *what, int capacity) {
+    ARGCHK(c && n && capacity >= 0);
+    *n = (int)c->trace_cars.size();
+    if (what) *what = c->trace_what;
+    if (cars) memcpy(cars, c->trace_cars.data(), sizeof(int) * (size_t)std::min(capacity, *n));
+    return LMPC_OK;
+}
+
+int lmpc_rollout_trace_bytes(lmpc_ctx *c, int n, unsigned what, int T_max, long long *bytes) {
+    ARGCHK(c && bytes && n >= 0 && T_max >= 0 && (what & ~LMPC_TRACE_ALL) == 0);
+    size_t pb[LMPC_TRACE_PLANES], per = 0; trace_plane_bytes(c, what, pb);
+    for (int i = 0; i < LMPC_TRACE_PLANES; i++) per += pb[i];
+    *bytes = (long long)per * (long long)n * (long long)T_max;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_fetch_trace(lmpc_ctx *c, int t0, int t1, const lmpc_trace_out *out) {
+    // trace rows of steps [t0, t1), every plane [t - t0][k][...] with k the position in the session's car list; a NULL pointer skips its plane
+    ARGCHK(c && out);
+    if (!(c->ro && c->ro->active)) return set_err(LMPC_E_STATE, "lmpc_rollout_fetch_trace", "no rollout session is active");
+    lmpc_rollout_session *r = c->ro;
+    if (r->kind == RO_PID || r->tr_n == 0) return set_err(LMPC_E_STATE, "lmpc_rollout_fetch_trace", r->kind == RO_PID ? "a PID session records no trace" : "the session was begun without a trace (lmpc_rollout_set_trace)");
+    ARGCHK(t0 >= 0 && t1 >= t0 && t1 <= r->t);
+    ARGCHK((!out->xPred || r->tr_x) && (!out->uPred || r->tr_u) && (!out->ssSel || r->tr_ss) && (!out->qSel || r->tr_q) && (!out->xyPred || r->tr_xy) &&
+           (!out->xySS || r->tr_xys) && (!out->iters || r->tr_it) && (!out->status || r->tr_st) && (!out->mapStatus || r->tr_map));     // (a plane the session does not record)
+    HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(r->tstream)); HIPCHK(hipStreamSynchronize(r->pstream));
+    size_t pb[LMPC_TRACE_PLANES]; trace_plane_bytes(c, r->tr_what, pb);
+    const size_t first = (size_t)t0 * (size_t)r->tr_n, rows = (size_t)(t1 - t0) * (size_t)r->tr_n;
+    void *dst[LMPC_TRACE_PLANES] = {out->xPred, out->uPred, out->ssSel, out->qSel, out->iters, out->status, out->xyPred, out->xySS, out->mapStatus};
+    const void *src[LMPC_TRACE_PLANES] = {r->tr_x, r->tr_u, r->tr_ss, r->tr_q, r->tr_it, r->tr_st, r->tr_xy, r->tr_xys, r->tr_map};
+    for (int i = 0; i < LMPC_TRACE_PLANES; i++)
+        if (dst[i] && rows && pb[i]) HIPCHK(hipMemcpyAsync(dst[i], (const char *)src[i] + first * pb[i], rows * pb[i], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LMPC_OK;
 }
@@ -2021,6 +2130,7 @@ int lmpc_rollout_end(lmpc_ctx *c) {
     ARGCHK(c); HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(c->stream));
     if (c->ro) {
         if (c->ro->pstream) HIPCHK(hipStreamSynchronize(c->ro->pstream));
+        if (c->ro->tstream) HIPCHK(hipStreamSynchronize(c->ro->tstream));
 #ifdef LMPC_GUARD
         rollout_free(c);                                   // (guard builds check the zone behind every buffer when it is freed: keep doing that per session)
 #else

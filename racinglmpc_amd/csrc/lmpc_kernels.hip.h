@@ -224,23 +224,17 @@ __device__ __forceinline__ double frsqrt(double x) {
 // Map.getGlobalPosition, Track.py:135-189: curvilinear (s, ey) -> inertial (X, Y), one thread per point (batched plotting /
 // logging export of predicted trajectories and safe-set points).  Row i - 1 of the table wraps to the last
 // row for i = 0, as the reference's negative index does.
-// TRK: point e reads row e of trk (stride doubles between rows; 0: one row serves every point) instead of the parameter block's track (lmpc_track_set).
-template <bool TRK>
-__global__ void lmpc_global_position_kernel(lmpc_dev_params p_, int n, const double *__restrict__ s_in, const double *__restrict__ ey_in,
-                                            double *__restrict__ xy, int *__restrict__ status, const double *__restrict__ trk, int trkStride) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(trk, (size_t)trkStride, (size_t)e);
-    const auto &p = track_src<TRK>(p_, tr_);
+// One point of the map on the track source TK (the parameter block or an element's own row): false, with (x, y) = (0, 0), where s lies on no segment.  The body of
+// lmpc_global_position_kernel, shared with the session trace (lmpc_trace.hip.h: lmpc_rollout_trace_kernel).
+template <class TK>
+__device__ __forceinline__ bool global_position_point(const TK &p, double s, const double ey, double &x, double &y) {
     const double PI = 3.141592653589793;
-    double s = s_in[e]; const double ey = ey_in[e];
     for (int lap = 0; lap < 4096 && s > p.TL; lap++) s = s - p.TL;                          // (`while s > TrackLength`, bounded: an infinite s must not hang the GPU)
     int i = -1;
     if (!(s <= p.TL)) s = -1.0;                                                               // -> on no segment
     for (int r = 0; r < p.track_rows; r++) { const double c0 = p.track[r * 6 + 3]; if (s >= c0 && s < c0 + p.track[r * 6 + 4]) { i = r; break; } }
-    if (i < 0) { status[e] = LMPC_ST_NO_SEGMENT; xy[2 * e] = 0.0; xy[2 * e + 1] = 0.0; return; }
+    if (i < 0) { x = 0.0; y = 0.0; return false; }
     const double *ti = p.track + i * 6, *tp = p.track + (i > 0 ? i - 1 : p.track_rows - 1) * 6;
-    double x, y;
     if (ti[5] == 0.0) {
         const double deltaL = ti[4], reltaL = s - ti[3], psi = ti[2];
         x = (1 - reltaL / deltaL) * tp[0] + reltaL / deltaL * ti[0] + ey * cos(psi + PI / 2);
@@ -255,7 +249,18 @@ __global__ void lmpc_global_position_kernel(lmpc_dev_params p_, int n, const dou
         x = cx + (ar - dir * ey) * cos(angle + dir * span);
         y = cy + (ar - dir * ey) * sin(angle + dir * span);
     }
-    xy[2 * e] = x; xy[2 * e + 1] = y; status[e] = 0;
+    return true;
+}
+// TRK: point e reads row e of trk (stride doubles between rows; 0: one row serves every point) instead of the parameter block's track (lmpc_track_set).
+template <bool TRK>
+__global__ void lmpc_global_position_kernel(lmpc_dev_params p_, int n, const double *__restrict__ s_in, const double *__restrict__ ey_in,
+                                            double *__restrict__ xy, int *__restrict__ status, const double *__restrict__ trk, int trkStride) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    lmpc_track_row tr_ = {nullptr, 0, 0.0}; if constexpr (TRK) tr_ = track_row_at(trk, (size_t)trkStride, (size_t)e);
+    double x, y;
+    const bool on = global_position_point(track_src<TRK>(p_, tr_), s_in[e], ey_in[e], x, y);
+    xy[2 * e] = x; xy[2 * e + 1] = y; status[e] = on ? 0 : LMPC_ST_NO_SEGMENT;
 }
 
 #endif  // LMPC_VARIANT_TU

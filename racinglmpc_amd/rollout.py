@@ -19,8 +19,14 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set, or (ss_table) each car against its own (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None, tracks=None):
-        """tracks: the tracks of the cars of THIS object (this rank's shard) -- one PointAndTangent table for all cars or a sequence of them, one per car (tables, or
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None, tracks=None, trace=None, trace_what=None):
+        """trace / trace_what: the cars of THIS object whose controller output every LMPC / MPC session records step by step, and the planes (_capi.TRACE_* bits; None:
+        every plane the context can record) -- the reference's xStoredPredTraj / uStoredPredTraj / SSStoredPredTraj (PredictiveControllers.py:364-379) with the
+        Q-values, the solver's words and the inertial positions beside them (Context.rollout_set_trace); handed to the context before every begin and run_mpc_laps,
+        beside tuning.  run_lap_device, run_mpc_laps and PerCarLMPC.run then leave the session's trace in `last_trace`: the planes (steps, listed cars, ...) of
+        Context.rollout_fetch_trace plus "cars" and "doneAt" (the crossing step of each listed car, -1: none) -- TraceView turns it into one car's history.  None:
+        the context's trace is left as it is and last_trace stays None.
+        tracks: the tracks of the cars of THIS object (this rank's shard) -- one PointAndTangent table for all cars or a sequence of them, one per car (tables, or
         (table, trackLength) pairs, or (n, 98) rows as _capi.track_rows builds them); handed to the context (Context.track_set) before every begin, run_pid_laps and
         run_mpc_laps, beside plant_params.  `TL` is then an array, one length per row (track_lengths(B): one per car).  None: the context's rows are left as they
         are and `TL` is the length of `track`, the table of the context's configuration.
@@ -62,6 +68,8 @@ class BatchedRollouts:
         if ss_table is None and ss_last is not None:
             raise ValueError("ss_last: needs ss_table")
         self.tuning = None if tuning is None else _capi.check_tuning(tuning, ctx.cfg.numSS_it)
+        self.trace = None if trace is None else _capi.check_trace(trace, trace_what, ctx.cfg.numSS_it)
+        self.last_trace = None
         self.device_noise = bool(device_noise)
         if self.device_noise:
             import operator
@@ -219,6 +227,27 @@ class BatchedRollouts:
             raise ValueError("tuning: one row or one per car (%d) expected, got %d" % (B, rows.shape[0]))
         self.ctx.tuning_set(rows)
 
+    def _apply_trace(self, B):
+        """The traced cars of this object go to the context in front of a session that solves."""
+        tr = getattr(self, "trace", None)              # (objects built without __init__ -- tests/test_host_checks.py -- have none)
+        if tr is None:
+            return
+        cars, what = tr
+        if cars.size and int(cars.max()) >= B:
+            raise ValueError("trace: car %d listed, the session has %d cars" % (int(cars.max()), B))
+        self.ctx.rollout_set_trace(cars, what)
+
+    def _fetch_trace(self, t, done):
+        """last_trace of the active session, to be called before rollout_end: the planes of steps [0, t) and the listed cars' crossing steps."""
+        tr = getattr(self, "trace", None)
+        if tr is None or tr[0].size == 0:
+            self.last_trace = None
+            return None
+        out = self.ctx.rollout_fetch_trace(0, t)
+        out["cars"] = tr[0].copy(); out["doneAt"] = np.asarray(done)[tr[0]].copy()
+        self.last_trace = out
+        return out
+
     @staticmethod
     def _per_rollout(a, B):
         a = np.asarray(a, float)
@@ -233,6 +262,7 @@ class BatchedRollouts:
         self._apply_lap_table(B)
         self._apply_ss_table(B)
         self._apply_tuning(B)
+        self._apply_trace(B)
         if self._device_noise_session(B):
             self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, None, T_max=max_steps)
         else:
@@ -253,6 +283,7 @@ class BatchedRollouts:
                 on_ext(X, U)
         t, nd = self.ctx.rollout_run(max_steps)
         X, U, G, done, st, fx, fg = self.ctx.rollout_fetch(0, t)
+        self._fetch_trace(t, done)
         self.ctx.rollout_end()
         self.last_status, self.last_done = st, done
         laps = []
@@ -307,6 +338,7 @@ class BatchedRollouts:
         if A is None:
             self._apply_lap_table(nb)              # (the LTI form runs no regression)
         self._apply_tuning(nb)
+        self._apply_trace(nb)
         kw = dict(T_max=max_steps) if self._device_noise_session(nb) else {}       # (noise is None then: the session's buffer is filled on the device)
         if A is not None:
             self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line, **kw)
@@ -314,6 +346,7 @@ class BatchedRollouts:
             self.ctx.rollout_begin_mpc(x0, x0, noise, xLin0=self._per_rollout(xLin0, nb), uLin0=self._per_rollout(uLin0, nb), stop_at_line=stop_at_line, **kw)
         t, _ = self.ctx.rollout_run(max_steps)
         out = self.ctx.rollout_fetch(0, t)
+        self._fetch_trace(t, out[3])
         self.ctx.rollout_end()
         return self._collect(nb, *out, whole=not stop_at_line, keep_invalid=keep_invalid)
 
@@ -667,15 +700,20 @@ class PerCarLMPC:
     logged rows are downloaded.  The tuples run() returns, and latest[b], then carry only the first min(T, N + 2) rows of x and u -- what the next generation
     linearises about -- and None for x_glob; the full lap is in the stores (Context.store_read_lap).
     tuning: rows of _capi.tuning_rows, one for all cars or one per car -- what BatchedRollouts(tuning=) takes; car b then also runs its own controller tuning.
+    trace / trace_what: what BatchedRollouts(trace=) takes; `traces` then holds one entry per generation, the session's trace (planes, "cars", "doneAt"), the same with
+    and without device_commit -- TraceView(track, car, traces) is one car's history as the reference's plots read an LMPC object.
     Tracks: with BatchedRollouts(tracks=) holding one track per car, car b drives, regresses and selects on its own track; its start state is its crossing state
     shifted by its OWN TrackLength, and its laps and extensions are stored with track_row = b (Context.ss_add_trajectory / ss_extend_lap, or the device commit, which
     takes the car's row by itself)."""
 
     EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
 
-    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None):
+    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None, trace=None, trace_what=None):
         self.ro, self.T_max, self.ext = rollouts, int(T_max), int(ext)
         self.device_commit = bool(device_commit)
+        if trace is not None:              # (the cars whose predictions every generation records: what BatchedRollouts(trace=) takes)
+            self.ro.trace = _capi.check_trace(trace, trace_what, self.ro.ctx.cfg.numSS_it)
+        self.traces = []                   # one entry per generation run with a trace: the rollouts object's last_trace of that session
         if tuning is not None:             # (one row, or one per car: each learner its own cost weights and bounds; the rollouts object hands them to the context before every begin)
             self.ro.tuning = _capi.check_tuning(tuning, self.ro.ctx.cfg.numSS_it)
         self.B = None
@@ -763,6 +801,8 @@ class PerCarLMPC:
                         ctx.ss_extend_lap(int(self.last[b]), X[:n, b], U[:n, b], track_row=b)     # (the table is live in the session: the next step selects from the longer lap)
             t, _ = ctx.rollout_run(self.T_max)
             X, U, G, done, st, fx, fg = ctx.rollout_fetch(0, t)
+            if ro._fetch_trace(t, done) is not None:
+                self.traces.append(ro.last_trace)
         finally:
             ctx.rollout_end()
         self.last_status, self.last_done = st, done
@@ -811,6 +851,8 @@ class PerCarLMPC:
             t, _ = ctx.rollout_run(self.T_max)
             _, _, _, done, st, fx, fg = ctx.rollout_fetch(0, 0)
             Xh, Uh = ctx.rollout_fetch(0, min(t, N + 2))[:2]
+            if ro._fetch_trace(t, done) is not None:
+                self.traces.append(ro.last_trace)
             valid = []
             for b in range(B):
                 if b in self.retired:
@@ -836,3 +878,68 @@ class PerCarLMPC:
         self._hand_tables()
         self.generation += 1
         return out
+
+
+def _track_angle(table, s):
+    """Tangent angle of the centre line at arc length s of a PointAndTangent table (Track.py:54-133: column 2 is the angle at a row's END point); NaN on no row."""
+    TL = table[-1, 3] + table[-1, 4]
+    s = np.mod(np.asarray(s, float), TL)
+    out = np.full(s.shape, np.nan)
+    for i in range(table.shape[0]):
+        on = (s >= table[i, 3]) & (s < table[i, 3] + table[i, 4])
+        out[on] = table[i, 2] if table[i, 5] == 0.0 else table[i - 1, 2] + (s[on] - table[i, 3]) * table[i, 5]
+    return out
+
+
+class TraceView:
+    """One car's history in the attribute shape the reference's plots read from an LMPC object (plot.py:50-103 plotClosedLoopLMPC, :106-175 animation_xy,
+    animation_states): SS_glob, LapTime, SS, uSS, it, N, numSS_Points, xStoredPredTraj[it][i] (N + 1, 6), uStoredPredTraj[it][i] (N, 2) and SSStoredPredTraj[it][i]
+    (S, 6) -- the three per-step logs of LMPC.unpackSolution (PredictiveControllers.py:364-379) -- built from session traces instead of a host loop.  Beside them
+    xyPred[it][i] (N + 1, 2) and xySS[it][i] (S, 2), the inertial positions the device has already mapped (no per-point getGlobalPosition on the host), qSel, iters,
+    status and mapStatus where recorded.  Every lap is cut at the car's crossing step (all recorded steps for a car that did not cross).
+
+    track_or_map: the PointAndTangent table of the car's track, or an object that has one (the reference's Map).
+    car: the car's index in its batch.
+    laps: one entry per lap, in order -- a trace (an element of PerCarLMPC.traces, or BatchedRollouts.last_trace) or a pair (trace, lap) with lap the car's tuple
+    (x, u, x_glob, ...) as run_lap_device returns it.  Without the tuple the lap's states and inputs are row 0 of the predictions (x_0 = x0 is an equality row of the
+    QP) and SS_glob is put together from them: vx, vy, wz, the track's tangent angle + epsi, and (X, Y) of row 0 of xyPred (NaN without the XY plane)."""
+
+    PLANES = ("xPred", "uPred", "ssSel", "qSel", "xyPred", "xySS", "iters", "status", "mapStatus")
+
+    def __init__(self, track_or_map, car, laps):
+        self.track = np.asarray(getattr(track_or_map, "PointAndTangent", track_or_map), float)
+        self.TrackLength = float(self.track[-1, 3] + self.track[-1, 4])
+        self.car = int(car)
+        self.SS, self.uSS, self.SS_glob, self.LapTime = [], [], [], []
+        self.xStoredPredTraj, self.uStoredPredTraj, self.SSStoredPredTraj = [], [], []
+        self.qSel, self.xyPred, self.xySS, self.iters, self.status, self.mapStatus = [], [], [], [], [], []
+        self.N = self.numSS_Points = None
+        for entry in laps:
+            tr, lap = entry if isinstance(entry, (tuple, list)) else (entry, None)
+            where = np.flatnonzero(np.asarray(tr["cars"]) == self.car)
+            if where.size != 1:
+                raise ValueError("TraceView: car %d is not among the traced cars %s" % (self.car, list(np.asarray(tr["cars"]))))
+            k = int(where[0])
+            if "xPred" not in tr:
+                raise ValueError("TraceView: the trace has no XPRED plane")
+            steps = tr["xPred"].shape[0]
+            done = int(tr["doneAt"][k])
+            T = done if 0 <= done <= steps else steps
+            cut = {key: tr[key][:T, k] for key in self.PLANES if key in tr}
+            xP = cut["xPred"]
+            self.N = xP.shape[1] - 1
+            if "ssSel" in cut:
+                self.numSS_Points = cut["ssSel"].shape[1]
+            if lap is not None:
+                x, u, xg = (np.asarray(a, float)[:T] for a in lap[:3])
+            else:
+                x = xP[:, 0, :].copy()
+                u = cut["uPred"][:, 0, :].copy() if "uPred" in cut else np.full((T, 2), np.nan)
+                xy = cut["xyPred"][:, 0, :] if "xyPred" in cut else np.full((T, 2), np.nan)
+                xg = np.column_stack([x[:, 0:3], _track_angle(self.track, x[:, 4]) + x[:, 3], xy])
+            self.SS.append(x); self.uSS.append(u); self.SS_glob.append(xg); self.LapTime.append(T)
+            self.xStoredPredTraj.append(xP)
+            for name, key in (("uStoredPredTraj", "uPred"), ("SSStoredPredTraj", "ssSel"), ("qSel", "qSel"), ("xyPred", "xyPred"), ("xySS", "xySS"),
+                              ("iters", "iters"), ("status", "status"), ("mapStatus", "mapStatus")):
+                getattr(self, name).append(cut.get(key))
+        self.it = len(self.LapTime)
