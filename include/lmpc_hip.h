@@ -123,7 +123,7 @@ int lmpc_model_add_trajectory(lmpc_ctx *, const double *x /*T x 6*/, const doubl
 int lmpc_model_num_laps(lmpc_ctx *, int *n);
 int lmpc_model_replace_lap(lmpc_ctx *, int pos /*position in sorted order*/, const double *x, const double *u, int T);
 int lmpc_model_set_lap_table(lmpc_ctx *, int n, const int *laps /*n x trToUse insertion indices, or NULL with n = 0*/);
-        /* Per-problem regression laps: which stored laps the regression (PredictiveModel.regressionAndLinearization) of each problem of a batch reads -- each car's
+        /* Per-problem regression laps (one of the five per-car row sets, one contract: INTEGRATION.md section 4, "The per-car row sets"): which stored laps the regression (PredictiveModel.regressionAndLinearization) of each problem of a batch reads -- each car's
          * LTV model from its own data, main.py:88-89 per car.  An entry is the INSERTION index of a regression-store lap (0 = the first lmpc_model_add_trajectory):
          * stable under later inserts and store growth, unrelated to the lap's position in the sorted order.  Duplicates inside a row are allowed (main.py:103-104 adds
          * one lap four times).  Each row is used in the order a context holding only those laps would use them -- ascending length, ties by insertion index
@@ -150,7 +150,7 @@ int lmpc_ss_set_selected(lmpc_ctx *, const int *laps, int n);
         /* override of argsort(LapTime)[0:numSS_it] (:395,402); n = 0 restores the built-in stable sort */
 int lmpc_ss_set_lap_table(lmpc_ctx *, int n, const int *laps /* n x numSS_it safe-set lap indices, lmpc_ss_add_trajectory order; NULL with n = 0 */,
                           const int *last /* n, or NULL */);
-        /* Per-problem safe sets: which stored laps the selection (LMPC.addTerminalComponents / selectPoints, :386-412, :478-514) of each problem of a batch reads -- each
+        /* Per-problem safe sets (one of the five per-car row sets, one contract: INTEGRATION.md section 4, "The per-car row sets"): which stored laps the selection (LMPC.addTerminalComponents / selectPoints, :386-412, :478-514) of each problem of a batch reads -- each
          * car's terminal set and terminal cost from its own laps, as every LMPC object of the reference owns SS / uSS / Qfun / LapTime (:395-412).  Row b names the numSS_it
          * laps problem b selects from, by their index in lmpc_ss_add_trajectory order.  Duplicates are allowed (main.py:109-110 adds one lap four times), so a row may be
          * served by fewer than numSS_it stored laps.  Each row is used in the order a controller holding only those laps would use them -- ascending LapTime
@@ -184,7 +184,7 @@ int lmpc_ss_get_lap_table(lmpc_ctx *, int *n, int *laps /* capacity x numSS_it, 
 int lmpc_tuning_from_config(const lmpc_config *, double *row /*98*/);
         /* the row a context created from that config uses by default (MPCParams, PredictiveControllers.py:24-51).  Needs no device */
 int lmpc_tuning_set(lmpc_ctx *, int n, const double *rows /*n x 98, or NULL with n = 0*/);
-        /* The tuning (MPCParams, PredictiveControllers.py:24-51) of every later solve on this context.  n = 0: back to the config's weights, bit for bit (the kernels
+        /* The tuning (MPCParams, PredictiveControllers.py:24-51) of every later solve on this context (one of the five per-car row sets, one contract: INTEGRATION.md section 4, "The per-car row sets").  n = 0: back to the config's weights, bit for bit (the kernels
          * that read the parameter block).  n = 1: that row serves every problem.  n > 1: problem b of a call uses row b, and a launch whose batch B != n returns
          * LMPC_E_ARG and says so in lmpc_last_error (the context stays usable) -- the lap tables' rule.  LMPC_E_ARG, with the rows in force kept, for a non-finite
          * entry, Q, R or Qf not exactly symmetric, a negative dR or Qslack entry, a QtermSlack entry <= 0 on a context with numSS_it > 0, n < 0, n > max_batch, NULL
@@ -211,7 +211,7 @@ int lmpc_tuning_get(lmpc_ctx *, int *n, double *rows /*capacity x 98, or NULL*/,
 int lmpc_track_row_from_config(const lmpc_config *, double *row /*98*/);
         /* the row a context created from that config uses by default (track, track_rows, trackLength).  Needs no device */
 int lmpc_track_set(lmpc_ctx *, int n, const double *rows /*n x 98, or NULL with n = 0*/);
-        /* n = 0: the config's track; every path returns the bits it returned before there were rows (the kernels that read the parameter block run).  n = 1: that row
+        /* Per-car tracks (one of the five per-car row sets, one contract: INTEGRATION.md section 4, "The per-car row sets").  n = 0: the config's track; every path returns the bits it returned before there were rows (the kernels that read the parameter block run).  n = 1: that row
          * serves every car.  n > 1: element b of a batched call uses row b, and a call whose count differs from n returns LMPC_E_ARG and says so in lmpc_last_error
          * (the context stays usable).  LMPC_E_ARG, with the rows in force kept, for a non-finite entry, a row count that is not an integer in 1..16, trackLength <= 0, a
          * negative segment length (a zero or rounding-sized one is a row no s lies on, e.g. the closing row of an oval: accepted), n < 0, n > max_batch, NULL rows with
@@ -331,7 +331,7 @@ int lmpc_plant_params_default(double *par /*10*/);
          * order.  Needs no device */
 int lmpc_plant_set_params(lmpc_ctx *, int n, const double *par /*n x 10, or NULL with n = 0*/);
         /* the vehicle(s) of every later lmpc_plant_step_batch, lmpc_rollout_begin, lmpc_rollout_begin_mpc and lmpc_rollout_pid on this context (Simulator.dynModel,
-         * SysModel.py:56-147, with the constants of :60-70 replaced).  n = 0: the reference's vehicle (the kernels that carry the literals).  n = 1: every car uses
+         * SysModel.py:56-147, with the constants of :60-70 replaced; one of the five per-car row sets, one contract: INTEGRATION.md section 4, "The per-car row sets").  n = 0: the reference's vehicle (the kernels that carry the literals).  n = 1: every car uses
          * that row.  n > 1: car b uses row b, n <= max_batch; a later call with B > n returns LMPC_E_ARG and says so in lmpc_last_error.  LMPC_E_ARG for a non-finite
          * entry, m <= 0 or Iz <= 0: the parameters in force stay.  A rollout session takes a snapshot when it begins: setting parameters while a session is active
          * is allowed and reaches the next session only; kept session buffers of the same shape are reused whatever the parameters */

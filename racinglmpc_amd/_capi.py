@@ -263,34 +263,49 @@ def plant_params_default():
     return par
 
 
+def _check_rows(rows, width, label, allow_none, values=None):
+    """What every check of float rows opens with: None for "no rows" (allow_none: None or empty), else (n, width) float64 rows, a flat row being one row; ValueError
+    under `label` for another shape or a non-finite entry.  values: how the message names a row's entries (default "<width> values")."""
+    if allow_none and (rows is None or np.size(rows) == 0):
+        return None
+    r = np.array(rows, dtype=np.float64, ndmin=2)
+    if r.ndim != 2 or r.shape[1] != width:
+        raise ValueError("%s: rows of %s expected, got shape %s" % (label, values or "%d values" % width, r.shape))
+    if not np.all(np.isfinite(r)):
+        raise ValueError("%s: non-finite entry in row(s) %s" % (label, np.where(~np.isfinite(r).all(1))[0].tolist()))
+    return np.ascontiguousarray(r)
+
+
 def check_plant_params(par):
     """(n, 10) float64 rows, or ValueError for what lmpc_plant_set_params refuses: a wrong shape, a non-finite entry, m <= 0 or Iz <= 0."""
-    par = np.array(par, dtype=np.float64, ndmin=2)
-    if par.ndim != 2 or par.shape[1] != PLANT_NPAR:
-        raise ValueError("plant parameters: rows of %d values %s expected, got shape %s" % (PLANT_NPAR, PLANT_PARAM_NAMES, par.shape))
-    if not np.all(np.isfinite(par)):
-        raise ValueError("plant parameters: non-finite entry in row(s) %s" % np.where(~np.isfinite(par).all(1))[0].tolist())
+    par = _check_rows(par, PLANT_NPAR, "plant parameters", False, "%d values %s" % (PLANT_NPAR, PLANT_PARAM_NAMES))
     if not (np.all(par[:, 0] > 0) and np.all(par[:, 3] > 0)):
         raise ValueError("plant parameters: m and Iz must be positive (rows %s)" % np.where(~((par[:, 0] > 0) & (par[:, 3] > 0)))[0].tolist())
-    return np.ascontiguousarray(par)
+    return par
+
+
+def _check_lap_rows(rows, L, label, width_name):
+    """The shape rule of both lap tables: (n, L) int32 rows of lap indices, or None for "no table" (None or no rows); ValueError under `label`, which calls the row
+    width `width_name`.  A flat list is one row per entry when L is 1, else one row."""
+    if rows is None or np.size(rows) == 0:
+        return None
+    L = int(L)
+    a = np.asarray(rows)
+    if L < 1 or not np.issubdtype(a.dtype, np.integer) or a.ndim > 2:
+        raise ValueError("%s: integer rows of %s = %d lap indices expected, got dtype %s, shape %s" % (label, width_name, L, a.dtype, a.shape))
+    if a.ndim < 2:
+        a = a.reshape(-1, 1) if L == 1 else a.reshape(1, -1)
+    if a.shape[1] != L:
+        raise ValueError("%s: rows of %s = %d lap indices expected, got shape %s" % (label, width_name, L, a.shape))
+    if a.min() < 0:
+        raise ValueError("%s: negative lap index in row(s) %s" % (label, np.where((a < 0).any(1))[0].tolist()))
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def check_lap_table(rows, trToUse):
     """(n, trToUse) int32 rows of a per-problem lap table, or None for "no table" (None or no rows); ValueError for a shape that is not rows of trToUse entries or
     for a negative index (the library checks the upper end against the laps stored).  A flat list is one row per entry when trToUse is 1, else one row."""
-    if rows is None or np.size(rows) == 0:
-        return None
-    L = int(trToUse)
-    a = np.asarray(rows)
-    if L < 1 or not np.issubdtype(a.dtype, np.integer) or a.ndim > 2:
-        raise ValueError("lap table: integer rows of trToUse = %d lap indices expected, got dtype %s, shape %s" % (L, a.dtype, a.shape))
-    if a.ndim < 2:
-        a = a.reshape(-1, 1) if L == 1 else a.reshape(1, -1)
-    if a.shape[1] != L:
-        raise ValueError("lap table: rows of trToUse = %d lap indices expected, got shape %s" % (L, a.shape))
-    if a.min() < 0:
-        raise ValueError("lap table: negative lap index in row(s) %s" % np.where((a < 0).any(1))[0].tolist())
-    return np.ascontiguousarray(a, dtype=np.int32)
+    return _check_lap_rows(rows, trToUse, "lap table", "trToUse")
 
 
 SS_LAST_SHARED = -2        # LMPC_SS_LAST_SHARED: lmpc_ss_get_lap_table's `last` entries when the table was set without one
@@ -301,10 +316,7 @@ def check_ss_table(rows, numSS_it, last=None):
     rules are check_lap_table's, with numSS_it entries per row.  last: one integer entry per row, each -1 ("none of the row's laps is the car's latest") or a lap
     index; ValueError for another shape, a non-integer dtype, an entry below -1, or a `last` given without rows (the library checks the upper ends against the
     laps stored)."""
-    try:
-        r = check_lap_table(rows, numSS_it)
-    except ValueError as e:
-        raise ValueError(str(e).replace("lap table:", "safe-set lap table:").replace("trToUse", "numSS_it")) from None
+    r = _check_lap_rows(rows, numSS_it, "safe-set lap table", "numSS_it")
     if r is None:
         if last is not None and np.size(last):
             raise ValueError("safe-set lap table: `last` given without rows")
@@ -350,13 +362,9 @@ _TUNING_SHAPES = {"Q": (6, 6), "R": (2, 2), "Qf": (6, 6), "dR": (2,), "Qslack": 
 def check_tuning(rows, numSS_it=0):
     """(n, 98) float64 rows, or None for "no rows" (None or empty); ValueError for what lmpc_tuning_set refuses in a row: a wrong shape, a non-finite entry, Q, R or
     Qf not exactly symmetric, a negative dR or Qslack entry, and (numSS_it > 0) a QtermSlack entry <= 0.  bu <= 0 is no error here either (LMPC_ST_NOT_INTERIOR)."""
-    if rows is None or np.size(rows) == 0:
+    r = _check_rows(rows, TUNING_NPAR, "tuning", True)
+    if r is None:
         return None
-    r = np.array(rows, dtype=np.float64, ndmin=2)
-    if r.ndim != 2 or r.shape[1] != TUNING_NPAR:
-        raise ValueError("tuning: rows of %d values expected, got shape %s" % (TUNING_NPAR, r.shape))
-    if not np.all(np.isfinite(r)):
-        raise ValueError("tuning: non-finite entry in row(s) %s" % np.where(~np.isfinite(r).all(1))[0].tolist())
     for name in ("Q", "R", "Qf"):
         m = r[:, TUNING_FIELDS[name]].reshape((-1,) + _TUNING_SHAPES[name])
         if not np.array_equal(m, m.transpose(0, 2, 1)):
@@ -366,7 +374,7 @@ def check_tuning(rows, numSS_it=0):
             raise ValueError("tuning: negative %s entry" % name)
     if int(numSS_it) > 0 and not (r[:, TUNING_FIELDS["QtermSlack"]] > 0).all():
         raise ValueError("tuning: QtermSlack entries must be positive on a context with a terminal set")
-    return np.ascontiguousarray(r)
+    return r
 
 
 def tuning_rows(cfg, B, **fields):
@@ -440,13 +448,9 @@ def track_table(row):
 def check_tracks(rows):
     """(n, 98) float64 rows, or None for "no rows" (None or empty); ValueError for what lmpc_track_set refuses in a row: a wrong shape, a non-finite entry, a row count
     that is not an integer in 1..16, trackLength <= 0, a negative segment length."""
-    if rows is None or np.size(rows) == 0:
+    r = _check_rows(rows, TRACK_NPAR, "tracks", True)
+    if r is None:
         return None
-    r = np.array(rows, dtype=np.float64, ndmin=2)
-    if r.ndim != 2 or r.shape[1] != TRACK_NPAR:
-        raise ValueError("tracks: rows of %d values expected, got shape %s" % (TRACK_NPAR, r.shape))
-    if not np.all(np.isfinite(r)):
-        raise ValueError("tracks: non-finite entry in row(s) %s" % np.where(~np.isfinite(r).all(1))[0].tolist())
     n = r[:, 0]
     if not np.all((n >= 1) & (n <= MAX_TRACK_ROWS) & (n == np.floor(n))):
         raise ValueError("tracks: the row count must be an integer in 1..%d" % MAX_TRACK_ROWS)
@@ -455,7 +459,7 @@ def check_tracks(rows):
     for k in range(r.shape[0]):
         if (r[k, 2:].reshape(MAX_TRACK_ROWS, 6)[:int(n[k]), 4] < 0).any():
             raise ValueError("tracks: negative segment length in row %d" % k)
-    return np.ascontiguousarray(r)
+    return r
 
 
 def _chk(rc):
@@ -557,6 +561,24 @@ class Context:
         self.close()
 
     # ---- stores
+    # ---- the per-car row sets (csrc/lmpc_rows.h): every `set` and `get` of the five goes through these two
+    def _rows_set(self, fn, rows, *extra):
+        """rows (n, width) as its check returned them go to the setter `fn`, None as (0, NULL); extra: per-row arrays (or None) that travel with the rows."""
+        if rows is None:
+            _chk(fn(self._h, 0, None, *[None] * len(extra)))
+        else:
+            _chk(fn(self._h, rows.shape[0], _d(rows), *[_d(e) for e in extra]))
+
+    def _rows_get(self, fn, width, dtype, *extra):
+        """The rows in force behind the getter `fn`, (n, width) of dtype: the count first, then the rows.  extra: the dtypes of further (n,) outputs of the getter;
+        with any, (rows, *those) is returned."""
+        n = C.c_int()
+        _chk(fn(self._h, C.byref(n), None, *[None] * len(extra), 0))
+        out = [np.zeros((n.value, width), dtype)] + [np.zeros(n.value, t) for t in extra]
+        if n.value:
+            _chk(fn(self._h, C.byref(n), *[_d(a) for a in out], n.value))
+        return tuple(out) if extra else out[0]
+
     def model_add_trajectory(self, x, u):
         x = _f64(x); u = _f64(u)
         _chk(self.lib.lmpc_model_add_trajectory(self._h, _d(x), _d(u), C.c_int(x.shape[0])))
@@ -576,12 +598,7 @@ class Context:
         problem; one row -- every problem; n rows -- problem b of a later regress_batch / regress_points / step_batch / step_batch_dev / rollout_begin /
         LTV rollout_begin_mpc uses row b, and a call with another batch size is refused.  A session uses the table in force when it began.  On an LMPC context
         only the regression follows the table: the safe set has a table of its own, ss_set_lap_table."""
-        L = int(self.cfg.trToUse)
-        rows = check_lap_table(rows, L)
-        if rows is None:
-            _chk(self.lib.lmpc_model_set_lap_table(self._h, 0, None))
-            return
-        _chk(self.lib.lmpc_model_set_lap_table(self._h, rows.shape[0], rows.ctypes.data))
+        self._rows_set(self.lib.lmpc_model_set_lap_table, check_lap_table(rows, int(self.cfg.trToUse)))
 
     def model_lap_info(self, lap):
         """(rows, position in the sorted order) of the regression-store lap with insertion index `lap` (lmpc_model_lap_info)."""
@@ -591,12 +608,7 @@ class Context:
 
     def model_lap_table(self):
         """The rows in force, (n, trToUse) int32 as model_set_lap_table received them; n = 0: the default (lmpc_model_get_lap_table)."""
-        n = C.c_int()
-        _chk(self.lib.lmpc_model_get_lap_table(self._h, C.byref(n), None, 0))
-        rows = np.zeros((n.value, int(self.cfg.trToUse)), np.int32)
-        if n.value:
-            _chk(self.lib.lmpc_model_get_lap_table(self._h, C.byref(n), rows.ctypes.data, rows.shape[0]))
-        return rows
+        return self._rows_get(self.lib.lmpc_model_get_lap_table, int(self.cfg.trToUse), np.int32)
 
     def ss_add_trajectory(self, x, u, track_row=None):
         """LMPC.addTrajectory.  track_row: the row of track_set whose TrackLength computeCost uses (lmpc_ss_add_trajectory_on) -- needed when one row per car is in
@@ -627,19 +639,12 @@ class Context:
         with another batch size is refused.  The table names laps, not snapshots, and is live in a rollout session: a later ss_extend_lap or a new `set` reaches
         the next step."""
         rows, last = check_ss_table(rows, int(self.cfg.numSS_it), last)
-        if rows is None:
-            _chk(self.lib.lmpc_ss_set_lap_table(self._h, 0, None, None))
-            return
-        _chk(self.lib.lmpc_ss_set_lap_table(self._h, rows.shape[0], rows.ctypes.data, None if last is None else last.ctypes.data))
+        self._rows_set(self.lib.lmpc_ss_set_lap_table, rows, last)
 
     def ss_lap_table(self):
         """(rows (n, numSS_it) int32, last (n,) int32 or None) in force, as ss_set_lap_table received them; n = 0: the shared selection (lmpc_ss_get_lap_table)."""
-        n = C.c_int()
-        _chk(self.lib.lmpc_ss_get_lap_table(self._h, C.byref(n), None, None, 0))
-        rows = np.zeros((n.value, int(self.cfg.numSS_it)), np.int32); last = np.zeros(n.value, np.int32)
-        if n.value:
-            _chk(self.lib.lmpc_ss_get_lap_table(self._h, C.byref(n), rows.ctypes.data, last.ctypes.data, rows.shape[0]))
-        return rows, (None if n.value == 0 or np.all(last == SS_LAST_SHARED) else last)
+        rows, last = self._rows_get(self.lib.lmpc_ss_get_lap_table, int(self.cfg.numSS_it), np.int32, np.int32)
+        return rows, (None if last.size == 0 or np.all(last == SS_LAST_SHARED) else last)
 
     def ss_get_qfun(self, lap):
         T = C.c_int()
@@ -797,59 +802,32 @@ class Context:
         """Vehicle constants of the plant for every later plant_step_batch / rollout_begin / rollout_begin_mpc / rollout_pid (lmpc_plant_set_params): None or no rows --
         the reference's vehicle; one row of PLANT_PARAM_NAMES -- every car; (n, 10) -- car b uses row b (n <= max_batch; a later call with more cars is refused).
         A session uses the rows in force when it began.  plant_params() builds the rows."""
-        if par is None or np.size(par) == 0:
-            _chk(self.lib.lmpc_plant_set_params(self._h, C.c_int(0), None))
-            return
-        par = _f64(par).reshape(-1, PLANT_NPAR)
-        _chk(self.lib.lmpc_plant_set_params(self._h, C.c_int(par.shape[0]), _d(par)))
+        self._rows_set(self.lib.lmpc_plant_set_params, None if par is None or np.size(par) == 0 else _f64(par).reshape(-1, PLANT_NPAR))
 
     def tuning_set(self, rows):
         """Per-problem controller tuning (lmpc_tuning_set): None or no rows -- the config's weights and bounds; one row of TUNING_FIELDS -- every problem; (n, 98) --
         problem b uses row b, and a launch of another batch size is refused (LmpcError, the context stays usable).  The rows are live: a call between two rollout_run
         calls reaches the next step.  They apply to qp_solve_batch, step_batch, step_batch_dev, every step of a rollout session and assemble_batch.  tuning_rows()
         builds the rows."""
-        rows = check_tuning(rows, int(self.cfg.numSS_it))
-        if rows is None:
-            _chk(self.lib.lmpc_tuning_set(self._h, 0, None))
-            return
-        _chk(self.lib.lmpc_tuning_set(self._h, rows.shape[0], rows.ctypes.data))
+        self._rows_set(self.lib.lmpc_tuning_set, check_tuning(rows, int(self.cfg.numSS_it)))
 
     def track_set(self, rows):
         """Per-car tracks (lmpc_track_set): None or no rows -- the config's track; one row of TRACK_NPAR doubles (track_row) -- every car; (n, 98) -- element b of a
         batched call uses row b, and a call of another count is refused (LmpcError, the context stays usable).  Refused while a rollout session is active.
         track_rows() builds the rows from PointAndTangent tables."""
-        rows = check_tracks(rows)
-        if rows is None:
-            _chk(self.lib.lmpc_track_set(self._h, 0, None))
-            return
-        _chk(self.lib.lmpc_track_set(self._h, rows.shape[0], rows.ctypes.data))
+        self._rows_set(self.lib.lmpc_track_set, check_tracks(rows))
 
     def tracks(self):
         """The rows in force, (n, 98), as track_set received them; n = 0: the config's track (lmpc_track_get)."""
-        n = C.c_int()
-        _chk(self.lib.lmpc_track_get(self._h, C.byref(n), None, 0))
-        rows = np.zeros((n.value, TRACK_NPAR))
-        if n.value:
-            _chk(self.lib.lmpc_track_get(self._h, C.byref(n), rows.ctypes.data, rows.shape[0]))
-        return rows
+        return self._rows_get(self.lib.lmpc_track_get, TRACK_NPAR, np.float64)
 
     def tuning(self):
         """The rows in force, (n, 98), as tuning_set received them; n = 0: the config's weights (lmpc_tuning_get)."""
-        n = C.c_int()
-        _chk(self.lib.lmpc_tuning_get(self._h, C.byref(n), None, 0))
-        rows = np.zeros((n.value, TUNING_NPAR))
-        if n.value:
-            _chk(self.lib.lmpc_tuning_get(self._h, C.byref(n), rows.ctypes.data, rows.shape[0]))
-        return rows
+        return self._rows_get(self.lib.lmpc_tuning_get, TUNING_NPAR, np.float64)
 
     def plant_params(self):
         """The rows in force, (n, 10); n = 0: the reference's vehicle (lmpc_plant_get_params)."""
-        n = C.c_int()
-        _chk(self.lib.lmpc_plant_get_params(self._h, C.byref(n), None, C.c_int(0)))
-        par = np.zeros((n.value, PLANT_NPAR))
-        if n.value:
-            _chk(self.lib.lmpc_plant_get_params(self._h, C.byref(n), _d(par), C.c_int(par.shape[0])))
-        return par
+        return self._rows_get(self.lib.lmpc_plant_get_params, PLANT_NPAR, np.float64)
 
     # ---- counter-based noise generated on the device (lmpc_noise_*, lmpc_rollout_set_noise; csrc/lmpc_noise.hip.h)
     def noise_raw(self, seed, stream, lap, t0, T, car0, B):

@@ -7,6 +7,7 @@
 #include "lmpc_commit.hip.h"
 #include "lmpc_trace.hip.h"
 #include "lmpc_arrays.h"
+#include "lmpc_rows.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <algorithm>
@@ -46,6 +47,7 @@ static const char *dev_knob(const char *name) {
 }
 #define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return set_err(LMPC_E_HIP, #call, hipGetErrorString(e_)); } while (0)
 #define ARGCHK(cond) do { if (!(cond)) return set_err(LMPC_E_ARG, "argument check failed", #cond); } while (0)
+#define RCCHK(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 
 // ---- device allocations of a context.  Builds with -DLMPC_GUARD (the "asan" developer flavour, racinglmpc_amd.build: host code under AddressSanitizer) put a
 // 256-byte guard zone filled with 0xA5 behind every allocation -- and between the work-buffer ranges of the two slabs -- and check it when the buffer is
@@ -88,6 +90,9 @@ static hipError_t g_free(void *p) { return p ? hipFree(p) : hipSuccess; }
 template <class T> static hipError_t g_malloc(T **p, size_t bytes) { return g_malloc_raw((void **)p, bytes); }
 
 struct evpair { hipEvent_t a, b; int kind; };
+// the device image of a row set (lmpc_rows.h), filled by image_upload; cap: the bytes allocated
+struct dev_image { void *p; size_t cap; };
+enum { IMG_LT = 0, IMG_SST, IMG_TUNE, IMG_TRK, IMG_COUNT };
 
 struct lmpc_ctx {
     lmpc_config cfg;
@@ -128,22 +133,23 @@ struct lmpc_ctx {
     struct lmpc_rollout_session *ro;
     int noise_on; unsigned long long noise_seed, noise_lap; long long noise_car0;   // lmpc_rollout_set_noise: sessions begun with noise = NULL fill their buffer on the device (lmpc_noise.hip.h); 0 after lmpc_create
     std::vector<int> trace_cars; unsigned trace_what;   // lmpc_rollout_set_trace: the cars and planes later sessions record at every step (lmpc_trace.hip.h); empty / 0 after lmpc_create
-    std::vector<double> plant_par; int plant_n;   // lmpc_plant_set_params: plant_n rows of LMPC_PLANT_NPAR vehicle constants (0: the reference's vehicle, the kernels with the literals)
-    // lmpc_model_set_lap_table: lt_n rows of trToUse insertion indices as the caller gave them (0 rows: the first trToUse laps of the sorted order serve every problem);
-    // d_lt: the same rows on the device as resolved (slot, rows) pairs in each row's sorted order, uploaded by `set` and rebuilt when the stores move or a lap is
-    // replaced (resolve_lap_table); lt_small: every lap named anywhere has at most 512 rows, i.e. the 8-rows-per-lane scan serves the whole table (launch_k1)
-    std::vector<int> lt_idx; int lt_n; int *d_lt; size_t d_lt_cap; bool lt_small;
-    // lmpc_ss_set_lap_table: sst_n rows of numSS_it safe-set lap indices and (sst_has_last) one "latest lap" index per row, as the caller gave them.  d_sst: the rows
-    // on the device as the solve kernels read them (LMPC_SSTAB_ENTRY ints per entry: slot, current rows, latest flag, pad; each row in ascending LapTime, ties by
-    // index).  The image names rows of laps, so every edit of the safe set marks it dirty and the next launch that reads it uploads it again (ss_table_for)
-    std::vector<int> sst_idx, sst_last; int sst_n; bool sst_has_last, sst_dirty; int *d_sst; size_t d_sst_cap;
-    // lmpc_tuning_set: tune_n rows of LMPC_TUNING_NPAR doubles as the caller gave them (0 rows: the config's weights serve every problem).  d_tune: the device image the
-    // per-problem-rows instantiations of the solve kernels and the assemble kernel stage from -- PAR_TOT doubles per row in the PAR_* layout, doubled weights, Fx / Fu of
-    // the config; with no rows in force it holds the config's own row (what a launch with a safe-set table alone reads).  Uploaded by `set`, never per launch
-    std::vector<double> tune_rows; int tune_n; double *d_tune; size_t d_tune_cap;
-    // lmpc_track_set: trk_n rows of LMPC_TRACK_NPAR doubles as the caller gave them (0 rows: the config's track, read from the parameter block by the kernels that ran
-    // before there were rows); d_trk: the same rows on the device, uploaded by `set` (allocated with the first rows)
-    std::vector<double> trk_rows; int trk_n; double *d_trk; size_t d_trk_cap;
+    // The per-car row sets (lmpc_rows.h: the rows as the caller gave them, 0 rows = the config's value, one row serves all, else row b for problem b) and img[], their device images.
+    lmpc_row_set<double> plant{LMPC_PLANT_NPAR, "lmpc_plant_set_params"};   // vehicle constants (0 rows: the reference's vehicle, the kernels with the literals); no image: a call uploads its cars' rows
+    // trToUse insertion indices per row (0 rows: the first trToUse laps of the sorted order serve every problem).  img[IMG_LT]: the same rows as resolved (slot, rows)
+    // pairs in each row's sorted order, uploaded by `set` and rebuilt when the stores move or a lap is replaced (resolve_lap_table); lt_small: every lap named anywhere
+    // has at most 512 rows, i.e. the 8-rows-per-lane scan serves the whole table (launch_k1)
+    lmpc_row_set<int> lt{0, "lmpc_model_set_lap_table"}; bool lt_small;
+    // numSS_it safe-set lap indices per row and (sst_has_last) one "latest lap" index per row.  img[IMG_SST]: the rows as the solve kernels read them (LMPC_SSTAB_ENTRY
+    // ints per entry: slot, current rows, latest flag, pad; each row in ascending LapTime, ties by index).  The image names rows of laps, so every edit of the safe set
+    // marks it dirty and the next launch that reads it uploads it again (ss_table_for)
+    lmpc_row_set<int> sst{0, "lmpc_ss_set_lap_table"}; std::vector<int> sst_last; bool sst_has_last, sst_dirty;
+    // LMPC_TUNING_NPAR doubles per row (0 rows: the config's weights serve every problem).  img[IMG_TUNE]: what the per-problem-rows instantiations of the solve kernels and
+    // the assemble kernel stage from -- PAR_TOT doubles per row in the PAR_* layout, doubled weights, Fx / Fu of the config; with no rows in force it holds the config's
+    // own row (what a launch with a safe-set table alone reads).  Uploaded by `set`, never per launch
+    lmpc_row_set<double> tune{LMPC_TUNING_NPAR, "lmpc_tuning_set"};
+    // LMPC_TRACK_NPAR doubles per row (0 rows: the config's track, read from the parameter block by the kernels that ran before there were rows).  img[IMG_TRK]: the rows, uploaded by `set`
+    lmpc_row_set<double> trk{LMPC_TRACK_NPAR, "lmpc_track_set"};
+    dev_image img[IMG_COUNT];
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
 };
@@ -308,28 +314,37 @@ int lmpc_track_row_from_config(const lmpc_config *f, double *row) {
 // The track of element b of a batched call with rows in force: the device image and its stride (0: one row serves all).  No rows: dev stays null -- the kernels
 // that read the parameter block run.  B against the rows is checked by track_for before anything is queued.
 struct trk_src { const double *dev; int stride; };
+// The one count check of the row sets: a call of B `noun` ("problems" / "elements" / "cars") against the rows in force, refused under `what` (the set's name in messages).
+template <class T> static int rows_fit(const lmpc_row_set<T> &s, long long B, lmpc_row_rule rule, const char *noun, const char *what) {
+    if (s.fits(B, rule)) return LMPC_OK;
+    char msg[128]; snprintf(msg, sizeof(msg), "B = %lld %s but %s holds %d %srows", B, noun, s.setter, s.n, rule == LMPC_ROWS_AT_LEAST ? "per-car " : "");
+    return set_err(LMPC_E_ARG, what, msg);
+}
+// the body of the five getters: the rows in force of set `m` of the context
+template <class T> static int rows_get(lmpc_ctx *c, lmpc_row_set<T> lmpc_ctx::*m, int *n, T *out, int capacity) {
+    ARGCHK(c && n && capacity >= 0);
+    (c->*m).get(n, out, capacity);
+    return LMPC_OK;
+}
 static int track_for(lmpc_ctx *c, long long B, trk_src *t) {
     t->dev = nullptr; t->stride = 0;
-    if (c->trk_n == 0) return LMPC_OK;
-    if (c->trk_n > 1 && B != c->trk_n) {
-        char msg[128]; snprintf(msg, sizeof(msg), "B = %lld elements but lmpc_track_set holds %d rows", B, c->trk_n);
-        return set_err(LMPC_E_ARG, "track rows", msg);
-    }
-    t->dev = c->d_trk; t->stride = c->trk_n == 1 ? 0 : LMPC_TRACK_NPAR;
+    if (!c->trk.in_force()) return LMPC_OK;
+    RCCHK(rows_fit(c->trk, B, LMPC_ROWS_EXACT, "elements", "track rows"));
+    t->dev = (const double *)c->img[IMG_TRK].p; t->stride = c->trk.stride(LMPC_TRACK_NPAR);
     return LMPC_OK;
 }
 // TrackLength of track row `row` (computeCost, addPoint): the config's without rows, the one row's with one
 static double track_length_of(const lmpc_ctx *c, int row) {
-    return c->trk_n == 0 ? c->cfg.trackLength : c->trk_rows[(size_t)(c->trk_n == 1 ? 0 : row) * LMPC_TRACK_NPAR + 1];
+    return c->trk.in_force() ? c->trk.row(row)[1] : c->cfg.trackLength;
 }
 // the host-side lap writers have no car: the config's TrackLength, or row 0 of one; with one row per car the caller must say which (the _on forms)
 static int track_length_host(lmpc_ctx *c, const char *who, const char *on_form, double *TL) {
-    if (c->trk_n > 1) { char msg[160]; snprintf(msg, sizeof(msg), "lmpc_track_set holds %d rows and this call names no car: use %s", c->trk_n, on_form); return set_err(LMPC_E_STATE, who, msg); }
+    if (c->trk.n > 1) { char msg[160]; snprintf(msg, sizeof(msg), "lmpc_track_set holds %d rows and this call names no car: use %s", c->trk.n, on_form); return set_err(LMPC_E_STATE, who, msg); }
     *TL = track_length_of(c, 0);
     return LMPC_OK;
 }
 static int track_length_on(lmpc_ctx *c, const char *who, int row, double *TL) {
-    if (row < 0 || row >= std::max(c->trk_n, 1)) { char msg[128]; snprintf(msg, sizeof(msg), "track_row %d, %d rows in force", row, c->trk_n); return set_err(LMPC_E_ARG, who, msg); }
+    if (row < 0 || row >= std::max(c->trk.n, 1)) { char msg[128]; snprintf(msg, sizeof(msg), "track_row %d, %d rows in force", row, c->trk.n); return set_err(LMPC_E_ARG, who, msg); }
     *TL = track_length_of(c, row);
     return LMPC_OK;
 }
@@ -365,6 +380,18 @@ static int pooled_scratch(lmpc_ctx *c, size_t bytes, void **out) {
         HIPCHK(g_malloc(&c->scr_dev, want)); c->scr_bytes = want;
     }
     *out = c->scr_dev;
+    return LMPC_OK;
+}
+// `bytes` of host data become the device image `img` of a row set.  A larger image goes into a new allocation that replaces the old one only once it is filled: a HIP
+// failure on the way leaves the image in force, and its capacity, as they were.  The callers have resolved the launches still pending their retry pass and drained the
+// stream (those read the image of THEIR launch); nothing is drained here.  what: the copy, named in the error.
+static int image_upload(dev_image *img, const void *host, size_t bytes, const char *what) {
+    const bool grow = bytes > img->cap;
+    void *buf = img->p;
+    if (grow) HIPCHK(g_malloc(&buf, bytes));
+    const hipError_t e = hipMemcpy(buf, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { if (grow) (void)g_free(buf); return set_err(LMPC_E_HIP, what, hipGetErrorString(e)); }
+    if (grow) { (void)g_free(img->p); img->p = buf; img->cap = bytes; }
     return LMPC_OK;
 }
 // everything of lmpc_create that can fail; the caller destroys the context on any error (one failure path, no leaks)
@@ -473,7 +500,7 @@ int lmpc_create_ex(const lmpc_config *cfg, unsigned flags, lmpc_ctx **out) {
     ARGCHK(cfg->slacks || cfg->numSS_it == 0);          // hard lane rows: plain MPC only (the reference's LMPC.unpackSolution mis-slices without slack variables)
     ARGCHK(cfg->max_batch >= 1 && cfg->max_laps >= 1 && cfg->max_lap_len >= 8);
     lmpc_ctx *c = new lmpc_ctx();                      // value-initialised: every pointer starts as nullptr, so lmpc_destroy is safe at any point
-    c->cfg = *cfg; c->create_flags = flags; c->profiling = 0; c->ro = nullptr; c->var_dl = nullptr; c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1;
+    c->cfg = *cfg; c->lt.width = cfg->trToUse; c->sst.width = cfg->numSS_it; c->create_flags = flags; c->profiling = 0; c->ro = nullptr; c->var_dl = nullptr; c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1;
     memset(&c->stats, 0, sizeof(c->stats));
     int rc = create_body(c);
     if (rc != LMPC_OK) { const std::string keep = g_err; lmpc_destroy(c); g_err = keep; return rc; }
@@ -504,9 +531,10 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->d_lt, c->d_sst, c->d_tune, c->d_trk};      // (the work buffers are ranges of the two slabs)
+    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack};      // (the work buffers are ranges of the two slabs)
     check_slab_gaps(c);
     for (void *q : ptrs) if (q) (void)g_free(q);
+    for (dev_image &im : c->img) (void)g_free(im.p);
     if (c->h_retry) (void)hipHostFree(c->h_retry);
     if (c->h_in) (void)hipHostFree(c->h_in);
     if (c->h_out) (void)hipHostFree(c->h_out);
@@ -524,7 +552,6 @@ static int resolve_retries(lmpc_ctx *c);
 // re-solved against the data of ITS launch, never against a changed safe set or overwritten inputs.  (No launch pending -- the drop-in flow,
 // where lmpc_step_batch resolves before it returns -- costs nothing: no stream drain is added.)  The retry pass reads nothing else of the
 // context's: not the per-point regression status (it keeps the first pass's bits), not the [A_k | B_k] scratch (it stages them in LDS).
-#define RCCHK(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 #define RESOLVE_PENDING() RCCHK(resolve_retries(c))
 
 // ---------------------------------------------------------------------------------------------- stores
@@ -546,21 +573,16 @@ static void resolve_lap_row(const lmpc_ctx *c, const int *idx, int *pairs, bool 
 // the whole table, resolved: rows x trToUse x 2 ints
 static std::vector<int> resolve_lap_rows(const lmpc_ctx *c, bool *small) {
     const size_t L = (size_t)c->cfg.trToUse;
-    std::vector<int> pairs((size_t)c->lt_n * L * 2);
+    std::vector<int> pairs((size_t)c->lt.n * L * 2);
     *small = true;
-    for (int r = 0; r < c->lt_n; r++) resolve_lap_row(c, &c->lt_idx[(size_t)r * L], &pairs[(size_t)r * L * 2], small);
+    for (int r = 0; r < c->lt.n; r++) resolve_lap_row(c, &c->lt.rows[(size_t)r * L], &pairs[(size_t)r * L * 2], small);
     return pairs;
 }
 // (re)build the device image from the indices the context keeps: after `set`, after the stores moved, after a lap was replaced.  No kernel is in flight (callers drain the stream).
 static int resolve_lap_table(lmpc_ctx *c) {
-    if (c->lt_n == 0) return LMPC_OK;
+    if (!c->lt.in_force()) return LMPC_OK;
     const std::vector<int> pairs = resolve_lap_rows(c, &c->lt_small);
-    if (pairs.size() > c->d_lt_cap) {
-        if (c->d_lt) { (void)g_free(c->d_lt); c->d_lt = nullptr; c->d_lt_cap = 0; }
-        HIPCHK(g_malloc(&c->d_lt, pairs.size() * sizeof(int))); c->d_lt_cap = pairs.size();
-    }
-    HIPCHK(hipMemcpy(c->d_lt, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice));
-    return LMPC_OK;
+    return image_upload(&c->img[IMG_LT], pairs.data(), pairs.size() * sizeof(int), "hipMemcpy (lap-table image)");
 }
 
 static int grow_stores(lmpc_ctx *c, int need_laps, int need_len) {
@@ -712,7 +734,7 @@ int lmpc_model_replace_lap(lmpc_ctx *c, int pos, const double *x, const double *
 int lmpc_model_set_lap_table(lmpc_ctx *c, int n, const int *laps) {
     // checked in full before anything is changed: a refused table leaves the one in force
     ARGCHK(c && n >= 0 && (n == 0 || laps));
-    if (n == 0) { c->lt_n = 0; c->lt_idx.clear(); return LMPC_OK; }
+    if (n == 0) { c->lt.clear(); return LMPC_OK; }
     const int L = c->cfg.trToUse, stored = (int)c->m_len.size();
     ARGCHK(L >= 1 && (long long)n <= (long long)c->cfg.max_batch * c->cfg.N);         // (lmpc_regress_points serves up to max_batch x N points)
     for (size_t i = 0; i < (size_t)n * L; i++)
@@ -721,9 +743,9 @@ int lmpc_model_set_lap_table(lmpc_ctx *c, int n, const int *laps) {
             return set_err(LMPC_E_ARG, "lap table", msg);
         }
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));   // (a regression still in flight reads the image about to be overwritten)
-    c->lt_idx.assign(laps, laps + (size_t)n * L); c->lt_n = n;
+    c->lt.assign(n, laps);
     const int rc = resolve_lap_table(c);
-    if (rc) { c->lt_n = 0; c->lt_idx.clear(); }
+    if (rc) c->lt.clear();
     return rc;
 }
 int lmpc_model_lap_info(lmpc_ctx *c, int lap, int *rows, int *sorted_pos) {
@@ -733,12 +755,7 @@ int lmpc_model_lap_info(lmpc_ctx *c, int lap, int *rows, int *sorted_pos) {
     if (sorted_pos) *sorted_pos = (int)(std::find(c->m_order.begin(), c->m_order.end(), lap) - c->m_order.begin());
     return LMPC_OK;
 }
-int lmpc_model_get_lap_table(lmpc_ctx *c, int *n, int *laps, int capacity) {
-    ARGCHK(c && n && capacity >= 0);
-    *n = c->lt_n;
-    if (laps && c->lt_n) memcpy(laps, c->lt_idx.data(), sizeof(int) * (size_t)c->cfg.trToUse * (size_t)std::min(capacity, c->lt_n));
-    return LMPC_OK;
-}
+int lmpc_model_get_lap_table(lmpc_ctx *c, int *n, int *laps, int capacity) { return rows_get(c, &lmpc_ctx::lt, n, laps, capacity); }
 
 static int ss_add_trajectory_tl(lmpc_ctx *c, const double *x, const double *u, int T, double TL) {
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -795,7 +812,7 @@ int lmpc_ss_set_selected(lmpc_ctx *c, const int *laps, int n) {
 int lmpc_ss_set_lap_table(lmpc_ctx *c, int n, const int *laps, const int *last) {
     // checked in full before anything is changed: a refused table leaves the one in force.  Nothing is uploaded here: the image is built by the next launch that reads it
     ARGCHK(c && n >= 0 && (n == 0 || laps));
-    if (n == 0) { c->sst_n = 0; c->sst_idx.clear(); c->sst_last.clear(); c->sst_has_last = false; return LMPC_OK; }
+    if (n == 0) { c->sst.clear(); c->sst_last.clear(); c->sst_has_last = false; return LMPC_OK; }
     const int L = c->cfg.numSS_it, stored = (int)c->s_len.size();
     ARGCHK(L >= 1);
     char msg[128];
@@ -809,16 +826,14 @@ int lmpc_ss_set_lap_table(lmpc_ctx *c, int n, const int *laps, const int *last) 
             snprintf(msg, sizeof(msg), "last[%d] = %d, %d laps are stored", r, last[r], stored);
             return set_err(LMPC_E_ARG, "safe-set lap table", msg);
         }
-    c->sst_idx.assign(laps, laps + (size_t)n * L); c->sst_n = n; c->sst_has_last = last != nullptr;
+    c->sst.assign(n, laps); c->sst_has_last = last != nullptr;
     if (last) c->sst_last.assign(last, last + n); else c->sst_last.clear();
     c->sst_dirty = true;
     return LMPC_OK;
 }
 int lmpc_ss_get_lap_table(lmpc_ctx *c, int *n, int *laps, int *last, int capacity) {
-    ARGCHK(c && n && capacity >= 0);
-    *n = c->sst_n;
-    const size_t rows = (size_t)std::min(capacity, c->sst_n);
-    if (laps && rows) memcpy(laps, c->sst_idx.data(), sizeof(int) * (size_t)c->cfg.numSS_it * rows);
+    RCCHK(rows_get(c, &lmpc_ctx::sst, n, laps, capacity));
+    const size_t rows = (size_t)std::min(capacity, c->sst.n);
     for (size_t r = 0; last && r < rows; r++) last[r] = c->sst_has_last ? c->sst_last[r] : LMPC_SS_LAST_SHARED;
     return LMPC_OK;
 }
@@ -1004,12 +1019,9 @@ struct k1_table { const int *dev; int stride; bool small; const double *trk; int
 static int k1_table_for(lmpc_ctx *c, int B, k1_table *t) {
     t->dev = nullptr; t->stride = 0; t->small = true;
     { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; t->trk = ts.dev; t->trkStride = ts.stride; }
-    if (c->lt_n == 0) return LMPC_OK;
-    if (c->lt_n > 1 && B != c->lt_n) {
-        char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_model_set_lap_table holds %d rows", B, c->lt_n);
-        return set_err(LMPC_E_ARG, "lap table", msg);
-    }
-    t->dev = c->d_lt; t->stride = c->lt_n == 1 ? 0 : 2 * c->cfg.trToUse; t->small = c->lt_small;
+    if (!c->lt.in_force()) return LMPC_OK;
+    RCCHK(rows_fit(c->lt, B, LMPC_ROWS_EXACT, "problems", "lap table"));
+    t->dev = (const int *)c->img[IMG_LT].p; t->stride = c->lt.stride(2 * c->cfg.trToUse); t->small = c->lt_small;
     return LMPC_OK;
 }
 static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, int xstride, const double *uLin, double *dA, double *dB, double *dC, int *dst, const k1_table &t) {
@@ -1023,7 +1035,7 @@ static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, 
     hipLaunchKernelGGL(k, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride);
 }
 static int launch_regress(lmpc_ctx *c, int B, const double *d_xLin, int xstride, const double *d_uLin, double *dA, double *dB, double *dC, int *dst) {
-    int rc = refresh_params(c, true, false, c->lt_n != 0); if (rc) return rc;
+    int rc = refresh_params(c, true, false, c->lt.in_force()); if (rc) return rc;
     k1_table tab; rc = k1_table_for(c, B, &tab); if (rc) return rc;
     ev_begin(c, 0);
     int qg, nblk; k1_grid(c, B, &qg, &nblk);
@@ -1074,19 +1086,16 @@ static int resolve_retries(lmpc_ctx *c) {
 // the latest lap is the last one stored at launch time.  Launches still pending their retry pass read the image of THEIR launch: they are resolved, and the
 // stream is drained, before it is overwritten.
 static int ss_table_for(lmpc_ctx *c, int B, lmpc_solve_io *io) {
-    if (c->sst_n == 0 || c->cfg.numSS_it == 0 || !(io->mode & 1)) return LMPC_OK;
-    if (c->sst_n > 1 && B != c->sst_n) {
-        char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_ss_set_lap_table holds %d rows", B, c->sst_n);
-        return set_err(LMPC_E_ARG, "safe-set lap table", msg);
-    }
+    if (!c->sst.in_force() || c->cfg.numSS_it == 0 || !(io->mode & 1)) return LMPC_OK;
+    RCCHK(rows_fit(c->sst, B, LMPC_ROWS_EXACT, "problems", "safe-set lap table"));
     const int L = c->cfg.numSS_it;
     if (c->sst_dirty) {
         RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
         const int latest_shared = (int)c->s_len.size() - 1;
-        std::vector<int> img((size_t)c->sst_n * L * LMPC_SSTAB_ENTRY, 0), o((size_t)L);
-        for (int r = 0; r < c->sst_n; r++) {
+        std::vector<int> img((size_t)c->sst.n * L * LMPC_SSTAB_ENTRY, 0), o((size_t)L);
+        for (int r = 0; r < c->sst.n; r++) {
             // the order a controller holding only these laps would use them: argsort(LapTime), stable (:395, :402) -- ascending LapTime, ties by lap index
-            std::copy(&c->sst_idx[(size_t)r * L], &c->sst_idx[(size_t)r * L] + L, o.begin());
+            std::copy(c->sst.row(r), c->sst.row(r) + L, o.begin());
             std::sort(o.begin(), o.end(), [&](int a, int b) { return c->s_laptime[a] != c->s_laptime[b] ? c->s_laptime[a] < c->s_laptime[b] : a < b; });
             const int latest = c->sst_has_last ? c->sst_last[r] : latest_shared;
             for (int l = 0; l < L; l++) {
@@ -1094,25 +1103,18 @@ static int ss_table_for(lmpc_ctx *c, int B, lmpc_solve_io *io) {
                 e[0] = o[l]; e[1] = c->s_len[o[l]]; e[2] = o[l] == latest ? 1 : 0;       // (safe-set lap index == slot)
             }
         }
-        if (img.size() > c->d_sst_cap) {
-            if (c->d_sst) { (void)g_free(c->d_sst); c->d_sst = nullptr; c->d_sst_cap = 0; }
-            HIPCHK(g_malloc(&c->d_sst, img.size() * sizeof(int))); c->d_sst_cap = img.size();
-        }
-        HIPCHK(hipMemcpy(c->d_sst, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+        RCCHK(image_upload(&c->img[IMG_SST], img.data(), img.size() * sizeof(int), "hipMemcpy (safe-set table image)"));
         c->sst_dirty = false;
     }
-    io->ssTab = c->d_sst; io->ssTabStride = c->sst_n == 1 ? 0 : L * LMPC_SSTAB_ENTRY;
+    io->ssTab = (const int *)c->img[IMG_SST].p; io->ssTabStride = c->sst.stride(L * LMPC_SSTAB_ENTRY);
     return LMPC_OK;
 }
 // Per-problem controller tuning (lmpc_tuning_set) for a launch of B problems that solves: B against the rows, io.tune / io.tuneStride set.  No rows in force, or a
 // launch that only selects (the selection reads no weights): io stays as it is.  Called where ss_table_for is, before the first launch of a step.
 static int tuning_for(lmpc_ctx *c, int B, lmpc_solve_io *io) {
-    if (c->tune_n == 0 || !(io->mode & 2)) return LMPC_OK;
-    if (c->tune_n > 1 && B != c->tune_n) {
-        char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_tuning_set holds %d rows", B, c->tune_n);
-        return set_err(LMPC_E_ARG, "tuning rows", msg);
-    }
-    io->tune = c->d_tune; io->tuneStride = c->tune_n == 1 ? 0 : PAR_TOT;
+    if (!c->tune.in_force() || !(io->mode & 2)) return LMPC_OK;
+    RCCHK(rows_fit(c->tune, B, LMPC_ROWS_EXACT, "problems", "tuning rows"));
+    io->tune = (const double *)c->img[IMG_TUNE].p; io->tuneStride = c->tune.stride(PAR_TOT);
     return LMPC_OK;
 }
 // The device image of n rows (n = 0: the config's own row).  Launches still pending their retry pass read the image of THEIR launch: they are resolved, and the stream
@@ -1124,14 +1126,7 @@ static int tuning_upload(lmpc_ctx *c, int n, const double *rows) {
     std::vector<double> img((size_t)nr * PAR_TOT);
     for (int r = 0; r < nr; r++) tuning_image_row(c->cfg, rows + (size_t)r * LMPC_TUNING_NPAR, &img[(size_t)r * PAR_TOT]);
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
-    // (a larger image goes into a new allocation that replaces the old one only once it is filled: a HIP failure on the way leaves the image in force as it was)
-    const bool grow = img.size() > c->d_tune_cap;
-    double *buf = c->d_tune;
-    if (grow) HIPCHK(g_malloc(&buf, img.size() * sizeof(double)));
-    const hipError_t e = hipMemcpy(buf, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { if (grow) (void)g_free(buf); return set_err(LMPC_E_HIP, "hipMemcpy (tuning image)", hipGetErrorString(e)); }
-    if (grow) { if (c->d_tune) (void)g_free(c->d_tune); c->d_tune = buf; c->d_tune_cap = img.size(); }
-    return LMPC_OK;
+    return image_upload(&c->img[IMG_TUNE], img.data(), img.size() * sizeof(double), "hipMemcpy (tuning image)");
 }
 static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false) {
     lmpc_solve_io io = io_in;
@@ -1139,7 +1134,7 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
     if (!io.tune) { const int rc = tuning_for(c, B, &io); if (rc) return rc; }
     // (per-problem tracks, lmpc_track_set: the selection reads the problem's TrackLength; B against the rows)
     if (!io.trk && (io.mode & 1)) { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; io.trk = ts.dev; io.trkStride = ts.stride; }
-    if ((io.ssTab || io.trk) && !io.tune) { io.tune = c->d_tune; io.tuneStride = 0; }      // (a table or tracks alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
+    if ((io.ssTab || io.trk) && !io.tune) { io.tune = (const double *)c->img[IMG_TUNE].p; io.tuneStride = 0; }      // (a table or tracks alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
     // [A_k | B_k] from global memory only when the batch does not fit the CUs with it in LDS (N = 40: more than two QPs per CU); a batch that
     // fits runs 3 % faster from LDS (measured at N = 40, batch 512: 0.997 vs 1.030 ms)
     io.abPack = nullptr;
@@ -1173,7 +1168,7 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
     } else
 #endif
     // (a safe-set lap table, tuning rows: the condensed kernel has no per-problem lookup -- it takes Q pre-digested by the host, cd_hasq -- and is not taken: the kernels below serve them)
-    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune && c->trk_n == 0) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
+    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune && !c->trk.in_force()) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
        : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, B, io)        // fused step: the one-wave kernel runs the regression itself
        : (B <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, B, io)
        : (lmpc_solver_waves(c, B) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
@@ -1345,7 +1340,7 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     // (a lap table in force: the fused form reads the laps of the parameter block -- it lives in the variant libraries -- so the two-kernel step runs)
     // (likewise a safe-set lap table, lmpc_ss_set_lap_table: the fused form's LDS layout has no room behind it for the selected laps)
     // (likewise tuning rows, lmpc_tuning_set: the fused form has no per-problem-rows instantiation)
-    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && c->lt_n == 0 && !(term && c->sst_n) && c->tune_n == 0 && c->trk_n == 0;      // (likewise track rows, lmpc_track_set)
+    const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && !c->lt.in_force() && !(term && c->sst.in_force()) && !c->tune.in_force() && !c->trk.in_force();      // (likewise track rows, lmpc_track_set)
     double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
     // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
     // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
@@ -1427,7 +1422,7 @@ int lmpc_assemble_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     ARGCHK(c && A && Bm && C && x0 && uOld && Pdense && q && Adense && l && u && B >= 1 && B <= c->cfg.max_batch);
     int nz, mi, me; lmpc_qp_dims(c, &nz, &mi, &me); const int mm = mi + me;
     if (c->dims.S > 0) ARGCHK(ssSel && qSel);
-    if (c->tune_n > 1 && B != c->tune_n) { char msg[128]; snprintf(msg, sizeof(msg), "B = %d problems but lmpc_tuning_set holds %d rows", B, c->tune_n); return set_err(LMPC_E_ARG, "tuning rows", msg); }
+    RCCHK(rows_fit(c->tune, B, LMPC_ROWS_EXACT, "problems", "tuning rows"));
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
     call_temps tmp; double *dP, *dq, *dA, *dl, *du;
     HIPCHK(tmp.alloc(&dP, sizeof(double) * (size_t)B * nz * nz)); HIPCHK(tmp.alloc(&dq, sizeof(double) * (size_t)B * nz));
@@ -1435,7 +1430,7 @@ int lmpc_assemble_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     RCCHK(upload_qp(c, B, A, Bm, C, x0, uOld, ssSel, qSel));
     // (the matrices of problem b from tuning row b; no rows in force: the image holds the config's own row)
     hipLaunchKernelGGL(lmpc_assemble_kernel, dim3(B), dim3(256), 0, c->stream, c->dp, B, c->w.A, c->w.Bm, c->w.C, c->w.x0, c->w.uOld, c->w.ssSel, c->w.qSel, dP, dq, dA, dl, du,
-                       (const double *)c->d_tune, c->tune_n > 1 ? (int)PAR_TOT : 0);
+                       (const double *)c->img[IMG_TUNE].p, c->tune.stride(PAR_TOT));
     HIPCHK(hipGetLastError());
     D2H(Pdense, dP, (size_t)B * nz * nz); D2H(q, dq, (size_t)B * nz); D2H(Adense, dA, (size_t)B * mm * nz); D2H(l, dl, (size_t)B * mm); D2H(u, du, (size_t)B * mm);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1457,15 +1452,10 @@ int lmpc_tuning_set(lmpc_ctx *c, int n, const double *rows) {
         if (bad) { snprintf(msg, sizeof(msg), "row %d: %s (the rows in force stay)", r, bad); return set_err(LMPC_E_ARG, "lmpc_tuning_set", msg); }
     }
     RCCHK(tuning_upload(c, n, rows));
-    c->tune_rows.assign(rows, rows + (size_t)n * LMPC_TUNING_NPAR); c->tune_n = n;
+    c->tune.assign(n, rows);
     return LMPC_OK;
 }
-int lmpc_tuning_get(lmpc_ctx *c, int *n, double *rows, int capacity) {
-    ARGCHK(c && n && capacity >= 0);
-    *n = c->tune_n;
-    if (rows) memcpy(rows, c->tune_rows.data(), sizeof(double) * LMPC_TUNING_NPAR * (size_t)std::min(c->tune_n, capacity));
-    return LMPC_OK;
-}
+int lmpc_tuning_get(lmpc_ctx *c, int *n, double *rows, int capacity) { return rows_get(c, &lmpc_ctx::tune, n, rows, capacity); }
 
 // ---------------------------------------------------------------------------------------------- track rows
 int lmpc_track_set(lmpc_ctx *c, int n, const double *rows) {
@@ -1482,25 +1472,11 @@ int lmpc_track_set(lmpc_ctx *c, int n, const double *rows) {
     }
     // launches still pending their retry pass read the image of THEIR launch: they are resolved, and the stream is drained, before it is overwritten (as for tuning)
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
-    if (n > 0) {
-        const size_t len = (size_t)n * LMPC_TRACK_NPAR;
-        // (a larger image goes into a new allocation that replaces the old one only once it is filled: a HIP failure on the way leaves the image in force as it was)
-        const bool grow = len > c->d_trk_cap;
-        double *buf = c->d_trk;
-        if (grow) HIPCHK(g_malloc(&buf, len * sizeof(double)));
-        const hipError_t e = hipMemcpy(buf, rows, len * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { if (grow) (void)g_free(buf); return set_err(LMPC_E_HIP, "hipMemcpy (track image)", hipGetErrorString(e)); }
-        if (grow) { if (c->d_trk) (void)g_free(c->d_trk); c->d_trk = buf; c->d_trk_cap = len; }
-    }
-    c->trk_rows.assign(rows, rows + (size_t)n * LMPC_TRACK_NPAR); c->trk_n = n;
+    if (n > 0) RCCHK(image_upload(&c->img[IMG_TRK], rows, sizeof(double) * LMPC_TRACK_NPAR * (size_t)n, "hipMemcpy (track image)"));
+    c->trk.assign(n, rows);
     return LMPC_OK;
 }
-int lmpc_track_get(lmpc_ctx *c, int *n, double *rows, int capacity) {
-    ARGCHK(c && n && capacity >= 0);
-    *n = c->trk_n;
-    if (rows) memcpy(rows, c->trk_rows.data(), sizeof(double) * LMPC_TRACK_NPAR * (size_t)std::min(c->trk_n, capacity));
-    return LMPC_OK;
-}
+int lmpc_track_get(lmpc_ctx *c, int *n, double *rows, int capacity) { return rows_get(c, &lmpc_ctx::trk, n, rows, capacity); }
 
 // ---------------------------------------------------------------------------------------------- device buffers
 int lmpc_dev_alloc(lmpc_ctx *c, long long bytes, void **dptr) { ARGCHK(c && dptr && bytes > 0); HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipMalloc(dptr, (size_t)bytes)); return LMPC_OK; }
@@ -1553,12 +1529,9 @@ int lmpc_debug_k1_timing(lmpc_ctx *c, int B, const double *xLin, const double *u
 }  // extern "C"
 // Per-car vehicle constants (lmpc_plant_set_params).  The rows in force for a call of B cars, one per car: the single row repeated, or the first B of the n rows.
 static int plant_rows_for(lmpc_ctx *c, int B, std::vector<double> &rows) {
-    if (c->plant_n > 1 && B > c->plant_n) {
-        char msg[128]; snprintf(msg, sizeof(msg), "B = %d cars but lmpc_plant_set_params holds %d per-car rows", B, c->plant_n);
-        return set_err(LMPC_E_ARG, "plant parameters", msg);
-    }
+    RCCHK(rows_fit(c->plant, B, LMPC_ROWS_AT_LEAST, "cars", "plant parameters"));
     rows.resize((size_t)B * LMPC_PLANT_NPAR);
-    for (int b = 0; b < B; b++) memcpy(&rows[(size_t)b * LMPC_PLANT_NPAR], &c->plant_par[(size_t)(c->plant_n == 1 ? 0 : b) * LMPC_PLANT_NPAR], sizeof(double) * LMPC_PLANT_NPAR);
+    c->plant.expand(B, rows.data(), c->plant.rows.data(), LMPC_PLANT_NPAR);
     return LMPC_OK;
 }
 extern "C" {
@@ -1582,17 +1555,12 @@ int lmpc_plant_set_params(lmpc_ctx *c, int n, const double *par) {
             if (!std::isfinite(q[j])) { char msg[96]; snprintf(msg, sizeof(msg), "row %d, entry %d is not finite", b, j); return set_err(LMPC_E_ARG, "plant parameters", msg); }
         if (!(q[0] > 0.0) || !(q[3] > 0.0)) { char msg[96]; snprintf(msg, sizeof(msg), "row %d: m and Iz must be positive", b); return set_err(LMPC_E_ARG, "plant parameters", msg); }
     }
-    c->plant_par.assign(par, par + (size_t)n * LMPC_PLANT_NPAR); c->plant_n = n;
+    c->plant.assign(n, par);
     return LMPC_OK;
 }
 
-int lmpc_plant_get_params(lmpc_ctx *c, int *n, double *par, int capacity) {
-    // the rows lmpc_plant_set_params left in force (n = 0: the literals of SysModel.py:60-70, see lmpc_plant_params_default)
-    ARGCHK(c && n && capacity >= 0);
-    *n = c->plant_n;
-    if (par) memcpy(par, c->plant_par.data(), sizeof(double) * LMPC_PLANT_NPAR * (size_t)std::min(capacity, c->plant_n));
-    return LMPC_OK;
-}
+// the rows lmpc_plant_set_params left in force (n = 0: the literals of SysModel.py:60-70, see lmpc_plant_params_default)
+int lmpc_plant_get_params(lmpc_ctx *c, int *n, double *par, int capacity) { return rows_get(c, &lmpc_ctx::plant, n, par, capacity); }
 
 // ---- counter-based noise (lmpc_noise.hip.h).  No reference counterpart beyond np.random.randn() at SysModel.py:139-141 and Utilities.py:67-68.
 #define NOISE_RANGE_CHK() do { ARGCHK(T >= 1 && B >= 1 && t0 >= 0 && car0 >= 0); ARGCHK(((unsigned long long)T * (unsigned long long)B + LMPC_NOISE_NT - 1) / LMPC_NOISE_NT <= 0x7fffffffull); } while (0)
@@ -1642,7 +1610,7 @@ int lmpc_rollout_get_noise(lmpc_ctx *c, int *on, unsigned long long *seed, unsig
 int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg, const double *u, const double *noise, double *xn, double *xgn, int *status) {
     ARGCHK(c && x && xg && u && noise && xn && xgn && B >= 1);
     HIPCHK(hipSetDevice(c->cfg.device));
-    const bool par = c->plant_n > 0;
+    const bool par = c->plant.in_force();
     std::vector<double> rows;
     if (par) { const int rc = plant_rows_for(c, B, rows); if (rc) return rc; }
     trk_src ts; { const int rc = track_for(c, B, &ts); if (rc) return rc; }      // (car b on track row b)
@@ -1766,7 +1734,7 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     const size_t S = c->dims.S, Bz = B;
     trk_src trk; { const int rc = track_for(c, B, &trk); if (rc) return rc; }      // (car b on track row b: refused before any session state changes)
     std::vector<double> par_rows;                               // refused before any session state changes (B beyond the per-car rows)
-    if (c->plant_n > 0) { const int rc = plant_rows_for(c, B, par_rows); if (rc) return rc; }
+    if (c->plant.in_force()) RCCHK(plant_rows_for(c, B, par_rows));
     // the trace in force (lmpc_rollout_set_trace; a PID session has no predictions and records none): a listed car the session does not have is refused here
     const int tn = kind == RO_PID ? 0 : (int)c->trace_cars.size(); const unsigned tw = tn ? c->trace_what : 0u;
     for (int k = 0; k < tn; k++) if (c->trace_cars[(size_t)k] >= B) {
@@ -1776,12 +1744,12 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     // SS, QSEL and XY of an LMPC session read the selection outputs the step writes only into the capture buffers: a traced session has them, capture or not
     const bool need_sel = c->dbg_capture != 0 || (tn > 0 && S > 0 && (tw & (LMPC_TRACE_SS | LMPC_TRACE_QSEL | LMPC_TRACE_XY)) != 0);
     std::vector<int> lt_rows; bool lt_small = true;             // sessions that run the regression: the lap table in force, one resolved row per car (refused here as well when B is not its row count)
-    if ((kind == RO_LMPC || kind == RO_LTV) && c->lt_n > 0) {
-        k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc;
+    if ((kind == RO_LMPC || kind == RO_LTV) && c->lt.in_force()) {
+        k1_table tab; RCCHK(k1_table_for(c, B, &tab));
         const std::vector<int> pairs = resolve_lap_rows(c, &lt_small);
         const size_t rowlen = (size_t)c->cfg.trToUse * 2;
         lt_rows.resize((size_t)B * rowlen);
-        for (int b = 0; b < B; b++) memcpy(&lt_rows[(size_t)b * rowlen], &pairs[(size_t)(c->lt_n == 1 ? 0 : b) * rowlen], sizeof(int) * rowlen);
+        c->lt.expand(B, lt_rows.data(), pairs.data(), rowlen);
     }
     // A generation loop begins a session of the same shape every lap: its ~35 device buffers (55 MB of logs at 1024 rollouts x 400 steps), the plant stream and
     // the two events are kept from one session to the next (round 5: allocating and freeing them was ~5 ms of every generation) and released by
@@ -1885,7 +1853,7 @@ int lmpc_rollout_begin_mpc(lmpc_ctx *c, int B, int T_max, const double *x0, cons
     ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
     HIPCHK(hipSetDevice(c->cfg.device));
     const bool lti = A_lti != nullptr;
-    if (!lti) { const int rc = refresh_params(c, true, false, c->lt_n != 0); if (rc) return rc; }       // LMPC_E_STATE without trToUse stored laps, as lmpc_step_batch
+    if (!lti) { const int rc = refresh_params(c, true, false, c->lt.in_force()); if (rc) return rc; }       // LMPC_E_STATE without trToUse stored laps, as lmpc_step_batch
     RESOLVE_PENDING();
     int rc = rollout_setup(c, lti ? RO_LTI : RO_LTV, stop_at_line ? 1 : 0, B, T_max, x0, xg0, lti ? nullptr : xLin0, lti ? nullptr : uLin0, noise);
     if (rc) return rc;

@@ -182,50 +182,21 @@ class BatchedRollouts:
         rows = getattr(self, "tracks", None)
         return int(b) if rows is not None and rows.shape[0] > 1 else None
 
-    def _apply_tracks(self, B):
-        """The track rows of this object's cars go to the context in front of a session (the context refuses a change while one is active)."""
-        rows = getattr(self, "tracks", None)           # (objects built without __init__ -- tests/test_host_checks.py -- have none)
-        if rows is None:
-            return
-        if rows.shape[0] not in (1, B):
-            raise ValueError("tracks: one row or one per car (%d) expected, got %d" % (B, rows.shape[0]))
-        self.ctx.track_set(rows)
+    # The per-car row sets this object hands to the context in front of a session: attribute -> (setter of the context, attributes that travel with the rows).
+    # Tracks are refused by the context while a session is active; the vehicle rows and the lap table are snapshotted when one begins; the others are live.
+    _ROW_SETS = {"tracks": ("track_set", ()), "plant_params": ("plant_set_params", ()), "lap_table": ("model_set_lap_table", ()),
+                 "ss_table": ("ss_set_lap_table", ("ss_last",)), "tuning": ("tuning_set", ())}
 
-    def _apply_plant_params(self, B):
-        """The vehicle rows of this object's cars go to the context in front of a session (the session takes its snapshot when it begins)."""
-        par = getattr(self, "plant_params", None)      # (objects built without __init__ -- tests/test_host_checks.py -- have none)
-        if par is None:
-            return
-        if par.shape[0] not in (1, B):
-            raise ValueError("plant_params: one row or one per car (%d) expected, got %d" % (B, par.shape[0]))
-        self.ctx.plant_set_params(par)
-
-    def _apply_lap_table(self, B):
-        """The lap-table rows of this object's cars go to the context in front of a session that runs the regression (the session takes its snapshot when it begins)."""
-        tab = getattr(self, "lap_table", None)         # (objects built without __init__ -- tests/test_host_checks.py -- have none)
-        if tab is None:
-            return
-        if tab.shape[0] not in (1, B):
-            raise ValueError("lap_table: one row or one per car (%d) expected, got %d" % (B, tab.shape[0]))
-        self.ctx.model_set_lap_table(tab)
-
-    def _apply_ss_table(self, B):
-        """The safe-set rows of this object's cars go to the context in front of an LMPC session."""
-        tab = getattr(self, "ss_table", None)          # (objects built without __init__ -- tests/test_host_checks.py -- have none)
-        if tab is None:
-            return
-        if tab.shape[0] not in (1, B):
-            raise ValueError("ss_table: one row or one per car (%d) expected, got %d" % (B, tab.shape[0]))
-        self.ctx.ss_set_lap_table(tab, getattr(self, "ss_last", None))
-
-    def _apply_tuning(self, B):
-        """The tuning rows of this object's cars go to the context in front of a session that solves."""
-        rows = getattr(self, "tuning", None)           # (objects built without __init__ -- tests/test_host_checks.py -- have none)
-        if rows is None:
-            return
-        if rows.shape[0] not in (1, B):
-            raise ValueError("tuning: one row or one per car (%d) expected, got %d" % (B, rows.shape[0]))
-        self.ctx.tuning_set(rows)
+    def _apply_rows(self, B, which):
+        """The named row sets (keys of _ROW_SETS, in the order given) of this object's B cars go to the context; a set this object does not hold is left alone."""
+        for name in which:
+            setter, extra = self._ROW_SETS[name]
+            rows = getattr(self, name, None)           # (objects built without __init__ -- tests/test_host_checks.py -- have none)
+            if rows is None:
+                continue
+            if rows.shape[0] not in (1, B):
+                raise ValueError("%s: one row or one per car (%d) expected, got %d" % (name, B, rows.shape[0]))
+            getattr(self.ctx, setter)(rows, *[getattr(self, e, None) for e in extra])
 
     def _apply_trace(self, B):
         """The traced cars of this object go to the context in front of a session that solves."""
@@ -257,11 +228,7 @@ class BatchedRollouts:
         B = x0.shape[0]
         xl = self._per_rollout(xLin0, B); ul = self._per_rollout(uLin0, B)
         noise = self._draw_noise(max_steps, B)
-        self._apply_tracks(B)
-        self._apply_plant_params(B)
-        self._apply_lap_table(B)
-        self._apply_ss_table(B)
-        self._apply_tuning(B)
+        self._apply_rows(B, ("tracks", "plant_params", "lap_table", "ss_table", "tuning"))
         self._apply_trace(B)
         if self._device_noise_session(B):
             self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, None, T_max=max_steps)
@@ -317,8 +284,7 @@ class BatchedRollouts:
         x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1)) if x0 is None else np.asarray(x0, float)
         noise_u = self._draw_noise(max_steps, B, width=2)
         noise = self._draw_noise(max_steps, B)
-        self._apply_tracks(B)
-        self._apply_plant_params(B)
+        self._apply_rows(B, ("tracks", "plant_params"))
         if self._device_noise_session(B):
             t, _ = self.ctx.rollout_pid(x0, x0, vt, None, None, stop_at_line=stop_at_line, T_max=max_steps)
         else:
@@ -333,11 +299,7 @@ class BatchedRollouts:
         context's regression store.  Generator consumption: one plant-noise draw (max_steps, nb, 3) (device_noise: none, one session of the device generator).  Returns lap tuples as run_pid_laps does."""
         x0 = np.asarray(x0, float); nb = x0.shape[0]
         noise = self._draw_noise(max_steps, nb)
-        self._apply_tracks(nb)
-        self._apply_plant_params(nb)
-        if A is None:
-            self._apply_lap_table(nb)              # (the LTI form runs no regression)
-        self._apply_tuning(nb)
+        self._apply_rows(nb, ("tracks", "plant_params") + (("lap_table",) if A is None else ()) + ("tuning",))      # (the LTI form runs no regression)
         self._apply_trace(nb)
         kw = dict(T_max=max_steps) if self._device_noise_session(nb) else {}       # (noise is None then: the session's buffer is filled on the device)
         if A is not None:
@@ -728,7 +690,7 @@ class PerCarLMPC:
             raise ValueError("PerCarLMPC.seed needs a context with empty lap stores")
         laps_per_car = [list(l) if isinstance(l, list) else [l] for l in laps_per_car]
         B = self.B = len(laps_per_car)
-        self.ro._apply_tracks(B)           # (per-car tracks: car b's laps are stored with the TrackLength of row b)
+        self.ro._apply_rows(B, ("tracks",))           # (per-car tracks: car b's laps are stored with the TrackLength of row b)
         self.ss_hist, self.model_hist = PerCarHistory(B, ctx.cfg.numSS_it), PerCarHistory(B, ctx.cfg.trToUse)
         self.last = np.full(B, -1, np.int32)
         self.latest = [None] * B           # (x, u, final12, ends at the line) of each car's most recent lap
