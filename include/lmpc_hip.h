@@ -425,6 +425,35 @@ int lmpc_rollout_fetch_trace(lmpc_ctx *, int t0, int t1, const lmpc_trace_out *o
          * mapStatus[t][k]: LMPC_ST_NO_SEGMENT if a point of that row lies on no segment of the car's track (written as (0, 0), the rule of
          * lmpc_global_position_batch), else 0.  LMPC_E_STATE with no session active, on a session begun without a trace and on a lmpc_rollout_pid session;
          * LMPC_E_ARG for a non-NULL pointer of a plane the session does not record, t0 < 0, t1 < t0, t1 beyond the steps taken */
+/* ---- parking (version 111; kernel: racinglmpc_amd/csrc/lmpc_live.hip.h).  A car that has crossed the line, or that the caller lists before the session begins, is taken
+ * out of the launches: the kernels of a session step run over the ascending list of the cars still live, and the session ends when none is left.  Cars are independent
+ * problems, so a live car computes bit for bit what it computes in the session without parking.  No reference counterpart (Simulator.sim runs one car, SysModel.py:22-54). */
+#define LMPC_PARK_FINISHED 1u   /* in a session that stops at the line, a car leaves the launches at the first poll after its crossing step */
+#define LMPC_PARK_REROUTE  2u   /* the solve-kernel route (4 / 2 / 1 waves per QP) follows the live count; default: the route of the session's B */
+int lmpc_rollout_set_parking(lmpc_ctx *, unsigned mode, int n, const int *cars /* n distinct cars parked from step 0; NULL with n = 0 */);
+        /* the parking of later sessions of lmpc_rollout_begin and lmpc_rollout_begin_mpc (LTV and LTI form); lmpc_rollout_pid ignores it, as it ignores traces.  Off
+         * (mode 0, no cars) after lmpc_create, and then every path allocates, launches and returns what it did before this entry point existed.  A session takes
+         * (mode, cars) as a snapshot when it begins, like the trace and the noise source: a `set` during a session reaches the next session only.  Needs no device.
+         * LMPC_E_ARG, with the setting in force kept, for unknown mode bits, n < 0, n > 0 with NULL cars, a negative or repeated car.  A car >= B is refused, and
+         * named, by the `begin` that meets it, before any session state changes.  LMPC_PARK_FINISHED acts only in sessions that stop at the line (lmpc_rollout_begin,
+         * lmpc_rollout_begin_mpc with stop_at_line = 1); a session that logs its cars past the crossing parks the start list only.
+         * The live list is built at `begin` and rebuilt at the finished-lap poll lmpc_rollout_run makes anyway (every 8 steps and at the end of a run), when nDone has
+         * moved since the last rebuild: a car is stepped for up to 7 steps past its crossing.  The live count comes back in the copy that brings nDone.  A session that
+         * stops at the line ends when no car is live (with a start list only: when every car not on it has crossed); n_done keeps its meaning.  With every car on the
+         * start list `begin` succeeds and lmpc_rollout_run returns at once with 0 steps.
+         * statusAcc, doneAt, finX and finG of a car are what they are without parking (frozen at the crossing step either way).  NOT WRITTEN for a parked car, from its
+         * parking step on: its state, its log rows and its trace planes -- lmpc_rollout_fetch and lmpc_rollout_fetch_trace return what the kept buffers held there
+         * (a reused session: the previous lap's rows); cut at lmpc_rollout_parked_at.  lmpc_rollout_commit_laps with explicit rows[k] beyond a parked car's parking
+         * step and lmpc_rollout_extend_laps with n_rows beyond it are LMPC_E_ARG, car named; rows = NULL (up to doneAt) is always inside.
+         * A parking session runs the per-problem-rows instantiations of the regression and solve kernels (the config's own row where no rows are in force) and never
+         * the condensed kernel; the four-wave route needs the live count <= the four-wave batch limit on either route, which holds because it never exceeds B */
+int lmpc_rollout_get_parking(lmpc_ctx *, unsigned *mode, int *n, int *cars /*capacity, or NULL*/, int capacity);
+        /* what lmpc_rollout_set_parking left in force (mode 0, n 0: off); cars receives min(n, capacity) entries; any pointer may be NULL.  No reference counterpart */
+int lmpc_rollout_parked_at(lmpc_ctx *, int *at /*B: -1 live, else the first step the car was not stepped*/, int *n_live);
+        /* of the active session (LMPC_E_STATE without one); a session without parking answers -1 for every car and n_live = B.  Either pointer may be NULL */
+int lmpc_debug_live_compact(lmpc_ctx *, int n, const int *doneAt, const int *parked0 /*n flags*/, int t, unsigned mode, int *live /*n; n_live written*/, int *parkedAt /*n, in and out: -1 = not parked so far*/, int *n_live);
+        /* (every build) the session's own compaction kernel between host arrays: car b is parked if parkedAt[b] >= 0 on entry, parked0[b] != 0, or (LMPC_PARK_FINISHED)
+         * doneAt[b] >= 0; a car parked by this call gets parkedAt[b] = t; live receives the others in ascending order.  Any n >= 1 */
 int lmpc_ss_extend_lap(lmpc_ctx *, int lap, const double *x /*n x 6*/, const double *u /*n x 2*/, int n);
 /* Undo extensions: keep the first T rows of stored lap `lap` (LapTime <= T <= current rows).  rollout.LmpcGeneration rolls a failed
  * generation back with it, so that a generation either completes or leaves the safe set as it found it.  No reference counterpart. */

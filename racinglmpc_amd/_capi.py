@@ -27,6 +27,9 @@ COMMIT_SS, COMMIT_MODEL = 1, 2         # LMPC_COMMIT_SS / LMPC_COMMIT_MODEL: the
 TRACE_XPRED, TRACE_UPRED, TRACE_SS, TRACE_QSEL, TRACE_SOLVER, TRACE_XY = 1, 2, 4, 8, 16, 32
 TRACE_ALL = 63
 TRACE_DEFAULT = None                   # rollout_set_trace(what=TRACE_DEFAULT): every plane the context can record (no SS / QSEL without a safe set)
+# LMPC_PARK_*: parking (lmpc_rollout_set_parking) -- FINISHED: a car leaves the launches of a session that stops at the line at the first poll after its crossing step;
+# REROUTE: the solve-kernel route follows the live count instead of the session's B
+PARK_FINISHED, PARK_REROUTE = 1, 2
 PLANT_PARAM_NAMES = ("m", "lf", "lr", "Iz", "Df", "Cf", "Bf", "Dr", "Cr", "Br")       # one row of vehicle constants, the order of SysModel.py:60-70
 
 
@@ -122,6 +125,25 @@ def check_trace(cars, what, numSS_it):
     return cars, what
 
 
+def check_parking(mode, cars):
+    """(mode, cars as int32) of a rollout_set_parking call, or ValueError for what the library refuses with LMPC_E_ARG: unknown mode bits, a negative or repeated
+    car.  mode may be True (PARK_FINISHED) or False / None (0); cars None: no car parked from step 0."""
+    mode = PARK_FINISHED if mode is True else 0 if mode is None or mode is False else int(mode)
+    if mode < 0 or mode & ~(PARK_FINISHED | PARK_REROUTE):
+        raise ValueError("parking: mode = %d has unknown bits" % mode)
+    cars = np.zeros(0, np.int32) if cars is None else np.asarray(cars)
+    if cars.ndim != 1:
+        raise ValueError("parking: cars must be one-dimensional")
+    if cars.size and not np.issubdtype(cars.dtype, np.integer):
+        raise ValueError("parking: cars must be integers")
+    cars = _i32(cars)
+    if (cars < 0).any():
+        raise ValueError("parking: negative car index")
+    if np.unique(cars).size != cars.size:
+        raise ValueError("parking: a car is listed twice")
+    return mode, cars
+
+
 EXPORTS = [
     "lmpc_config_default", "lmpc_create", "lmpc_create_ex", "lmpc_solver_kind", "lmpc_destroy", "lmpc_last_error", "lmpc_active_knobs", "lmpc_version", "lmpc_device_memory",
     "lmpc_model_add_trajectory", "lmpc_model_num_laps", "lmpc_model_replace_lap", "lmpc_model_set_lap_table", "lmpc_model_get_lap_table", "lmpc_model_lap_info",
@@ -134,6 +156,7 @@ EXPORTS = [
     "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_debug_model_image", "lmpc_tuning_from_config", "lmpc_tuning_set", "lmpc_tuning_get",
     "lmpc_track_row_from_config", "lmpc_track_set", "lmpc_track_get", "lmpc_ss_add_trajectory_on", "lmpc_ss_extend_lap_on",
     "lmpc_rollout_set_trace", "lmpc_rollout_get_trace", "lmpc_rollout_trace_bytes", "lmpc_rollout_fetch_trace",
+    "lmpc_rollout_set_parking", "lmpc_rollout_get_parking", "lmpc_rollout_parked_at", "lmpc_debug_live_compact",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
 ]
 
@@ -204,6 +227,13 @@ def load():
         lib.lmpc_rollout_trace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_longlong)]
         lib.lmpc_rollout_fetch_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(TraceOut)]
         for f in (lib.lmpc_rollout_set_trace, lib.lmpc_rollout_get_trace, lib.lmpc_rollout_trace_bytes, lib.lmpc_rollout_fetch_trace):
+            f.restype = C.c_int
+        # (parking: mode bits, an int32 car list; the compaction kernel between int32 host arrays)
+        lib.lmpc_rollout_set_parking.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.c_void_p]
+        lib.lmpc_rollout_get_parking.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_int), C.c_void_p, C.c_int]
+        lib.lmpc_rollout_parked_at.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        lib.lmpc_debug_live_compact.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        for f in (lib.lmpc_rollout_set_parking, lib.lmpc_rollout_get_parking, lib.lmpc_rollout_parked_at, lib.lmpc_debug_live_compact):
             f.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
@@ -948,6 +978,41 @@ class Context:
         cars = np.zeros(n.value, np.int32)
         _chk(self.lib.lmpc_rollout_get_trace(self._h, C.byref(n), cars.ctypes.data, C.byref(what), cars.shape[0]))
         return cars, int(what.value)
+
+    # ---- parking (lmpc_rollout_set_parking; csrc/lmpc_live.hip.h)
+    def rollout_set_parking(self, mode=0, cars=None):
+        """The parking of the sessions begun after this call: mode (PARK_* bits; True: PARK_FINISHED) and the cars parked from step 0.  A parked car leaves the
+        launches of every later step; a session that stops at the line ends when no car is live.  mode 0 and no cars: off.  A session keeps the setting it began
+        with; rollout_pid ignores it."""
+        mode, cars = check_parking(mode, cars)
+        _chk(self.lib.lmpc_rollout_set_parking(self._h, mode, cars.shape[0], cars.ctypes.data if cars.size else None))
+
+    def rollout_parking(self):
+        """(mode, cars (n,) int32) in force (lmpc_rollout_get_parking); 0 and no cars: off."""
+        n = C.c_int(); mode = C.c_uint()
+        _chk(self.lib.lmpc_rollout_get_parking(self._h, C.byref(mode), C.byref(n), None, 0))
+        cars = np.zeros(n.value, np.int32)
+        _chk(self.lib.lmpc_rollout_get_parking(self._h, C.byref(mode), C.byref(n), cars.ctypes.data if cars.size else None, cars.shape[0]))
+        return int(mode.value), cars
+
+    def rollout_parked_at(self):
+        """(parked_at (B,) int32, n_live) of the active session (lmpc_rollout_parked_at): -1 for a live car, else the first step the car was not stepped -- its
+        state, log rows and trace planes stand still from there."""
+        ro = getattr(self, "_ro", None)           # (no session begun so far: the library says so)
+        at = np.zeros(ro[0] if ro else 0, np.int32); nl = C.c_int()
+        _chk(self.lib.lmpc_rollout_parked_at(self._h, at.ctypes.data if at.size else None, C.byref(nl)))
+        return at, nl.value
+
+    def debug_live_compact(self, doneAt, parked0, t, mode, parkedAt=None):
+        """The sessions' compaction kernel on host arrays (lmpc_debug_live_compact): returns (live (n_live,) int32 ascending, parkedAt (n,) int32).  parkedAt given:
+        the result of an earlier call, on top of which this one parks more cars."""
+        done = _i32(doneAt); p0 = _i32(parked0); n = done.shape[0]
+        assert done.shape == p0.shape == (n,)
+        at = np.full(n, -1, np.int32) if parkedAt is None else _i32(parkedAt).copy()
+        assert at.shape == (n,)
+        live = np.zeros(n, np.int32); nl = C.c_int()
+        _chk(self.lib.lmpc_debug_live_compact(self._h, n, done.ctypes.data, p0.ctypes.data, int(t), int(mode), live.ctypes.data, at.ctypes.data, C.byref(nl)))
+        return live[:nl.value].copy(), at
 
     def rollout_trace_bytes(self, n, what, T_max):
         """Device memory the trace planes of a session of that shape take (lmpc_rollout_trace_bytes)."""

@@ -6,6 +6,7 @@
 #include "lmpc_track.hip.h"
 #include "lmpc_commit.hip.h"
 #include "lmpc_trace.hip.h"
+#include "lmpc_live.hip.h"
 #include "lmpc_arrays.h"
 #include "lmpc_rows.h"
 #include <rccl/rccl.h>
@@ -133,6 +134,7 @@ struct lmpc_ctx {
     struct lmpc_rollout_session *ro;
     int noise_on; unsigned long long noise_seed, noise_lap; long long noise_car0;   // lmpc_rollout_set_noise: sessions begun with noise = NULL fill their buffer on the device (lmpc_noise.hip.h); 0 after lmpc_create
     std::vector<int> trace_cars; unsigned trace_what;   // lmpc_rollout_set_trace: the cars and planes later sessions record at every step (lmpc_trace.hip.h); empty / 0 after lmpc_create
+    std::vector<int> park_cars; unsigned park_mode;     // lmpc_rollout_set_parking: the cars later sessions park from step 0 and the LMPC_PARK_* bits (lmpc_live.hip.h); empty / 0 after lmpc_create
     // The per-car row sets (lmpc_rows.h: the rows as the caller gave them, 0 rows = the config's value, one row serves all, else row b for problem b) and img[], their device images.
     lmpc_row_set<double> plant{LMPC_PLANT_NPAR, "lmpc_plant_set_params"};   // vehicle constants (0 rows: the reference's vehicle, the kernels with the literals); no image: a call uploads its cars' rows
     // trToUse insertion indices per row (0 rows: the first trToUse laps of the sorted order serve every problem).  img[IMG_LT]: the same rows as resolved (slot, rows)
@@ -177,6 +179,11 @@ struct lmpc_rollout_session {
     int tr_n; unsigned tr_what; int *d_trCars;
     double *tr_x, *tr_u, *tr_ss, *tr_q, *tr_xy, *tr_xys; int *tr_it, *tr_st, *tr_map;
     hipStream_t tstream; hipEvent_t e_trace;
+    // the session's snapshot of the parking (lmpc_rollout_set_parking), taken when it begins.  parked: the step's kernels run over d_live[0 .. nLive), the ascending
+    // list of the cars still stepped (lmpc_live.hip.h); pk_mode: the bits that act in this session (LMPC_PARK_FINISHED only where it stops at the line); pk_n0: cars
+    // parked from step 0; nd_host: nDone as the last poll read it.  d_live / d_parkedAt / d_park0 (B ints each) are allocated by the first parking session on the
+    // kept buffers; d_nDone holds four ints: nDone, nLive, nDone at the last rebuild, unused
+    bool parked; unsigned pk_mode; int pk_n0, nLive, nd_host; int *d_live, *d_parkedAt, *d_park0;
     bool tr_own_stream;                                         // (developer knob LMPC_TRACE_OWN_STREAM=1, read when a traced session begins: the trace kernel on a stream of its own beside the plant, the next solve waiting for a second event -- the A / B of tools/trace_bench.py, measured slower; same bits)
 };
 
@@ -234,7 +241,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 110; }
+int lmpc_version(void) { return 111; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -914,6 +921,14 @@ int lmpc_debug_model_image(lmpc_ctx *c, int lap, unsigned *q, double *par, int *
 }
 
 // ---- laps of the active session straight into the stores: no log leaves the device
+// Parking sessions: the step each car was parked at (-1: live), for the row checks below; empty for a session without parking
+static int session_parked_at(lmpc_rollout_session *r, std::vector<int> &at) {
+    at.clear();
+    if (!r->parked) return LMPC_OK;
+    at.resize((size_t)r->B);
+    HIPCHK(hipMemcpy(at.data(), r->d_parkedAt, sizeof(int) * (size_t)r->B, hipMemcpyDeviceToHost));
+    return LMPC_OK;
+}
 int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *rows, unsigned stores, int *first_ss, int *first_model) {
     // For i = 0 .. n-1 in the order listed: lmpc_ss_add_trajectory (LMPC.addTrajectory + computeCost, PredictiveControllers.py:418-464) and lmpc_model_add_trajectory
     // (PredictiveModel.addTrajectory, PredictiveModel.py:35-46) of rows [0, rows[i]) of car cars[i] as the session logged them, all in one commit_laps.
@@ -927,9 +942,12 @@ int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *row
     HIPCHK(hipMemcpy(done.data(), r->d_done, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
     const int ns0 = (int)c->s_len.size(), nm0 = (int)c->m_len.size();
     std::vector<lmpc_commit_entry> tab((size_t)n);
+    std::vector<int> pat; RCCHK(session_parked_at(r, pat));
     char msg[160];
     for (int i = 0; i < n; i++) {
         const int car = cars[i], T = rows ? rows[i] : done[car];
+        // (a parked car is not logged from its parking step on; rows = NULL stops at doneAt, which lies inside)
+        if (rows && !pat.empty() && pat[(size_t)car] >= 0 && T > pat[(size_t)car]) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, which was parked at step %d (lmpc_rollout_parked_at)", i, T, car, pat[(size_t)car]); return set_err(LMPC_E_ARG, "lmpc_rollout_commit_laps", msg); }
         if (!rows && done[car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0) and no row count was given", car); return set_err(LMPC_E_STATE, "lmpc_rollout_commit_laps", msg); }
         // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
         const int logged = (r->kind == RO_PID && r->stop_at_line && done[car] >= 0) ? done[car] : r->t;
@@ -955,6 +973,10 @@ int lmpc_rollout_extend_laps(lmpc_ctx *c, int n, const int *cars, const int *lap
         if (seen[(size_t)laps[i]]) { char msg[96]; snprintf(msg, sizeof(msg), "lap %d is listed twice", laps[i]); return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); }
         seen[(size_t)laps[i]] = 1;
     }
+    { std::vector<int> pat; RCCHK(session_parked_at(c->ro, pat));
+      if (!pat.empty()) for (int i = 0; i < n; i++) if (pat[(size_t)cars[i]] >= 0 && n_rows > pat[(size_t)cars[i]]) {
+          char msg[160]; snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, which was parked at step %d (lmpc_rollout_parked_at)", i, n_rows, cars[i], pat[(size_t)cars[i]]);
+          return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); } }
     store_rows s; RCCHK(session_rows(c, LMPC_EXTEND_TAIL(n), &s));
     return extend_laps(c, s, n, cars, laps, n_rows, extended);
 }
@@ -1014,10 +1036,11 @@ static void k1_grid(lmpc_ctx *c, int B, int *qg, int *nblk) {
 // 8-rows-per-lane scan when every lap in use lies inside its first quantisation chunk half (<= 512 rows; k1_scan_lap).
 // The lap table a regression launch reads: the context's (k1_table_for) or a rollout session's snapshot.  dev == nullptr: none, the laps of the parameter block.
 // trk / trkStride: the per-problem tracks of the same launch (lmpc_track_set; null: the parameter block's track)
-struct k1_table { const int *dev; int stride; bool small; const double *trk; int trkStride; };
+// live: parking -- the launch covers B entries of that list (table builds only: a parking session without a lap table hands in the block's own laps as a one-row table)
+struct k1_table { const int *dev; int stride; bool small; const double *trk; int trkStride; const int *live; };      // live != null needs dev != null
 // the context's table for a call of B problems (B points for lmpc_regress_points): one row serves all, else row b belongs to problem b and the counts must agree
 static int k1_table_for(lmpc_ctx *c, int B, k1_table *t) {
-    t->dev = nullptr; t->stride = 0; t->small = true;
+    t->dev = nullptr; t->stride = 0; t->small = true; t->live = nullptr;
     { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; t->trk = ts.dev; t->trkStride = ts.stride; }
     if (!c->lt.in_force()) return LMPC_OK;
     RCCHK(rows_fit(c->lt, B, LMPC_ROWS_EXACT, "problems", "lap table"));
@@ -1032,6 +1055,12 @@ static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, 
     const bool occ = nblk > c->n_cu;
     auto k = occ ? (small ? lmpc_regress_kernel<true, 8> : lmpc_regress_kernel<true, K1_RPL>) : (small ? lmpc_regress_kernel<false, 8> : lmpc_regress_kernel<false, K1_RPL>);
     if (t.dev) k = occ ? (small ? lmpc_regress_kernel<true, 8, true> : lmpc_regress_kernel<true, K1_RPL, true>) : (small ? lmpc_regress_kernel<false, 8, true> : lmpc_regress_kernel<false, K1_RPL, true>);
+    if (t.dev && t.live) {                                               // a parking session: the table builds with the live list (B entries of it)
+        auto kl = occ ? (small ? lmpc_regress_kernel<true, 8, true, lmpc_live_list> : lmpc_regress_kernel<true, K1_RPL, true, lmpc_live_list>)
+                      : (small ? lmpc_regress_kernel<false, 8, true, lmpc_live_list> : lmpc_regress_kernel<false, K1_RPL, true, lmpc_live_list>);
+        hipLaunchKernelGGL(kl, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride, lmpc_live_list{t.live, B});
+        return;
+    }
     hipLaunchKernelGGL(k, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride);
 }
 static int launch_regress(lmpc_ctx *c, int B, const double *d_xLin, int xstride, const double *d_uLin, double *dA, double *dB, double *dC, int *dst) {
@@ -1068,7 +1097,7 @@ static int resolve_retries(lmpc_ctx *c) {
         if (no_retry || c->h_retry[pe.epoch % LMPC_RETRY_RING] != pe.epoch) continue;
         pe.io.retry_flag = nullptr;
         // the retry runs against the parameter block of ITS launch (selected laps, lap lengths, cur_it), not the context's current one
-        rc = c->var.launch_retry(c->stream, pe.dp, pe.B, pe.io); if (rc) break;
+        rc = c->var.launch_retry(c->stream, pe.dp, pe.B, pe.io, nullptr); if (rc) break;
         if (hipGetLastError() != hipSuccess) { rc = set_err(LMPC_E_HIP, "retry launch", ""); break; }
         c->stats.n_retry++; launched++;
     }
@@ -1128,13 +1157,18 @@ static int tuning_upload(lmpc_ctx *c, int n, const double *rows) {
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     return image_upload(&c->img[IMG_TUNE], img.data(), img.size() * sizeof(double), "hipMemcpy (tuning image)");
 }
-static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false) {
+// live / nLive (parking sessions): the live list and its entries -- what the kernels are launched over; B stays the session's batch, which the per-car rows are
+// checked against and the abPack scratch is sized for.  reroute (LMPC_PARK_REROUTE): the route (waves per QP) follows nLive instead of B.  The choice between [A_k | B_k] in
+// LDS and in the abPack scratch (long horizons) stays with B on either route: a rerouted one-wave launch at N = 40 may take the global-memory build where a session of
+// nLive cars would not -- same QP answer to the routes' bound, not the same kernel
+static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false, const int *live = nullptr, int nLive = -1, bool reroute = false) {
     lmpc_solve_io io = io_in;
+    const int Bl = live ? nLive : B, Br = (live && reroute) ? nLive : B;      // problems launched; the batch the route is chosen for
     if (!io.ssTab) { const int rc = ss_table_for(c, B, &io); if (rc) return rc; }
     if (!io.tune) { const int rc = tuning_for(c, B, &io); if (rc) return rc; }
     // (per-problem tracks, lmpc_track_set: the selection reads the problem's TrackLength; B against the rows)
     if (!io.trk && (io.mode & 1)) { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; io.trk = ts.dev; io.trkStride = ts.stride; }
-    if ((io.ssTab || io.trk) && !io.tune) { io.tune = (const double *)c->img[IMG_TUNE].p; io.tuneStride = 0; }      // (a table or tracks alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
+    if ((io.ssTab || io.trk || live) && !io.tune) { io.tune = (const double *)c->img[IMG_TUNE].p; io.tuneStride = 0; }      // (a table or tracks alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
     // [A_k | B_k] from global memory only when the batch does not fit the CUs with it in LDS (N = 40: more than two QPs per CU); a batch that
     // fits runs 3 % faster from LDS (measured at N = 40, batch 512: 0.997 vs 1.030 ms)
     io.abPack = nullptr;
@@ -1164,21 +1198,22 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
 #ifdef LMPC_DEV_FAST
     if (const char *f = dev_knob("LMPC_FORCE_NW")) {
         const int nw = atoi(f);
-        rc = nw == 4 ? c->var.launch_mw4(c->stream, c->dp, B, io) : nw == 2 ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
+        rc = nw == 4 ? c->var.launch_mw4(c->stream, c->dp, Bl, io, live) : nw == 2 ? c->var.launch_mw2(c->stream, c->dp, Bl, io, live) : c->var.launch_1w(c->stream, c->dp, Bl, io, live);
     } else
 #endif
     // (a safe-set lap table, tuning rows: the condensed kernel has no per-problem lookup -- it takes Q pre-digested by the host, cd_hasq -- and is not taken: the kernels below serve them)
-    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune && !c->trk.in_force()) ? c->var.launch_cd(c->stream, c->dp, B, io, c->cd_hasq)
-       : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, B, io)        // fused step: the one-wave kernel runs the regression itself
-       : (B <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, B, io)
-       : (lmpc_solver_waves(c, B) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, B, io) : c->var.launch_1w(c->stream, c->dp, B, io);
+    // (parking: the list comes with io.tune, so the condensed kernel is not taken; Br <= B, so the four-wave launch has nLive <= mw_max_batch on either route)
+    rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune && !c->trk.in_force()) ? c->var.launch_cd(c->stream, c->dp, Bl, io, c->cd_hasq)
+       : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, Bl, io, live)        // fused step: the one-wave kernel runs the regression itself
+       : (Br <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, Bl, io, live)
+       : (lmpc_solver_waves(c, Br) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, Bl, io, live) : c->var.launch_1w(c->stream, c->dp, Bl, io, live);
     ev_end(c);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-    c->stats.n_solve++; if (io.mode & 2) c->stats.qp_solved += B;
-    if (deferred) c->pending.push_back({io, B, io.retry_epoch, c->dp, io.A == c->w.A || io.Bm == c->w.Bm || io.C == c->w.C});
+    c->stats.n_solve++; if (io.mode & 2) c->stats.qp_solved += Bl;
+    if (deferred) c->pending.push_back({io, Bl, io.retry_epoch, c->dp, io.A == c->w.A || io.Bm == c->w.Bm || io.C == c->w.C});
     else if (io.mode & 2) {
-        rc = c->var.launch_retry(c->stream, c->dp, B, io);
+        rc = c->var.launch_retry(c->stream, c->dp, Bl, io, live);
         if (rc) return rc;
         HIPCHK(hipGetLastError());
     }
@@ -1741,6 +1776,12 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
         char msg[128]; snprintf(msg, sizeof(msg), "traced car %d (entry %d of lmpc_rollout_set_trace) but the session has B = %d cars", c->trace_cars[(size_t)k], k, B);
         return set_err(LMPC_E_ARG, "session trace", msg);
     }
+    // the parking in force (lmpc_rollout_set_parking; a PID session is one launch and ignores it): a listed car the session does not have is refused here
+    const bool park = kind != RO_PID && (c->park_mode != 0u || !c->park_cars.empty());
+    if (park) for (size_t k = 0; k < c->park_cars.size(); k++) if (c->park_cars[k] >= B) {
+        char msg[128]; snprintf(msg, sizeof(msg), "parked car %d (entry %d of lmpc_rollout_set_parking) but the session has B = %d cars", c->park_cars[k], (int)k, B);
+        return set_err(LMPC_E_ARG, "session parking", msg);
+    }
     // SS, QSEL and XY of an LMPC session read the selection outputs the step writes only into the capture buffers: a traced session has them, capture or not
     const bool need_sel = c->dbg_capture != 0 || (tn > 0 && S > 0 && (tw & (LMPC_TRACE_SS | LMPC_TRACE_QSEL | LMPC_TRACE_XY)) != 0);
     std::vector<int> lt_rows; bool lt_small = true;             // sessions that run the regression: the lap table in force, one resolved row per car (refused here as well when B is not its row count)
@@ -1761,7 +1802,7 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
     rollout_free(c);
     {
     lmpc_rollout_session *r = new lmpc_rollout_session(); c->ro = r; r->B = B; r->T_max = T_max; r->t = 0; r->pstream = nullptr; r->active = true; r->kind = kind; r->stop_at_line = stop_at_line;
-    r->tr_n = tn; r->tr_what = tw; r->tstream = nullptr;
+    r->tr_n = tn; r->tr_what = tw; r->tstream = nullptr; r->d_live = nullptr;
     if (tn) { HIPCHK(hipStreamCreate(&r->tstream)); HIPCHK(hipEventCreateWithFlags(&r->e_trace, hipEventDisableTiming)); }
     HIPCHK(hipStreamCreate(&r->pstream)); HIPCHK(hipEventCreateWithFlags(&r->e_solved, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&r->e_plant, hipEventDisableTiming));
     bool ok = true;
@@ -1774,7 +1815,7 @@ static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_m
         if (shared)
             r->a.*m = (std::remove_reference_t<decltype(r->a.*m)>)dalloc(elem * n * Bz);
     });
-    DA(double, d_xg, Bz * 6) DA(int, d_done, Bz) DA(int, d_nDone, 1) DA(int, d_stAcc, Bz) DA(double, d_finX, Bz * 6) DA(double, d_finG, Bz * 6)
+    DA(double, d_xg, Bz * 6) DA(int, d_done, Bz) DA(int, d_nDone, 4) DA(int, d_stAcc, Bz) DA(double, d_finX, Bz * 6) DA(double, d_finG, Bz * 6)
     DA(double, d_par, Bz * LMPC_PLANT_NPAR) DA(int, d_lt, Bz * (size_t)std::max(c->cfg.trToUse, 1) * 2)
     if (need_sel) { DA(double, a.ssSel, Bz * S * 6) DA(double, a.qSel, Bz * S) DA(double, a.succ, Bz * S * 6) DA(double, a.succU, Bz * S * 2) }
     DA(double, d_logX, (size_t)T_max * Bz * 6) DA(double, d_logU, (size_t)T_max * Bz * 2) DA(double, d_logG, (size_t)T_max * Bz * 6) DA(double, d_noise, (size_t)T_max * Bz * 3)
@@ -1820,9 +1861,30 @@ init_state:
         H2D(r->d_trCars, c->trace_cars.data(), (size_t)r->tr_n);
         if (r->tr_map) HIPCHK(hipMemsetAsync(r->tr_map, 0, sizeof(int) * (size_t)T_max * (size_t)r->tr_n, c->stream));
     }
-    HIPCHK(hipMemsetAsync(r->d_nDone, 0, sizeof(int), c->stream)); HIPCHK(hipMemsetAsync(r->d_stAcc, 0, sizeof(int) * Bz, c->stream));
+    HIPCHK(hipMemsetAsync(r->d_nDone, 0, sizeof(int) * 4, c->stream)); HIPCHK(hipMemsetAsync(r->d_stAcc, 0, sizeof(int) * Bz, c->stream));
     HIPCHK(hipMemsetAsync(r->d_finX, 0, sizeof(double) * Bz * 6, c->stream)); HIPCHK(hipMemsetAsync(r->d_finG, 0, sizeof(double) * Bz * 6, c->stream));
+    // the snapshot of the parking: lmpc_rollout_set_parking during the session reaches the next one only.  The first live list -- every car but the start list -- is
+    // built by the session's compaction kernel behind the uploads above; its length comes back before the drain that ends the set-up anyway
+    r->parked = park; r->pk_mode = 0u; r->pk_n0 = 0; r->nLive = B; r->nd_host = 0;
+    std::vector<int> flags; int hdr[2] = {0, B};
+    if (park) {
+        r->pk_mode = c->park_mode & (stop_at_line ? ~0u : ~(unsigned)LMPC_PARK_FINISHED);      // (a session that logs its cars past the crossing parks the start list only)
+        r->pk_n0 = (int)c->park_cars.size();
+        if (!r->d_live) {                   // beside the kept set, as the PID noise is: sessions of the same shape reuse the buffers whatever their parking
+            void *q = nullptr;
+            if (g_malloc(&q, sizeof(int) * 3 * Bz) != hipSuccess) { r->active = false; return set_err(LMPC_E_HIP, "hipMalloc", "live list"); }
+            r->keep.push_back(q); r->d_live = (int *)q; r->d_parkedAt = r->d_live + Bz; r->d_park0 = r->d_parkedAt + Bz;
+        }
+        flags.assign(Bz, 0); for (int car : c->park_cars) flags[(size_t)car] = 1;
+        H2D(r->d_park0, flags.data(), Bz);
+        HIPCHK(hipMemsetAsync(r->d_parkedAt, 0xff, sizeof(int) * Bz, c->stream));              // -1: live
+        const lmpc_live_args la = {B, 0, r->pk_mode, 1, r->d_done, r->d_park0, r->d_parkedAt, r->d_live, r->d_nDone};
+        hipLaunchKernelGGL(lmpc_rollout_live_kernel, dim3(1), dim3(LMPC_LIVE_NT), 0, c->stream, la);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hdr, r->d_nDone, sizeof(hdr), hipMemcpyDeviceToHost, c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (park) r->nLive = hdr[1];
     return LMPC_OK;
 }
 static void rollout_state(lmpc_rollout_session *r, lmpc_rollout_state &st) {
@@ -1937,7 +1999,22 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
     lmpc_rollout_state st; rollout_state(r, st);
     int nd = 0, rc = LMPC_OK;
     const int t_end = std::min(r->T_max, r->t + max_steps);
+    // Parking (lmpc_rollout_set_parking): every launch of a step covers the nL entries of the live list instead of the B cars; the list is rebuilt at the
+    // finished-lap poll below.  No live car: nothing to step
+    const bool park = r->parked, reroute = park && (r->pk_mode & LMPC_PARK_REROUTE) != 0;
+    if (park && r->nLive == 0) { if (steps_total) *steps_total = r->t; if (n_done) *n_done = r->nd_host; return LMPC_OK; }
+    if (park) nd = r->nd_host;
+    if (park && !lti && !r->has_lt) {
+        // the regression kernel reads the live list in its table builds: a session without a lap table hands them the block's own laps as ONE row for every car
+        rc = refresh_params(c, true, lmpc, false, false); if (rc) return rc;
+        std::vector<int> row((size_t)c->cfg.trToUse * 2); bool small = true;
+        for (int i = 0; i < c->cfg.trToUse; i++) { row[(size_t)2 * i] = c->dp.mslot[i]; row[(size_t)2 * i + 1] = c->dp.mlen[i]; small = small && c->dp.mlen[i] - 1 <= 8 * WAVE; }
+        HIPCHK(hipMemcpyAsync(r->d_lt, row.data(), sizeof(int) * row.size(), hipMemcpyHostToDevice, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
+        r->lt_small = small;
+    }
     while (r->t < t_end) {
+        const int nL = park ? r->nLive : B;
+        const lmpc_live_list ll = {park ? r->d_live : nullptr, nL};
         lmpc_solve_io io = solve_io(lmpc ? 3 : 2, r->a);
         // the safe-set lap table is live in a session (as lmpc_ss_set_selected is): B against its rows before the first launch of the step
         if (lmpc) { rc = ss_table_for(c, B, &io); if (rc) return rc; }
@@ -1945,15 +2022,15 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         if (!lti) {
         rc = refresh_params(c, true, lmpc, r->has_lt, io.ssTab != nullptr); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
         ev_begin(c, 0);
-        { int qg, nblk; k1_grid(c, B, &qg, &nblk);
-          const k1_table tab = {r->has_lt ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small, r->trk, r->trk_stride};
-          launch_k1(c, nblk, B, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
+        { int qg, nblk; k1_grid(c, nL, &qg, &nblk);
+          const k1_table tab = {(r->has_lt || park) ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small, r->trk, r->trk_stride, ll.car};
+          launch_k1(c, nblk, nL, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
         ev_end(c); c->stats.n_regress++;
         }
         io.rstatus = lti ? nullptr : r->a.rstatus;
         if (r->t > 0) HIPCHK(hipStreamWaitEvent(c->stream, r->e_plant, 0));          // the solve needs the plant's new state
         if (r->t > 0 && r->tr_n && r->tr_own_stream) HIPCHK(hipStreamWaitEvent(c->stream, r->e_trace, 0));   // (traced sessions: and must not overwrite outputs the trace kernel of the last step still reads)
-        rc = launch_solve(c, B, io, true); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
+        rc = launch_solve(c, B, io, true, ll.car, nL, reroute); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
         HIPCHK(hipEventRecord(r->e_solved, c->stream));
         HIPCHK(hipStreamWaitEvent(r->pstream, r->e_solved, 0));
         // the trace of this step: behind the plant kernel on the plant stream, in front of e_plant -- off the solve -> shift -> regression chain of the context's
@@ -1962,6 +2039,10 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         auto launch_trace = [&](hipStream_t on) {
             lmpc_trace_args ta = {r->d_trCars, r->tr_n, (int)N, (int)c->dims.S, r->a.xPred, r->a.uPred, r->a.ssSel, r->a.qSel, r->a.iters, r->a.status,
                                   r->tr_x, r->tr_u, r->tr_ss, r->tr_q, r->tr_xy, r->tr_xys, r->tr_it, r->tr_st, r->tr_map, r->trk, r->trk_stride};
+            if (park) {                                            // (a parked car's planes keep what they held)
+                auto kp = r->trk ? lmpc_rollout_trace_kernel<true, const int *> : lmpc_rollout_trace_kernel<false, const int *>;
+                hipLaunchKernelGGL(kp, dim3(r->tr_n), dim3(LMPC_TRACE_NT), 0, on, c->dp, r->t, ta, (const int *)r->d_parkedAt);
+            } else
             hipLaunchKernelGGL(r->trk ? lmpc_rollout_trace_kernel<true> : lmpc_rollout_trace_kernel<false>, dim3(r->tr_n), dim3(LMPC_TRACE_NT), 0, on, c->dp, r->t, ta);
         };
         if (r->tr_n && r->tr_own_stream) {
@@ -1972,10 +2053,19 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         {
             auto k = r->has_par ? lmpc_rollout_plant_kernel<true> : lmpc_rollout_plant_kernel<false>;
             if (r->trk) k = r->has_par ? lmpc_rollout_plant_kernel<true, true> : lmpc_rollout_plant_kernel<false, true>;
+            if (park) {
+                auto kl = r->trk ? (r->has_par ? lmpc_rollout_plant_kernel<true, true, lmpc_live_list> : lmpc_rollout_plant_kernel<false, true, lmpc_live_list>)
+                                 : (r->has_par ? lmpc_rollout_plant_kernel<true, false, lmpc_live_list> : lmpc_rollout_plant_kernel<false, false, lmpc_live_list>);
+                hipLaunchKernelGGL(kl, dim3((nL + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st, ll);
+            } else
             hipLaunchKernelGGL(k, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
         }
         if (r->tr_n && !r->tr_own_stream) launch_trace(r->pstream);
         HIPCHK(hipEventRecord(r->e_plant, r->pstream));
+        if (park) {
+            if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_live_kernel, dim3((nL * 2 + 255) / 256), dim3(256), 0, c->stream, (int)N, (const double *)r->a.uPred, r->a.uOld, ll);
+            else hipLaunchKernelGGL(lmpc_rollout_shift_live_kernel, dim3((nL * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, r->t, st, ll);
+        } else
         if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->a.uPred, r->a.uOld);
         else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression
         HIPCHK(hipGetLastError());
@@ -1983,6 +2073,20 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         if ((r->t & 7) == 0 || r->t == t_end) {
             HIPCHK(hipStreamSynchronize(r->pstream));
             if (r->tr_n) HIPCHK(hipStreamSynchronize(r->tstream));
+            if (park) {
+                // the plant stream is idle, so doneAt and nDone stand; the compaction kernel (which returns at once unless nDone has moved since the last rebuild)
+                // goes behind the shift on the context's stream, and nLive comes back in the copy that brings nDone: no drain of its own
+                if (r->pk_mode & LMPC_PARK_FINISHED) {
+                    const lmpc_live_args la = {B, r->t, r->pk_mode, 0, r->d_done, r->d_park0, r->d_parkedAt, r->d_live, r->d_nDone};
+                    hipLaunchKernelGGL(lmpc_rollout_live_kernel, dim3(1), dim3(LMPC_LIVE_NT), 0, c->stream, la);
+                    HIPCHK(hipGetLastError());
+                }
+                int hd[2] = {0, 0};
+                HIPCHK(hipMemcpyAsync(hd, r->d_nDone, sizeof(hd), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
+                nd = hd[0]; r->nd_host = nd; r->nLive = hd[1];
+                if (r->nLive == 0 || (r->stop_at_line && nd >= B - r->pk_n0)) break;      // (with a start list only: every car not on it has crossed)
+                continue;
+            }
             HIPCHK(hipMemcpyAsync(&nd, r->d_nDone, sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
             if (nd >= B && r->stop_at_line) break;
         }
@@ -2017,6 +2121,72 @@ int lmpc_rollout_set_trace(lmpc_ctx *c, int n, const int *cars, unsigned what) {
         for (int k = 1; k < n; k++) if (sorted[(size_t)k] == sorted[(size_t)k - 1]) { char msg[64]; snprintf(msg, sizeof(msg), "car %d is listed twice", sorted[(size_t)k]); return set_err(LMPC_E_ARG, "lmpc_rollout_set_trace", msg); }
     }
     c->trace_cars.assign(cars, cars + n); c->trace_what = n ? what : 0u;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_set_parking(lmpc_ctx *c, unsigned mode, int n, const int *cars) {
+    // the cars later sessions park from step 0 and the LMPC_PARK_* bits; everything is checked before anything changes, no device needed.
+    // A car >= B can only be judged by the begin that meets it (rollout_setup)
+    if (!c) return set_err(LMPC_E_ARG, "lmpc_rollout_set_parking", "null context");
+    if (mode & ~(unsigned)(LMPC_PARK_FINISHED | LMPC_PARK_REROUTE)) return set_err(LMPC_E_ARG, "lmpc_rollout_set_parking", "unknown mode bits");
+    if (n < 0 || (n > 0 && !cars)) return set_err(LMPC_E_ARG, "lmpc_rollout_set_parking", n < 0 ? "n is negative" : "n > 0 with NULL cars");
+    if (n > 0) {
+        std::vector<int> sorted(cars, cars + n); std::sort(sorted.begin(), sorted.end());
+        if (sorted[0] < 0) { char msg[64]; snprintf(msg, sizeof(msg), "car %d is negative", sorted[0]); return set_err(LMPC_E_ARG, "lmpc_rollout_set_parking", msg); }
+        for (int k = 1; k < n; k++) if (sorted[(size_t)k] == sorted[(size_t)k - 1]) { char msg[64]; snprintf(msg, sizeof(msg), "car %d is listed twice", sorted[(size_t)k]); return set_err(LMPC_E_ARG, "lmpc_rollout_set_parking", msg); }
+    }
+    if (n > 0) c->park_cars.assign(cars, cars + n); else c->park_cars.clear();
+    c->park_mode = mode;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_get_parking(lmpc_ctx *c, unsigned *mode, int *n, int *cars, int capacity) {
+    ARGCHK(c && capacity >= 0);
+    if (mode) *mode = c->park_mode;
+    if (n) *n = (int)c->park_cars.size();
+    if (cars) for (int k = 0; k < capacity && k < (int)c->park_cars.size(); k++) cars[k] = c->park_cars[(size_t)k];
+    return LMPC_OK;
+}
+
+int lmpc_rollout_parked_at(lmpc_ctx *c, int *at, int *n_live) {
+    // per car of the active session: -1 while it is live, else the first step it was not stepped (its state, log rows and trace planes stand still from there)
+    ARGCHK(c);
+    if (!(c->ro && c->ro->active)) return set_err(LMPC_E_STATE, "lmpc_rollout_parked_at", "no rollout session is active");
+    lmpc_rollout_session *r = c->ro;
+    if (n_live) *n_live = r->parked ? r->nLive : r->B;
+    if (at) {
+        if (r->parked) { HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipMemcpy(at, r->d_parkedAt, sizeof(int) * (size_t)r->B, hipMemcpyDeviceToHost)); }
+        else for (int b = 0; b < r->B; b++) at[b] = -1;
+    }
+    return LMPC_OK;
+}
+
+int lmpc_debug_live_compact(lmpc_ctx *c, int n, const int *doneAt, const int *parked0, int t, unsigned mode, int *live, int *parkedAt, int *n_live) {
+    // (every build) the sessions' compaction kernel on host arrays: doneAt, parked0 (n flags) in; parkedAt (n) in and out -- -1 for a car not parked so far;
+    // live (n: the first n_live entries are written) and n_live out.  One launch, as a session makes it
+    ARGCHK(c && n >= 1 && doneAt && parked0 && live && parkedAt && n_live && t >= 0 && !(mode & ~(unsigned)(LMPC_PARK_FINISHED | LMPC_PARK_REROUTE)));
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t nz = (size_t)n;
+    int *d = nullptr; HIPCHK(g_malloc((void **)&d, sizeof(int) * (4 * nz + 4)));
+    int *d_done = d, *d_p0 = d + nz, *d_at = d + 2 * nz, *d_live = d + 3 * nz, *d_hdr = d + 4 * nz;
+    int hdr[4] = {0, 0, 0, 0};
+    hipError_t e = hipMemcpyAsync(d_done, doneAt, sizeof(int) * nz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_p0, parked0, sizeof(int) * nz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_at, parkedAt, sizeof(int) * nz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_live, 0xff, sizeof(int) * nz, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_hdr, 0, sizeof(int) * 4, c->stream);
+    if (e == hipSuccess) {
+        const lmpc_live_args la = {n, t, mode, 1, d_done, d_p0, d_at, d_live, d_hdr};
+        hipLaunchKernelGGL(lmpc_rollout_live_kernel, dim3(1), dim3(LMPC_LIVE_NT), 0, c->stream, la);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(live, d_live, sizeof(int) * nz, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(parkedAt, d_at, sizeof(int) * nz, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hdr, d_hdr, sizeof(int) * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)g_free(d);
+    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_debug_live_compact", hipGetErrorString(e));
+    *n_live = hdr[1];
     return LMPC_OK;
 }
 

@@ -17,7 +17,7 @@
 #include "../../include/lmpc_hip.h"
 
 #define WAVE 64
-#define LMPC_VARIANT_ABI_REV 10         // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
+#define LMPC_VARIANT_ABI_REV 11         // bumped whenever lmpc_dev_params / lmpc_solve_io / the variant table change; the value a variant library is asked for
                                         // (LMPC_VARIANT_ABI, lmpc_variant.hip.h) also folds in the three struct sizes, so that layout drift cannot pass on the number alone
 #define LMPC_COLS 9                 // lap-store columns: x0..x5, u0, u1, Qfun
 
@@ -670,6 +670,13 @@ __device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &
 
 // OCC: compile for four waves per SIMD (two work-groups per CU; <= 128 VGPRs) -- pays when the grid exceeds one work-group
 // per CU (1.47x at batch 4096); the other variant has the shorter latency when each CU runs a single group.
+// Parking (lmpc_rollout_set_parking, lmpc_live.hip.h): the regression, plant, trace and runtime-(N, S) kernels take the ascending list of the cars still stepped as a TRAILING PARAMETER PACK,
+// `LIVE... lv`, which is either empty or one lmpc_live_list.  Empty -- every launch outside a parking session -- the kernel has the signature, the argument layout and
+// the text it had before there was a list, hence its machine code (profiles/parking_kernel_diff.txt).  With a list the launch covers lv.n entries and entry j stands for
+// car lv.car[j]; every array stays indexed by car.
+struct lmpc_live_list { const int *car; int n; };
+__device__ __forceinline__ lmpc_live_list live_list_of() { return {nullptr, 0}; }
+__device__ __forceinline__ lmpc_live_list live_list_of(lmpc_live_list l) { return l; }
 // TAB: every problem names its own laps (k1_lap_slot): lapTab holds (slot, rows) pairs, trToUse per row, and problem b reads the row at lapTab + b * tabStride
 // (tabStride = 0: one row for every problem).  The TAB = false builds take neither argument into account.
 // (The table build of the 8-rows-per-lane occupancy kernel is compiled for five waves per SIMD, not six: the 80 registers of six cost its twin seven spilled
@@ -678,12 +685,12 @@ __device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &
 #ifndef LMPC_K1_TAB_WAVES8
 #define LMPC_K1_TAB_WAVES8 5
 #endif
-template <bool OCC, int RPL, bool TAB = false>
+template <bool OCC, int RPL, bool TAB = false, class... LIVE>
 __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 : 6) : 4) : 2) void lmpc_regress_kernel(lmpc_dev_params p, int B, int qg, const double *__restrict__ xLin, int xstride,
                                                              const double *__restrict__ uLin, double *__restrict__ Aout,
                                                              double *__restrict__ Bout, double *__restrict__ Cout, int *__restrict__ status,
                                                              const int *__restrict__ lapTab, int tabStride,
-                                                             const double *__restrict__ trk, int trkStride) {      // trk: per-problem tracks (lmpc_track_set), or null: the parameter block's; see k1_fit
+                                                             const double *__restrict__ trk, int trkStride, LIVE... lv) {      // trk: per-problem tracks (lmpc_track_set), or null: the parameter block's; see k1_fit.  lv: parking, B entries (above)
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);             // wave-uniform by construction: lap pointers, row counts and loop bounds stay in SGPRs
     __shared__ double qf[K1_QG][5];
@@ -704,8 +711,10 @@ __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 
     const int MAXP = p.maxNumPoint > 8 ? 8 : p.maxNumPoint;
     const int QGe = k1_queries_per_block(qg, L, p.maxNumPoint);            // queries of this block
     const int npass = (N + QGe - 1) / QGe;
-    const int b = blockIdx.x / npass;
-    if (b >= B) return;
+    int b_ = blockIdx.x / npass;
+    if (b_ >= B) return;
+    if constexpr (sizeof...(LIVE) > 0) b_ = live_list_of(lv...).car[b_];
+    const int b = b_;
     const int nsub = K1_NW / L > 0 ? K1_NW / L : 1;                        // waves sharing one lap split its queries
     const int myc = wave % L, sgi = wave / L;
     const int i0 = (blockIdx.x % npass) * QGe;
@@ -1349,13 +1358,13 @@ __device__ __forceinline__ int term_factor7(const double *Wl, double *Ri, int la
 
 #include "lmpc_solve_common.hip.h"   // lmpc_solve_io, the step rules, the selection K2, and what else the solve-kernel families share around the Newton iteration
 
-template <int N, int S, bool EQ = false, bool ABG = false, bool TAB = false>
+template <int N, int S, bool EQ = false, bool ABG = false, bool TAB = false, class... LIVE>      // LIVE: empty, or lmpc_live_list -- a parking session, work-group j solves problem lv.car[j]; with TAB only
 // (two waves per SIMD -- at most 256 registers -- only where the LDS footprint lets more than four QPs share a CU and the terminal
 // block keeps one column per lane)
 #ifdef LMPC_AB_OCC3     // (developer A / B, tools/resource_usage.py: what a third resident wave per SIMD -- at most 168 registers -- would cost this kernel; profiles/r6_onewave_occ3_resource_usage.txt)
-__global__ __launch_bounds__(WAVE, 3) void lmpc_solve_kernel(lmpc_dev_params p, int B, lmpc_solve_io io) {
+__global__ __launch_bounds__(WAVE, 3) void lmpc_solve_kernel(lmpc_dev_params p, int B, lmpc_solve_io io, LIVE... lv) {
 #else
-__global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 1024 && solve_lds1<N, S, ABG>::CH == 1) ? 2 : 1) void lmpc_solve_kernel(lmpc_dev_params p, int B, lmpc_solve_io io) {
+__global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 1024 && solve_lds1<N, S, ABG>::CH == 1) ? 2 : 1) void lmpc_solve_kernel(lmpc_dev_params p, int B, lmpc_solve_io io, LIVE... lv) {
 #endif
     extern __shared__ double sm[];
     using LL = solve_lds1<N, S, ABG>;
@@ -1363,8 +1372,10 @@ __global__ __launch_bounds__(WAVE, (solve_lds1<N, S, ABG>::tot * 8 * 5 <= 160 * 
     constexpr bool term = S > 0;
     constexpr int RPL = (M + WAVE - 1) / WAVE;              // inequality rows per lane
     constexpr int CH = LL::CH;                              // terminal-block columns per lane (1 for numSS_points <= 58)
-    const int b = blockIdx.x;
-    if (b >= B) return;
+    int b_ = blockIdx.x;
+    if (b_ >= B) return;
+    if constexpr (sizeof...(LIVE) > 0) b_ = __builtin_amdgcn_readfirstlane(live_list_of(lv...).car[b_]);      // (parking: entry b_ of the live list, wave-uniform: kept in an SGPR)
+    const int b = b_;
     // retry variant (EQ): only problems that hit the iteration limit (or broke down numerically far from the optimum) run again,
     // with equal primal / dual steps throughout and a neighbourhood safeguard on the step length
     if constexpr (EQ) { if (!(io.status[b] & (LMPC_ST_MAXITER | LMPC_ST_NUMERIC))) return; }
@@ -2345,11 +2356,39 @@ __global__ __launch_bounds__(256) void lmpc_rollout_shift_kernel(lmpc_dev_params
     }
     if (e == 0) { r.hasPred[b] = 1; r.timeStep[b] = t + 1; }
 }
-template <bool PAR, bool TRK = false>
-__global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_params p, int B, int t, lmpc_rollout_state r) {
+// The same for a parking session: ll.n entries of the live list, entry j the car ll.car[j].  (A kernel of its own, the text above once more: as a template over the list
+// the plain kernel did not keep its machine code -- 180 instructions for 187 -- and the plain kernel is what every un-parked session runs.)
+__global__ __launch_bounds__(256) void lmpc_rollout_shift_live_kernel(lmpc_dev_params p, int t, lmpc_rollout_state r, lmpc_live_list ll) {
+    const int N = p.N, tpr = LMPC_SHIFT_TPR(N);
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, j = tid / tpr, e = tid - j * tpr;
+    if (j >= ll.n) return;
+    const int b = ll.car[j];
+    const int row = e >> 3, col = e & 7;
+    const double *uP = r.uPred + (size_t)b * N * 2, *xP = r.xPred + (size_t)b * (N + 1) * 6;
+    double *xl = r.xLin + (size_t)b * (N + 1) * 6, *ul = r.uLin + (size_t)b * N * 2, *xpp = r.xPP + (size_t)b * (N + 1) * 6;
+    if (col < 6) {
+        const double v = xP[row * 6 + col];
+        xpp[row * 6 + col] = v;
+        if (row >= 1) xl[(row - 1) * 6 + col] = v;
+        if (row == N) { const double z = r.ztNext[(size_t)b * 6 + col]; xl[N * 6 + col] = z; r.zt[(size_t)b * 6 + col] = z; }
+    } else {
+        const int c = col - 6;
+        if (row >= 1 && row < N) ul[(row - 1) * 2 + c] = uP[row * 2 + c];
+        if (row == N) ul[(N - 1) * 2 + c] = r.ztuNext[(size_t)b * 2 + c];
+        if (row == 0) r.uOld[(size_t)b * 2 + c] = uP[c];
+    }
+    if (e == 0) { r.hasPred[b] = 1; r.timeStep[b] = t + 1; }
+}
+// (parking: the grid covers lv.n entries of the live list, 32 per work-group; lanes past lv.n keep repeating the last entry for the barriers, as they repeat car B - 1
+//  without a list; B stays the stride of the logs and of the noise)
+template <bool PAR, bool TRK = false, class... LIVE>
+__global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_params p, int B, int t, lmpc_rollout_state r, LIVE... lv) {
     __shared__ plant_lds L;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, cl = lane >> 1, role = lane & 1;     // two waves per 32 cars, see plant_step_duo
-    const int b0 = blockIdx.x * PLANT_CARS + cl; const bool on = b0 < B; const int b = on ? b0 : B - 1;
+    const int b0 = blockIdx.x * PLANT_CARS + cl; bool on_; int b_;
+    if constexpr (sizeof...(LIVE) > 0) { const lmpc_live_list ll = live_list_of(lv...); on_ = b0 < ll.n; b_ = ll.car[on_ ? b0 : ll.n - 1]; }
+    else { on_ = b0 < B; b_ = on_ ? b0 : B - 1; }
+    const bool on = on_; const int b = b_;
     const int N = p.N;
     double *x = r.x + (size_t)b * 6, *xg = r.xg + (size_t)b * 6;
     const double *uP = r.uPred + (size_t)b * N * 2;
@@ -2380,6 +2419,11 @@ __global__ __launch_bounds__(PLANT_NT) void lmpc_rollout_plant_kernel(lmpc_dev_p
 __global__ __launch_bounds__(256) void lmpc_rollout_oldinput_kernel(int B, int N, const double *__restrict__ uPred, double *__restrict__ uOld) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < B * 2) uOld[e] = uPred[(size_t)(e >> 1) * N * 2 + (e & 1)];
+}
+// (a parking session: ll.n entries of the live list; a kernel of its own for the reason given at lmpc_rollout_shift_live_kernel)
+__global__ __launch_bounds__(256) void lmpc_rollout_oldinput_live_kernel(int N, const double *__restrict__ uPred, double *__restrict__ uOld, lmpc_live_list ll) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < ll.n * 2) { const size_t b = (size_t)ll.car[e >> 1]; uOld[b * 2 + (e & 1)] = uPred[b * N * 2 + (e & 1)]; }
 }
 
 // Whole PID laps in ONE launch (main.py:61-70: Simulator.sim driven by Utilities.PID.solve, Utilities.py:60-67).  There is no QP between two steps, so the

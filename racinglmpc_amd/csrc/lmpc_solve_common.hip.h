@@ -46,6 +46,9 @@ struct lmpc_solve_io {
     const double *trk;        // optional: per-problem tracks (lmpc_track_set), the device image of the rows (LMPC_TRACK_NPAR doubles each; [1] is the trackLength the selection reads).
     int trkStride;            // Served by the per-problem-rows instantiations (the host sets io.tune with it); doubles between rows (0: one row serves every problem)
 };
+// Parking: the solve kernels take the live list as a trailing parameter pack BESIDE lmpc_solve_io (lmpc_live_list, lmpc_kernels.hip.h), and lmpc_solve_io keeps its
+// layout -- grown by a pointer, the two- and four-wave per-problem-rows kernels came out with other scalar loads and registers although no line of theirs read it.
+// With the pack empty a kernel is the kernel it was: its prologue keeps the text it had, the lookup stands behind it under `if constexpr`.
 #define LMPC_SSTAB_ENTRY 4
 // With a table the selection keeps (slot, rows) of every selected lap for the successor rows of feasibleStateInput, beside sel_start: in LMPC_SSTAB_LDS bytes of
 // dynamic LDS behind the kernel's layout, which the launchers add only when io.ssTab is set -- a launch without a table has the footprint it always had.
@@ -143,7 +146,10 @@ __device__ __forceinline__ void stage_params(const lmpc_dev_params &p, double *p
 // <N_, S_, NW, TAB_>: the fixed-(N, S) kernels hand in their template constants, and the instantiation is the text it was when N, S and TAB were the template's
 // own parameters (same machine code).  N_ = 0: N and S come from the parameter block; TAB_ < 0: a table or none is found out at run time (the runtime kernel).
 // ------------------------------------------------------------------------------------------------
-template <int N_, int S_, int NW, int TAB_ = 0>
+// TAG: nothing in the function reads it.  The parking instantiation of a two- or four-wave kernel hands in its LIVE pack, so that it has a k2_select of its own: with
+// ONE instance inlined into both the per-problem-rows kernel and its parking sibling, the per-problem-rows kernel came out with other scalar registers than it has
+// alone (measured on all 44 of them; profiles/parking_kernel_diff.txt is taken with the tag).
+template <int N_, int S_, int NW, int TAB_ = 0, class... TAG>
 __device__ __forceinline__ void k2_select(const lmpc_dev_params &p, const lmpc_solve_io &io, int b, int lane, int wave, double *SS, double *Qsel,
                                           int *sel_start, int *sel_lap, int *st_sh) {
     const int N = N_ ? N_ : p.N, S = N_ ? S_ : p.S;

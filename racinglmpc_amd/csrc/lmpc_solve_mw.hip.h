@@ -26,11 +26,11 @@
 #define TSMW(id) do { } while (0)
 #endif
 
-template <int N, int S, int NW, bool TAB = false>
+template <int N, int S, int NW, bool TAB = false, class... LIVE>      // LIVE: empty, or lmpc_live_list -- a parking session, work-group j solves problem lv.car[j]; with TAB only
 // (registers: four waves per QP = one wave per SIMD; two waves per QP = two waves per SIMD only where the LDS footprint lets three or more
 // QPs share a CU -- long horizons keep their sweep operands (3 N doubles per lane) in registers and need the full file: at N = 40 the
 // 256-register build spilled 221 VGPRs to scratch)
-__global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 > 160 * 1024 || solve_lds<N, S>::CH > 1) ? 1 : 2) void lmpc_solve_kernel_mw(lmpc_dev_params p, int B, lmpc_solve_io io) {
+__global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 > 160 * 1024 || solve_lds<N, S>::CH > 1) ? 1 : 2) void lmpc_solve_kernel_mw(lmpc_dev_params p, int B, lmpc_solve_io io, LIVE... lv) {
     static_assert(NW == 2 || NW == 4, "wave 0 runs the sequential recursions, waves 1 .. NW-1 everything that can run beside them");
     constexpr bool BCF = true;                              // bound_ctrl cross-lane moves (dpp_mv) in every reduction: the EXEC mask is full there (lmpc_debug_exec_audit)
     extern __shared__ double sm[];
@@ -40,8 +40,10 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
     constexpr int NT = WAVE * NW;
     constexpr bool ROWS_OFF_W0 = S > 0 && S <= WAVE && NT >= 8 * N + WAVE && SWEEP_BF<N>;     // wave 0 owns the lambda rows and nothing else (see slot_row; the four-wave kernel: the other rows fit threads 64 .. 255)
     constexpr int RPL = ((ROWS_OFF_W0 ? 8 * N + WAVE : M) + NT - 1) / NT;           // inequality rows per thread
-    const int b = blockIdx.x;
-    if (b >= B) return;
+    int b_ = blockIdx.x;
+    if (b_ >= B) return;
+    if constexpr (sizeof...(LIVE) > 0) b_ = __builtin_amdgcn_readfirstlane(live_list_of(lv...).car[b_]);      // (parking: entry b_ of the live list, wave-uniform: kept in an SGPR)
+    const int b = b_;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction: tests on it are scalar branches, not exec-mask regions with a v_cmp each
     const int lg = lane >> 3, lc = lane & 7;
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
 
     // K2: safe-set selection, one lap per wave (k2_select, lmpc_solve_common.hip.h), then the regression status bits of this problem
     if constexpr (term) {
-        k2_select<N, S, NW, TAB>(p, io, b, lane, wave, SS, Qsel, sel_start, sel_lap, &st_sh); __syncthreads();
+        k2_select<N, S, NW, TAB, LIVE...>(p, io, b, lane, wave, SS, Qsel, sel_start, sel_lap, &st_sh); __syncthreads();
         if (tid < 6) { double v = 0.0; for (int c = 0; c < S; c++) v += SS[tid * S + c]; ss_rowsum[tid] = v; }
     }
     if (io.rstatus && tid < N) { const int rs_ = io.rstatus[(size_t)b * N + tid]; if (rs_) atomicOr(&st_sh, rs_); }

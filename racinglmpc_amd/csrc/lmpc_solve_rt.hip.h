@@ -39,11 +39,15 @@ __host__ __device__ inline rt_lds rt_layout(int N, int S) {
 #define RT_FOR(i, n) for (int i = lane; i < (n); i += WAVE)
 
 // EQ: the retry pass (equal primal / dual steps, neighbourhood safeguard), as in lmpc_solve_kernel<N, S, true>
-template <bool EQ>
-__global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, int B, lmpc_solve_io io) {
+// LIVE: empty, or lmpc_live_list: a parking session, work-group j solves problem lv.car[j] -- an instantiation of its own, so that
+// every other launch runs the kernel it ran before
+template <bool EQ, class... LIVE>
+__global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, int B, lmpc_solve_io io, LIVE... lv) {
     extern __shared__ double sm[];
-    const int b = blockIdx.x;
-    if (b >= B) return;
+    int b_ = blockIdx.x;
+    if (b_ >= B) return;
+    if constexpr (sizeof...(LIVE) > 0) b_ = __builtin_amdgcn_readfirstlane(live_list_of(lv...).car[b_]);      // (parking: entry b_ of the live list, wave-uniform: kept in an SGPR)
+    const int b = b_;
     if constexpr (EQ) { if (!(io.status[b] & (LMPC_ST_MAXITER | LMPC_ST_NUMERIC))) return; }
     const int lane = threadIdx.x;
     const int N = p.N, S = p.S, M = 8 * N + S;
@@ -426,8 +430,14 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
 #undef RT_FOR
 
 // launchers of the runtime kernel (the table of lmpc_variant.hip.h is filled by lmpc_variant_fill_rt there): one wave per QP on every route
-static int lmpc_rt_launch(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-    hipLaunchKernelGGL((lmpc_solve_kernel_rt<false>), dim3(B), dim3(WAVE), (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0), st, p, B, io); return 0; }
-static int lmpc_rt_launch_retry(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-    hipLaunchKernelGGL((lmpc_solve_kernel_rt<true>), dim3(B), dim3(WAVE), (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0), st, p, B, io); return 0; }
-static int lmpc_rt_launch_cd(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int) { return lmpc_rt_launch(st, p, B, io); }
+static int lmpc_rt_launch(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
+    const size_t lds = (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0);
+    if (live) hipLaunchKernelGGL((lmpc_solve_kernel_rt<false, lmpc_live_list>), dim3(B), dim3(WAVE), lds, st, p, B, io, lmpc_live_list{live, B});
+    else hipLaunchKernelGGL((lmpc_solve_kernel_rt<false>), dim3(B), dim3(WAVE), lds, st, p, B, io);
+    return 0; }
+static int lmpc_rt_launch_retry(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
+    const size_t lds = (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0);
+    if (live) hipLaunchKernelGGL((lmpc_solve_kernel_rt<true, lmpc_live_list>), dim3(B), dim3(WAVE), lds, st, p, B, io, lmpc_live_list{live, B});
+    else hipLaunchKernelGGL((lmpc_solve_kernel_rt<true>), dim3(B), dim3(WAVE), lds, st, p, B, io);
+    return 0; }
+static int lmpc_rt_launch_cd(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int) { return lmpc_rt_launch(st, p, B, io, nullptr); }

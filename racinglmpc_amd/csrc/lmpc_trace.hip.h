@@ -21,10 +21,13 @@ struct lmpc_trace_args {
 };
 
 // TRK: car cars[k] maps its points on its own track row (lmpc_track_set), as the plant kernels integrate it there.
-template <bool TRK>
-__global__ __launch_bounds__(LMPC_TRACE_NT) void lmpc_rollout_trace_kernel(lmpc_dev_params p_, int t, lmpc_trace_args a) {
+// PARKED: empty, or (a parking session, lmpc_live.hip.h) one `const int *parkedAt` over all B cars -- a listed car with parkedAt >= 0 returns at once: its outputs are no
+// longer written, and its planes keep what they held.  Empty, the kernel is the one it was (signature, argument layout, text).
+template <bool TRK, class... PARKED>
+__global__ __launch_bounds__(LMPC_TRACE_NT) void lmpc_rollout_trace_kernel(lmpc_dev_params p_, int t, lmpc_trace_args a, PARKED... parkedAt) {
     const int k = blockIdx.x;
     const size_t b = (size_t)a.cars[k], row = (size_t)t * (size_t)a.n + (size_t)k;
+    if constexpr (sizeof...(PARKED) > 0) { if ((parkedAt[b], ...) >= 0) return; }
     const int nx = (a.N + 1) * 6, nu = a.N * 2, ns = a.S * 6, nq = a.S;
     const int e1 = a.oX ? nx : 0, e2 = e1 + (a.oU ? nu : 0), e3 = e2 + (a.oSS ? ns : 0), e4 = e3 + (a.oQ ? nq : 0), e5 = e4 + (a.oIt ? 2 : 0);
     for (int e = threadIdx.x; e < e5; e += LMPC_TRACE_NT) {

@@ -18,10 +18,10 @@
 struct lmpc_variant_api {
     int N, S;
     size_t lds_mw, lds_1w;                    // dynamic LDS per QP: multi-wave kernels / one-wave kernels
-    int (*launch_1w)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &);      // lmpc_solve_kernel<N,S>
-    int (*launch_retry)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &);   // lmpc_solve_kernel<N,S,true>
-    int (*launch_mw4)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &);     // lmpc_solve_kernel_mw<N,S,4>
-    int (*launch_mw2)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &);     // lmpc_solve_kernel_mw<N,S,2>
+    int (*launch_1w)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &, const int *live);      // lmpc_solve_kernel<N,S>
+    int (*launch_retry)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &, const int *live);   // lmpc_solve_kernel<N,S,true>
+    int (*launch_mw4)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &, const int *live);     // lmpc_solve_kernel_mw<N,S,4>
+    int (*launch_mw2)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &, const int *live);     // lmpc_solve_kernel_mw<N,S,2>
     size_t lds_1w_abg;                        // one-wave kernel with [A_k | B_k] in global memory (long horizons): dynamic LDS per QP; 0 = not used for this (N, S)
     size_t lds_cd;                            // condensed one-wave kernel (lmpc_solve_cd.hip.h): dynamic LDS per QP without the state-cost block; 0 = not built for this (N, S)
     size_t lds_cd_q;                          //   ... with it (Q or Qf non-zero)
@@ -37,8 +37,12 @@ static_assert(sizeof(lmpc_dev_params) < 4096 && sizeof(lmpc_solve_io) < 1024, "b
 // One kernel, its plain and its TAB instantiation: a launch with per-problem rows -- safe-set laps (io.ssTab), controller tuning (lmpc_tuning_set), or both; the
 // host sets io.tune for every such launch (lmpc_capi.hip, launch_solve) -- takes the second, with LMPC_SSTAB_LDS bytes behind `lds` for the (slot, rows) of the
 // selected laps.  (S = 0 has the TAB instantiations for the tuning rows alone: no table there, lmpc_capi.hip, ss_table_for.)
-template <class K> static int lmpc_launch_pair(K plain, K tab, int threads, size_t lds, hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
+// kl / live: the parking instantiation of the same kernel and the list it takes beside io (B entries; per-problem rows as well, the host sets io.tune with the list) --
+// an instantiation of its own, so that `plain` and `tab` are the kernels they were for every launch outside a parking session.  (`live`: the last argument of the
+// launchers of lmpc_variant_api, null outside a parking session.)
+template <class K, class KL> static int lmpc_launch_pair(K plain, K tab, KL kl, int threads, size_t lds, hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
     const bool t = io.tune != nullptr;
+    if (live) { hipLaunchKernelGGL(kl, dim3(B), dim3(threads), lds + LMPC_SSTAB_LDS, st, p, B, io, lmpc_live_list{live, B}); return 0; }
     const K kernel = t ? tab : plain;
     hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds + (t ? LMPC_SSTAB_LDS : 0), st, p, B, io);
     return 0;
@@ -92,27 +96,31 @@ template <int N, int S> struct lmpc_variant_launchers {
             {(const void *)lmpc_solve_kernel<N, S, false, use_abg>, lds1g, use_abg},         {(const void *)lmpc_solve_kernel<N, S, false, use_abg, has_tab>, lds1g + LMPC_SSTAB_LDS, use_abg && has_tab},
             {(const void *)lmpc_solve_kernel_mw<N, S, 4>, ldsm, true},                       {(const void *)lmpc_solve_kernel_mw<N, S, 4, has_tab>, ldsm + LMPC_SSTAB_LDS, has_tab},
             {(const void *)lmpc_solve_kernel_mw<N, S, 2>, ldsm, true},                       {(const void *)lmpc_solve_kernel_mw<N, S, 2, has_tab>, ldsm + LMPC_SSTAB_LDS, has_tab},
+            // the parking instantiations (LIVE)
+            {(const void *)lmpc_solve_kernel<N, S, false, false, true, lmpc_live_list>, lds1_max(), true}, {(const void *)lmpc_solve_kernel<N, S, true, false, true, lmpc_live_list>, lds1_max(), true},
+            {(const void *)lmpc_solve_kernel<N, S, false, use_abg, true, lmpc_live_list>, lds1g + LMPC_SSTAB_LDS, use_abg},
+            {(const void *)lmpc_solve_kernel_mw<N, S, 4, true, lmpc_live_list>, ldsm + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_mw<N, S, 2, true, lmpc_live_list>, ldsm + LMPC_SSTAB_LDS, true},
             {cd_kernel(), lds_cd(true), has_cd},
         };
         return lmpc_raise_lds_limits(k);
     }
 
-    static int l1(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
+    static int l1(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
         if constexpr (use_abg) {
-            if (!(io.mode & 4) && io.abPack) return lmpc_launch_pair(lmpc_solve_kernel<N, S, false, true>, lmpc_solve_kernel<N, S, false, true, has_tab>, WAVE, lds1g, st, p, B, io);
+            if (!(io.mode & 4) && io.abPack) return lmpc_launch_pair(lmpc_solve_kernel<N, S, false, true>, lmpc_solve_kernel<N, S, false, true, has_tab>, lmpc_solve_kernel<N, S, false, true, true, lmpc_live_list>, WAVE, lds1g, st, p, B, io, live);
         }
-        return lmpc_launch_pair(lmpc_solve_kernel<N, S>, lmpc_solve_kernel<N, S, false, false, has_tab>, WAVE, lds_for(p, io), st, p, B, io); }
-    static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        return lmpc_launch_pair(lmpc_solve_kernel<N, S, true>, lmpc_solve_kernel<N, S, true, false, has_tab>, WAVE, lds_for(p, io), st, p, B, io); }
-    static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 4>, lmpc_solve_kernel_mw<N, S, 4, has_tab>, WAVE * 4, ldsm, st, p, B, io); }
-    static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io) {
-        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 2>, lmpc_solve_kernel_mw<N, S, 2, has_tab>, WAVE * 2, ldsm, st, p, B, io); }
+        return lmpc_launch_pair(lmpc_solve_kernel<N, S>, lmpc_solve_kernel<N, S, false, false, has_tab>, lmpc_solve_kernel<N, S, false, false, true, lmpc_live_list>, WAVE, lds_for(p, io), st, p, B, io, live); }
+    static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
+        return lmpc_launch_pair(lmpc_solve_kernel<N, S, true>, lmpc_solve_kernel<N, S, true, false, has_tab>, lmpc_solve_kernel<N, S, true, false, true, lmpc_live_list>, WAVE, lds_for(p, io), st, p, B, io, live); }
+    static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
+        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 4>, lmpc_solve_kernel_mw<N, S, 4, has_tab>, lmpc_solve_kernel_mw<N, S, 4, true, lmpc_live_list>, WAVE * 4, ldsm, st, p, B, io, live); }
+    static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
+        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 2>, lmpc_solve_kernel_mw<N, S, 2, has_tab>, lmpc_solve_kernel_mw<N, S, 2, true, lmpc_live_list>, WAVE * 2, ldsm, st, p, B, io, live); }
     static int lc(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int hasQ) {
 #ifdef LMPC_WITH_CD
         if constexpr (has_cd) { hipLaunchKernelGGL((lmpc_solve_kernel_cd<N, S>), dim3(B), dim3(WAVE), lds_cd(hasQ), st, p, B, io, hasQ); return 0; }
 #endif
-        (void)hasQ; return l1(st, p, B, io);
+        (void)hasQ; return l1(st, p, B, io, nullptr);
     }
 };
 
@@ -136,7 +144,8 @@ static bool lmpc_variant_fill_rt(lmpc_variant_api *v, int N, int S) {
     if (N < 2 || N > LMPC_MAX_N || S < 0 || S > LMPC_MAX_SS_POINTS) return false;
     const size_t lds = (size_t)rt_layout(N, S).tot * sizeof(double);
     if (lds + 1024 > (size_t)160 * 1024) return false;
-    const lmpc_kernel_lds k[] = {{(const void *)lmpc_solve_kernel_rt<false>, lds + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_rt<true>, lds + LMPC_SSTAB_LDS, true}};
+    const lmpc_kernel_lds k[] = {{(const void *)lmpc_solve_kernel_rt<false>, lds + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_rt<true>, lds + LMPC_SSTAB_LDS, true},
+                                 {(const void *)lmpc_solve_kernel_rt<false, lmpc_live_list>, lds + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_rt<true, lmpc_live_list>, lds + LMPC_SSTAB_LDS, true}};
     if (!lmpc_raise_lds_limits(k)) return false;
     v->N = N; v->S = S; v->lds_mw = 0; v->lds_1w = lds; v->lds_1w_abg = 0; v->lds_cd = 0; v->lds_cd_q = 0; v->occ_mw2 = 0;
     v->launch_1w = &lmpc_rt_launch; v->launch_retry = &lmpc_rt_launch_retry; v->launch_mw4 = &lmpc_rt_launch; v->launch_mw2 = &lmpc_rt_launch; v->launch_cd = &lmpc_rt_launch_cd;

@@ -19,7 +19,7 @@ from . import _capi, parallel
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set, or (ss_table) each car against its own (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None, tracks=None, trace=None, trace_what=None):
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None, tracks=None, trace=None, trace_what=None, park=None):
         """trace / trace_what: the cars of THIS object whose controller output every LMPC / MPC session records step by step, and the planes (_capi.TRACE_* bits; None:
         every plane the context can record) -- the reference's xStoredPredTraj / uStoredPredTraj / SSStoredPredTraj (PredictiveControllers.py:364-379) with the
         Q-values, the solver's words and the inertial positions beside them (Context.rollout_set_trace); handed to the context before every begin and run_mpc_laps,
@@ -70,6 +70,13 @@ class BatchedRollouts:
         self.tuning = None if tuning is None else _capi.check_tuning(tuning, ctx.cfg.numSS_it)
         self.trace = None if trace is None else _capi.check_trace(trace, trace_what, ctx.cfg.numSS_it)
         self.last_trace = None
+        # park: the parking of every LMPC / MPC session of this object (Context.rollout_set_parking) -- True (PARK_FINISHED: a car leaves the launches once it has
+        # crossed the line, and a session that stops at the line ends when no car is live), a mode of _capi.PARK_* bits, or (mode, cars) with the cars parked from
+        # step 0.  Handed to the context before every begin and run_mpc_laps, where the trace is; run_lap_device, run_mpc_laps and PerCarLMPC.run then leave the
+        # session's parking steps in `last_parked_at` (Context.rollout_parked_at: -1 for a car stepped to the end; a parked car's log rows stand still from its
+        # step on).  None: the context's parking is left as it is and last_parked_at stays None.
+        self.park = self._check_park(park)
+        self.last_parked_at = None
         self.device_noise = bool(device_noise)
         if self.device_noise:
             import operator
@@ -208,6 +215,31 @@ class BatchedRollouts:
             raise ValueError("trace: car %d listed, the session has %d cars" % (int(cars.max()), B))
         self.ctx.rollout_set_trace(cars, what)
 
+    @staticmethod
+    def _check_park(park):
+        if park is None:
+            return None
+        if isinstance(park, (tuple, list)):
+            if len(park) != 2:
+                raise ValueError("park: True, a mode, or (mode, cars) expected")
+            return _capi.check_parking(park[0], park[1])
+        return _capi.check_parking(park, None)
+
+    def _apply_park(self, B):
+        """The parking of this object goes to the context in front of a session that solves."""
+        pk = getattr(self, "park", None)               # (objects built without __init__ have none)
+        if pk is None:
+            return
+        mode, cars = pk
+        if cars.size and int(cars.max()) >= B:
+            raise ValueError("park: car %d listed, the session has %d cars" % (int(cars.max()), B))
+        self.ctx.rollout_set_parking(mode, cars)
+
+    def _fetch_parked(self):
+        """last_parked_at of the active session, to be called before rollout_end."""
+        self.last_parked_at = None if getattr(self, "park", None) is None else self.ctx.rollout_parked_at()[0]
+        return self.last_parked_at
+
     def _fetch_trace(self, t, done):
         """last_trace of the active session, to be called before rollout_end: the planes of steps [0, t) and the listed cars' crossing steps."""
         tr = getattr(self, "trace", None)
@@ -230,6 +262,7 @@ class BatchedRollouts:
         noise = self._draw_noise(max_steps, B)
         self._apply_rows(B, ("tracks", "plant_params", "lap_table", "ss_table", "tuning"))
         self._apply_trace(B)
+        self._apply_park(B)
         if self._device_noise_session(B):
             self.ctx.rollout_begin(x0, x0 if xglob0 is None else xglob0, xl, ul, None, T_max=max_steps)
         else:
@@ -251,6 +284,7 @@ class BatchedRollouts:
         t, nd = self.ctx.rollout_run(max_steps)
         X, U, G, done, st, fx, fg = self.ctx.rollout_fetch(0, t)
         self._fetch_trace(t, done)
+        self._fetch_parked()
         self.ctx.rollout_end()
         self.last_status, self.last_done = st, done
         laps = []
@@ -301,6 +335,7 @@ class BatchedRollouts:
         noise = self._draw_noise(max_steps, nb)
         self._apply_rows(nb, ("tracks", "plant_params") + (("lap_table",) if A is None else ()) + ("tuning",))      # (the LTI form runs no regression)
         self._apply_trace(nb)
+        self._apply_park(nb)
         kw = dict(T_max=max_steps) if self._device_noise_session(nb) else {}       # (noise is None then: the session's buffer is filled on the device)
         if A is not None:
             self.ctx.rollout_begin_mpc(x0, x0, noise, A=A, B=B, stop_at_line=stop_at_line, **kw)
@@ -309,6 +344,7 @@ class BatchedRollouts:
         t, _ = self.ctx.rollout_run(max_steps)
         out = self.ctx.rollout_fetch(0, t)
         self._fetch_trace(t, out[3])
+        self._fetch_parked()
         self.ctx.rollout_end()
         return self._collect(nb, *out, whole=not stop_at_line, keep_invalid=keep_invalid)
 
@@ -666,13 +702,22 @@ class PerCarLMPC:
     and without device_commit -- TraceView(track, car, traces) is one car's history as the reference's plots read an LMPC object.
     Tracks: with BatchedRollouts(tracks=) holding one track per car, car b drives, regresses and selects on its own track; its start state is its crossing state
     shifted by its OWN TrackLength, and its laps and extensions are stored with track_row = b (Context.ss_add_trajectory / ss_extend_lap, or the device commit, which
-    takes the car's row by itself)."""
+    takes the car's row by itself).
+    park=True: every generation begins with the retired cars parked from step 0 and _capi.PARK_FINISHED set (Context.rollout_set_parking), with and without
+    device_commit: a retired car is no longer solved, a car that has crossed the line leaves the launches at the next poll, and the session ends when no car is
+    live instead of at T_max.  Stores, histories, tables, `last`, lap_times, `retired` and the returned tuples come out as without it; `steps[g]` -- the session steps
+    generation g took -- is what differs.  (A lap that crosses the line within the first `ext` steps, whose extension rows a parked car no longer logs, is refused.)
+    park=_capi.PARK_REROUTE adds that bit: the solve route then follows the live count, and another route answers to the routes' bound (2e-7 in x, u), not bit for
+    bit -- the laps are no longer promised equal to those without parking.  The rollouts object's own `park` is put back after every generation."""
 
     EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
 
-    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None, trace=None, trace_what=None):
+    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None, trace=None, trace_what=None, park=False):
         self.ro, self.T_max, self.ext = rollouts, int(T_max), int(ext)
         self.device_commit = bool(device_commit)
+        self.park = bool(park)             # True, or _capi.PARK_* bits to go with PARK_FINISHED (PARK_REROUTE)
+        self.park_mode = _capi.check_parking(_capi.PARK_FINISHED | (0 if park is True or not park else int(park)), None)[0]
+        self.steps = []                    # session steps of each generation (T_max or the last crossing's poll without park)
         if trace is not None:              # (the cars whose predictions every generation records: what BatchedRollouts(trace=) takes)
             self.ro.trace = _capi.check_trace(trace, trace_what, self.ro.ctx.cfg.numSS_it)
         self.traces = []                   # one entry per generation run with a trace: the rollouts object's last_trace of that session
@@ -736,12 +781,23 @@ class PerCarLMPC:
         """One generation; returns the lap tuples (x, u, x_glob, final12, done_at, status) of every car, None for a retired one."""
         if self.B is None:
             raise RuntimeError("PerCarLMPC.run before seed")
+        if not self.park:
+            return self._run()
+        own = getattr(self.ro, "park", None)          # (the retired cars are this loop's business: other sessions of the rollouts object keep its own setting)
+        try:
+            return self._run()
+        finally:
+            self.ro.park = own
+
+    def _run(self):
         ro, ctx, B, N = self.ro, self.ro.ctx, self.B, self.ro.ctx.N
         gen = self.generation
         fin = np.stack([self.latest[b][2] for b in range(B)])
         x0 = fin[:, 0:6].copy(); x0[:, 4] -= ro.track_lengths(B) if getattr(ro, "tracks", None) is not None else ro.TL   # xF = x_cl[-1] - [0,0,0,0,TrackLength_b,0]: each car's own track
         xg0 = fin[:, 6:12].copy()
         xl = np.stack([self.latest[b][0][1:N + 2] for b in range(B)]); ul = np.stack([self.latest[b][1][1:N + 1] for b in range(B)])
+        if self.park:                      # (the retired cars keep their slots and are not stepped; the rollouts object hands this to the context in begin)
+            ro.park = _capi.check_parking(self.park_mode, sorted(self.retired))
         ro.begin(x0, xl, ul, xg0, self.T_max)
         if self.device_commit:
             return self._finish_on_device(gen)
@@ -750,9 +806,12 @@ class PerCarLMPC:
                 t, _ = ctx.rollout_run(self.ext)
                 X, U, G, done, st, fx, fg = ctx.rollout_fetch(0, t)
                 n = min(t, self.ext)
+                at = ctx.rollout_parked_at()[0] if self.park else None
                 for b in range(B):
                     if b in self.retired or not self.latest[b][3]:
                         continue
+                    if at is not None and 0 <= at[b] < n:      # (the device path: rollout_extend_laps refuses the same rows)
+                        raise ValueError("PerCarLMPC(park=True): car %d was parked at step %d, inside the %d extension rows" % (b, int(at[b]), n))
                     clean = n > 0 and (int(st[b]) & ~_capi.ST_INEXACT) == 0 and bool(np.all(np.isfinite(X[:n, b]))) and bool(np.all(np.isfinite(U[:n, b])))
                     if not clean:
                         self.retired[b] = (gen, int(st[b]) | self.EXT_SKIPPED)
@@ -765,9 +824,11 @@ class PerCarLMPC:
             X, U, G, done, st, fx, fg = ctx.rollout_fetch(0, t)
             if ro._fetch_trace(t, done) is not None:
                 self.traces.append(ro.last_trace)
+            ro._fetch_parked()
         finally:
             ctx.rollout_end()
         self.last_status, self.last_done = st, done
+        self.steps.append(int(t))
         out = [None] * B
         for b in range(B):
             if b in self.retired:
@@ -815,6 +876,7 @@ class PerCarLMPC:
             Xh, Uh = ctx.rollout_fetch(0, min(t, N + 2))[:2]
             if ro._fetch_trace(t, done) is not None:
                 self.traces.append(ro.last_trace)
+            ro._fetch_parked()
             valid = []
             for b in range(B):
                 if b in self.retired:
@@ -827,6 +889,7 @@ class PerCarLMPC:
         finally:
             ctx.rollout_end()
         self.last_status, self.last_done = st, done
+        self.steps.append(int(t))
         out = [None] * B
         for k, b in enumerate(valid):
             T, idx = int(done[b]), first + k

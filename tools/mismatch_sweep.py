@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--horizon", type=int, default=12)
     ap.add_argument("--own-model", action="store_true", help="also the LMPC lap with each car's regression laps taken from its own PID lap (nominal safe set)")
+    ap.add_argument("--park", action="store_true", help="parking (BatchedRollouts(park=True)): a car that has crossed the line leaves the launches of the LMPC lap; same laps")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mismatch_sweep.json"))
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -64,7 +65,7 @@ def main():
     cfg, _ = common.lmpc_config(g, N, max_batch=B)
     ctx = _capi.Context(cfg)
     rollout.seed_lmpc(ctx, seed_laps)
-    ro = rollout.BatchedRollouts(ctx, g["track"], seed=args.seed + 2, plant_params=rows)
+    ro = rollout.BatchedRollouts(ctx, g["track"], seed=args.seed + 2, plant_params=rows, park=True if args.park else None)
     x0 = np.tile(np.array([0.5, 0, 0, 0, 0, 0.0]), (B, 1))
     lmpc = ro.run_lap_device(x0, seed_laps[0][0][1:N + 2], seed_laps[0][1][1:N + 1], max_steps=400, keep_invalid=True)
     ro.close(); ctx.close()
@@ -83,7 +84,7 @@ def main():
                 table[b] = len(seed_laps) + b
             else:
                 fallback += 1
-        ro = rollout.BatchedRollouts(ctx, g["track"], seed=args.seed + 2, plant_params=rows, lap_table=table)       # (the seed of the lap above: the same disturbance)
+        ro = rollout.BatchedRollouts(ctx, g["track"], seed=args.seed + 2, plant_params=rows, lap_table=table, park=True if args.park else None)       # (the seed of the lap above: the same disturbance)
         own = ro.run_lap_device(x0, seed_laps[0][0][1:N + 2], seed_laps[0][1][1:N + 1], max_steps=400, keep_invalid=True)
         ro.close(); ctx.close()
     ps, ls = cell_stats(pid, cells, len(grid)), cell_stats(lmpc, cells, len(grid))

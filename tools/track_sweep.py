@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--vt", type=float, default=0.8, help="target speed of the PID and MPC stages (main.py:50)")
     ap.add_argument("--horizon", type=int, default=12)
+    ap.add_argument("--park", action="store_true", help="parking (PerCarLMPC(park=True)): retired cars are not stepped, finished cars leave the launches, a generation ends when no car is live; same lap times")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "per_car_tracks.json"))
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -47,7 +48,7 @@ def main():
     cfg, _ = common.lmpc_config(g, N, max_batch=B, max_laps=max(16, B * (G + 1)), max_lap_len=1024)
     with _capi.Context(cfg) as ctx:
         ro = rollout.BatchedRollouts(ctx, g["track"], seed=args.seed, device_noise=True, tracks=tables)
-        loop = rollout.PerCarLMPC(ro, T_max=400, ext=40, device_commit=True)
+        loop = rollout.PerCarLMPC(ro, T_max=400, ext=40, device_commit=True, park=args.park)
         loop.seed(boot["pid"])
         status = []
         for _ in range(G):
@@ -57,6 +58,7 @@ def main():
         loop.close()
     result["lap_steps"] = [t + [None] * (G - len(t)) for t in loop.lap_times]
     result["status_per_generation"] = status
+    result["park"] = bool(args.park); result["session_steps"] = list(loop.steps)
     result["retired"] = {str(b): list(v) for b, v in sorted(loop.retired.items())}
     result["per_track"] = {n: dict(pid=[result["bootstrap"]["pid"]["crossing_steps"][b] for b in range(B) if names[b] == n],
                                    ltvmpc=[result["bootstrap"]["ltvmpc"]["crossing_steps"][b] for b in range(B) if names[b] == n],

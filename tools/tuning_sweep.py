@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--generations", type=int, default=3)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--horizon", type=int, default=12)
+    ap.add_argument("--park", action="store_true", help="parking (PerCarLMPC(park=True)): retired cars are not stepped, finished cars leave the launches, a generation ends when no car is live; same lap times")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tuning_sweep.json"))
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -48,7 +49,7 @@ def main():
         bad = [b for b, l in enumerate(pid) if l[4] < 0 or (l[5] & ~_capi.ST_INEXACT) != 0 or not np.all(np.isfinite(l[0]))]
         if bad:
             raise SystemExit("PID lap of car(s) %s did not finish or was flagged: no seed lap" % bad)
-        loop = rollout.PerCarLMPC(ro, T_max=400, ext=40, device_commit=True, tuning=rows)
+        loop = rollout.PerCarLMPC(ro, T_max=400, ext=40, device_commit=True, tuning=rows, park=args.park)
         loop.seed(pid)
         status = []
         for _ in range(G):
@@ -59,6 +60,7 @@ def main():
     result["pid_lap_steps"] = [int(l[4]) for l in pid]
     result["lap_steps"] = [t + [None] * (G - len(t)) for t in loop.lap_times]
     result["status_per_generation"] = status
+    result["park"] = bool(args.park); result["session_steps"] = list(loop.steps)
     result["retired"] = {str(b): list(v) for b, v in sorted(loop.retired.items())}
     print("%-4s %-8s %-8s %-8s %-6s | %s" % ("car", "Qslack1", "dR1", "Qterm x", "PID", "LMPC lap steps"))
     for b, (a, d, c) in enumerate(grid):
