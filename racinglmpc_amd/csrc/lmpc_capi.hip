@@ -9,6 +9,7 @@
 #include "lmpc_live.hip.h"
 #include "lmpc_arrays.h"
 #include "lmpc_rows.h"
+#include "lmpc_pick.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <algorithm>
@@ -1036,11 +1037,11 @@ static void k1_grid(lmpc_ctx *c, int B, int *qg, int *nblk) {
 // 8-rows-per-lane scan when every lap in use lies inside its first quantisation chunk half (<= 512 rows; k1_scan_lap).
 // The lap table a regression launch reads: the context's (k1_table_for) or a rollout session's snapshot.  dev == nullptr: none, the laps of the parameter block.
 // trk / trkStride: the per-problem tracks of the same launch (lmpc_track_set; null: the parameter block's track)
-// live: parking -- the launch covers B entries of that list (table builds only: a parking session without a lap table hands in the block's own laps as a one-row table)
-struct k1_table { const int *dev; int stride; bool small; const double *trk; int trkStride; const int *live; };      // live != null needs dev != null
+// ll: parking -- the launch covers the B entries of that list (table builds only: a parking session without a lap table hands in the block's own laps as a one-row table)
+struct k1_table { const int *dev; int stride; bool small; const double *trk; int trkStride; lmpc_live_list ll; };      // ll.car != null needs dev != null
 // the context's table for a call of B problems (B points for lmpc_regress_points): one row serves all, else row b belongs to problem b and the counts must agree
 static int k1_table_for(lmpc_ctx *c, int B, k1_table *t) {
-    t->dev = nullptr; t->stride = 0; t->small = true; t->live = nullptr;
+    t->dev = nullptr; t->stride = 0; t->small = true; t->ll = {};
     { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; t->trk = ts.dev; t->trkStride = ts.stride; }
     if (!c->lt.in_force()) return LMPC_OK;
     RCCHK(rows_fit(c->lt, B, LMPC_ROWS_EXACT, "problems", "lap table"));
@@ -1053,15 +1054,13 @@ static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, 
     else for (int i = 0; i < c->cfg.trToUse; i++) small = small && c->dp.mlen[i] - 1 <= 8 * WAVE;
     if (c->k1_force16) small = false;                                    // (LMPC_K1_RPL16 at lmpc_create: A / B of the two scan builds, tests/test_gpu_configs.py)
     const bool occ = nblk > c->n_cu;
-    auto k = occ ? (small ? lmpc_regress_kernel<true, 8> : lmpc_regress_kernel<true, K1_RPL>) : (small ? lmpc_regress_kernel<false, 8> : lmpc_regress_kernel<false, K1_RPL>);
-    if (t.dev) k = occ ? (small ? lmpc_regress_kernel<true, 8, true> : lmpc_regress_kernel<true, K1_RPL, true>) : (small ? lmpc_regress_kernel<false, 8, true> : lmpc_regress_kernel<false, K1_RPL, true>);
-    if (t.dev && t.live) {                                               // a parking session: the table builds with the live list (B entries of it)
-        auto kl = occ ? (small ? lmpc_regress_kernel<true, 8, true, lmpc_live_list> : lmpc_regress_kernel<true, K1_RPL, true, lmpc_live_list>)
-                      : (small ? lmpc_regress_kernel<false, 8, true, lmpc_live_list> : lmpc_regress_kernel<false, K1_RPL, true, lmpc_live_list>);
-        hipLaunchKernelGGL(kl, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride, lmpc_live_list{t.live, B});
-        return;
-    }
-    hipLaunchKernelGGL(k, dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin, dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride);
+    lmpc_pick([&](auto OCC, auto SMALL, auto TAB, auto LIVE) {
+        constexpr bool o = OCC, tab = TAB; constexpr int rpl = SMALL ? 8 : K1_RPL;
+        auto go = [&](auto... lv) { hipLaunchKernelGGL((lmpc_regress_kernel<o, rpl, tab, decltype(lv)...>), dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin,
+                                                       dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride, lv...); };
+        if constexpr (!LIVE) go();
+        else if constexpr (tab) go(t.ll);                              // a parking session: the table builds with the live list (its B entries)
+    }, occ, small, t.dev != nullptr, t.dev && t.ll.car);
 }
 static int launch_regress(lmpc_ctx *c, int B, const double *d_xLin, int xstride, const double *d_uLin, double *dA, double *dB, double *dC, int *dst) {
     int rc = refresh_params(c, true, false, c->lt.in_force()); if (rc) return rc;
@@ -1157,18 +1156,18 @@ static int tuning_upload(lmpc_ctx *c, int n, const double *rows) {
     HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     return image_upload(&c->img[IMG_TUNE], img.data(), img.size() * sizeof(double), "hipMemcpy (tuning image)");
 }
-// live / nLive (parking sessions): the live list and its entries -- what the kernels are launched over; B stays the session's batch, which the per-car rows are
-// checked against and the abPack scratch is sized for.  reroute (LMPC_PARK_REROUTE): the route (waves per QP) follows nLive instead of B.  The choice between [A_k | B_k] in
+// ll (parking sessions; ll.car null: none): the live list and its entries -- what the kernels are launched over; B stays the session's batch, which the per-car rows are
+// checked against and the abPack scratch is sized for.  reroute (LMPC_PARK_REROUTE): the route (waves per QP) follows ll.n instead of B.  The choice between [A_k | B_k] in
 // LDS and in the abPack scratch (long horizons) stays with B on either route: a rerouted one-wave launch at N = 40 may take the global-memory build where a session of
 // nLive cars would not -- same QP answer to the routes' bound, not the same kernel
-static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false, const int *live = nullptr, int nLive = -1, bool reroute = false) {
+static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false, lmpc_live_list ll = {}, bool reroute = false) {
     lmpc_solve_io io = io_in;
-    const int Bl = live ? nLive : B, Br = (live && reroute) ? nLive : B;      // problems launched; the batch the route is chosen for
+    const int Bl = ll.car ? ll.n : B, Br = (ll.car && reroute) ? ll.n : B;      // problems launched; the batch the route is chosen for
     if (!io.ssTab) { const int rc = ss_table_for(c, B, &io); if (rc) return rc; }
     if (!io.tune) { const int rc = tuning_for(c, B, &io); if (rc) return rc; }
     // (per-problem tracks, lmpc_track_set: the selection reads the problem's TrackLength; B against the rows)
     if (!io.trk && (io.mode & 1)) { trk_src ts; const int rc = track_for(c, B, &ts); if (rc) return rc; io.trk = ts.dev; io.trkStride = ts.stride; }
-    if ((io.ssTab || io.trk || live) && !io.tune) { io.tune = (const double *)c->img[IMG_TUNE].p; io.tuneStride = 0; }      // (a table or tracks alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
+    if ((io.ssTab || io.trk || ll.car) && !io.tune) { io.tune = (const double *)c->img[IMG_TUNE].p; io.tuneStride = 0; }      // (a table or tracks alone: the per-problem-rows kernels stage the config's own row -- or, selecting only, read none)
     // [A_k | B_k] from global memory only when the batch does not fit the CUs with it in LDS (N = 40: more than two QPs per CU); a batch that
     // fits runs 3 % faster from LDS (measured at N = 40, batch 512: 0.997 vs 1.030 ms)
     io.abPack = nullptr;
@@ -1198,22 +1197,22 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
 #ifdef LMPC_DEV_FAST
     if (const char *f = dev_knob("LMPC_FORCE_NW")) {
         const int nw = atoi(f);
-        rc = nw == 4 ? c->var.launch_mw4(c->stream, c->dp, Bl, io, live) : nw == 2 ? c->var.launch_mw2(c->stream, c->dp, Bl, io, live) : c->var.launch_1w(c->stream, c->dp, Bl, io, live);
+        rc = nw == 4 ? c->var.launch_mw4(c->stream, c->dp, Bl, io, ll.car) : nw == 2 ? c->var.launch_mw2(c->stream, c->dp, Bl, io, ll.car) : c->var.launch_1w(c->stream, c->dp, Bl, io, ll.car);
     } else
 #endif
     // (a safe-set lap table, tuning rows: the condensed kernel has no per-problem lookup -- it takes Q pre-digested by the host, cd_hasq -- and is not taken: the kernels below serve them)
     // (parking: the list comes with io.tune, so the condensed kernel is not taken; Br <= B, so the four-wave launch has nLive <= mw_max_batch on either route)
     rc = (c->cd_ok && c->cd_mode == 1 && !(io.mode & 4) && !io.tune && !c->trk.in_force()) ? c->var.launch_cd(c->stream, c->dp, Bl, io, c->cd_hasq)
-       : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, Bl, io, live)        // fused step: the one-wave kernel runs the regression itself
-       : (Br <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, Bl, io, live)
-       : (lmpc_solver_waves(c, Br) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, Bl, io, live) : c->var.launch_1w(c->stream, c->dp, Bl, io, live);
+       : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, Bl, io, ll.car)        // fused step: the one-wave kernel runs the regression itself
+       : (Br <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, Bl, io, ll.car)
+       : (lmpc_solver_waves(c, Br) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, Bl, io, ll.car) : c->var.launch_1w(c->stream, c->dp, Bl, io, ll.car);
     ev_end(c);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     c->stats.n_solve++; if (io.mode & 2) c->stats.qp_solved += Bl;
     if (deferred) c->pending.push_back({io, Bl, io.retry_epoch, c->dp, io.A == c->w.A || io.Bm == c->w.Bm || io.C == c->w.C});
     else if (io.mode & 2) {
-        rc = c->var.launch_retry(c->stream, c->dp, Bl, io, live);
+        rc = c->var.launch_retry(c->stream, c->dp, Bl, io, ll.car);
         if (rc) return rc;
         HIPCHK(hipGetLastError());
     }
@@ -1659,9 +1658,8 @@ int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg,
         H2D(dp, rows.data(), rows.size());                            // (`rows` lives until the stream is drained below)
     }
     const double *kp = par ? dp : nullptr;
-    auto k = par ? lmpc_plant_kernel<true> : lmpc_plant_kernel<false>;
-    if (ts.dev) k = par ? lmpc_plant_kernel<true, true> : lmpc_plant_kernel<false, true>;
-    hipLaunchKernelGGL(k, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds, kp, ts.dev, ts.stride);
+    lmpc_pick([&](auto PAR, auto TRK) { hipLaunchKernelGGL((lmpc_plant_kernel<PAR, TRK>), grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, dx, dg, du, dn, dxn, dgn, ds, kp, ts.dev, ts.stride); },
+              par, ts.dev != nullptr);
     HIPCHK(hipGetLastError());
     D2H(xn, dxn, (size_t)B * 6); D2H(xgn, dgn, (size_t)B * 6); D2H(status, ds, B);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1967,11 +1965,9 @@ int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const doub
     if (e != hipSuccess) return fail(set_err(LMPC_E_HIP, "lmpc_rollout_pid", hipGetErrorString(e)));
     lmpc_rollout_state st; rollout_state(r, st);
     const dim3 grid((B + PLANT_CARS - 1) / PLANT_CARS);
-    {
-        auto k = r->has_par ? lmpc_pid_rollout_kernel<true> : lmpc_pid_rollout_kernel<false>;
-        if (r->trk) k = r->has_par ? lmpc_pid_rollout_kernel<true, true> : lmpc_pid_rollout_kernel<false, true>;
-        hipLaunchKernelGGL(k, grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0, (const double *)r->d_vt, (const double *)r->d_noiseU, st);
-    }
+    lmpc_pick([&](auto PAR, auto TRK) {
+        hipLaunchKernelGGL((lmpc_pid_rollout_kernel<PAR, TRK>), grid, dim3(PLANT_NT), 0, c->stream, c->dp, B, T_max, stop_at_line ? 1 : 0, (const double *)r->d_vt, (const double *)r->d_noiseU, st);
+    }, r->has_par, r->trk != nullptr);
     e = hipGetLastError();
     std::vector<int> done(Bz);
     if (e == hipSuccess) e = hipMemcpyAsync(done.data(), r->d_done, sizeof(int) * Bz, hipMemcpyDeviceToHost, c->stream);
@@ -1983,6 +1979,36 @@ int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const doub
     if (steps_total) *steps_total = r->t;
     if (n_done) *n_done = nd;
     return LMPC_OK;
+}
+
+// The launches of a session step over the live list ll.  ll.car == nullptr: a session without parking -- the grids cover ll.n = B cars, the kernels are the ones without a list
+static void launch_rollout_plant(lmpc_ctx *c, lmpc_rollout_session *r, const lmpc_rollout_state &st, lmpc_live_list ll) {
+    const dim3 grid((ll.n + PLANT_CARS - 1) / PLANT_CARS);
+    lmpc_pick([&](auto PAR, auto TRK, auto LIVE) {
+        constexpr bool par = PAR, trk = TRK;
+        auto go = [&](auto... lv) { hipLaunchKernelGGL((lmpc_rollout_plant_kernel<par, trk, decltype(lv)...>), grid, dim3(PLANT_NT), 0, r->pstream, c->dp, r->B, r->t, st, lv...); };
+        if constexpr (LIVE) go(ll); else go();
+    }, r->has_par, r->trk != nullptr, ll.car != nullptr);
+}
+static void launch_rollout_trace(lmpc_ctx *c, lmpc_rollout_session *r, hipStream_t on, lmpc_live_list ll) {      // (a parking session hands in parkedAt: a parked car's planes keep what they held)
+    lmpc_trace_args ta = {r->d_trCars, r->tr_n, c->cfg.N, (int)c->dims.S, r->a.xPred, r->a.uPred, r->a.ssSel, r->a.qSel, r->a.iters, r->a.status,
+                          r->tr_x, r->tr_u, r->tr_ss, r->tr_q, r->tr_xy, r->tr_xys, r->tr_it, r->tr_st, r->tr_map, r->trk, r->trk_stride};
+    lmpc_pick([&](auto TRK, auto PARKED) {
+        constexpr bool trk = TRK;
+        auto go = [&](auto... at) { hipLaunchKernelGGL((lmpc_rollout_trace_kernel<trk, decltype(at)...>), dim3(r->tr_n), dim3(LMPC_TRACE_NT), 0, on, c->dp, r->t, ta, at...); };
+        if constexpr (PARKED) go((const int *)r->d_parkedAt); else go();
+    }, r->trk != nullptr, ll.car != nullptr);
+}
+// (the shift and old-input kernels keep a parking twin each: DESIGN.md, "Shipped kernels keep their machine code")
+static void launch_rollout_shift(lmpc_ctx *c, lmpc_rollout_session *r, const lmpc_rollout_state &st, lmpc_live_list ll) {
+    const dim3 grid((ll.n * LMPC_SHIFT_TPR(c->cfg.N) + 255) / 256);
+    if (ll.car) hipLaunchKernelGGL(lmpc_rollout_shift_live_kernel, grid, dim3(256), 0, c->stream, c->dp, r->t, st, ll);
+    else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, grid, dim3(256), 0, c->stream, c->dp, r->B, r->t, st);
+}
+static void launch_rollout_oldinput(lmpc_ctx *c, lmpc_rollout_session *r, lmpc_live_list ll) {
+    const dim3 grid((ll.n * 2 + 255) / 256);
+    if (ll.car) hipLaunchKernelGGL(lmpc_rollout_oldinput_live_kernel, grid, dim3(256), 0, c->stream, c->cfg.N, (const double *)r->a.uPred, r->a.uOld, ll);
+    else hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, grid, dim3(256), 0, c->stream, r->B, c->cfg.N, (const double *)r->a.uPred, r->a.uOld);
 }
 
 int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) {
@@ -2012,9 +2038,8 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         HIPCHK(hipMemcpyAsync(r->d_lt, row.data(), sizeof(int) * row.size(), hipMemcpyHostToDevice, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
         r->lt_small = small;
     }
+    lmpc_live_list ll = {park ? r->d_live : nullptr, r->nLive};      // (a session without parking: nLive = B)
     while (r->t < t_end) {
-        const int nL = park ? r->nLive : B;
-        const lmpc_live_list ll = {park ? r->d_live : nullptr, nL};
         lmpc_solve_io io = solve_io(lmpc ? 3 : 2, r->a);
         // the safe-set lap table is live in a session (as lmpc_ss_set_selected is): B against its rows before the first launch of the step
         if (lmpc) { rc = ss_table_for(c, B, &io); if (rc) return rc; }
@@ -2022,73 +2047,46 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         if (!lti) {
         rc = refresh_params(c, true, lmpc, r->has_lt, io.ssTab != nullptr); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
         ev_begin(c, 0);
-        { int qg, nblk; k1_grid(c, nL, &qg, &nblk);
-          const k1_table tab = {(r->has_lt || park) ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small, r->trk, r->trk_stride, ll.car};
-          launch_k1(c, nblk, nL, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
+        { int qg, nblk; k1_grid(c, ll.n, &qg, &nblk);
+          const k1_table tab = {(r->has_lt || ll.car) ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small, r->trk, r->trk_stride, ll};
+          launch_k1(c, nblk, ll.n, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
         ev_end(c); c->stats.n_regress++;
         }
         io.rstatus = lti ? nullptr : r->a.rstatus;
         if (r->t > 0) HIPCHK(hipStreamWaitEvent(c->stream, r->e_plant, 0));          // the solve needs the plant's new state
         if (r->t > 0 && r->tr_n && r->tr_own_stream) HIPCHK(hipStreamWaitEvent(c->stream, r->e_trace, 0));   // (traced sessions: and must not overwrite outputs the trace kernel of the last step still reads)
-        rc = launch_solve(c, B, io, true, ll.car, nL, reroute); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
+        rc = launch_solve(c, B, io, true, ll, reroute); if (rc) return rc;      // (the plant consumes uPred without a host round trip: unconditional retry pass)
         HIPCHK(hipEventRecord(r->e_solved, c->stream));
         HIPCHK(hipStreamWaitEvent(r->pstream, r->e_solved, 0));
         // the trace of this step: behind the plant kernel on the plant stream, in front of e_plant -- off the solve -> shift -> regression chain of the context's
         // stream, and the one event the next solve waits for anyway covers it.  (LMPC_TRACE_OWN_STREAM=1: on a stream of its own beside the plant, with an event of its
         // own for the next solve -- measured slower, DESIGN.md "Session traces")
-        auto launch_trace = [&](hipStream_t on) {
-            lmpc_trace_args ta = {r->d_trCars, r->tr_n, (int)N, (int)c->dims.S, r->a.xPred, r->a.uPred, r->a.ssSel, r->a.qSel, r->a.iters, r->a.status,
-                                  r->tr_x, r->tr_u, r->tr_ss, r->tr_q, r->tr_xy, r->tr_xys, r->tr_it, r->tr_st, r->tr_map, r->trk, r->trk_stride};
-            if (park) {                                            // (a parked car's planes keep what they held)
-                auto kp = r->trk ? lmpc_rollout_trace_kernel<true, const int *> : lmpc_rollout_trace_kernel<false, const int *>;
-                hipLaunchKernelGGL(kp, dim3(r->tr_n), dim3(LMPC_TRACE_NT), 0, on, c->dp, r->t, ta, (const int *)r->d_parkedAt);
-            } else
-            hipLaunchKernelGGL(r->trk ? lmpc_rollout_trace_kernel<true> : lmpc_rollout_trace_kernel<false>, dim3(r->tr_n), dim3(LMPC_TRACE_NT), 0, on, c->dp, r->t, ta);
-        };
         if (r->tr_n && r->tr_own_stream) {
             HIPCHK(hipStreamWaitEvent(r->tstream, r->e_solved, 0));
-            launch_trace(r->tstream);
+            launch_rollout_trace(c, r, r->tstream, ll);
             HIPCHK(hipEventRecord(r->e_trace, r->tstream));
         }
-        {
-            auto k = r->has_par ? lmpc_rollout_plant_kernel<true> : lmpc_rollout_plant_kernel<false>;
-            if (r->trk) k = r->has_par ? lmpc_rollout_plant_kernel<true, true> : lmpc_rollout_plant_kernel<false, true>;
-            if (park) {
-                auto kl = r->trk ? (r->has_par ? lmpc_rollout_plant_kernel<true, true, lmpc_live_list> : lmpc_rollout_plant_kernel<false, true, lmpc_live_list>)
-                                 : (r->has_par ? lmpc_rollout_plant_kernel<true, false, lmpc_live_list> : lmpc_rollout_plant_kernel<false, false, lmpc_live_list>);
-                hipLaunchKernelGGL(kl, dim3((nL + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st, ll);
-            } else
-            hipLaunchKernelGGL(k, dim3((B + PLANT_CARS - 1) / PLANT_CARS), dim3(PLANT_NT), 0, r->pstream, c->dp, B, r->t, st);
-        }
-        if (r->tr_n && !r->tr_own_stream) launch_trace(r->pstream);
+        launch_rollout_plant(c, r, st, ll);
+        if (r->tr_n && !r->tr_own_stream) launch_rollout_trace(c, r, r->pstream, ll);
         HIPCHK(hipEventRecord(r->e_plant, r->pstream));
-        if (park) {
-            if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_live_kernel, dim3((nL * 2 + 255) / 256), dim3(256), 0, c->stream, (int)N, (const double *)r->a.uPred, r->a.uOld, ll);
-            else hipLaunchKernelGGL(lmpc_rollout_shift_live_kernel, dim3((nL * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, r->t, st, ll);
-        } else
-        if (lti) hipLaunchKernelGGL(lmpc_rollout_oldinput_kernel, dim3((B * 2 + 255) / 256), dim3(256), 0, c->stream, B, (int)N, (const double *)r->a.uPred, r->a.uOld);
-        else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, dim3((B * LMPC_SHIFT_TPR((int)N) + 255) / 256), dim3(256), 0, c->stream, c->dp, B, r->t, st);   // then the next step's regression
+        if (lti) launch_rollout_oldinput(c, r, ll); else launch_rollout_shift(c, r, st, ll);      // then the next step's regression
         HIPCHK(hipGetLastError());
         r->t++;
         if ((r->t & 7) == 0 || r->t == t_end) {
             HIPCHK(hipStreamSynchronize(r->pstream));
             if (r->tr_n) HIPCHK(hipStreamSynchronize(r->tstream));
-            if (park) {
-                // the plant stream is idle, so doneAt and nDone stand; the compaction kernel (which returns at once unless nDone has moved since the last rebuild)
-                // goes behind the shift on the context's stream, and nLive comes back in the copy that brings nDone: no drain of its own
-                if (r->pk_mode & LMPC_PARK_FINISHED) {
-                    const lmpc_live_args la = {B, r->t, r->pk_mode, 0, r->d_done, r->d_park0, r->d_parkedAt, r->d_live, r->d_nDone};
-                    hipLaunchKernelGGL(lmpc_rollout_live_kernel, dim3(1), dim3(LMPC_LIVE_NT), 0, c->stream, la);
-                    HIPCHK(hipGetLastError());
-                }
-                int hd[2] = {0, 0};
-                HIPCHK(hipMemcpyAsync(hd, r->d_nDone, sizeof(hd), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-                nd = hd[0]; r->nd_host = nd; r->nLive = hd[1];
-                if (r->nLive == 0 || (r->stop_at_line && nd >= B - r->pk_n0)) break;      // (with a start list only: every car not on it has crossed)
-                continue;
+            // Parking: the plant stream is idle, so doneAt and nDone stand; the compaction kernel (which returns at once unless nDone has moved since the last rebuild)
+            // goes behind the shift on the context's stream, and nLive comes back in the copy that brings nDone: no drain of its own
+            if (park && (r->pk_mode & LMPC_PARK_FINISHED)) {
+                const lmpc_live_args la = {B, r->t, r->pk_mode, 0, r->d_done, r->d_park0, r->d_parkedAt, r->d_live, r->d_nDone};
+                hipLaunchKernelGGL(lmpc_rollout_live_kernel, dim3(1), dim3(LMPC_LIVE_NT), 0, c->stream, la);
+                HIPCHK(hipGetLastError());
             }
-            HIPCHK(hipMemcpyAsync(&nd, r->d_nDone, sizeof(int), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-            if (nd >= B && r->stop_at_line) break;
+            int hd[2] = {0, 0};                                        // nDone, nLive (the second: parking sessions only)
+            HIPCHK(hipMemcpyAsync(hd, r->d_nDone, sizeof(hd), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
+            nd = hd[0]; r->nd_host = nd;
+            if (park) ll.n = r->nLive = hd[1];
+            if (r->nLive == 0 || (r->stop_at_line && nd >= B - r->pk_n0)) break;      // (with a start list only: every car not on it has crossed; pk_n0 = 0 without parking)
         }
     }
     if (steps_total) *steps_total = r->t;

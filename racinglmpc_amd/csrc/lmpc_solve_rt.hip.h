@@ -429,15 +429,11 @@ __global__ __launch_bounds__(WAVE) void lmpc_solve_kernel_rt(lmpc_dev_params p, 
 #undef RT_SYNC
 #undef RT_FOR
 
-// launchers of the runtime kernel (the table of lmpc_variant.hip.h is filled by lmpc_variant_fill_rt there): one wave per QP on every route
-static int lmpc_rt_launch(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
+// launchers of the runtime kernel (the table of lmpc_variant.hip.h is filled by lmpc_variant_fill_rt there): one wave per QP on every route.  EQ: the retry pass
+template <bool EQ> struct lmpc_rt_family { static constexpr auto plain = lmpc_solve_kernel_rt<EQ>; static constexpr auto list = lmpc_solve_kernel_rt<EQ, lmpc_live_list>; };
+template <bool EQ> static int lmpc_rt_launch(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
     const size_t lds = (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0);
-    if (live) hipLaunchKernelGGL((lmpc_solve_kernel_rt<false, lmpc_live_list>), dim3(B), dim3(WAVE), lds, st, p, B, io, lmpc_live_list{live, B});
-    else hipLaunchKernelGGL((lmpc_solve_kernel_rt<false>), dim3(B), dim3(WAVE), lds, st, p, B, io);
+    if (live) hipLaunchKernelGGL(lmpc_rt_family<EQ>::list, dim3(B), dim3(WAVE), lds, st, p, B, io, lmpc_live_list{live, B});
+    else hipLaunchKernelGGL(lmpc_rt_family<EQ>::plain, dim3(B), dim3(WAVE), lds, st, p, B, io);
     return 0; }
-static int lmpc_rt_launch_retry(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
-    const size_t lds = (size_t)rt_layout(p.N, p.S).tot * sizeof(double) + (io.ssTab ? LMPC_SSTAB_LDS : 0);
-    if (live) hipLaunchKernelGGL((lmpc_solve_kernel_rt<true, lmpc_live_list>), dim3(B), dim3(WAVE), lds, st, p, B, io, lmpc_live_list{live, B});
-    else hipLaunchKernelGGL((lmpc_solve_kernel_rt<true>), dim3(B), dim3(WAVE), lds, st, p, B, io);
-    return 0; }
-static int lmpc_rt_launch_cd(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int) { return lmpc_rt_launch(st, p, B, io, nullptr); }
+static int lmpc_rt_launch_cd(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int) { return lmpc_rt_launch<false>(st, p, B, io, nullptr); }

@@ -34,25 +34,24 @@ struct lmpc_variant_api {
 constexpr int LMPC_VARIANT_ABI = LMPC_VARIANT_ABI_REV * 0x1000000 + (int)((sizeof(lmpc_dev_params) * 31u + sizeof(lmpc_solve_io) * 7u + sizeof(lmpc_variant_api)) & 0xffffffu);
 static_assert(sizeof(lmpc_dev_params) < 4096 && sizeof(lmpc_solve_io) < 1024, "by-value kernel arguments: keep them inside the kernarg segment's preload range");
 
-// One kernel, its plain and its TAB instantiation: a launch with per-problem rows -- safe-set laps (io.ssTab), controller tuning (lmpc_tuning_set), or both; the
-// host sets io.tune for every such launch (lmpc_capi.hip, launch_solve) -- takes the second, with LMPC_SSTAB_LDS bytes behind `lds` for the (slot, rows) of the
-// selected laps.  (S = 0 has the TAB instantiations for the tuning rows alone: no table there, lmpc_capi.hip, ss_table_for.)
-// kl / live: the parking instantiation of the same kernel and the list it takes beside io (B entries; per-problem rows as well, the host sets io.tune with the list) --
-// an instantiation of its own, so that `plain` and `tab` are the kernels they were for every launch outside a parking session.  (`live`: the last argument of the
-// launchers of lmpc_variant_api, null outside a parking session.)
-template <class K, class KL> static int lmpc_launch_pair(K plain, K tab, KL kl, int threads, size_t lds, hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
-    const bool t = io.tune != nullptr;
-    if (live) { hipLaunchKernelGGL(kl, dim3(B), dim3(threads), lds + LMPC_SSTAB_LDS, st, p, B, io, lmpc_live_list{live, B}); return 0; }
-    const K kernel = t ? tab : plain;
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds + (t ? LMPC_SSTAB_LDS : 0), st, p, B, io);
+// One solve family of an (N, S) -- a kernel with its plain, its TAB and its list instantiation -- described once; the launchers, the dynamic-LDS limits and the occupancy
+// query read this.  A launch with per-problem rows -- safe-set laps (io.ssTab), controller tuning (lmpc_tuning_set), or both; the host sets io.tune for every such launch
+// (lmpc_capi.hip, launch_solve) -- takes `tab`, with LMPC_SSTAB_LDS bytes behind the launch's LDS for the (slot, rows) of the selected laps.  (S = 0 has the TAB
+// instantiations for the tuning rows alone: no table there, lmpc_capi.hip, ss_table_for.)
+// list: the parking instantiation of the same kernel, which takes the list beside io (B entries; per-problem rows as well, the host sets io.tune with the list) --
+// an instantiation of its own, so that `plain` and `tab` are the kernels they were for every launch outside a parking session.
+// lds: the dynamic LDS of a plain launch;  lim / lim_tab: the limit of `plain` and that of `tab` and `list`.
+template <class K, class KL> struct lmpc_solve_family { K plain, tab; KL list; int threads; size_t lds, lim, lim_tab; };
+template <class K, class KL> lmpc_solve_family(K, K, KL, int, size_t, size_t, size_t) -> lmpc_solve_family<K, KL>;
+// (`live`: the last argument of the launchers of lmpc_variant_api, null outside a parking session)
+template <class K, class KL> static int lmpc_launch_pair(const lmpc_solve_family<K, KL> &f, hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
+    if (live) hipLaunchKernelGGL(f.list, dim3(B), dim3(f.threads), f.lds + LMPC_SSTAB_LDS, st, p, B, io, lmpc_live_list{live, B});
+    else hipLaunchKernelGGL(io.tune ? f.tab : f.plain, dim3(B), dim3(f.threads), f.lds + (io.tune ? LMPC_SSTAB_LDS : 0), st, p, B, io);
     return 0;
 }
-// An instantiation and the most dynamic LDS it is launched with; `built` = false: the name stands for another entry's kernel (no instantiation of its own)
-struct lmpc_kernel_lds { const void *fn; size_t lds; bool built; };
-template <int K> static bool lmpc_raise_lds_limits(const lmpc_kernel_lds (&k)[K]) {
-    for (const lmpc_kernel_lds &e : k)
-        if (e.built && hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.lds) != hipSuccess) return false;
-    return true;
+static bool lmpc_raise_lds_limit(const void *fn, size_t lds) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; }
+template <class K, class KL> static bool lmpc_raise_lds_limits(const lmpc_solve_family<K, KL> &f) {
+    return lmpc_raise_lds_limit((const void *)f.plain, f.lim) && lmpc_raise_lds_limit((const void *)f.tab, f.lim_tab) && lmpc_raise_lds_limit((const void *)f.list, f.lim_tab);
 }
 
 template <int N, int S> struct lmpc_variant_launchers {
@@ -65,8 +64,6 @@ template <int N, int S> struct lmpc_variant_launchers {
         return f > lds1 ? f : lds1;
     }
     static constexpr size_t lds1_max() { const size_t f = (size_t)(54 * N + k1_fused_doubles(N, LMPC_MAX_USED_LAPS, 8)) * sizeof(double); return (f > lds1 ? f : lds1) + LMPC_SSTAB_LDS; }
-    // per-problem rows (io.ssTab, io.tune): every (N, S) has the TAB instantiations of its kernels -- S = 0 for the tuning rows
-    static constexpr bool has_tab = true;
     // long horizons: [A_k | B_k] in global memory where that lets more QPs share a CU than the 160 KB of LDS otherwise hold and fewer than four do (idle SIMDs)
     static constexpr size_t lds1g = (size_t)solve_lds1<N, S, true>::tot * sizeof(double);
     // (measured, solve kernel, ms at batch 1024 / 4096: N = 40 LDS 1.467 / 4.073, global 1.092 / 3.398 -- two -> four QPs per CU;  N = 20 LDS 0.655 / 1.571,
@@ -82,40 +79,30 @@ template <int N, int S> struct lmpc_variant_launchers {
         if constexpr (has_cd) return (size_t)(hasQ ? solve_ldsc<N, S>::tot_q : solve_ldsc<N, S>::tot) * sizeof(double);
 #endif
         return 0; }
-    static const void *cd_kernel() {
-#ifdef LMPC_WITH_CD
-        if constexpr (has_cd) return (const void *)lmpc_solve_kernel_cd<N, S>;
-#endif
-        return nullptr; }
 
-    // Every instantiation of this (N, S) and its dynamic-LDS limit
+    // The families of this (N, S), each instantiation named here and nowhere else (per-problem rows, io.ssTab / io.tune: every (N, S) has the TAB instantiations -- S = 0 for the tuning rows).
+    // one-wave (EQ: its retry pass): a launch says what it takes (lds_for), the limit is lds1_max;  ABG: [A_k | B_k] in global memory, instantiated only where use_abg
+    template <bool EQ, bool ABG = false> static auto one_wave(size_t lds = ABG ? lds1g : lds1) {
+        return lmpc_solve_family{lmpc_solve_kernel<N, S, EQ, ABG>, lmpc_solve_kernel<N, S, EQ, ABG, true>, lmpc_solve_kernel<N, S, EQ, ABG, true, lmpc_live_list>, WAVE,
+                                 lds, ABG ? lds1g : lds1_max(), ABG ? lds1g + LMPC_SSTAB_LDS : lds1_max()}; }
+    template <int NW> static auto multi_wave() {
+        return lmpc_solve_family{lmpc_solve_kernel_mw<N, S, NW>, lmpc_solve_kernel_mw<N, S, NW, true>, lmpc_solve_kernel_mw<N, S, NW, true, lmpc_live_list>, WAVE * NW,
+                                 ldsm, ldsm, ldsm + LMPC_SSTAB_LDS}; }
+
     static bool raise_limits() {
-        const lmpc_kernel_lds k[] = {
-            {(const void *)lmpc_solve_kernel<N, S>, lds1_max(), true},                       {(const void *)lmpc_solve_kernel<N, S, false, false, has_tab>, lds1_max(), has_tab},
-            {(const void *)lmpc_solve_kernel<N, S, true>, lds1_max(), true},                 {(const void *)lmpc_solve_kernel<N, S, true, false, has_tab>, lds1_max(), has_tab},
-            {(const void *)lmpc_solve_kernel<N, S, false, use_abg>, lds1g, use_abg},         {(const void *)lmpc_solve_kernel<N, S, false, use_abg, has_tab>, lds1g + LMPC_SSTAB_LDS, use_abg && has_tab},
-            {(const void *)lmpc_solve_kernel_mw<N, S, 4>, ldsm, true},                       {(const void *)lmpc_solve_kernel_mw<N, S, 4, has_tab>, ldsm + LMPC_SSTAB_LDS, has_tab},
-            {(const void *)lmpc_solve_kernel_mw<N, S, 2>, ldsm, true},                       {(const void *)lmpc_solve_kernel_mw<N, S, 2, has_tab>, ldsm + LMPC_SSTAB_LDS, has_tab},
-            // the parking instantiations (LIVE)
-            {(const void *)lmpc_solve_kernel<N, S, false, false, true, lmpc_live_list>, lds1_max(), true}, {(const void *)lmpc_solve_kernel<N, S, true, false, true, lmpc_live_list>, lds1_max(), true},
-            {(const void *)lmpc_solve_kernel<N, S, false, use_abg, true, lmpc_live_list>, lds1g + LMPC_SSTAB_LDS, use_abg},
-            {(const void *)lmpc_solve_kernel_mw<N, S, 4, true, lmpc_live_list>, ldsm + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_mw<N, S, 2, true, lmpc_live_list>, ldsm + LMPC_SSTAB_LDS, true},
-            {cd_kernel(), lds_cd(true), has_cd},
-        };
-        return lmpc_raise_lds_limits(k);
+        if constexpr (use_abg) { if (!lmpc_raise_lds_limits(one_wave<false, true>())) return false; }
+#ifdef LMPC_WITH_CD
+        if constexpr (has_cd) { if (!lmpc_raise_lds_limit((const void *)lmpc_solve_kernel_cd<N, S>, lds_cd(true))) return false; }
+#endif
+        return lmpc_raise_lds_limits(one_wave<false>()) && lmpc_raise_lds_limits(one_wave<true>()) && lmpc_raise_lds_limits(multi_wave<4>()) && lmpc_raise_lds_limits(multi_wave<2>());
     }
 
     static int l1(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
-        if constexpr (use_abg) {
-            if (!(io.mode & 4) && io.abPack) return lmpc_launch_pair(lmpc_solve_kernel<N, S, false, true>, lmpc_solve_kernel<N, S, false, true, has_tab>, lmpc_solve_kernel<N, S, false, true, true, lmpc_live_list>, WAVE, lds1g, st, p, B, io, live);
-        }
-        return lmpc_launch_pair(lmpc_solve_kernel<N, S>, lmpc_solve_kernel<N, S, false, false, has_tab>, lmpc_solve_kernel<N, S, false, false, true, lmpc_live_list>, WAVE, lds_for(p, io), st, p, B, io, live); }
-    static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
-        return lmpc_launch_pair(lmpc_solve_kernel<N, S, true>, lmpc_solve_kernel<N, S, true, false, has_tab>, lmpc_solve_kernel<N, S, true, false, true, lmpc_live_list>, WAVE, lds_for(p, io), st, p, B, io, live); }
-    static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
-        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 4>, lmpc_solve_kernel_mw<N, S, 4, has_tab>, lmpc_solve_kernel_mw<N, S, 4, true, lmpc_live_list>, WAVE * 4, ldsm, st, p, B, io, live); }
-    static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
-        return lmpc_launch_pair(lmpc_solve_kernel_mw<N, S, 2>, lmpc_solve_kernel_mw<N, S, 2, has_tab>, lmpc_solve_kernel_mw<N, S, 2, true, lmpc_live_list>, WAVE * 2, ldsm, st, p, B, io, live); }
+        if constexpr (use_abg) { if (!(io.mode & 4) && io.abPack) return lmpc_launch_pair(one_wave<false, true>(), st, p, B, io, live); }
+        return lmpc_launch_pair(one_wave<false>(lds_for(p, io)), st, p, B, io, live); }
+    static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) { return lmpc_launch_pair(one_wave<true>(lds_for(p, io)), st, p, B, io, live); }
+    static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) { return lmpc_launch_pair(multi_wave<4>(), st, p, B, io, live); }
+    static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) { return lmpc_launch_pair(multi_wave<2>(), st, p, B, io, live); }
     static int lc(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int hasQ) {
 #ifdef LMPC_WITH_CD
         if constexpr (has_cd) { hipLaunchKernelGGL((lmpc_solve_kernel_cd<N, S>), dim3(B), dim3(WAVE), lds_cd(hasQ), st, p, B, io, hasQ); return 0; }
@@ -132,8 +119,8 @@ template <int N, int S> static bool lmpc_variant_fill(lmpc_variant_api *v) {
     v->N = N; v->S = S;
     v->lds_mw = L::ldsm; v->lds_1w = L::lds1; v->lds_1w_abg = L::use_abg ? L::lds1g : 0; v->lds_cd = L::lds_cd(false); v->lds_cd_q = L::lds_cd(true);
     v->launch_1w = &L::l1; v->launch_retry = &L::lr; v->launch_mw4 = &L::l4; v->launch_mw2 = &L::l2; v->launch_cd = &L::lc;
-    int nb = 0;
-    v->occ_mw2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)lmpc_solve_kernel_mw<N, S, 2>, 2 * WAVE, v->lds_mw) == hipSuccess ? nb : 0;
+    int nb = 0; const auto m2 = L::template multi_wave<2>();
+    v->occ_mw2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)m2.plain, m2.threads, m2.lds) == hipSuccess ? nb : 0;
     return true;
 }
 
@@ -144,11 +131,10 @@ static bool lmpc_variant_fill_rt(lmpc_variant_api *v, int N, int S) {
     if (N < 2 || N > LMPC_MAX_N || S < 0 || S > LMPC_MAX_SS_POINTS) return false;
     const size_t lds = (size_t)rt_layout(N, S).tot * sizeof(double);
     if (lds + 1024 > (size_t)160 * 1024) return false;
-    const lmpc_kernel_lds k[] = {{(const void *)lmpc_solve_kernel_rt<false>, lds + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_rt<true>, lds + LMPC_SSTAB_LDS, true},
-                                 {(const void *)lmpc_solve_kernel_rt<false, lmpc_live_list>, lds + LMPC_SSTAB_LDS, true}, {(const void *)lmpc_solve_kernel_rt<true, lmpc_live_list>, lds + LMPC_SSTAB_LDS, true}};
-    if (!lmpc_raise_lds_limits(k)) return false;
+    for (const void *k : {(const void *)lmpc_rt_family<false>::plain, (const void *)lmpc_rt_family<false>::list, (const void *)lmpc_rt_family<true>::plain, (const void *)lmpc_rt_family<true>::list})
+        if (!lmpc_raise_lds_limit(k, lds + LMPC_SSTAB_LDS)) return false;
     v->N = N; v->S = S; v->lds_mw = 0; v->lds_1w = lds; v->lds_1w_abg = 0; v->lds_cd = 0; v->lds_cd_q = 0; v->occ_mw2 = 0;
-    v->launch_1w = &lmpc_rt_launch; v->launch_retry = &lmpc_rt_launch_retry; v->launch_mw4 = &lmpc_rt_launch; v->launch_mw2 = &lmpc_rt_launch; v->launch_cd = &lmpc_rt_launch_cd;
+    v->launch_1w = &lmpc_rt_launch<false>; v->launch_retry = &lmpc_rt_launch<true>; v->launch_mw4 = &lmpc_rt_launch<false>; v->launch_mw2 = &lmpc_rt_launch<false>; v->launch_cd = &lmpc_rt_launch_cd;
     return true;
 }
 #endif

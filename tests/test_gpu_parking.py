@@ -318,8 +318,8 @@ def test_a_parked_session_is_the_session_of_its_live_cars(g):
 
 
 # ---- 4
-def test_per_car_rows_travel_by_car(g, six):
-    """Test 2's session with per-car tuning rows, vehicle rows, a lap table, a safe-set table and three tracks in force: parked against un-parked, live cars equal."""
+def _rows_travel_by_car(g, six, sets):
+    """Test 2's session with the per-car row sets named in `sets` in force, parked against un-parked; returns the un-parked run."""
     from racinglmpc_amd import _capi
     from tests import track_cases as tk, tuning_cases
     inp = _inputs(g, K6)
@@ -331,19 +331,39 @@ def test_per_car_rows_travel_by_car(g, six):
     for park in (None, (_capi.PARK_FINISHED, [1])):
         ctx = _lmpc_ctx(g)
         try:
-            ctx.track_set(tk.rows_of(names)); ctx.tuning_set(tune); ctx.plant_set_params(veh)
-            ctx.model_set_lap_table(lt); ctx.ss_set_lap_table(lt[::-1].copy(), last=np.array([3, -1, 2, 0, 1, 3], np.int32))
+            if "tracks" in sets:
+                ctx.track_set(tk.rows_of(names))
+            if "tuning" in sets:
+                ctx.tuning_set(tune)
+            if "vehicle" in sets:
+                ctx.plant_set_params(veh)
+            if "laps" in sets:
+                ctx.model_set_lap_table(lt); ctx.ss_set_lap_table(lt[::-1].copy(), last=np.array([3, -1, 2, 0, 1, 3], np.int32))
             out.append(_session(ctx, inp, park))
         finally:
             ctx.close()
     ref, park = out
     d = ref["doneAt"]
-    print("per-car rows: doneAt", list(d), "parked_at", list(park["parked_at"]))
+    print("per-car rows", sets, ": doneAt", list(d), "parked_at", list(park["parked_at"]))
     want = [_poll_of(d[b]) if d[b] >= 0 else -1 for b in range(6)]; want[1] = 0
     assert list(park["parked_at"]) == want
     assert len({w for w in want if w > 0}) >= 2 and -1 in want, want         # cars parked at two different polls, and one still live: the grid positions moved twice
     _compare_cars(park, ref, [0, 2, 3, 4, 5], "per-car rows", upto=[d[b] if d[b] >= 0 else T for b in range(6)])
+    return ref
+
+
+def test_per_car_rows_travel_by_car(g, six):
+    """Test 2's session with per-car tuning rows, vehicle rows, a lap table, a safe-set table and three tracks in force: parked against un-parked, live cars equal."""
+    ref = _rows_travel_by_car(g, six, ("tracks", "tuning", "vehicle", "laps"))
     # and the rows are in force: a car with a row of its own in every set drives differently from test 2's
+    assert not np.array_equal(_bits(ref["U"][:3, 2]), _bits(six[1]["U"][:3, 2]))
+
+
+@pytest.mark.parametrize("one", ["vehicle", "tracks"])
+def test_per_car_rows_travel_by_car_one_set(g, six, one):
+    """The same with ONE set in force -- vehicle rows only, tracks only: the parked plant kernel with one of its two row flags (the case above sets both, test 2
+    neither).  Car 2 has a row of its own in either set (mass x 1.04; the oval): its first steps differ from test 2's, so the rows are in force."""
+    ref = _rows_travel_by_car(g, six, (one,))
     assert not np.array_equal(_bits(ref["U"][:3, 2]), _bits(six[1]["U"][:3, 2]))
 
 
@@ -366,6 +386,40 @@ def test_runtime_kernel_context(g, six):
     want = [_poll_of(d[b]) if d[b] >= 0 else -1 for b in range(6)]; want[1] = 0
     assert list(park["parked_at"]) == want and d[5] < 0 and sum(d[b] >= 1 for b in (0, 2, 3, 4)) == 4
     _compare_cars(park, ref, [0, 2, 3, 4, 5], "runtime kernel", upto=[d[b] if d[b] >= 0 else T for b in range(6)])
+
+
+# ---- 5b
+@pytest.mark.parametrize("B,rpl16", [(6, True), (300, False), (300, True)], ids=["B6-rpl16", "B300", "B300-rpl16"])
+def test_regression_kernel_with_the_list_in_every_build(g, B, rpl16):
+    """The regression kernel's list instantiations beyond the one-group-per-CU 8-row scan every other parked session here launches: the 16-rows-per-lane scan
+    (LMPC_K1_RPL16=1 at create, as tests/test_gpu_configs.py sets it) and, at B = 300 with cars 0..9 on the start list, the occupancy build -- 290 live cars are
+    more work-groups than the device has CUs.  9 steps (one poll, at step 8); parked against un-parked on one context, live cars bit for bit."""
+    import os
+    steps = 9
+    if B == 6:
+        ks, listed = K6, [1]
+    else:
+        ks, listed = 170 + (np.arange(B) * 7) % 40, np.arange(10)
+    live = np.setdiff1d(np.arange(B), listed)
+    inp = _inputs(g, ks, steps=steps)
+    if rpl16:
+        os.environ["LMPC_K1_RPL16"] = "1"
+    try:
+        ctx = _lmpc_ctx(g, max_batch=B)
+    finally:
+        os.environ.pop("LMPC_K1_RPL16", None)
+    try:
+        # the device's CU count (hipGetDeviceProperties at create) is the largest batch solved with four waves per QP, and what the regression launch compares its grid with
+        if B > 6 and ctx.solver_waves(len(live)) == 4:
+            pytest.skip("%d live cars do not exceed the device's CUs: the occupancy build would not be launched" % len(live))
+        ref = _session(ctx, inp, None, steps=steps)
+        park = _session(ctx, inp, (0, listed), steps=steps)
+    finally:
+        ctx.close()
+    want = np.full(B, -1, np.int32); want[listed] = 0
+    assert np.array_equal(park["parked_at"], want) and park["n_live"] == len(live) and park["t"] == ref["t"] == steps
+    _compare_cars(park, ref, live, "regression kernel with the list")
+    assert np.abs(park["U"][:, live]).max() > 1e-3                                             # (not a comparison of zeros)
 
 
 # ---- 6

@@ -2,10 +2,13 @@
 
     python tools/park_bench.py --parent DIR [--repeats 5] [--out profiles/parking.json]      all three measurements
     python tools/park_bench.py --skip-ab                                                       (b) and (c) only: no parent build at hand
+    python tools/park_bench.py --parent DIR --ab-only --ab-parked --out profiles/NAME_ab.json  (a) only, with its parked leg: a change that claims to alter nothing
 
 (a) No regression when off.  DIR is a built checkout of the parent commit.  Parent and this build alternate, `repeats` times each, every run a process of its own:
     `bench.py --gpus 1 --full --rollouts-only --no-cpu-baseline` (headline and rollout leg) and one un-parked PerCarLMPC.run() at B = 256 and B = 1024 (leg `off`
     below, run with the tree's own Python package).  Rule: this build's median inside the parent's own min .. max.
+    --ab-parked (a parent that has parking): also one parked PerCarLMPC(device_commit=True, park=True) generation at B = 256 -- host-launch bound -- and B = 4096,
+    where the live count moves most (leg `parked`); lap steps and retired cars must agree in every run of both builds.
 (b) Parked against un-parked on this build: one generation of PerCarLMPC(device_commit=True) on fresh contexts seeded with the same per-car PID laps, alternating,
     `repeats` times after one discarded warm-up, at B = 256, 1024 and 4096, B = 4096 with PARK_REROUTE, a three-track batch (track.REFERENCE_SPECS) and a batch in
     which 5 % of the cars carry a tuning row that cannot finish.  Beside each time the work fraction sum_t nLive(t) / (B x un-parked steps), from doneAt and the poll
@@ -68,14 +71,14 @@ def work_fraction(done, steps_unparked):
     return float(stepped.sum()) / float(done.size * steps_unparked)
 
 
-def leg_off(args):
-    """One un-parked PerCarLMPC.run() per batch size, on whatever tree sys.path names: one JSON line."""
+def leg(args, park):
+    """One un-parked (B = 256, 1024) or parked (B = 256, 4096) PerCarLMPC.run() per batch size, on whatever tree sys.path names: one JSON line."""
     from tests import common
     g = common.load_lmpc_golden()
     out = {}
-    for B in (256, 1024):
-        one_generation(g, args.horizon, B, args.seed, False)                    # warm-up, discarded
-        ms, laps, steps, done, retired = one_generation(g, args.horizon, B, args.seed, False)
+    for B in ((256, 4096) if park else (256, 1024)):
+        one_generation(g, args.horizon, B, args.seed, park)                     # warm-up, discarded
+        ms, laps, steps, done, retired = one_generation(g, args.horizon, B, args.seed, park)
         out[str(B)] = dict(run_ms=ms, lap_steps_sum=int(sum(t[0] for t in laps if t)), retired=len(retired))
     print(json.dumps(out))
 
@@ -84,6 +87,9 @@ def measure_ab(args):
     trees = [("parent", os.path.abspath(args.parent)), ("this", ROOT)]
     bench = ["bench.py", "--gpus", "1", "--steps", "200", "--warmup", "20", "--full", "--rollouts-only", "--no-cpu-baseline"]
     runs = {name: dict(headline_solves_per_s=[], rollout_two_generations_s=[], per_car_run_ms_B256=[], per_car_run_ms_B1024=[]) for name, _ in trees}
+    if args.ab_parked:
+        for name, _ in trees:
+            runs[name].update(parked_run_ms_B256=[], parked_run_ms_B4096=[])
     same = {name: set() for name, _ in trees}
     for rep in range(args.repeats):
         for name, tree in (trees if rep % 2 == 0 else trees[::-1]):
@@ -94,13 +100,18 @@ def measure_ab(args):
             o = json.loads(last([os.path.abspath(__file__), "--leg", "off", "--tree", tree, "--horizon", str(args.horizon), "--seed", str(args.seed)]))
             runs[name]["per_car_run_ms_B256"].append(o["256"]["run_ms"]); runs[name]["per_car_run_ms_B1024"].append(o["1024"]["run_ms"])
             same[name].add((tuple(tuple(x["best_lap_steps"]) for x in b["config_rollouts"]["generations"]), o["256"]["lap_steps_sum"], o["1024"]["lap_steps_sum"]))
+            if args.ab_parked:
+                k = json.loads(last([os.path.abspath(__file__), "--leg", "parked", "--tree", tree, "--horizon", str(args.horizon), "--seed", str(args.seed)]))
+                runs[name]["parked_run_ms_B256"].append(k["256"]["run_ms"]); runs[name]["parked_run_ms_B4096"].append(k["4096"]["run_ms"])
+                same[name].add(("parked",) + tuple(k[B][f] for B in ("256", "4096") for f in ("lap_steps_sum", "retired")))
+            print("a/b run %d, %s: %s" % (rep, name, {k: round(v[-1], 4) for k, v in runs[name].items()}), file=sys.stderr, flush=True)
     figures = {}
     for k in runs["this"]:
         p, t = runs["parent"][k], runs["this"][k]
         figures[k] = dict(parent_runs=p, this_runs=t, parent_median=float(np.median(p)), parent_range=[min(p), max(p)], this_median=float(np.median(t)), this_range=[min(t), max(t)],
                           this_median_inside_parent_range=bool(min(p) <= np.median(t) <= max(p)))
     return dict(what="parent's build and this one alternating, %d runs each, every run a process of its own; parking off" % args.repeats,
-                rule="this build's median inside the parent's own min .. max", same_lap_steps_in_all_runs=len(same["parent"] | same["this"]) == 1, figures=figures,
+                rule="this build's median inside the parent's own min .. max", same_lap_steps_in_all_runs=len(same["parent"] | same["this"]) == (2 if args.ab_parked else 1), figures=figures,
                 all_inside=all(f["this_median_inside_parent_range"] for f in figures.values()))
 
 
@@ -184,13 +195,15 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--horizon", type=int, default=12)
     ap.add_argument("--seed", type=int, default=3)
-    ap.add_argument("--leg", choices=["off"], help="(internal) one leg of (a), run on --tree")
+    ap.add_argument("--ab-only", action="store_true", help="(a) alone")
+    ap.add_argument("--ab-parked", action="store_true", help="(a) with a parked generation at B = 256 and B = 4096 (the parent must have parking)")
+    ap.add_argument("--leg", choices=["off", "parked"], help="(internal) one leg of (a), run on --tree")
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "parking.json"))
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.tree))
-    if args.leg == "off":
-        return leg_off(args)
+    if args.leg:
+        return leg(args, args.leg == "parked")
     if args.repeats < 5:
         raise SystemExit("at least five repeats")
     if not args.skip_ab and not args.parent:
@@ -208,8 +221,9 @@ def main():
     if os.path.exists(args.out):                                  # (a run with --skip-ab keeps the A / B of an earlier one)
         with open(args.out) as f:
             result = dict(json.load(f), **result)
-    result["b_parked_against_unparked"] = measure_parked(args, g)
-    result["c_compaction"] = measure_compaction(args, g)
+    if not args.ab_only:
+        result["b_parked_against_unparked"] = measure_parked(args, g)
+        result["c_compaction"] = measure_compaction(args, g)
     if not args.skip_ab:
         result["a_off_against_parent"] = measure_ab(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
