@@ -483,6 +483,44 @@ int lmpc_rollout_extend_laps(lmpc_ctx *, int n, const int *cars /*n*/, const int
          * repeated subtraction of 1.0, as the host loop does.  The caller keeps deciding on status bits (it has them from lmpc_rollout_fetch with t0 = t1 = 0).
          * LMPC_E_ARG, before anything changes, for n_rows < 1 or beyond the steps taken, a lap index that names no stored lap, the same lap twice, a car out of range.
          * One store growth, one launch, one download of the flags; the live safe-set table sees the longer laps at the next step */
+/* ---- lap metrics of the active session reduced ON THE DEVICE (version 112; kernel: racinglmpc_amd/csrc/lmpc_metrics.hip.h).  What a sweep over thousands of cars
+ * wants back per car and lap -- a lap time finer than one step, the distance kept from the lane edge and the input bounds, the cornering, the smoothness of the
+ * inputs, the realised cost under the car's own weights -- as one row of LMPC_METRICS_NCOL doubles per listed car instead of its T x 14 logged ones. */
+#define LMPC_METRICS_NCOL 20
+enum { LMPC_MET_ROWS = 0,              /* T */
+       LMPC_MET_T_CROSS = 1,           /* (T-1) + (TL - s_{T-1}) / (finX_s - s_{T-1}) when T == doneAt[c], else NaN: the line crossing (SysModel.py:45) interpolated
+                                          between the last logged row and finX (the state right after the crossing step), in steps */
+       LMPC_MET_NONFINITE_ROWS = 2,    /* rows with a non-finite value among the 14 logged ones: the entries to distrust */
+       LMPC_MET_VX_MIN = 3, LMPC_MET_VX_MAX = 4, LMPC_MET_VX_SUM = 5,
+       LMPC_MET_EY_ABSMAX = 6, LMPC_MET_EY_ABSMAX_ROW = 7,                 /* max |ey| and the FIRST row that attains it */
+       LMPC_MET_EPSI_ABSMAX = 8,
+       LMPC_MET_ALAT_ABSMAX = 9,       /* max |vx wz| */
+       LMPC_MET_LANE_EXCESS_MAX = 10, LMPC_MET_LANE_EXCESS_ROWS = 11,     /* max over t, r of v; rows with some v > 0 */
+       LMPC_MET_LANE_EXCESS_SUM = 12, LMPC_MET_LANE_EXCESS_SQSUM = 13,    /* sum_t sum_r v, sum_t sum_r v^2 */
+       LMPC_MET_INPUT_MARGIN_MIN = 14, /* min over t and the four rows of bu_r - Fu_r u_t; negative: a bound was exceeded */
+       LMPC_MET_DU0_SQSUM = 15, LMPC_MET_DU1_SQSUM = 16,                  /* sum_{t=1}^{T-1} (u_{t,j} - u_{t-1,j})^2, 0 at T = 1 */
+       LMPC_MET_COST_STATE = 17,       /* sum_t (x_t - xRef)' Q (x_t - xRef) */
+       LMPC_MET_COST_INPUT = 18,       /* sum_t u_t' R u_t */
+       LMPC_MET_PATH_LENGTH = 19 };    /* sum_{t=1}^{T-1} sqrt((X_t - X_{t-1})^2 + (Y_t - Y_{t-1})^2) */
+int lmpc_rollout_lap_metrics(lmpc_ctx *, int n, const int *cars /*n*/, const int *rows /*n, or NULL: doneAt[car]*/, double *out /*n x LMPC_METRICS_NCOL*/);
+        /* Entry i covers rows t = 0 .. T-1 of car c = cars[i] as the session logged them, T = rows[i] or doneAt[c]: x_t = logX[t][c] (vx, vy, wz, epsi, s, ey),
+         * u_t = logU[t][c], (X_t, Y_t) = logG[t][c][4:6] -- the arrays of lmpc_rollout_fetch.  TL is the car's own TrackLength (its lmpc_track_set row, else the
+         * config's); Q, R, xRef, bx, bu come from the car's own tuning row (lmpc_tuning_set, else the config's; more than one row in force must be one per car of
+         * the session, else LMPC_E_ARG); Fx, Fu are the context's; v_{t,r} = max(0, Fx_r x_t - bx_r) for the two lane rows.
+         * The realised stage cost of buildCost (PredictiveControllers.py:228-257: x' Q x about xRef, u' R u, the input-rate term of dR, the slack terms of Qslack) is
+         * composed by the caller, whose dR and Qslack they are:
+         *     cost_state + cost_input + dR[0] du0_sqsum + dR[1] du1_sqsum + Qslack[0] lane_excess_sqsum + Qslack[1] lane_excess_sum.
+         * Non-finite values: minima and maxima keep the first among equals and a comparison with NaN is false (the rule of the prefilter image,
+         * lmpc_commit.hip.h), so a NaN is skipped -- an entry without a comparable value keeps -inf (maxima), +inf (minima) and row -1; counts count only true
+         * comparisons; sums propagate NaN under IEEE rules; nonfinite_rows tells which entries to distrust.  A non-finite car does not affect any other entry.
+         * Every term and the order of the reduction are stated in the kernel's header; the order depends on T alone, so a result can be reproduced on the host
+         * bit for bit (tests/metrics_ref.py).
+         * Valid in an active session of any kind (lmpc_rollout_begin, _begin_mpc, _pid) with at least one step taken; a car may be listed more than once.  The rules
+         * of lmpc_rollout_commit_laps, everything checked before the launch: LMPC_E_ARG for n < 1, NULL cars or out, a car outside [0, B), rows[i] < 1, rows[i] beyond
+         * what the session logged for that car (the steps taken; a parked car's parking step; for a car of a stop_at_line PID session its crossing step);
+         * LMPC_E_STATE with no session active, or when rows == NULL and a listed car has doneAt < 0 (lmpc_last_error names the car).  `out` is written only on
+         * success.  Reads only: no store and no session state changes.  One upload of the entry table, one launch, one download of n x LMPC_METRICS_NCOL doubles.
+         * No reference counterpart beyond the lines named (the reference reports lap times in whole steps, main.py:113-121) */
 int lmpc_debug_model_image(lmpc_ctx *, int lap /*insertion index*/, unsigned *q /*3 x (rows-1)*/, double *par /*chunks used x 6*/, int *chunks);
         /* the prefilter image of one regression-store lap as the regression kernel reads it (the scan of PredictiveModel.py:180-197 on 16-bit fixed point): three planes
          * of packed words (vx | vy << 16), (wz | delta << 16), (a) over rows 0 .. rows-2, and per 1024-row chunk the five minima and the common scale.  Available in every

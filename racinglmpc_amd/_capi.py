@@ -23,6 +23,31 @@ ST_MAXITER, ST_REG_SINGULAR, ST_NO_SEGMENT, ST_WINDOW, ST_NUMERIC, ST_NOT_INTERI
 
 PLANT_NPAR = 10
 COMMIT_SS, COMMIT_MODEL = 1, 2         # LMPC_COMMIT_SS / LMPC_COMMIT_MODEL: the `stores` bits of lmpc_rollout_commit_laps
+# One row of lap metrics (lmpc_rollout_lap_metrics): name -> column, the LMPC_MET_* enumerators of include/lmpc_hip.h in their order.
+METRICS_NCOL = 20
+METRIC_FIELDS = {name: k for k, name in enumerate((
+    "rows", "t_cross", "nonfinite_rows", "vx_min", "vx_max", "vx_sum", "ey_absmax", "ey_absmax_row", "epsi_absmax", "alat_absmax", "lane_excess_max",
+    "lane_excess_rows", "lane_excess_sum", "lane_excess_sqsum", "input_margin_min", "du0_sqsum", "du1_sqsum", "cost_state", "cost_input", "path_length"))}
+
+
+def metrics_stage_cost(metrics, dR, Qslack):
+    """The realised stage cost of buildCost (PredictiveControllers.py:228-257) from rows of lap metrics: cost_state + cost_input + dR . du_sqsum +
+    Qslack[0] lane_excess_sqsum + Qslack[1] lane_excess_sum.  dR, Qslack: (2,) for all rows, or one pair per row -- the caller's own tuning."""
+    m, F = np.asarray(metrics, float), METRIC_FIELDS
+    dR, Qs = np.asarray(dR, float), np.asarray(Qslack, float)
+    return (m[..., F["cost_state"]] + m[..., F["cost_input"]] + dR[..., 0] * m[..., F["du0_sqsum"]] + dR[..., 1] * m[..., F["du1_sqsum"]]
+            + Qs[..., 0] * m[..., F["lane_excess_sqsum"]] + Qs[..., 1] * m[..., F["lane_excess_sum"]])
+
+
+def metrics_report(per_generation, dR, Qslack, fields=("t_cross", "ey_absmax", "lane_excess_max", "input_margin_min", "alat_absmax")):
+    """What the sweep tools print of PerCarLMPC(metrics=True).metrics: {name: [car][generation]} for `fields` and "stage_cost" (metrics_stage_cost under dR, Qslack:
+    (2,) or one pair per car), plain floats with None where a car has no lap in that generation -- ready for json.dump."""
+    m = np.stack([np.asarray(p, float) for p in per_generation], axis=1)                           # (B, G, METRICS_NCOL)
+    dR, Qs = np.asarray(dR, float), np.asarray(Qslack, float)
+    cost = metrics_stage_cost(m, dR[:, None, :] if dR.ndim == 2 else dR, Qs[:, None, :] if Qs.ndim == 2 else Qs)
+    cols = {name: m[..., METRIC_FIELDS[name]] for name in fields}
+    cols["stage_cost"] = cost
+    return {name: [[None if np.isnan(v) else float(v) for v in row] for row in a] for name, a in cols.items()}
 # LMPC_TRACE_*: the planes of a session trace (lmpc_rollout_set_trace), the per-step logs of LMPC.unpackSolution (PredictiveControllers.py:364-379) among them
 TRACE_XPRED, TRACE_UPRED, TRACE_SS, TRACE_QSEL, TRACE_SOLVER, TRACE_XY = 1, 2, 4, 8, 16, 32
 TRACE_ALL = 63
@@ -153,7 +178,7 @@ EXPORTS = [
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
     "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
-    "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_debug_model_image", "lmpc_tuning_from_config", "lmpc_tuning_set", "lmpc_tuning_get",
+    "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_rollout_lap_metrics", "lmpc_debug_model_image", "lmpc_tuning_from_config", "lmpc_tuning_set", "lmpc_tuning_get",
     "lmpc_track_row_from_config", "lmpc_track_set", "lmpc_track_get", "lmpc_ss_add_trajectory_on", "lmpc_ss_extend_lap_on",
     "lmpc_rollout_set_trace", "lmpc_rollout_get_trace", "lmpc_rollout_trace_bytes", "lmpc_rollout_fetch_trace",
     "lmpc_rollout_set_parking", "lmpc_rollout_get_parking", "lmpc_rollout_parked_at", "lmpc_debug_live_compact",
@@ -208,6 +233,9 @@ def load():
         lib.lmpc_rollout_extend_laps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         lib.lmpc_debug_model_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         lib.lmpc_rollout_commit_laps.restype = lib.lmpc_rollout_extend_laps.restype = lib.lmpc_debug_model_image.restype = C.c_int
+        # (lap metrics reduced on the device: int32 tables in, rows of METRICS_NCOL doubles out)
+        lib.lmpc_rollout_lap_metrics.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmpc_rollout_lap_metrics.restype = C.c_int
         # (per-problem controller tuning: rows of TUNING_NPAR doubles)
         lib.lmpc_tuning_from_config.argtypes = [C.c_void_p, C.c_void_p]
         lib.lmpc_tuning_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -1140,6 +1168,20 @@ class Context:
         stores = (COMMIT_SS if ss else 0) | (COMMIT_MODEL if model else 0)
         _chk(self.lib.lmpc_rollout_commit_laps(self._h, cars.shape[0], cars.ctypes.data, None if rows is None else rows.ctypes.data, stores, C.byref(fs), C.byref(fm)))
         return (fs.value if ss else None), (fm.value if model else None)
+
+    def rollout_lap_metrics(self, cars, rows=None):
+        """(n, METRICS_NCOL) lap metrics of the active session, reduced on the device (lmpc_rollout_lap_metrics): row i covers rows [0, rows[i]) of car cars[i] as the
+        session logged them (rows=None: up to each car's crossing step), columns METRIC_FIELDS.  Reads only; refused like rollout_commit_laps."""
+        cars = _i32(np.atleast_1d(cars))
+        if cars.ndim != 1:
+            raise ValueError("rollout_lap_metrics: cars must be one-dimensional")
+        if rows is not None:
+            rows = _i32(np.atleast_1d(rows))
+            if rows.shape != cars.shape:
+                raise ValueError("rollout_lap_metrics: one row count per listed car expected")
+        out = np.zeros((cars.shape[0], METRICS_NCOL))
+        _chk(self.lib.lmpc_rollout_lap_metrics(self._h, cars.shape[0], cars.ctypes.data, None if rows is None else rows.ctypes.data, out.ctypes.data))
+        return out
 
     def rollout_extend_laps(self, cars, laps, n_rows):
         """The first n_rows logged rows of car cars[i] appended to safe-set lap laps[i] on the device (lmpc_rollout_extend_laps: ss_extend_lap of the fetched rows

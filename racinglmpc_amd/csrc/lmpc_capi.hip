@@ -5,6 +5,7 @@
 #include "lmpc_noise.hip.h"
 #include "lmpc_track.hip.h"
 #include "lmpc_commit.hip.h"
+#include "lmpc_metrics.hip.h"
 #include "lmpc_trace.hip.h"
 #include "lmpc_live.hip.h"
 #include "lmpc_arrays.h"
@@ -242,7 +243,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 111; }
+int lmpc_version(void) { return 112; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -930,6 +931,20 @@ static int session_parked_at(lmpc_rollout_session *r, std::vector<int> &at) {
     HIPCHK(hipMemcpy(at.data(), r->d_parkedAt, sizeof(int) * (size_t)r->B, hipMemcpyDeviceToHost));
     return LMPC_OK;
 }
+// Entry i of a call that lists (car, rows) of the active session -- lmpc_rollout_commit_laps, lmpc_rollout_lap_metrics: *T = rows[i], or doneAt[car] with rows == NULL, checked
+// against what the session logged for the car (done: doneAt of every car; pat: session_parked_at; least: the fewest rows the call takes).  Refusals are reported under `who`.
+static int session_entry_rows(const lmpc_rollout_session *r, const char *who, int i, int car, const int *rows, const std::vector<int> &done, const std::vector<int> &pat, int least, int *T_out) {
+    const int T = rows ? rows[i] : done[(size_t)car];
+    char msg[160];
+    // (a parked car is not logged from its parking step on; rows = NULL stops at doneAt, which lies inside)
+    if (rows && !pat.empty() && pat[(size_t)car] >= 0 && T > pat[(size_t)car]) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, which was parked at step %d (lmpc_rollout_parked_at)", i, T, car, pat[(size_t)car]); return set_err(LMPC_E_ARG, who, msg); }
+    if (!rows && done[(size_t)car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0) and no row count was given", car); return set_err(LMPC_E_STATE, who, msg); }
+    // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
+    const int logged = (r->kind == RO_PID && r->stop_at_line && done[(size_t)car] >= 0) ? done[(size_t)car] : r->t;
+    if (T < least || T > logged) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, %d are logged (at least %d needed)", i, T, car, logged, least); return set_err(LMPC_E_ARG, who, msg); }
+    *T_out = T;
+    return LMPC_OK;
+}
 int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *rows, unsigned stores, int *first_ss, int *first_model) {
     // For i = 0 .. n-1 in the order listed: lmpc_ss_add_trajectory (LMPC.addTrajectory + computeCost, PredictiveControllers.py:418-464) and lmpc_model_add_trajectory
     // (PredictiveModel.addTrajectory, PredictiveModel.py:35-46) of rows [0, rows[i]) of car cars[i] as the session logged them, all in one commit_laps.
@@ -944,15 +959,9 @@ int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *row
     const int ns0 = (int)c->s_len.size(), nm0 = (int)c->m_len.size();
     std::vector<lmpc_commit_entry> tab((size_t)n);
     std::vector<int> pat; RCCHK(session_parked_at(r, pat));
-    char msg[160];
     for (int i = 0; i < n; i++) {
-        const int car = cars[i], T = rows ? rows[i] : done[car];
-        // (a parked car is not logged from its parking step on; rows = NULL stops at doneAt, which lies inside)
-        if (rows && !pat.empty() && pat[(size_t)car] >= 0 && T > pat[(size_t)car]) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, which was parked at step %d (lmpc_rollout_parked_at)", i, T, car, pat[(size_t)car]); return set_err(LMPC_E_ARG, "lmpc_rollout_commit_laps", msg); }
-        if (!rows && done[car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0) and no row count was given", car); return set_err(LMPC_E_STATE, "lmpc_rollout_commit_laps", msg); }
-        // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
-        const int logged = (r->kind == RO_PID && r->stop_at_line && done[car] >= 0) ? done[car] : r->t;
-        if (T < (model ? 2 : 1) || T > logged) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, %d are logged (at least %d needed)", i, T, car, logged, model ? 2 : 1); return set_err(LMPC_E_ARG, "lmpc_rollout_commit_laps", msg); }
+        const int car = cars[i]; int T;
+        RCCHK(session_entry_rows(r, "lmpc_rollout_commit_laps", i, car, rows, done, pat, model ? 2 : 1, &T));
         tab[(size_t)i] = {car, T, ss ? ns0 + i : -1, model ? nm0 + i : -1, track_length_of(c, car)};
     }
     std::vector<double> q0;
@@ -980,6 +989,49 @@ int lmpc_rollout_extend_laps(lmpc_ctx *c, int n, const int *cars, const int *lap
           return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); } }
     store_rows s; RCCHK(session_rows(c, LMPC_EXTEND_TAIL(n), &s));
     return extend_laps(c, s, n, cars, laps, n_rows, extended);
+}
+
+int lmpc_rollout_lap_metrics(lmpc_ctx *c, int n, const int *cars, const int *rows, double *out) {
+    // Per entry the reductions of lmpc_metrics.hip.h over rows [0, rows[i]) of car cars[i] as the session logged them, under the row checks of
+    // lmpc_rollout_commit_laps; all checked before the launch, nothing of the context or the session is written.  The upload is one buffer: the weights rows the
+    // entries name (one for all cars, or one per car: Q, R, xRef, bx, bu of the tuning rows in force, else of the config), then the entry table.
+    if (!c) return set_err(LMPC_E_ARG, "lmpc_rollout_lap_metrics", "null context");
+    if (!(c->ro && c->ro->active)) return set_err(LMPC_E_STATE, "lmpc_rollout_lap_metrics", "no rollout session is active");
+    ARGCHK(c->ro->t >= 1 && n >= 1 && cars && out);
+    lmpc_rollout_session *r = c->ro; const int B = r->B;
+    for (int i = 0; i < n; i++) ARGCHK(cars[i] >= 0 && cars[i] < B);
+    RCCHK(rows_fit(c->tune, B, LMPC_ROWS_EXACT, "cars", "lmpc_rollout_lap_metrics"));
+    const int nw = c->tune.n > 1 ? B : 1;
+    const size_t wbytes = sizeof(lmpc_metrics_weights) * (size_t)nw, obytes = sizeof(double) * LMPC_METRICS_NCOL * (size_t)n;
+    store_rows s; RCCHK(session_rows(c, obytes + wbytes + sizeof(lmpc_metrics_entry) * (size_t)n, &s));
+    std::vector<int> done((size_t)B);
+    HIPCHK(hipMemcpy(done.data(), r->d_done, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    std::vector<int> pat; RCCHK(session_parked_at(r, pat));
+    std::vector<char> up(wbytes + sizeof(lmpc_metrics_entry) * (size_t)n);
+    lmpc_metrics_weights *w = (lmpc_metrics_weights *)up.data(); lmpc_metrics_entry *tab = (lmpc_metrics_entry *)(up.data() + wbytes);
+    double cfg_row[LMPC_TUNING_NPAR]; RCCHK(lmpc_tuning_from_config(&c->cfg, cfg_row));
+    for (int b = 0; b < nw; b++) {
+        const double *row = c->tune.in_force() ? c->tune.row(b) : cfg_row;
+        memcpy(w[b].Q, row + TN_Q, sizeof(w[b].Q)); memcpy(w[b].R, row + TN_R, sizeof(w[b].R)); memcpy(w[b].xRef, row + TN_XREF, sizeof(w[b].xRef));
+        memcpy(w[b].bx, row + TN_BX, sizeof(w[b].bx)); memcpy(w[b].bu, row + TN_BU, sizeof(w[b].bu));
+    }
+    for (int i = 0; i < n; i++) {
+        const int car = cars[i]; int T;
+        RCCHK(session_entry_rows(r, "lmpc_rollout_lap_metrics", i, car, rows, done, pat, 1, &T));
+        tab[i] = {car, T, T == done[(size_t)car] ? 1 : 0, nw > 1 ? car : 0, track_length_of(c, car)};
+    }
+    double *d_out = (double *)s.tail; char *d_up = (char *)(d_out + LMPC_METRICS_NCOL * (size_t)n);
+    lmpc_metrics_args a; a.logX = r->d_logX; a.logU = r->d_logU; a.logG = r->d_logG; a.finX = r->d_finX; a.B = B;
+    a.weights = (const lmpc_metrics_weights *)d_up; a.table = (const lmpc_metrics_entry *)(d_up + wbytes);
+    memcpy(a.Fx, c->cfg.Fx, sizeof(a.Fx)); memcpy(a.Fu, c->cfg.Fu, sizeof(a.Fu));
+    std::vector<double> res(LMPC_METRICS_NCOL * (size_t)n);            // (`out` is the caller's: written only once everything has succeeded)
+    hipError_t e = hipMemcpyAsync(d_up, up.data(), up.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { hipLaunchKernelGGL(lmpc_lap_metrics_kernel, dim3((unsigned)n), dim3(LMPC_MET_NT), 0, c->stream, a, d_out); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_out, obytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return set_err(LMPC_E_HIP, "lmpc_lap_metrics_kernel", hipGetErrorString(e));
+    memcpy(out, res.data(), obytes);
+    return LMPC_OK;
 }
 
 // refresh the per-launch part of the device parameter block

@@ -16,11 +16,23 @@ import numpy as np
 from . import _capi, parallel
 
 
+def _lap_metrics_rows(ctx, B, cars):
+    """(B, METRICS_NCOL) of the active session: one Context.rollout_lap_metrics call over `cars`, up to their crossing steps; NaN rows for the cars not listed."""
+    cars = np.asarray(cars, np.int64).reshape(-1)
+    out = np.full((B, _capi.METRICS_NCOL), np.nan)
+    if cars.size:
+        out[cars] = ctx.rollout_lap_metrics(cars)
+    return out
+
+
 class BatchedRollouts:
     """B closed-loop LMPC laps against a shared safe set, or (ss_table) each car against its own (one GPU context, one rank)."""
 
-    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None, tracks=None, trace=None, trace_what=None, park=None):
-        """trace / trace_what: the cars of THIS object whose controller output every LMPC / MPC session records step by step, and the planes (_capi.TRACE_* bits; None:
+    def __init__(self, ctx, track, seed=0, global_noise=False, prefetch=True, plant_params=None, device_noise=False, lap_table=None, ss_table=None, ss_last=None, tuning=None, tracks=None, trace=None, trace_what=None, park=None, metrics=False):
+        """metrics: run_pid_laps, run_mpc_laps and run_lap_device leave the lap metrics of their session in `last_metrics` -- (B, _capi.METRICS_NCOL), columns
+        _capi.METRIC_FIELDS, one Context.rollout_lap_metrics call over the cars that crossed the line, taken before the session ends; NaN rows for the others.  The
+        returned tuples are what they are without it.  False: no call is made and last_metrics stays None.
+        trace / trace_what: the cars of THIS object whose controller output every LMPC / MPC session records step by step, and the planes (_capi.TRACE_* bits; None:
         every plane the context can record) -- the reference's xStoredPredTraj / uStoredPredTraj / SSStoredPredTraj (PredictiveControllers.py:364-379) with the
         Q-values, the solver's words and the inertial positions beside them (Context.rollout_set_trace); handed to the context before every begin and run_mpc_laps,
         beside tuning.  run_lap_device, run_mpc_laps and PerCarLMPC.run then leave the session's trace in `last_trace`: the planes (steps, listed cars, ...) of
@@ -77,6 +89,8 @@ class BatchedRollouts:
         # step on).  None: the context's parking is left as it is and last_parked_at stays None.
         self.park = self._check_park(park)
         self.last_parked_at = None
+        self.metrics = bool(metrics)
+        self.last_metrics = None
         self.device_noise = bool(device_noise)
         if self.device_noise:
             import operator
@@ -240,6 +254,12 @@ class BatchedRollouts:
         self.last_parked_at = None if getattr(self, "park", None) is None else self.ctx.rollout_parked_at()[0]
         return self.last_parked_at
 
+    def _fetch_metrics(self, done):
+        """last_metrics of the active session, to be called before rollout_end: the cars that crossed the line, up to their crossing steps."""
+        done = np.asarray(done)
+        self.last_metrics = _lap_metrics_rows(self.ctx, done.shape[0], np.flatnonzero(done >= 0)) if getattr(self, "metrics", False) else None
+        return self.last_metrics
+
     def _fetch_trace(self, t, done):
         """last_trace of the active session, to be called before rollout_end: the planes of steps [0, t) and the listed cars' crossing steps."""
         tr = getattr(self, "trace", None)
@@ -285,6 +305,7 @@ class BatchedRollouts:
         X, U, G, done, st, fx, fg = self.ctx.rollout_fetch(0, t)
         self._fetch_trace(t, done)
         self._fetch_parked()
+        self._fetch_metrics(done)
         self.ctx.rollout_end()
         self.last_status, self.last_done = st, done
         laps = []
@@ -324,6 +345,7 @@ class BatchedRollouts:
         else:
             t, _ = self.ctx.rollout_pid(x0, x0, vt, noise_u, noise, stop_at_line=stop_at_line)
         out = self.ctx.rollout_fetch(0, t)
+        self._fetch_metrics(out[3])
         self.ctx.rollout_end()
         return self._collect(B, *out, whole=not stop_at_line, keep_invalid=keep_invalid)
 
@@ -345,6 +367,7 @@ class BatchedRollouts:
         out = self.ctx.rollout_fetch(0, t)
         self._fetch_trace(t, out[3])
         self._fetch_parked()
+        self._fetch_metrics(out[3])
         self.ctx.rollout_end()
         return self._collect(nb, *out, whole=not stop_at_line, keep_invalid=keep_invalid)
 
@@ -708,12 +731,17 @@ class PerCarLMPC:
     live instead of at T_max.  Stores, histories, tables, `last`, lap_times, `retired` and the returned tuples come out as without it; `steps[g]` -- the session steps
     generation g took -- is what differs.  (A lap that crosses the line within the first `ext` steps, whose extension rows a parked car no longer logs, is refused.)
     park=_capi.PARK_REROUTE adds that bit: the solve route then follows the live count, and another route answers to the routes' bound (2e-7 in x, u), not bit for
-    bit -- the laps are no longer promised equal to those without parking.  The rollouts object's own `park` is put back after every generation."""
+    bit -- the laps are no longer promised equal to those without parking.  The rollouts object's own `park` is put back after every generation.
+    metrics=True: `metrics[g]` is the (B, _capi.METRICS_NCOL) lap metrics of generation g (columns _capi.METRIC_FIELDS): one Context.rollout_lap_metrics call over the
+    generation's valid cars, up to their crossing steps, before the session ends -- with and without device_commit, with and without park; NaN rows for cars that
+    are retired or not valid.  Everything else comes out as without it."""
 
     EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
 
-    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None, trace=None, trace_what=None, park=False):
+    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None, trace=None, trace_what=None, park=False, metrics=False):
         self.ro, self.T_max, self.ext = rollouts, int(T_max), int(ext)
+        self.with_metrics = bool(metrics)
+        self.metrics = []                  # one entry per generation run with metrics=True
         self.device_commit = bool(device_commit)
         self.park = bool(park)             # True, or _capi.PARK_* bits to go with PARK_FINISHED (PARK_REROUTE)
         self.park_mode = _capi.check_parking(_capi.PARK_FINISHED | (0 if park is True or not park else int(park)), None)[0]
@@ -789,6 +817,15 @@ class PerCarLMPC:
         finally:
             self.ro.park = own
 
+    def _take_metrics(self, valid):
+        """metrics[g] of the active session, before rollout_end: the valid cars of this generation up to their crossing steps."""
+        if self.with_metrics:
+            self.metrics.append(_lap_metrics_rows(self.ro.ctx, self.B, valid))
+
+    def _valid(self, done, st):
+        """The cars whose lap of this session counts: not retired, across the line, flagged with nothing but ST_INEXACT."""
+        return [b for b in range(self.B) if b not in self.retired and done[b] >= 0 and (int(st[b]) & ~_capi.ST_INEXACT) == 0]
+
     def _run(self):
         ro, ctx, B, N = self.ro, self.ro.ctx, self.B, self.ro.ctx.N
         gen = self.generation
@@ -825,6 +862,7 @@ class PerCarLMPC:
             if ro._fetch_trace(t, done) is not None:
                 self.traces.append(ro.last_trace)
             ro._fetch_parked()
+            self._take_metrics(self._valid(done, st))
         finally:
             ctx.rollout_end()
         self.last_status, self.last_done = st, done
@@ -885,6 +923,7 @@ class PerCarLMPC:
                     self.retired[b] = (gen, int(st[b]))
                     continue
                 valid.append(b)
+            self._take_metrics(valid)
             first = ctx.rollout_commit_laps(valid)[0] if valid else None
         finally:
             ctx.rollout_end()

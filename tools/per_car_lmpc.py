@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--horizon", type=int, default=12)
     ap.add_argument("--device-commit", action="store_true", help="laps are committed to the stores on the device (PerCarLMPC(device_commit=True)): same lap times, no log download")
     ap.add_argument("--park", action="store_true", help="parking (PerCarLMPC(park=True)): retired cars are not stepped, finished cars leave the launches, a generation ends when no car is live; same lap times")
+    ap.add_argument("--metrics", action="store_true", help="lap metrics reduced on the device (PerCarLMPC(metrics=True)): t_cross, ey_absmax, lane_excess_max, input_margin_min, alat_absmax and the realised stage cost under the config's dR and Qslack, per car and generation")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "per_car_lmpc.json"))
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -60,7 +61,7 @@ def main():
             pid = ro.run_pid_laps(np.full(B, 0.8), max_steps=1000, keep_invalid=True)           # (main.py:61-70, every car on its own vehicle)
             if seeds is None:
                 seeds = [int(l[4]) for l in pid]
-            loop = cls(ro, T_max=400, ext=40, device_commit=args.device_commit, park=args.park)
+            loop = cls(ro, T_max=400, ext=40, device_commit=args.device_commit, park=args.park, metrics=args.metrics)
             bad = [b for b, l in enumerate(pid) if l[4] < 0 or (l[5] & ~_capi.ST_INEXACT) != 0 or not np.all(np.isfinite(l[0]))]
             if bad:
                 raise SystemExit("PID lap of car(s) %s did not finish or was flagged: no seed lap" % bad)
@@ -69,6 +70,8 @@ def main():
                 loop.run()
             loop.close()
             result[name] = dict(session_steps=list(loop.steps), lap_steps=[t + [None] * (G - len(t)) for t in loop.lap_times], retired={str(b): list(v) for b, v in sorted(loop.retired.items())})
+            if args.metrics:
+                result[name]["metrics"] = _capi.metrics_report(loop.metrics, list(cfg.dR), list(cfg.Qslack))
     result["pid_lap_steps"] = seeds
     print("%-4s %-8s %-8s %-6s | %-28s | %-28s" % ("car", "mu", "m", "PID", "own safe set", "shared safe set"))
     for b in range(B):

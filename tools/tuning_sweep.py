@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--horizon", type=int, default=12)
     ap.add_argument("--park", action="store_true", help="parking (PerCarLMPC(park=True)): retired cars are not stepped, finished cars leave the launches, a generation ends when no car is live; same lap times")
+    ap.add_argument("--metrics", action="store_true", help="lap metrics reduced on the device (PerCarLMPC(metrics=True)): t_cross, ey_absmax, lane_excess_max, input_margin_min, alat_absmax and the realised stage cost under each car's own dR and Qslack, per car and generation")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tuning_sweep.json"))
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -49,7 +50,7 @@ def main():
         bad = [b for b, l in enumerate(pid) if l[4] < 0 or (l[5] & ~_capi.ST_INEXACT) != 0 or not np.all(np.isfinite(l[0]))]
         if bad:
             raise SystemExit("PID lap of car(s) %s did not finish or was flagged: no seed lap" % bad)
-        loop = rollout.PerCarLMPC(ro, T_max=400, ext=40, device_commit=True, tuning=rows, park=args.park)
+        loop = rollout.PerCarLMPC(ro, T_max=400, ext=40, device_commit=True, tuning=rows, park=args.park, metrics=args.metrics)
         loop.seed(pid)
         status = []
         for _ in range(G):
@@ -62,6 +63,8 @@ def main():
     result["status_per_generation"] = status
     result["park"] = bool(args.park); result["session_steps"] = list(loop.steps)
     result["retired"] = {str(b): list(v) for b, v in sorted(loop.retired.items())}
+    if args.metrics:
+        result["metrics"] = _capi.metrics_report(loop.metrics, rows[:, sl["dR"]], rows[:, sl["Qslack"]])
     print("%-4s %-8s %-8s %-8s %-6s | %s" % ("car", "Qslack1", "dR1", "Qterm x", "PID", "LMPC lap steps"))
     for b, (a, d, c) in enumerate(grid):
         print("%-4d %-8g %-8g %-8g %-6d | %s" % (b, a, d, c, result["pid_lap_steps"][b], result["lap_steps"][b]))
