@@ -24,8 +24,17 @@ extern "C" {
 #define LMPC_NU 2
 #define LMPC_MAX_TRACK_ROWS 16
 #define LMPC_MAX_USED_LAPS 32      /* trToUse / numSS_it upper bound (the reference takes any: PredictiveControllers.py:293-311, PredictiveModel.py:31) */
-#define LMPC_MAX_N 64
-#define LMPC_MAX_SS_POINTS 384     /* numSS_points upper bound = 32 laps x 12 points (beyond 58 the terminal block takes several columns per lane) */
+#define LMPC_MAX_N 64              /* horizon: 2 <= N <= 64 */
+#define LMPC_MAX_SS_POINTS 384     /* numSS_points upper bound = 32 laps x 12 points (beyond 58 the terminal block takes several columns per lane); at most 63 points per
+                                      lap (the selection's window of points-per-lap + 1 rows is one row per lane).  With an odd number of points per lap the reference's
+                                      window has one row more than its QP has columns and the reference cannot assemble the step; the library keeps the first
+                                      points-per-lap rows of that window.
+                                      The one-wave layout of every pair of the range fits a CU (at most 108 KB of LDS per QP).  The two- and four-wave kernels
+                                      exist where their layout fits the 160 KB as well -- not at N = 64 from 96 points or N = 40 with 384: such a pair runs one wave per QP at
+                                      every batch size (lmpc_solver_lds reports 0 for them).  The runtime-(N, S) kernel shares nothing between phases and stops earlier:
+                                      N = 64 beyond 146 points (209 KB at 384) and N = 40 beyond 366 are LMPC_E_ARG there and need their fixed variant.  A fixed variant
+                                      exists where its build passes the ISA check (racinglmpc_amd.build): (40, 384), (64, 192) and (64, 384) do and are tested; the other
+                                      pairs beyond the runtime kernel's limit have not been compiled -- one whose build fails would be refused with LMPC_E_ARG */
 
 /* error codes (function return values) */
 #define LMPC_OK 0
@@ -557,6 +566,10 @@ int lmpc_selftest(lmpc_ctx *);                   /* device self test of the cros
 /* Developer switch (environment, read at lmpc_create): LMPC_MW_MAX_BATCH=<n> overrides the largest batch that runs four waves per
  * QP (default: the number of CUs; 0 forces the one-wave kernel everywhere).  Results do not depend on it beyond summation order. */
 int lmpc_solver_waves(lmpc_ctx *, int B);         /* wavefronts per QP the solve kernel uses for a batch of B (4 or 2: lmpc_solve_kernel_mw, 1: lmpc_solve_kernel) */
+int lmpc_solver_lds(lmpc_ctx *, unsigned long long out4[4]);
+        /* what the routes of this context's (N, numSS_points) are chosen from: dynamic LDS per QP, in bytes, of the one-wave kernel with [A_k | B_k] in LDS, of the
+         * one-wave kernel with [A_k | B_k] in global memory (0: this (N, numSS_points) has none) and of the multi-wave kernels (0: none -- the runtime kernel, and a
+         * fixed (N, numSS_points) whose multi-wave layout exceeds the 160 KB of a CU: one wave per QP at every batch size); out4[3]: CUs of the device */
 int lmpc_set_profiling(lmpc_ctx *, int every);    /* 0: off; k > 0: HIP events on the launch stream around every k-th launch of each kernel (an event
                                                      record costs ~4 us of stream time: k = 1 adds 15 us to a two-kernel step) */
 int lmpc_get_stats(lmpc_ctx *, lmpc_stats *out);  /* drains pending events */

@@ -177,7 +177,7 @@ EXPORTS = [
     "lmpc_dev_alloc", "lmpc_dev_free", "lmpc_dev_upload", "lmpc_dev_download", "lmpc_dev_sync", "lmpc_step_batch_dev",
     "lmpc_lti_regression", "lmpc_lti_regression_batch", "lmpc_comm_unique_id", "lmpc_comm_init", "lmpc_comm_destroy", "lmpc_comm_info", "lmpc_comm_allgather_dev", "lmpc_comm_allgather",
     "lmpc_comm_allreduce_max", "lmpc_comm_barrier", "lmpc_rollout_exchange",
-    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
+    "lmpc_set_profiling", "lmpc_get_stats", "lmpc_reset_stats", "lmpc_selftest", "lmpc_solver_waves", "lmpc_solver_lds", "lmpc_plant_step_batch", "lmpc_plant_params_default", "lmpc_plant_set_params", "lmpc_plant_get_params", "lmpc_noise_raw", "lmpc_noise_fill", "lmpc_rollout_set_noise", "lmpc_rollout_get_noise", "lmpc_global_position_batch", "lmpc_local_position_batch", "lmpc_track_angle_batch", "lmpc_state_from_global_batch", "lmpc_rollout_begin", "lmpc_rollout_begin_mpc", "lmpc_rollout_pid", "lmpc_rollout_run", "lmpc_rollout_fetch", "lmpc_rollout_end", "lmpc_rollout_release", "lmpc_ss_extend_lap", "lmpc_ss_truncate_lap",
     "lmpc_rollout_commit_laps", "lmpc_rollout_extend_laps", "lmpc_rollout_lap_metrics", "lmpc_debug_model_image", "lmpc_tuning_from_config", "lmpc_tuning_set", "lmpc_tuning_get",
     "lmpc_track_row_from_config", "lmpc_track_set", "lmpc_track_get", "lmpc_ss_add_trajectory_on", "lmpc_ss_extend_lap_on",
     "lmpc_rollout_set_trace", "lmpc_rollout_get_trace", "lmpc_rollout_trace_bytes", "lmpc_rollout_fetch_trace",
@@ -1260,6 +1260,12 @@ class Context:
 
     def solver_waves(self, B):
         return int(self.lib.lmpc_solver_waves(self._h, C.c_int(int(B))))
+
+    def solver_lds(self):
+        """dict lds_1w, lds_1w_abg, lds_mw (dynamic LDS per QP in bytes; 0: this (N, numSS_points) has no such kernel) and n_cu: what the routes are chosen from."""
+        out = (C.c_ulonglong * 4)()
+        _chk(self.lib.lmpc_solver_lds(self._h, out))
+        return dict(lds_1w=int(out[0]), lds_1w_abg=int(out[1]), lds_mw=int(out[2]), n_cu=int(out[3]))
 
     def global_position_batch(self, s, ey):
         """Map.getGlobalPosition for arrays of (s, ey): returns xy (n, 2) and status (n,)."""

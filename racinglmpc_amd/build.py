@@ -10,7 +10,9 @@ VSRC = os.path.join(_HERE, "csrc", "lmpc_variant.hip")
 # (N, numSS_points) pairs compiled into liblmpc_hip.so itself (lmpc_capi.hip: builtin_variant) and the extra ones build() prepares as
 # shared objects of their own, in parallel; anything else is built the first time a Context asks for it
 BUILTIN = {(n, s) for n in (8, 12, 14, 20, 40) for s in (0, 48)}
-EXTRA_VARIANTS = [(10, 48), (16, 48), (24, 48), (30, 48), (12, 24), (12, 36), (16, 36), (10, 0), (16, 0), (12, 60), (12, 72), (12, 96), (14, 160), (12, 360)]
+# (first the corners of the supported range, tests/envelope_cases.py: the longest compiles, started first)
+EXTRA_VARIANTS = [(64, 48), (63, 48), (32, 384), (12, 384), (64, 384), (40, 384), (64, 0), (64, 192), (12, 59), (7, 48), (2, 48), (2, 0),
+                  (10, 48), (16, 48), (24, 48), (30, 48), (12, 24), (12, 36), (16, 36), (10, 0), (16, 0), (12, 60), (12, 72), (12, 96), (14, 160), (12, 360)]
 OUT = os.path.join(_HERE, "liblmpc_hip.so")
 
 
@@ -21,7 +23,9 @@ OUT = os.path.join(_HERE, "liblmpc_hip.so")
 # less hoisting, fewer live registers), headline and sweep within +-1 % (profiles/r5zz_bench.json).  So it is a base option now, not an accident of the fence.
 LIB_MLLVM = ["-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-disable-machine-licm"]
 SALTS = [[], ["-mllvm", "-disable-postra-machine-licm"], ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"], ["-mllvm", "-amdgpu-disable-loop-alignment"]]
-VARIANT_SALTS = [[], ["-mllvm", "-disable-postra-machine-licm"], ["-mllvm", "-disable-machine-licm"], ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"], ["-mllvm", "-amdgpu-disable-loop-alignment"]]
+VARIANT_SALTS = [[], ["-mllvm", "-disable-postra-machine-licm"], ["-mllvm", "-disable-machine-licm"], ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"], ["-mllvm", "-amdgpu-disable-loop-alignment"],
+                 # (N = 40 with 384 safe-set points, a variant without multi-wave kernels: each single option leaves the one-wave retry kernel flagged, the third and fourth together clear it)
+                 ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-use-amdgpu-trackers=1"]]
 
 
 def compile_checked(cmd, out, verbose=False, salts=None):
@@ -106,10 +110,15 @@ def variant_path(N, S):
 
 
 def build_variant(N, S, force=False):
-    """One (N, numSS_points) instantiation of the solve kernels as liblmpc_var_N<N>_S<S>.so (csrc/lmpc_variant.hip); ~20 s of hipcc."""
+    """One (N, numSS_points) instantiation of the solve kernels as liblmpc_var_N<N>_S<S>.so (csrc/lmpc_variant.hip); 20 s of hipcc at the reference's sizes, minutes
+    at N = 64.  The one-wave layout of every pair of the range fits a CU (108 KB of LDS per QP at N = 64 with 384 points); the two- and four-wave kernels are part of
+    the object only where their layout fits the 160 KB as well (not at N = 64 from 96 points or N = 40 at 384: such a pair runs one wave per QP at every batch size).
+    Raises RuntimeError where no code-generation option gives a build that passes the ISA check (compile_checked); Context() then tries the runtime kernel, whose layout
+    does not fit a CU at N = 64 beyond 146 points or N = 40 beyond 366 -- such a pair would be refused with LMPC_E_ARG.  Of these only the pairs build() prepares and the
+    GPU tests run -- (40, 384), (64, 192), (64, 384) -- are known to build; the other (N, numSS_points) with N from 37 and wide safe sets have not been compiled."""
     N, S = int(N), int(S)
     if not (2 <= N <= 64 and 0 <= S <= 384):
-        raise ValueError("solve kernels exist for 2 <= N <= 64 and numSS_points <= 384 (got N=%d, numSS_points=%d)" % (N, S))
+        raise ValueError("solve kernels exist for 2 <= N <= 64 and 0 <= numSS_points <= 384 (got N=%d, numSS_points=%d)" % (N, S))
     out = variant_path(N, S)
     deps = [VSRC] + KDEPS
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):

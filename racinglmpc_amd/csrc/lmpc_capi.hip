@@ -243,7 +243,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 112; }
+int lmpc_version(void) { return 113; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -432,8 +432,10 @@ static int create_body(lmpc_ctx *c) {
     // ... and never beyond what is resident at once: a second round of two-wave work-groups loses to the one-wave kernel (N = 12, batch 1024,
     // solve kernel: 0.425 ms in two rounds against 0.349 ms; round 4 found it out the hard way -- 512 bytes more static LDS, three QPs per CU instead of four)
     if (c->var.occ_mw2 > 0 && c->mw2_max_batch > c->var.occ_mw2 * c->n_cu) c->mw2_max_batch = c->var.occ_mw2 * c->n_cu;
-    if (c->var.lds_mw == 0) { c->mw_max_batch = 0; c->mw2_max_batch = 0; }        // (a variant without multi-wave kernels)
     if (const char *e = dev_knob("LMPC_MW2_MAX_BATCH")) c->mw2_max_batch = atoi(e);        // (experiments)
+    // a variant without multi-wave kernels -- the runtime kernel, and a fixed (N, S) whose multi-wave layout exceeds the LDS of a CU (lmpc_variant.hip.h: has_mw) --
+    // runs one wave per QP at every batch size, whatever the rules and knobs above said (the four-waves-throughout rule included: there is no four-wave kernel)
+    if (c->var.lds_mw == 0) { c->mw_max_batch = 0; c->mw2_max_batch = 0; }
     // Fused step (regression inside the one-wave solve kernel): bit-identical results, 42 MB less HBM traffic per step at batch 4096, but
     // MEASURED SLOWER -- 1.37 vs 1.01 + 0.23 ms at batch 4096, 2.48 vs 1.81 + 0.44 ms at batch 8192 with six QPs per CU; 1.92 vs 1.45 + 0.41 ms
     // at batch 8192 with eight: the regression's short dependent chains (DPP minima, 5 x 5 Cholesky, scattered L2 reads) want the four waves
@@ -2420,6 +2422,12 @@ int lmpc_solver_waves(lmpc_ctx *c, int B) {
     if (B <= c->mw_max_batch) return 4;
     if (B <= c->mw2_max_batch) return 2;
     return 1;
+}
+
+int lmpc_solver_lds(lmpc_ctx *c, unsigned long long out4[4]) {
+    ARGCHK(c && out4);
+    out4[0] = c->var.lds_1w; out4[1] = c->var.lds_1w_abg; out4[2] = c->var.lds_mw; out4[3] = (unsigned long long)c->n_cu;
+    return LMPC_OK;
 }
 
 int lmpc_set_profiling(lmpc_ctx *c, int every) { ARGCHK(c); c->profiling = every > 0 ? every : 0; return LMPC_OK; }

@@ -62,6 +62,8 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
     double *par = sm + LL::opar;
     const double *Fx = par + PAR_FX, *Fu = par + PAR_FU, *bx = par + PAR_BX, *bu = par + PAR_BU, *Q2 = par + PAR_Q2, *Qf2 = par + PAR_QF2,
                  *R2 = par + PAR_R2, *dR2 = par + PAR_DR2, *T2p = par + PAR_T2, *xRef = par + PAR_XREF;
+    // (static LDS: everything declared __shared__ in this kernel counts against the 160 KB of a CU beside the dynamic layout -- lmpc_variant.hip.h, mw_static, is an upper
+    //  bound of its sum, (8 N + 127) doubles today, and decides whether an (N, S) has the multi-wave kernels at all: a new array here has to fit under that bound or raise it)
     __shared__ double red[10 * 4];                           // cross-wave reduction slots
     __shared__ double phi_sh[8 * N];
     __shared__ int st_sh, bad_sh;

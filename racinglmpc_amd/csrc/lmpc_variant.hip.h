@@ -55,8 +55,14 @@ template <class K, class KL> static bool lmpc_raise_lds_limits(const lmpc_solve_
 }
 
 template <int N, int S> struct lmpc_variant_launchers {
-    // (every supported S has the multi-wave kernels: wave 0 carries ceil((S + 6) / 64) terminal-block columns per lane)
+    // (every supported S has the multi-wave kernels where their layout fits: wave 0 carries ceil((S + 6) / 64) terminal-block columns per lane)
     static constexpr size_t lds1 = (size_t)solve_lds1<N, S>::tot * sizeof(double), ldsm = (size_t)solve_lds<N, S>::tot * sizeof(double);
+    // The multi-wave layout shares nothing between phases and outgrows the 160 KB of a CU long before the one-wave layout does (N = 64 from 96 safe-set
+    // points, N = 40 at 384).  Such an (N, S) has no multi-wave kernels -- they are not instantiated -- and runs one wave per QP at every batch size (lds_mw = 0:
+    // lmpc_capi.hip, create_body).  mw_static: an upper bound of the multi-wave kernel's static LDS (red, phi_sh, gs0, ss_rowsum, sel_start, two words), which
+    // counts against the same 160 KB.
+    static constexpr size_t mw_static = (size_t)(8 * N + 160) * sizeof(double);
+    static constexpr bool has_mw = ldsm + LMPC_SSTAB_LDS + mw_static <= (size_t)160 * 1024;
     // fused step (io.mode & 4): the regression's work space sits behind [A_k | B_k], C_k; it fits the solve's footprint at the reference's
     // settings (4 laps x 7 points) and grows it a little beyond
     static size_t lds_for(const lmpc_dev_params &p, const lmpc_solve_io &io) {
@@ -94,7 +100,8 @@ template <int N, int S> struct lmpc_variant_launchers {
 #ifdef LMPC_WITH_CD
         if constexpr (has_cd) { if (!lmpc_raise_lds_limit((const void *)lmpc_solve_kernel_cd<N, S>, lds_cd(true))) return false; }
 #endif
-        return lmpc_raise_lds_limits(one_wave<false>()) && lmpc_raise_lds_limits(one_wave<true>()) && lmpc_raise_lds_limits(multi_wave<4>()) && lmpc_raise_lds_limits(multi_wave<2>());
+        if constexpr (has_mw) { if (!(lmpc_raise_lds_limits(multi_wave<4>()) && lmpc_raise_lds_limits(multi_wave<2>()))) return false; }
+        return lmpc_raise_lds_limits(one_wave<false>()) && lmpc_raise_lds_limits(one_wave<true>());
     }
 
     static int l1(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) {
@@ -111,22 +118,29 @@ template <int N, int S> struct lmpc_variant_launchers {
     }
 };
 
-// fills the table and raises the kernels' dynamic-LDS limit; false if the device refuses (footprint beyond 160 KB)
+// fills the table and raises the kernels' dynamic-LDS limit; false if the device refuses (a one-wave footprint beyond 160 KB -- no supported (N, S) has one:
+// the largest, N = 64 with 384 safe-set points, takes 108 KB).  An (N, S) whose multi-wave layout does not fit a CU (has_mw) gets lds_mw = 0 and the one-wave
+// launcher in the multi-wave slots.
 template <int N, int S> static bool lmpc_variant_fill(lmpc_variant_api *v) {
     static_assert(N >= 2 && N <= LMPC_MAX_N && S >= 0 && S <= LMPC_MAX_SS_POINTS, "unsupported variant");
     using L = lmpc_variant_launchers<N, S>;
     if (!L::raise_limits()) return false;
     v->N = N; v->S = S;
-    v->lds_mw = L::ldsm; v->lds_1w = L::lds1; v->lds_1w_abg = L::use_abg ? L::lds1g : 0; v->lds_cd = L::lds_cd(false); v->lds_cd_q = L::lds_cd(true);
-    v->launch_1w = &L::l1; v->launch_retry = &L::lr; v->launch_mw4 = &L::l4; v->launch_mw2 = &L::l2; v->launch_cd = &L::lc;
-    int nb = 0; const auto m2 = L::template multi_wave<2>();
-    v->occ_mw2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)m2.plain, m2.threads, m2.lds) == hipSuccess ? nb : 0;
+    v->lds_1w = L::lds1; v->lds_1w_abg = L::use_abg ? L::lds1g : 0; v->lds_cd = L::lds_cd(false); v->lds_cd_q = L::lds_cd(true);
+    v->launch_1w = &L::l1; v->launch_retry = &L::lr; v->launch_cd = &L::lc;
+    if constexpr (L::has_mw) {
+        v->lds_mw = L::ldsm; v->launch_mw4 = &L::l4; v->launch_mw2 = &L::l2;
+        int nb = 0; const auto m2 = L::template multi_wave<2>();
+        v->occ_mw2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)m2.plain, m2.threads, m2.lds) == hipSuccess ? nb : 0;
+    } else {
+        v->lds_mw = 0; v->launch_mw4 = &L::l1; v->launch_mw2 = &L::l1; v->occ_mw2 = 0;
+    }
     return true;
 }
 
 #ifndef LMPC_VARIANT_TU
 // The runtime-(N, S) kernel behind the same table (lmpc_solve_rt.hip.h): one wave per QP whatever the batch size, no multi-wave / condensed / fused forms.
-// false if the footprint of this (N, S) exceeds the LDS of a CU (N = 64 with 384 safe-set points does: 171 KB).
+// false if the footprint of this (N, S) exceeds the LDS of a CU: N = 64 beyond 146 safe-set points (209 KB at 384), N = 40 beyond 366 -- only a fixed variant serves those.
 static bool lmpc_variant_fill_rt(lmpc_variant_api *v, int N, int S) {
     if (N < 2 || N > LMPC_MAX_N || S < 0 || S > LMPC_MAX_SS_POINTS) return false;
     const size_t lds = (size_t)rt_layout(N, S).tot * sizeof(double);

@@ -11,19 +11,41 @@ import numpy as np
 _JOB = {}
 
 
+def select_laps(xS, uS, Qf, z, ppl, xPrev, cur_it, tstep, N, TL):
+    """SS_sel, Qfun_sel, Succ, SuccU of `ppl` points from each of the laps xS (oracle.terminal_components with numSS_Points = ppl len(xS)).
+
+    An even ppl is the reference's own selection.  With an odd ppl the reference's window arithmetic (selectPoints :492-495: numPoints = ppl + 1 is even, and
+    range(-numPoints / 2 + MinNorm, numPoints / 2 + MinNorm + 1) has numPoints + 1 entries) selects ppl + 1 columns per lap wherever the window is centred, one more
+    than its QP has (numSS_Points = ppl numSS_it columns, :340-362): the reference cannot assemble such a step, so there is nothing of it to restate.  The library
+    defines the case -- columns start .. start + ppl - 1 of the same window, successors start + 1 .. start + ppl (lmpc_solve_common.hip.h, k2_select) -- and the
+    records follow that rule: the first ppl columns of the reference's window, which is the reference's selection itself for every even ppl."""
+    from oracle import lmpc_oracle as orc
+    L = len(xS)
+    if ppl % 2 == 0:
+        return orc.terminal_components(xS, uS, Qf, [x.shape[0] for x in xS], z, ppl * L, L, xPrev, cur_it, tstep, N, TL)
+    SSsel = np.empty((6, 0)); Succ = np.empty((6, 0)); SuccU = np.empty((2, 0)); Qsel = np.empty(0)
+    for jj in np.argsort(np.array([x.shape[0] for x in xS]))[:L]:
+        P, U, Q = orc.select_points(xS[jj], uS[jj], Qf[jj], jj, z, ppl + 1, xPrev, cur_it, tstep, N, TL)
+        SSsel = np.append(SSsel, P[:, :ppl], axis=1); Qsel = np.append(Qsel, Q[:ppl], axis=0)
+        Succ = np.append(Succ, P[:, 1:ppl + 1], axis=1); SuccU = np.append(SuccU, U[:, 1:ppl + 1], axis=1)
+    return SSsel, Qsel, Succ, SuccU
+
+
 def _work(b):
     from oracle import lmpc_oracle as orc
     j = _JOB
     inp, N, TL, pt = j["inp"], j["N"], j["TL"], j["pt"]
-    xS = [l[0] for l in j["laps"]]; uS = [l[1] for l in j["laps"]]
-    A, B, C = orc.compute_ltv_dynamics(xS, uS, list(range(len(xS))), pt, inp["xLin"][b], inp["uLin"][b], N)
+    xM = [l[0] for l in j["laps"]]; uM = [l[1] for l in j["laps"]]
+    A, B, C = orc.compute_ltv_dynamics(xM, uM, list(range(len(xM))), pt, inp["xLin"][b], inp["uLin"][b], N)
+    ss = j["laps"] if j.get("ss_laps") is None else j["ss_laps"]
+    xS = [l[0] for l in ss]; uS = [l[1] for l in ss]
     Qf = [orc.compute_cost(x, TL) for x in xS]
     z = inp["zt"][b].copy()
     if z[4] - inp["x0"][b][4] > TL / 2:
         z[4] = np.max([z[4] - TL, 0])
     L = len(xS)
     xPrev = inp["xPredPrev"][b] if "hasPred" in inp and inp["hasPred"][b] else None          # (the reference's `self.xPred == []` on a first step)
-    SSsel, Qsel, Succ, SuccU = orc.terminal_components(xS, uS, Qf, [x.shape[0] for x in xS], z, 12 * L, L, xPrev, L, int(inp["timeStep"][b]), N, TL)
+    SSsel, Qsel, Succ, SuccU = select_laps(xS, uS, Qf, z, j.get("ppl", 12), xPrev, L, int(inp["timeStep"][b]), N, TL)
     res = dict(b=b, A=A, B=B, C=C, SSsel=SSsel, Qsel=Qsel, Succ=Succ, SuccU=SuccU)
     if b in j["solve"]:
         P, q, Ao, l, u = orc.assemble_lmpc_qp(j["par"], A, B, C, inp["x0"][b], inp["uOld"][b], SSsel, Qsel)
@@ -40,9 +62,10 @@ def _objf(P, q):
     return lambda z: float(0.5 * z @ P @ z + q @ z)
 
 
-def oracle_batch(par, pt, TL, laps, N, inp, idx, solve_idx=(), procs=None):
+def oracle_batch(par, pt, TL, laps, N, inp, idx, solve_idx=(), procs=None, ss_laps=None, ppl=12):
     """Oracle results for the problems `idx` of `inp` (stores: `laps`, used both as regression store and as safe set, in the library's order):
-    list of dicts b, A, B, C, SSsel (6, S), Qsel, Succ, SuccU and -- for b in solve_idx -- opt (the certified optimum z*), cert, obj."""
+    list of dicts b, A, B, C, SSsel (6, S), Qsel, Succ, SuccU and -- for b in solve_idx -- opt (the certified optimum z*), cert, obj.
+    ss_laps: the safe set where it is not the regression store;  ppl: safe-set points per lap (numSS_Points / numSS_it; select_laps)."""
     import multiprocessing as mp
     try:
         from threadpoolctl import threadpool_limits
@@ -50,7 +73,8 @@ def oracle_batch(par, pt, TL, laps, N, inp, idx, solve_idx=(), procs=None):
     except Exception:                                 # noqa: BLE001
         lim = None
     _JOB.clear()
-    _JOB.update(par=par, pt=np.asarray(pt), TL=float(TL), laps=[(np.asarray(x), np.asarray(u)) for x, u in laps], N=int(N), inp=inp, solve=set(int(b) for b in solve_idx))
+    _JOB.update(par=par, pt=np.asarray(pt), TL=float(TL), laps=[(np.asarray(x), np.asarray(u)) for x, u in laps], N=int(N), inp=inp, solve=set(int(b) for b in solve_idx),
+                ss_laps=None if ss_laps is None else [(np.asarray(x), np.asarray(u)) for x, u in ss_laps], ppl=int(ppl))
     idx = [int(b) for b in idx]
     n = procs or max(1, min(64, (os.cpu_count() or 2) - 2, len(idx)))
     try:
