@@ -88,7 +88,8 @@ typedef struct {
 } lmpc_config;
 
 typedef struct {
-    double ms_regress, ms_solve;      /* accumulated HIP-event time of the two kernels (profiling on) */
+    double ms_regress, ms_solve;      /* accumulated HIP-event time of the two kernels (profiling on).  A regression that ran ahead on the look-ahead stream
+                                         (lmpc_step_batch_dev, queued steps) shares the chip with the previous step's solve: its time includes the wait for a free CU */
     long long n_regress, n_solve;     /* launches accumulated */
     long long qp_solved;              /* problems passed through the solve kernel */
     long long ipm_iters;              /* interior-point iterations accumulated by the host-buffer entry points (lmpc_step_batch, lmpc_qp_solve_batch) */
@@ -101,19 +102,24 @@ int lmpc_create(const lmpc_config *cfg, lmpc_ctx **out);         /* MPC/LMPC.__i
 int lmpc_create_ex(const lmpc_config *cfg, unsigned flags, lmpc_ctx **out);
         /* lmpc_create with flags.  LMPC_CREATE_RUNTIME_KERNEL: an (N, numSS_points) pair that is neither built in nor available as a variant library is served by
          * the runtime-(N, S) solve kernel (any horizon without a compiler on the box, several times slower) instead of LMPC_E_VARIANT -- MPCParams.N is a plain
-         * parameter in the reference (:63-107, main.py:43).  LMPC_CREATE_FORCE_RUNTIME_KERNEL: use that kernel even where a fast one exists (tests) */
+         * parameter in the reference (:63-107, main.py:43).  LMPC_CREATE_FORCE_RUNTIME_KERNEL: use that kernel even where a fast one exists (tests).
+         * LMPC_CREATE_NO_K1_AHEAD: no look-ahead regression -- for contexts of which several run side by side on one device (racinglmpc_amd._capi.ContextPool): their batches
+         * fill each other's idle CUs already, and the look-ahead's event operations measured 3-5 % slower there */
 #define LMPC_CREATE_RUNTIME_KERNEL 1u
 #define LMPC_CREATE_FORCE_RUNTIME_KERNEL 2u
+#define LMPC_CREATE_NO_K1_AHEAD 4u       /* queued lmpc_step_batch_dev steps keep their regression on the context's stream (see lmpc_step_batch_dev); same results */
 int lmpc_solver_kind(lmpc_ctx *);                                /* 0: built-in solve kernels, 1: variant library, 2: runtime-(N, S) kernel */
 int lmpc_destroy(lmpc_ctx *ctx);
 const char *lmpc_last_error(void);
 const char *lmpc_active_knobs(void);                             /* developer environment variables this process has acted on ("NAME=value;..."; "" = none): LMPC_K1_QG,
-                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG, LMPC_TRACE_OWN_STREAM -- route / grid
+                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG, LMPC_TRACE_OWN_STREAM, LMPC_K1_AHEAD, LMPC_K1_AHEAD_MAX_BATCH -- route / grid
                                                                     choices, each announced once on stderr; no reference counterpart.  Bit-identical results: LMPC_TRACE_OWN_STREAM
                                                                     (traced sessions: the trace kernel on a stream of its own instead of the plant stream), LMPC_K1_QG, LMPC_K1_RPL16
                                                                     (regression grid / scan build: A, B, C do not depend on either), LMPC_FUSE (fused one-wave step against the
                                                                     two-kernel one-wave step; ignored by the runtime-(N, S) kernel, which has no fused form), LMPC_NO_ABG
-                                                                    ([A_k | B_k] in LDS instead of global memory).  LMPC_MW_MAX_BATCH and LMPC_MW2_MAX_BATCH move a batch to
+                                                                    ([A_k | B_k] in LDS instead of global memory), LMPC_K1_AHEAD (=0 at lmpc_create: queued
+                                                                    lmpc_step_batch_dev steps keep their regression on the context's stream, behind the previous solve,
+                                                                    instead of the look-ahead stream beside it; LMPC_K1_AHEAD_MAX_BATCH: the largest batch that chains).  LMPC_MW_MAX_BATCH and LMPC_MW2_MAX_BATCH move a batch to
                                                                     another solve kernel (four / two / one wave(s) per QP): A, B, C, the selection and the status word stay
                                                                     bit-identical, the QP answer agrees to the termination rule's bound (x, u within 2e-7: measured by
                                                                     tests/test_gpu_routes.py).  LMPC_CD (condensed kernel, opt-in builds only): another QP method, same optimum
@@ -305,6 +311,13 @@ typedef struct {          /* all device pointers, layouts as in lmpc_step_batch.
     double *qSel;          /* B x S or NULL */
 } lmpc_step_dev_args;
 int lmpc_step_batch_dev(lmpc_ctx *, int B, const lmpc_step_dev_args *args);   /* async on the ctx stream; status as in lmpc_step_batch */
+        /* Queued steps.  When the previous call on the context was also a two-kernel lmpc_step_batch_dev, this step's regression is queued on a second stream of the
+         * context's and runs BESIDE the previous step's solve (it needs nothing of it); the solves themselves stay strictly one after the other, each behind its own
+         * regression.  The regression writes a hand-over set of the context's, which the solve reads, and copies A / Bm / C to the caller's arrays where given: those are
+         * outputs only, nothing on the device reads them except a retry pass at the next drain, so the caller keeps them (and every input: xLin / uLin of step i + 1 are
+         * read while step i solves) untouched until lmpc_dev_sync, as before.  Any other call on the context that queues work or edits what the regression reads (lap
+         * stores, lap table, track / tuning rows, lmpc_dev_upload, ...) breaks the chain: the next step's regression goes behind it on the context's stream.  A drain of
+         * the context (lmpc_dev_sync, lmpc_dev_download) covers both streams.  Results are bit-identical to the unchained step; LMPC_K1_AHEAD=0 turns chaining off. */
 
 /* ---- caller side of the path, next row of SURVEY 8(f): plant integrator + device-resident closed-loop laps ---- */
 /* Map.getGlobalPosition (Track.py:135-189), batched: curvilinear (s, ey) -> inertial (X, Y) for n points on the track given
@@ -591,6 +604,9 @@ int lmpc_debug_rollout_qp(lmpc_ctx *, int b0, int n, double *A, double *B, doubl
         /* (every build) the QP the LAST simulated step solved for rollouts b0 .. b0 + n - 1: the regression's A, B, C, the kernel's answer (xPred, uPred, lambda, zt / zt_u),
          * and (capture on) the selection with its successor rows -- what tests/closed_loop_probe.py hands to the oracle; x0 / uOld are rows t - 1 / t - 2 of the
          * session's logs.  Any pointer may be NULL */
+int lmpc_debug_k1_ahead(lmpc_ctx *, long long out[2]);
+        /* (every build) regression launches of lmpc_step_batch_dev since lmpc_create: out[0] chained (on the look-ahead stream, beside the previous step's solve),
+         * out[1] unchained (on the context's stream); the fused step launches no regression and counts as neither */
 int lmpc_debug_exec_audit(lmpc_ctx *, unsigned long long *out16, int reset);
         /* -DLMPC_EXEC_AUDIT: out16[site] = calls of a cross-lane primitive (DPP / permlane / bpermute reductions, MFMA stages) of the built-in
          * kernels that found an incomplete EXEC mask, out16[8 + site] = calls; sites are listed in csrc/lmpc_kernels.hip.h */

@@ -17,7 +17,7 @@ MAX_TRACK_ROWS = 16
 MAX_USED_LAPS = 32
 COMM_ID_BYTES = 128
 E_VARIANT = -5
-CREATE_RUNTIME_KERNEL, CREATE_FORCE_RUNTIME_KERNEL = 1, 2
+CREATE_RUNTIME_KERNEL, CREATE_FORCE_RUNTIME_KERNEL, CREATE_NO_K1_AHEAD = 1, 2, 4
 
 ST_MAXITER, ST_REG_SINGULAR, ST_NO_SEGMENT, ST_WINDOW, ST_NUMERIC, ST_NOT_INTERIOR, ST_INEXACT, ST_INFEASIBLE = 1, 2, 4, 8, 16, 32, 64, 128
 
@@ -183,6 +183,7 @@ EXPORTS = [
     "lmpc_rollout_set_trace", "lmpc_rollout_get_trace", "lmpc_rollout_trace_bytes", "lmpc_rollout_fetch_trace",
     "lmpc_rollout_set_parking", "lmpc_rollout_get_parking", "lmpc_rollout_parked_at", "lmpc_debug_live_compact",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
+    "lmpc_debug_k1_ahead",
 ]
 
 _lib = None
@@ -571,7 +572,9 @@ def set_arr(field, values):
 class Context:
     """One lmpc_ctx: device lap stores + batched solver for a fixed (N, safe-set size) configuration."""
 
-    def __init__(self, cfg, runtime_kernel=False):
+    def __init__(self, cfg, runtime_kernel=False, k1_ahead=True):
+        """k1_ahead=False: queued step_batch_dev steps keep their regression on the context's stream (LMPC_CREATE_NO_K1_AHEAD; ContextPool members: several batches in
+        flight fill the idle CUs already, and the look-ahead's event operations only cost them)."""
         self.lib = load()
         self.cfg = cfg
         self.N = cfg.N
@@ -581,20 +584,21 @@ class Context:
         self._ro_trace = None
         self._h = C.c_void_p()
         self._pid = os.getpid()         # the process that owns the device context (see close)
+        base = 0 if k1_ahead and not _POOL_MEMBER else CREATE_NO_K1_AHEAD
         if runtime_kernel:              # (tests: the runtime-(N, S) kernel even where a fast one exists)
-            rc = self.lib.lmpc_create_ex(C.byref(cfg), C.c_uint(CREATE_FORCE_RUNTIME_KERNEL), C.byref(self._h))
+            rc = self.lib.lmpc_create_ex(C.byref(cfg), C.c_uint(base | CREATE_FORCE_RUNTIME_KERNEL), C.byref(self._h))
         else:
-            rc = self.lib.lmpc_create(C.byref(cfg), C.byref(self._h))
+            rc = self.lib.lmpc_create_ex(C.byref(cfg), C.c_uint(base), C.byref(self._h)) if base else self.lib.lmpc_create(C.byref(cfg), C.byref(self._h))
         if rc == E_VARIANT:             # (N, numSS_points) outside the built-in set: compile its shared object once (hipcc, ~20 s), then retry ...
             from . import build
             try:
                 build.build_variant(self.N, self.S)
-                rc = self.lib.lmpc_create(C.byref(cfg), C.byref(self._h))
+                rc = self.lib.lmpc_create_ex(C.byref(cfg), C.c_uint(base), C.byref(self._h))
             except (OSError, RuntimeError, ValueError, subprocess.SubprocessError) as e:
                 # ... and where that is not possible (no hipcc on the box, a failed build): the runtime-(N, S) kernel serves the horizon, several times slower.
                 # MPCParams.N is a plain parameter in the reference (PredictiveControllers.py:63-107, main.py:43): LMPC_E_VARIANT never reaches a user.
                 warnings.warn("no solve-kernel variant for N = %d, numSS_points = %d (%s): using the runtime-(N, S) kernel" % (self.N, self.S, str(e).splitlines()[0][:120]))
-                rc = self.lib.lmpc_create_ex(C.byref(cfg), C.c_uint(CREATE_RUNTIME_KERNEL), C.byref(self._h))
+                rc = self.lib.lmpc_create_ex(C.byref(cfg), C.c_uint(base | CREATE_RUNTIME_KERNEL), C.byref(self._h))
         _chk(rc)
         self.solver_kind = int(self.lib.lmpc_solver_kind(self._h))      # 0 built-in, 1 variant library, 2 runtime-(N, S) kernel
 
@@ -1338,6 +1342,12 @@ class Context:
         v = np.array(list(out), dtype=np.uint64)
         return v[:8], v[8:]
 
+    def debug_k1_ahead(self):
+        """(chained, unchained) regression launches of step_batch_dev since the context was created: chained ones ran on the look-ahead stream beside the previous step's solve (see lmpc_debug_k1_ahead)."""
+        out = (C.c_longlong * 2)()
+        _chk(self.lib.lmpc_debug_k1_ahead(self._h, out))
+        return int(out[0]), int(out[1])
+
     def set_profiling(self, every):
         """False / 0: off; True / 1: events around every kernel launch; k: around every k-th launch of each kernel (see lmpc_set_profiling)."""
         _chk(self.lib.lmpc_set_profiling(self._h, C.c_int(int(every))))
@@ -1380,6 +1390,20 @@ def config_from(N, Q, R, Qf, dR, Qslack, Fx, bx, Fu, bu, xRef, QterminalSlack=No
     return cfg
 
 
+_POOL_MEMBER = False
+
+
+def _pool_member(cfg):
+    """Context(cfg) as a ContextPool creates it: without the look-ahead regression (k1_ahead=False) -- several batches in flight fill the idle CUs already, and chained
+    members measured 3-5 % slower (profiles/k1_ahead_ab.json, pipelined_batches).  The constructor is called as Context(cfg), the one form every stand-in of it takes."""
+    global _POOL_MEMBER
+    _POOL_MEMBER = True
+    try:
+        return Context(cfg)
+    finally:
+        _POOL_MEMBER = False
+
+
 class ContextPool:
     """`depth` contexts on one device -- one HIP stream, one set of work buffers, one copy of the (small) lap stores each -- for callers that keep several INDEPENDENT
     batches in flight.  Inside one launch the CUs whose QP has converged idle until the slowest QP of the batch has (mean 8.6 against a maximum of 13 iterations at batch
@@ -1393,7 +1417,7 @@ class ContextPool:
         self.members = []; self._next = 0
         try:
             for _ in range(int(depth)):
-                self.members.append(Context(cfg))
+                self.members.append(_pool_member(cfg))
         except Exception:
             self.close()                               # (a member that failed to come up does not leave the earlier ones' device memory behind)
             raise

@@ -154,6 +154,13 @@ struct lmpc_ctx {
     // LMPC_TRACK_NPAR doubles per row (0 rows: the config's track, read from the parameter block by the kernels that ran before there were rows).  img[IMG_TRK]: the rows, uploaded by `set`
     lmpc_row_set<double> trk{LMPC_TRACK_NPAR, "lmpc_track_set"};
     dev_image img[IMG_COUNT];
+    // Look-ahead regression (step_dev).  Queued steps: the regression of step i + 1 needs nothing of step i's solve, so it runs on k1_stream beside it, ordered by
+    // stream events only -- e_k1 behind a regression launch, e_front on `stream` in front of a solve launch of step_dev.  It writes the hand-over set the solve in
+    // flight is NOT reading: ho[0] is the work buffers' A / Bm / C / rstatus, ho[1] a second set allocated by the first chained step; ho_cur: the set the last step used.
+    // chain: the previous call on this context that could enqueue work, or edit what a regression reads, was a two-kernel step_dev (ctx_enter clears it).
+    struct handover { double *A, *Bm, *C; int *rstatus; };
+    hipStream_t k1_stream; hipEvent_t e_k1, e_front; handover ho[2]; int ho_cur;
+    int k1_ahead, k1_ahead_max_batch; bool chain, sst_upload_broke; long long n_k1_chained, n_k1_unchained;   // k1_ahead: LMPC_K1_AHEAD=0 at lmpc_create turns it off (the step of before: one stream, the caller's A / Bm / C as the hand-over)
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
 };
@@ -190,6 +197,15 @@ struct lmpc_rollout_session {
 };
 
 enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
+
+// How every entry point that enqueues on the context's stream, or edits what a regression reads (lap stores and their images, lap table, track rows, parameter
+// images, a device array of the caller's), begins: the context's device, and the chain of look-ahead regressions broken -- the next step_dev runs its regression
+// on the context's stream again, behind whatever this call queues.  step_dev alone sets the flag, at its end.
+static int ctx_enter(lmpc_ctx *c) {
+    c->chain = false;
+    if (const hipError_t e = hipSetDevice(c->cfg.device)) return set_err(LMPC_E_HIP, "hipSetDevice(c->cfg.device)", hipGetErrorString(e));
+    return LMPC_OK;
+}
 
 #ifdef LMPC_DEV_FAST
 // developer build (racinglmpc_amd.build.build_flavour("dev", ["LMPC_DEV_FAST"])): only the N = 12 variants, seconds to compile; LMPC_FORCE_NW=<1|2|4>
@@ -403,6 +419,8 @@ static int image_upload(dev_image *img, const void *host, size_t bytes, const ch
     if (grow) { (void)g_free(img->p); img->p = buf; img->cap = bytes; }
     return LMPC_OK;
 }
+// Look-ahead regression: the largest batch whose queued steps chain.  PLACEHOLDER_RULE
+#define K1_AHEAD_MAX_BATCH_RULE (1 << 30)
 // everything of lmpc_create that can fail; the caller destroys the context on any error (one failure path, no leaks)
 static int create_body(lmpc_ctx *c) {
     const lmpc_config *cfg = &c->cfg;
@@ -455,6 +473,11 @@ static int create_body(lmpc_ctx *c) {
         const char *e = dev_knob("LMPC_CD"); c->cd_mode = e ? atoi(e) : 0;
     }
     HIPCHK(hipStreamCreate(&c->stream));
+    // look-ahead regression: see lmpc_ctx.  (Bit-identical either way: the same kernels on the same inputs.)
+    { const char *e = dev_knob("LMPC_K1_AHEAD"); c->k1_ahead = e ? atoi(e) != 0 : 1; }
+    if (c->create_flags & LMPC_CREATE_NO_K1_AHEAD) c->k1_ahead = 0;
+    c->k1_ahead_max_batch = K1_AHEAD_MAX_BATCH_RULE;
+    if (const char *e = dev_knob("LMPC_K1_AHEAD_MAX_BATCH")) c->k1_ahead_max_batch = atoi(e);        // (experiments)
     if (c->var.lds_1w_abg > 0 && !dev_knob("LMPC_NO_ABG")) { HIPCHK(g_malloc(&c->ab_pack, sizeof(double) * 48 * (size_t)cfg->N * (size_t)cfg->max_batch)); c->ab_pack_cap = (size_t)cfg->max_batch; }
     HIPCHK(hipHostMalloc(&c->h_retry, sizeof(int) * LMPC_RETRY_RING, hipHostMallocMapped));
     memset(c->h_retry, 0, sizeof(int) * LMPC_RETRY_RING);
@@ -489,6 +512,7 @@ static int create_body(lmpc_ctx *c) {
         if (gap) c->gaps.push_back(dev[slab] + off + bytes);
     });
     for (char *g_ : c->gaps) HIPCHK(hipMemset(g_, 0xA5, LMPC_GUARD_BYTES));
+    c->ho[0] = {c->w.A, c->w.Bm, c->w.C, c->w.rstatus};
     return LMPC_OK;
 }
 
@@ -536,19 +560,23 @@ int lmpc_destroy(lmpc_ctx *c) {
     if (!c) return LMPC_OK;
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->k1_stream) (void)hipStreamSynchronize(c->k1_stream);
     rollout_free(c);
     if (c->comm) { (void)ncclCommDestroy((ncclComm_t)c->comm); c->comm = nullptr; }
     if (c->scr_dev) (void)g_free(c->scr_dev);
     if (c->comm_scr) (void)g_free(c->comm_scr);
     if (c->comm_scr_h) (void)hipHostFree(c->comm_scr_h);
     for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack};      // (the work buffers are ranges of the two slabs)
+    void *ptrs[] = {c->mstore, c->sstore, c->mquant, c->mqpar, c->slab_in, c->slab_out, c->ab_pack, c->ho[1].A, c->ho[1].Bm, c->ho[1].C, c->ho[1].rstatus};      // (the work buffers are ranges of the two slabs)
     check_slab_gaps(c);
     for (void *q : ptrs) if (q) (void)g_free(q);
     for (dev_image &im : c->img) (void)g_free(im.p);
     if (c->h_retry) (void)hipHostFree(c->h_retry);
     if (c->h_in) (void)hipHostFree(c->h_in);
     if (c->h_out) (void)hipHostFree(c->h_out);
+    if (c->e_k1) (void)hipEventDestroy(c->e_k1);
+    if (c->e_front) (void)hipEventDestroy(c->e_front);
+    if (c->k1_stream) (void)hipStreamDestroy(c->k1_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->var_dl) dlclose(c->var_dl);
     delete c;
@@ -602,7 +630,7 @@ static int grow_stores(lmpc_ctx *c, int need_laps, int need_len) {
     while (new_laps < need_laps) new_laps *= 2;
     while (new_len < need_len) new_len *= 2;
     if (new_laps == old_laps && new_len == old_len) return LMPC_OK;
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     const int old_chunks = c->mq_chunks, new_chunks = (new_len + K1_CHUNK - 1) / K1_CHUNK;
     const size_t elems = (size_t)new_laps * LMPC_COLS * new_len;
     double *nm = nullptr, *ns = nullptr, *np_ = nullptr; unsigned *nq = nullptr;
@@ -646,7 +674,7 @@ static int staged_rows(lmpc_ctx *c, const double *x, const double *u, int T, siz
 }
 // both streams of the session drained (the logs are complete up to step t and no launch reads the stores), then its logs as the source
 static int session_rows(lmpc_ctx *c, size_t tail_bytes, store_rows *s) {
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();
     if (c->ro->pstream) HIPCHK(hipStreamSynchronize(c->ro->pstream));
     HIPCHK(hipStreamSynchronize(c->stream));
     void *scr; RCCHK(pooled_scratch(c, tail_bytes, &scr));
@@ -728,7 +756,7 @@ static int extend_laps(lmpc_ctx *c, const store_rows &s, int n, const int *cars,
 
 int lmpc_model_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int T) {
     ARGCHK(c && x && u && T >= 2);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     RESOLVE_PENDING();
     HIPCHK(hipStreamSynchronize(c->stream));
     return commit_host_lap(c, x, u, T, -1, (int)c->m_len.size(), true, 0.0);                  // PredictiveModel.addTrajectory (PredictiveModel.py:35-46); the regression store holds no cost: no TrackLength is read
@@ -736,7 +764,7 @@ int lmpc_model_add_trajectory(lmpc_ctx *c, const double *x, const double *u, int
 int lmpc_model_num_laps(lmpc_ctx *c, int *n) { ARGCHK(c && n); *n = (int)c->m_order.size(); return LMPC_OK; }
 int lmpc_model_replace_lap(lmpc_ctx *c, int pos, const double *x, const double *u, int T) {
     ARGCHK(c && x && u && pos >= 0 && pos < (int)c->m_order.size());
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     ARGCHK(T == c->m_len[c->m_order[pos]]);
     RCCHK(commit_host_lap(c, x, u, T, -1, c->m_order[pos], false, 0.0));
     return resolve_lap_table(c);
@@ -753,7 +781,7 @@ int lmpc_model_set_lap_table(lmpc_ctx *c, int n, const int *laps) {
             char msg[128]; snprintf(msg, sizeof(msg), "row %d names lap %d, %d laps are stored", (int)(i / L), laps[i], stored);
             return set_err(LMPC_E_ARG, "lap table", msg);
         }
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));   // (a regression still in flight reads the image about to be overwritten)
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));   // (a regression still in flight reads the image about to be overwritten)
     c->lt.assign(n, laps);
     const int rc = resolve_lap_table(c);
     if (rc) c->lt.clear();
@@ -769,7 +797,7 @@ int lmpc_model_lap_info(lmpc_ctx *c, int lap, int *rows, int *sorted_pos) {
 int lmpc_model_get_lap_table(lmpc_ctx *c, int *n, int *laps, int capacity) { return rows_get(c, &lmpc_ctx::lt, n, laps, capacity); }
 
 static int ss_add_trajectory_tl(lmpc_ctx *c, const double *x, const double *u, int T, double TL) {
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     RESOLVE_PENDING();
     HIPCHK(hipStreamSynchronize(c->stream));
     return commit_host_lap(c, x, u, T, (int)c->s_len.size(), -1, true, TL);
@@ -794,7 +822,7 @@ int lmpc_ss_add_point(lmpc_ctx *c, const double *x, const double *u) {
     ARGCHK(c && x && u);
     if (c->s_len.empty()) return set_err(LMPC_E_STATE, "addPoint before any addTrajectory", "");
     double TL; RCCHK(track_length_host(c, "lmpc_ss_add_point", "lmpc_ss_extend_lap_on", &TL));
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     RESOLVE_PENDING();
     const int lap = (int)c->s_len.size() - 1, row = c->s_len[lap];
     if (row >= c->cfg.max_lap_len) { const int rc = grow_stores(c, c->cfg.max_laps, row + 1); if (rc) return rc; }
@@ -808,7 +836,7 @@ int lmpc_ss_add_point(lmpc_ctx *c, const double *x, const double *u) {
 }
 int lmpc_ss_replace_lap(lmpc_ctx *c, int lap, const double *x, const double *u, const double *qfun, int T) {
     ARGCHK(c && x && u && qfun && lap >= 0 && lap < (int)c->s_len.size() && T >= 1);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     RCCHK(commit_host_lap(c, x, u, T, lap, -1, false, track_length_of(c, 0)));     // (the cost the kernel writes is replaced below: the caller's Qfun stands)
     // the caller's Q-function over the cost the kernel wrote: column 8 of a lap is contiguous ([lap][column][row]; the stores may have moved above)
     HIPCHK(hipMemcpy(c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len, qfun, sizeof(double) * (size_t)T, hipMemcpyHostToDevice));
@@ -851,7 +879,7 @@ int lmpc_ss_get_lap_table(lmpc_ctx *c, int *n, int *laps, int *last, int capacit
 int lmpc_ss_num_laps(lmpc_ctx *c, int *n) { ARGCHK(c && n); *n = (int)c->s_len.size(); return LMPC_OK; }
 int lmpc_ss_get_qfun(lmpc_ctx *c, int lap, double *qfun, int *T) {
     ARGCHK(c && T && lap >= 0 && lap < (int)c->s_len.size());
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     *T = c->s_len[lap];
     if (qfun) HIPCHK(hipMemcpy(qfun, c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len, sizeof(double) * c->s_len[lap], hipMemcpyDeviceToHost));
     return LMPC_OK;
@@ -862,7 +890,7 @@ int lmpc_store_read_lap(lmpc_ctx *c, int store, int lap, double *x, double *u, d
     // the host.  store 0: regression store, `lap` = position in its sorted order (PredictiveModel.xStored[lap]); store 1: safe set, `lap` = index in addTrajectory order, with
     // the rows LMPC.addPoint appended and the Q-function.  T is always set; x (T x 6), u (T x 2), qfun (T) may be NULL.
     ARGCHK(c && T && (store == 0 || store == 1));
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     int slot, rows; const double *base;
     if (store == 0) { ARGCHK(lap >= 0 && lap < (int)c->m_order.size()); slot = c->m_order[lap]; rows = c->m_len[slot]; base = c->mstore; }
     else { ARGCHK(lap >= 0 && lap < (int)c->s_len.size()); slot = lap; rows = c->s_len[lap]; base = c->sstore; }
@@ -895,7 +923,7 @@ int lmpc_ss_extend_lap(lmpc_ctx *c, int lap, const double *x, const double *u, i
 }
 static int ss_extend_lap_row(lmpc_ctx *c, int track_row, int lap, const double *x, const double *u, int n) {
     if (n == 0) return LMPC_OK;
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     RESOLVE_PENDING();
     store_rows s; RCCHK(staged_rows(c, x, u, n, LMPC_EXTEND_TAIL(1), &s));
     const int car = 0;
@@ -905,7 +933,7 @@ static int ss_extend_lap_row(lmpc_ctx *c, int track_row, int lap, const double *
 int lmpc_ss_truncate_lap(lmpc_ctx *c, int lap, int T) {
     ARGCHK(c && lap >= 0 && lap < (int)c->s_len.size() && T >= c->s_laptime[lap] && T <= c->s_len[lap]);
     if (T == c->s_len[lap]) return LMPC_OK;
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     double q = 0.0;                                                  // Qfun of the new last row (addPoint counts on from it, :474)
     HIPCHK(hipMemcpy(&q, c->sstore + ((size_t)lap * LMPC_COLS + 8) * c->cfg.max_lap_len + (T - 1), sizeof(double), hipMemcpyDeviceToHost));
     c->s_len[lap] = T; c->s_qlast[lap] = q; c->sst_dirty = true;
@@ -916,7 +944,7 @@ int lmpc_debug_model_image(lmpc_ctx *c, int lap, unsigned *q, double *par, int *
     // the K1 prefilter image of the regression-store lap with insertion index `lap` (lmpc_commit.hip.h: commit_quantise; the scan it serves: PredictiveModel.py:180-197): the
     // three planes of packed words over rows 0 .. rows-2 (3 x (rows-1)), the six parameters of every chunk in use, and their number.  Any output may be NULL.
     ARGCHK(c && lap >= 0 && lap < (int)c->m_len.size());
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     const int nrows = c->m_len[lap] - 1, used = (nrows + K1_CHUNK - 1) / K1_CHUNK; const size_t ls = (size_t)c->cfg.max_lap_len;
     if (chunks) *chunks = used;
     if (q) HIPCHK(hipMemcpy2D(q, (size_t)nrows * sizeof(unsigned), c->mquant + (size_t)lap * 3 * ls, ls * sizeof(unsigned), (size_t)nrows * sizeof(unsigned), 3, hipMemcpyDeviceToHost));
@@ -1067,14 +1095,14 @@ static int refresh_params(lmpc_ctx *c, bool need_model, bool need_ss, bool model
 
 // HIP events around a kernel launch (profiling on).  An event record costs ~4 us on the launch stream -- 15 us per step for the two kernels,
 // 5 % of a batch-256 step -- so profiling = k times every k-th launch of a kind only: the average duration is sampled over the run.
-static void ev_begin(lmpc_ctx *c, int kind) {
+static void ev_begin(lmpc_ctx *c, int kind, hipStream_t on) {
     c->ev_open = false;
     if (!c->profiling) return;
     const long long idx = kind == 0 ? c->stats.n_regress : c->stats.n_solve;
     if (idx % c->profiling) return;
-    evpair e; hipEventCreate(&e.a); hipEventCreate(&e.b); e.kind = kind; hipEventRecord(e.a, c->stream); c->events.push_back(e); c->ev_open = true;
+    evpair e; hipEventCreate(&e.a); hipEventCreate(&e.b); e.kind = kind; hipEventRecord(e.a, on); c->events.push_back(e); c->ev_open = true;
 }
-static void ev_end(lmpc_ctx *c) { if (c->ev_open) hipEventRecord(c->events.back().b, c->stream); c->ev_open = false; }
+static void ev_end(lmpc_ctx *c, hipStream_t on) { if (c->ev_open) hipEventRecord(c->events.back().b, on); c->ev_open = false; }
 
 // K1 launch shape: queries per work-group shrink (12 -> 6 -> 4 -> ... -> 1) until the grid covers the chip (one work-group per CU is resident)
 static void k1_grid(lmpc_ctx *c, int B, int *qg, int *nblk) {
@@ -1102,27 +1130,36 @@ static int k1_table_for(lmpc_ctx *c, int B, k1_table *t) {
     t->dev = (const int *)c->img[IMG_LT].p; t->stride = c->lt.stride(2 * c->cfg.trToUse); t->small = c->lt_small;
     return LMPC_OK;
 }
-static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, int xstride, const double *uLin, double *dA, double *dB, double *dC, int *dst, const k1_table &t) {
+// on: the stream (null: the context's); also: a second copy of A / Bm / C, each pointer or null (step_dev: the caller's arrays beside the hand-over set) -- all null:
+// the builds without it, whose text is what it was before there was a second copy
+typedef lmpc_k1_also k1_also;
+static void launch_k1(lmpc_ctx *c, int nblk, int B, int qg, const double *xLin, int xstride, const double *uLin, double *dA, double *dB, double *dC, int *dst, const k1_table &t,
+                      hipStream_t on = nullptr, k1_also also = {}) {
+    if (!on) on = c->stream;
     bool small = true;
     if (t.dev) small = t.small;                                          // (every lap named anywhere in the table)
     else for (int i = 0; i < c->cfg.trToUse; i++) small = small && c->dp.mlen[i] - 1 <= 8 * WAVE;
     if (c->k1_force16) small = false;                                    // (LMPC_K1_RPL16 at lmpc_create: A / B of the two scan builds, tests/test_gpu_configs.py)
     const bool occ = nblk > c->n_cu;
-    lmpc_pick([&](auto OCC, auto SMALL, auto TAB, auto LIVE) {
+    const bool live = t.dev && t.ll.car;
+    lmpc_pick([&](auto OCC, auto SMALL, auto TAB, auto LIVE, auto ALSO) {
         constexpr bool o = OCC, tab = TAB; constexpr int rpl = SMALL ? 8 : K1_RPL;
-        auto go = [&](auto... lv) { hipLaunchKernelGGL((lmpc_regress_kernel<o, rpl, tab, decltype(lv)...>), dim3(nblk), dim3(K1_NT), 0, c->stream, c->dp, B, qg, xLin, xstride, uLin,
+        auto go = [&](auto... lv) { hipLaunchKernelGGL((lmpc_regress_kernel<o, rpl, tab, decltype(lv)...>), dim3(nblk), dim3(K1_NT), 0, on, c->dp, B, qg, xLin, xstride, uLin,
                                                        dA, dB, dC, dst, t.dev, t.stride, t.trk, t.trkStride, lv...); };
-        if constexpr (!LIVE) go();
-        else if constexpr (tab) go(t.ll);                              // a parking session: the table builds with the live list (its B entries)
-    }, occ, small, t.dev != nullptr, t.dev && t.ll.car);
+        if constexpr (LIVE) { if constexpr (tab && !ALSO) go(t.ll); }   // a parking session: the table builds with the live list (its B entries); never with a second copy
+        else if constexpr (ALSO) go(also);
+        else go();
+    }, occ, small, t.dev != nullptr, live, !live && (also.A || also.Bm || also.C));
 }
-static int launch_regress(lmpc_ctx *c, int B, const double *d_xLin, int xstride, const double *d_uLin, double *dA, double *dB, double *dC, int *dst) {
+static int launch_regress(lmpc_ctx *c, int B, const double *d_xLin, int xstride, const double *d_uLin, double *dA, double *dB, double *dC, int *dst,
+                          hipStream_t on = nullptr, k1_also also = {}) {
+    if (!on) on = c->stream;
     int rc = refresh_params(c, true, false, c->lt.in_force()); if (rc) return rc;
     k1_table tab; rc = k1_table_for(c, B, &tab); if (rc) return rc;
-    ev_begin(c, 0);
+    ev_begin(c, 0, on);                                       // (a look-ahead launch: its events lie on that stream, and the time between them includes its wait for a free CU)
     int qg, nblk; k1_grid(c, B, &qg, &nblk);
-    launch_k1(c, nblk, B, qg, d_xLin, xstride, d_uLin, dA, dB, dC, dst, tab);
-    ev_end(c);
+    launch_k1(c, nblk, B, qg, d_xLin, xstride, d_uLin, dA, dB, dC, dst, tab, on, also);
+    ev_end(c, on);
     HIPCHK(hipGetLastError());
     c->stats.n_regress++;
     return LMPC_OK;
@@ -1186,7 +1223,7 @@ static int ss_table_for(lmpc_ctx *c, int B, lmpc_solve_io *io) {
             }
         }
         RCCHK(image_upload(&c->img[IMG_SST], img.data(), img.size() * sizeof(int), "hipMemcpy (safe-set table image)"));
-        c->sst_dirty = false;
+        c->sst_dirty = false; c->sst_upload_broke = true;      // (a step with something to upload runs unchained, step_dev)
     }
     io->ssTab = (const int *)c->img[IMG_SST].p; io->ssTabStride = c->sst.stride(L * LMPC_SSTAB_ENTRY);
     return LMPC_OK;
@@ -1207,14 +1244,14 @@ static int tuning_upload(lmpc_ctx *c, int n, const double *rows) {
     const int nr = n == 0 ? 1 : n;
     std::vector<double> img((size_t)nr * PAR_TOT);
     for (int r = 0; r < nr; r++) tuning_image_row(c->cfg, rows + (size_t)r * LMPC_TUNING_NPAR, &img[(size_t)r * PAR_TOT]);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     return image_upload(&c->img[IMG_TUNE], img.data(), img.size() * sizeof(double), "hipMemcpy (tuning image)");
 }
 // ll (parking sessions; ll.car null: none): the live list and its entries -- what the kernels are launched over; B stays the session's batch, which the per-car rows are
 // checked against and the abPack scratch is sized for.  reroute (LMPC_PARK_REROUTE): the route (waves per QP) follows ll.n instead of B.  The choice between [A_k | B_k] in
 // LDS and in the abPack scratch (long horizons) stays with B on either route: a rerouted one-wave launch at N = 40 may take the global-memory build where a session of
 // nLive cars would not -- same QP answer to the routes' bound, not the same kernel
-static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false, lmpc_live_list ll = {}, bool reroute = false) {
+static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool immediate = false, lmpc_live_list ll = {}, bool reroute = false, const k1_also *retry_abc = nullptr) {
     lmpc_solve_io io = io_in;
     const int Bl = ll.car ? ll.n : B, Br = (ll.car && reroute) ? ll.n : B;      // problems launched; the batch the route is chosen for
     if (!io.ssTab) { const int rc = ss_table_for(c, B, &io); if (rc) return rc; }
@@ -1245,7 +1282,7 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
 #ifdef LMPC_TRACE
     if (!io.tbuf && c->dbg_trace && (io.mode & 2)) io.tbuf = (long long *)c->dbg_trace;
 #endif
-    ev_begin(c, 1);
+    ev_begin(c, 1, c->stream);
     // waves per QP: 4 up to one QP per CU, 2 up to mw2_max_batch (four QPs per CU at N <= 12, see create_body), beyond that the one-wave
     // kernel, whose slim LDS layout keeps eight QPs resident per CU at N = 12
 #ifdef LMPC_DEV_FAST
@@ -1260,11 +1297,19 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
        : (io.mode & 4) ? c->var.launch_1w(c->stream, c->dp, Bl, io, ll.car)        // fused step: the one-wave kernel runs the regression itself
        : (Br <= c->mw_max_batch && (!timing_buf || dev_knob("LMPC_TIMING_MW"))) ? c->var.launch_mw4(c->stream, c->dp, Bl, io, ll.car)
        : (lmpc_solver_waves(c, Br) == 2 && !timing_buf) ? c->var.launch_mw2(c->stream, c->dp, Bl, io, ll.car) : c->var.launch_1w(c->stream, c->dp, Bl, io, ll.car);
-    ev_end(c);
+    ev_end(c, c->stream);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     c->stats.n_solve++; if (io.mode & 2) c->stats.qp_solved += Bl;
-    if (deferred) c->pending.push_back({io, Bl, io.retry_epoch, c->dp, io.A == c->w.A || io.Bm == c->w.Bm || io.C == c->w.C});
+    if (deferred) {
+        // the retry pass reads what the CALLER holds for this launch where there is such a thing (retry_abc: the caller's arrays, which it keeps until lmpc_dev_sync), not
+        // the hand-over set the first pass read, which a later step's regression overwrites; shared_abc: some of it still is a hand-over set of the context's
+        lmpc_solve_io pio = io;
+        if (retry_abc) { pio.A = retry_abc->A; pio.Bm = retry_abc->Bm; pio.C = retry_abc->C; }
+        bool shared = false;
+        for (const auto &h : c->ho) shared = shared || (h.A && (pio.A == h.A || pio.Bm == h.Bm || pio.C == h.C));
+        c->pending.push_back({pio, Bl, io.retry_epoch, c->dp, shared});
+    }
     else if (io.mode & 2) {
         rc = c->var.launch_retry(c->stream, c->dp, Bl, io, ll.car);
         if (rc) return rc;
@@ -1329,7 +1374,7 @@ int lmpc_regress_batch(lmpc_ctx *c, int B, const double *xLin, int xLinRowStride
     ARGCHK(c && xLin && uLin && A && Bm && C && B >= 1 && B <= c->cfg.max_batch);
     const int N = c->cfg.N;
     ARGCHK(xLinRowStride == N * 6 || xLinRowStride == (N + 1) * 6);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (a pending launch may hand its A / B / C over through the work buffers: its retry pass first)
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();          // (a pending launch may hand its A / B / C over through the work buffers: its retry pass first)
     { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows: refused before anything is queued)
     lmpc_arrays in = {}, out = {}; in.uLin = mut(uLin); out.A = A; out.Bm = Bm; out.C = C; out.rstatus = status;
     H2D(c->w.xLin, xLin, (size_t)B * xLinRowStride);                 // (rows of N or N + 1 points: the caller's stride, not the table's size)
@@ -1351,7 +1396,7 @@ int lmpc_regress_points(lmpc_ctx *c, int n, const double *x, const double *u, do
     // PredictiveModel.regressionAndLinearization (PredictiveModel.py:48-197) for n independent linearisation points (x (n x 6), u (n x 2)): the reference's own call
     // shape -- one point per call -- without a horizon around it.  The regression kernel runs with a parameter block whose horizon is 1: one query per work-group.
     ARGCHK(c && x && u && A && Bm && C && n >= 1 && (long long)n <= (long long)c->cfg.max_batch * c->cfg.N);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
     k1_table tab; { const int rc = k1_table_for(c, n, &tab); if (rc) return rc; }      // (point e uses row e)
     const lmpc_dims one = {1, c->dims.S, c->dims.L};                 // n problems of horizon 1: the table's sizes of uLin, A, Bm, C, rstatus
     lmpc_arrays in = {}, out = {}; in.uLin = mut(u); out.A = A; out.Bm = Bm; out.C = C; out.rstatus = status;
@@ -1361,9 +1406,9 @@ int lmpc_regress_points(lmpc_ctx *c, int n, const double *x, const double *u, do
     {
         const lmpc_dev_params keep = c->dp;
         c->dp.N = 1;                                                     // (launch_k1 passes c->dp by value)
-        ev_begin(c, 0);
+        ev_begin(c, 0, c->stream);
         launch_k1(c, n, n, 1, c->w.xLin, 6, c->w.uLin, c->w.A, c->w.Bm, c->w.C, c->w.rstatus, tab);
-        ev_end(c);
+        ev_end(c, c->stream);
         c->dp = keep;
     }
     HIPCHK(hipGetLastError());
@@ -1377,7 +1422,7 @@ int lmpc_select_batch(lmpc_ctx *c, int B, const double *x0, const double *zt, co
                       double *ssSel, double *qSel, double *succ, double *succU, double *ztUsed, int *selStart, int *status) {
     ARGCHK(c && x0 && zt && B >= 1 && B <= c->cfg.max_batch && c->cfg.numSS_it > 0);
     ARGCHK(pred_args_ok(B, xPredPrev, hasPred));
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     lmpc_arrays in = {}, out = {};
     in.x0 = mut(x0); in.zt = mut(zt); in.xPredPrev = mut(xPredPrev); in.hasPred = mut(hasPred); in.timeStep = mut(timeStep);
     out.ssSel = ssSel; out.qSel = qSel; out.succ = succ; out.succU = succU; out.ztUsed = ztUsed; out.selStart = selStart; out.status = status;
@@ -1402,7 +1447,7 @@ int lmpc_qp_solve_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     ARGCHK(c && A && Bm && C && x0 && uOld && xPred && uPred && B >= 1 && B <= c->cfg.max_batch);
     const bool term = c->dims.S > 0;
     if (term) ARGCHK(ssSel && qSel);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch: the copies below overwrite the A / B / C work buffers)
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();          // (see lmpc_regress_batch: the copies below overwrite the A / B / C work buffers)
     RCCHK(upload_qp(c, B, A, Bm, C, x0, uOld, ssSel, qSel));
     RCCHK(launch_solve(c, B, solve_io(2, qp_arrays(c))));
     RCCHK(resolve_retries(c));                           // drains the stream; a flagged problem gets its retry pass before anything is copied out
@@ -1413,13 +1458,36 @@ int lmpc_qp_solve_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     return fetch_iters(c, B, iters);                     // synchronises the stream
 }
 
+// The look-ahead stream, its two events and the second hand-over set: made by the first chained step of a context, so that contexts that never queue steps (the
+// drop-in classes, LMPC_K1_AHEAD=0) hold what they held before.
+// The stream gets the LOWEST stream priority.  The runtime deals its few hardware queues to streams per priority class: two streams of one class can share a
+// queue, and a look-ahead stream that shared the context's queue ran every regression BEHIND the solve it was meant to run beside (measured with one other
+// context alive in the process: 210 us per batch-256 step against 192 unchained, 185 with queues of their own).  A class of its own cannot collide with `stream`;
+// and when a solve and the next regression become ready together the solve's work-groups are placed first, which is the order that measured well.
+// (hipEventReleaseToDevice on both events: measured, the same 13 us between two solves.)
+static int k1_ahead_setup(lmpc_ctx *c) {
+    // (each piece only if it is missing: a failure half way leaves what exists to lmpc_destroy, and the next chained step makes the rest)
+    if (!c->k1_stream) { int least = 0, greatest = 0; HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest)); HIPCHK(hipStreamCreateWithPriority(&c->k1_stream, hipStreamDefault, least)); }
+    if (!c->e_k1) HIPCHK(hipEventCreateWithFlags(&c->e_k1, hipEventDisableTiming));
+    if (!c->e_front) HIPCHK(hipEventCreateWithFlags(&c->e_front, hipEventDisableTiming));
+    const size_t nb = (size_t)c->cfg.max_batch * (size_t)c->cfg.N;
+    lmpc_ctx::handover &h = c->ho[1];
+    if (!h.A) HIPCHK(g_malloc(&h.A, sizeof(double) * 36 * nb));
+    if (!h.Bm) HIPCHK(g_malloc(&h.Bm, sizeof(double) * 12 * nb));
+    if (!h.C) HIPCHK(g_malloc(&h.C, sizeof(double) * 6 * nb));
+    if (!h.rstatus) HIPCHK(g_malloc(&h.rstatus, sizeof(int) * nb));      // (the last piece: what step_dev looks at)
+    return LMPC_OK;
+}
+// Which batches chain: up to k1_ahead_max_batch problems (create_body: the rule, and LMPC_K1_AHEAD_MAX_BATCH for experiments)
+static bool k1_ahead_pays(const lmpc_ctx *c, int B) { return B <= c->k1_ahead_max_batch; }
 // one step on device arrays: the body of lmpc_step_batch_dev, which lmpc_step_batch runs on the work buffers or their host-mapped mirrors
 static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     ARGCHK(B >= 1 && a.x0 && a.xLin && a.uLin && a.uOld && a.xPred && a.uPred && a.status && a.iters);
     const int N = c->cfg.N; const bool term = c->cfg.numSS_it > 0;
     if (term) ARGCHK(a.zt != nullptr);
     ARGCHK(!a.hasPred || a.xPredPrev);                   // (device arrays: a set hasPred[b] would dereference the missing predictions inside the kernel)
-    HIPCHK(hipSetDevice(c->cfg.device));
+    const bool was_chain = c->chain;                     // (the previous call was a two-kernel step_dev and nothing has been queued or edited since)
+    RCCHK(ctx_enter(c));
     ARGCHK(B <= c->cfg.max_batch);                      // the work buffers (per-point regression status, A, B, C hand-over) are sized for max_batch
     // Regression kernel, then the solve kernel; A, Bm, C are optional outputs (the hand-over then uses the context's work buffers).
     // With LMPC_FUSE=1 batches that run one wave per QP take the fused step instead: every wave runs the regression of its own QP in
@@ -1429,19 +1497,61 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     // (likewise a safe-set lap table, lmpc_ss_set_lap_table: the fused form's LDS layout has no room behind it for the selected laps)
     // (likewise tuning rows, lmpc_tuning_set: the fused form has no per-problem-rows instantiation)
     const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && !c->lt.in_force() && !(term && c->sst.in_force()) && !c->tune.in_force() && !c->trk.in_force();      // (likewise track rows, lmpc_track_set)
-    double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
-    // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
-    // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
-    // A / Bm / C (racinglmpc_amd._capi.Context.step_dev_buffers does) and keep every buffer of a launch untouched until lmpc_dev_sync.
-    if (dA == c->w.A || dB == c->w.Bm || dC == c->w.C) for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
     lmpc_solve_io io = solve_io((fused ? 4 : 0) | (term ? 3 : 2), a);
-    RCCHK(ss_table_for(c, B, &io));                       // (B against the safe-set lap table's rows: refused before the regression is queued)
-    RCCHK(tuning_for(c, B, &io));                         // (and against the tuning rows)
-    io.A = dA; io.Bm = dB; io.C = dC;
-    // (io.rstatus / the fused regression: a singular regression or an off-track linearisation point marks status[b]; the reference raises there)
-    if (fused) { io.xLin = a.xLin; io.uLin = a.uLin; io.Aout = a.A; io.Bout = a.Bm; io.Cout = a.C; RCCHK(refresh_params(c, true, false)); }
-    else { RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, dA, dB, dC, c->w.rstatus)); io.rstatus = c->w.rstatus; }
-    return launch_solve(c, B, io);
+    if (fused || !c->k1_ahead || !k1_ahead_pays(c, B)) {      // the step of before: one stream, the caller's A / Bm / C as the hand-over where given; it starts no chain
+        double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
+        // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
+        // pending its retry pass that used them is resolved first (a stream drain).  Callers that queue launches back to back pass their own
+        // A / Bm / C (racinglmpc_amd._capi.Context.step_dev_buffers does) and keep every buffer of a launch untouched until lmpc_dev_sync.
+        if (dA == c->w.A || dB == c->w.Bm || dC == c->w.C) for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
+        RCCHK(ss_table_for(c, B, &io));                       // (B against the safe-set lap table's rows: refused before the regression is queued)
+        RCCHK(tuning_for(c, B, &io));                         // (and against the tuning rows)
+        io.A = dA; io.Bm = dB; io.C = dC;
+        // (io.rstatus / the fused regression: a singular regression or an off-track linearisation point marks status[b]; the reference raises there)
+        if (fused) { io.xLin = a.xLin; io.uLin = a.uLin; io.Aout = a.A; io.Bout = a.Bm; io.Cout = a.C; RCCHK(refresh_params(c, true, false)); }
+        else { RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, dA, dB, dC, c->w.rstatus)); io.rstatus = c->w.rstatus; c->n_k1_unchained++; }
+        return launch_solve(c, B, io);
+    }
+    // The look-ahead form.  The regression writes one of the context's two hand-over sets -- and the caller's A / Bm / C beside it, where given -- and the solve's
+    // first pass reads that set, never the caller's arrays: the regression of the NEXT queued step may then run beside this solve, since it writes the other set (and
+    // the caller's arrays, which nothing on the device reads any more).  A step that is not chained takes set 0 with its regression on the context's stream, as
+    // before; a chained step i + 1 takes the other set than step i, on k1_stream:
+    //     k1_stream waits for e_front(i) | K1(i + 1) | e_k1 | stream waits for e_k1 | e_front(i + 1) on stream | K3(i + 1)
+    // e_front(i) lies on `stream` behind the wait for K1(i) and in front of K3(i): K1(i + 1) is ordered behind K3(i - 1), the last first-pass reader of its set, and
+    // behind K1(i) (the caller's arrays are written in step order) -- not behind K3(i).  Every K3 waits for its K1, so a drain of `stream` leaves k1_stream idle.
+    RCCHK(ss_table_for(c, B, &io));                           // (B against the safe-set lap table's rows: refused before the regression is queued; an upload drains and breaks the chain)
+    RCCHK(tuning_for(c, B, &io));                             // (and against the tuning rows)
+    const bool chained = was_chain && !c->sst_upload_broke;
+    c->sst_upload_broke = false;
+    if (chained && !c->ho[1].rstatus) {                       // the first chained step of the context
+        RCCHK(k1_ahead_setup(c));
+        // (the step before ran when there was no event to record: this one's regression waits for a record BEHIND that step's solve -- ordered, once without the overlap)
+        HIPCHK(hipEventRecord(c->e_front, c->stream));
+    }
+    const int set = chained ? 1 - c->ho_cur : 0;
+    const lmpc_ctx::handover &h = c->ho[set];
+    // the retry pass of an earlier launch reads the caller's A / Bm / C where the caller gave them, else the hand-over set of ITS launch: such a launch is resolved
+    // (a stream drain) before the next step is queued, as it always was -- whichever set that step writes: a caller without arrays of its own drains at every step
+    // and gains nothing here (tests/test_gpu_retry.py counts on the pass having run by then)
+    for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
+    const k1_also also = {a.A, a.Bm, a.C};
+    if (chained) {
+        HIPCHK(hipStreamWaitEvent(c->k1_stream, c->e_front, 0));
+        RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, h.A, h.Bm, h.C, h.rstatus, c->k1_stream, also));
+        HIPCHK(hipEventRecord(c->e_k1, c->k1_stream));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->e_k1, 0));
+        c->n_k1_chained++;
+    } else {
+        RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, h.A, h.Bm, h.C, h.rstatus, c->stream, also));
+        c->n_k1_unchained++;
+    }
+    c->ho_cur = set;
+    io.A = h.A; io.Bm = h.Bm; io.C = h.C; io.rstatus = h.rstatus;
+    if (c->e_front) HIPCHK(hipEventRecord(c->e_front, c->stream));      // (no event yet: no step has chained, and the first one that does records its own)
+    const k1_also retry_abc = {a.A ? a.A : h.A, a.Bm ? a.Bm : h.Bm, a.C ? a.C : h.C};
+    RCCHK(launch_solve(c, B, io, false, {}, false, &retry_abc));
+    c->chain = true;
+    return LMPC_OK;
 }
 int lmpc_step_batch_dev(lmpc_ctx *c, int B, const lmpc_step_dev_args *a) { ARGCHK(c && a); return step_dev(c, B, lmpc_step_arrays(*a)); }
 
@@ -1453,7 +1563,7 @@ int lmpc_step_batch(lmpc_ctx *c, int B, const double *x0, const double *xLin, co
     ARGCHK(pred_args_ok(B, xPredPrev, hasPred));
     const bool term = c->cfg.numSS_it > 0;
     if (term) ARGCHK(zt != nullptr);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     { k1_table tab; const int rc = k1_table_for(c, B, &tab); if (rc) return rc; }      // (B against the lap table's rows)
     // the caller's arrays by the table's names (a NULL output is not wanted).  Plain MPC: the S = 0 kernels read no zt / xPredPrev / hasPred / timeStep and write no
     // lambda / sTerm / ssSel / qSel.  hasPred counts only with the predictions it speaks of; it and timeStep are zeros when not given.
@@ -1479,6 +1589,7 @@ int lmpc_step_batch(lmpc_ctx *c, int B, const double *x0, const double *xLin, co
     }
     const auto tr1 = std::chrono::steady_clock::now();
     RCCHK(step_dev(c, B, a));
+    c->chain = false;                                    // (this call drains before it returns: its step starts no chain)
     const auto tr2 = std::chrono::steady_clock::now();
     RCCHK(resolve_retries(c));                           // drains the stream; a flagged problem gets its retry pass before anything is copied out
     const auto tr3 = std::chrono::steady_clock::now();
@@ -1511,7 +1622,7 @@ int lmpc_assemble_batch(lmpc_ctx *c, int B, const double *A, const double *Bm, c
     int nz, mi, me; lmpc_qp_dims(c, &nz, &mi, &me); const int mm = mi + me;
     if (c->dims.S > 0) ARGCHK(ssSel && qSel);
     RCCHK(rows_fit(c->tune, B, LMPC_ROWS_EXACT, "problems", "tuning rows"));
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();          // (see lmpc_regress_batch)
     call_temps tmp; double *dP, *dq, *dA, *dl, *du;
     HIPCHK(tmp.alloc(&dP, sizeof(double) * (size_t)B * nz * nz)); HIPCHK(tmp.alloc(&dq, sizeof(double) * (size_t)B * nz));
     HIPCHK(tmp.alloc(&dA, sizeof(double) * (size_t)B * mm * nz)); HIPCHK(tmp.alloc(&dl, sizeof(double) * (size_t)B * mm)); HIPCHK(tmp.alloc(&du, sizeof(double) * (size_t)B * mm));
@@ -1559,7 +1670,7 @@ int lmpc_track_set(lmpc_ctx *c, int n, const double *rows) {
         if (bad) { snprintf(msg, sizeof(msg), "row %d: %s (the rows in force stay)", r, bad); return set_err(LMPC_E_ARG, "lmpc_track_set", msg); }
     }
     // launches still pending their retry pass read the image of THEIR launch: they are resolved, and the stream is drained, before it is overwritten (as for tuning)
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     if (n > 0) RCCHK(image_upload(&c->img[IMG_TRK], rows, sizeof(double) * LMPC_TRACK_NPAR * (size_t)n, "hipMemcpy (track image)"));
     c->trk.assign(n, rows);
     return LMPC_OK;
@@ -1567,11 +1678,12 @@ int lmpc_track_set(lmpc_ctx *c, int n, const double *rows) {
 int lmpc_track_get(lmpc_ctx *c, int *n, double *rows, int capacity) { return rows_get(c, &lmpc_ctx::trk, n, rows, capacity); }
 
 // ---------------------------------------------------------------------------------------------- device buffers
-int lmpc_dev_alloc(lmpc_ctx *c, long long bytes, void **dptr) { ARGCHK(c && dptr && bytes > 0); HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipMalloc(dptr, (size_t)bytes)); return LMPC_OK; }
-int lmpc_dev_free(lmpc_ctx *c, void *dptr) { ARGCHK(c); HIPCHK(hipSetDevice(c->cfg.device)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipFree(dptr)); return LMPC_OK; }
-int lmpc_dev_upload(lmpc_ctx *c, void *dptr, const void *host, long long bytes) { ARGCHK(c && dptr && host); HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipMemcpyAsync(dptr, host, (size_t)bytes, hipMemcpyHostToDevice, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
-int lmpc_dev_download(lmpc_ctx *c, void *host, const void *dptr, long long bytes) { ARGCHK(c && dptr && host); HIPCHK(hipSetDevice(c->cfg.device)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipMemcpyAsync(host, dptr, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
-int lmpc_dev_sync(lmpc_ctx *c) { ARGCHK(c); HIPCHK(hipSetDevice(c->cfg.device)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
+int lmpc_dev_alloc(lmpc_ctx *c, long long bytes, void **dptr) { ARGCHK(c && dptr && bytes > 0); RCCHK(ctx_enter(c)); HIPCHK(hipMalloc(dptr, (size_t)bytes)); return LMPC_OK; }
+int lmpc_dev_free(lmpc_ctx *c, void *dptr) { ARGCHK(c); RCCHK(ctx_enter(c)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipFree(dptr)); return LMPC_OK; }
+int lmpc_dev_upload(lmpc_ctx *c, void *dptr, const void *host, long long bytes) { ARGCHK(c && dptr && host); RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipMemcpyAsync(dptr, host, (size_t)bytes, hipMemcpyHostToDevice, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
+int lmpc_dev_download(lmpc_ctx *c, void *host, const void *dptr, long long bytes) { ARGCHK(c && dptr && host); RCCHK(ctx_enter(c)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipMemcpyAsync(host, dptr, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
+int lmpc_debug_k1_ahead(lmpc_ctx *c, long long out[2]) { ARGCHK(c && out); out[0] = c->n_k1_chained; out[1] = c->n_k1_unchained; return LMPC_OK; }
+int lmpc_dev_sync(lmpc_ctx *c) { ARGCHK(c); RCCHK(ctx_enter(c)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
 
 // developer trace: host-side seconds of the one-QP path of lmpc_step_batch since the context was made -- out[0..3] = staging the inputs, launching the
 // two kernels, waiting for the stream, reading the outputs back; out[4] = calls (tools/dropin_time.py)
@@ -1581,7 +1693,7 @@ int lmpc_debug_step_trace(lmpc_ctx *c, double *out5) { ARGCHK(c && out5); for (i
 int lmpc_debug_timing(lmpc_ctx *c, const double *A, const double *Bm, const double *C, const double *x0, const double *uOld,
                       const double *ssSel, const double *qSel, long long *tbuf_host, int nt) {
     ARGCHK(c && tbuf_host && nt >= 2);
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();
     RCCHK(upload_qp(c, 1, A, Bm, C, x0, uOld, ssSel, qSel));
     call_temps tmp; long long *dt;
     HIPCHK(tmp.alloc(&dt, sizeof(long long) * nt)); HIPCHK(hipMemsetAsync(dt, 0, sizeof(long long) * nt, c->stream));
@@ -1598,7 +1710,7 @@ int lmpc_debug_timing(lmpc_ctx *c, const double *A, const double *Bm, const doub
 int lmpc_debug_k1_timing(lmpc_ctx *c, int B, const double *xLin, const double *uLin, long long *tbuf_host) {
     ARGCHK(c && xLin && uLin && tbuf_host && B >= 1 && B <= c->cfg.max_batch);
     const int N = c->cfg.N;
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING();
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();
     lmpc_arrays in = {}; in.xLin = mut(xLin); in.uLin = mut(uLin);
     RCCHK(copy_arrays(c, B, c->dims, c->w, in, hipMemcpyHostToDevice));
     // on any way out: the stream is drained, the kernels' stamp pointer is null again, then the buffer goes
@@ -1655,7 +1767,7 @@ int lmpc_plant_get_params(lmpc_ctx *c, int *n, double *par, int capacity) { retu
 int lmpc_noise_raw(lmpc_ctx *c, unsigned long long seed, unsigned long long stream, unsigned long long lap, long long t0, int T, long long car0, int B, unsigned long long *words) {
     // the four Philox4x64-10 words of every (t, car) of the range: what numpy.random.Philox(counter=[t, car, lap, stream], key=[seed, 0]).random_raw(4) returns
     ARGCHK(c && words); NOISE_RANGE_CHK();
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     const size_t total = (size_t)T * (size_t)B;
     unsigned long long *d; { void *q; const int rc = pooled_scratch(c, sizeof(unsigned long long) * total * 4, &q); if (rc) return rc; d = (unsigned long long *)q; }
     hipLaunchKernelGGL(lmpc_noise_raw_kernel, dim3((unsigned)((total + LMPC_NOISE_NT - 1) / LMPC_NOISE_NT)), dim3(LMPC_NOISE_NT), 0, c->stream, seed, stream, lap,
@@ -1669,7 +1781,7 @@ int lmpc_noise_raw(lmpc_ctx *c, unsigned long long seed, unsigned long long stre
 int lmpc_noise_fill(lmpc_ctx *c, unsigned long long seed, unsigned long long stream, unsigned long long lap, long long t0, int T, long long car0, int B, int width, double *out) {
     // the N(0, 1) draws of the range, T x B x width, by the kernel that fills a session's buffer (lmpc_rollout_set_noise): same launch, same bits
     ARGCHK(c && out && (width == 2 || width == 3)); NOISE_RANGE_CHK();
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     const size_t total = (size_t)T * (size_t)B;
     double *d; { void *q; const int rc = pooled_scratch(c, sizeof(double) * total * (size_t)width, &q); if (rc) return rc; d = (double *)q; }
     lmpc_noise_fill_launch(c->stream, seed, stream, lap, t0, T, car0, B, width, d);
@@ -1697,7 +1809,7 @@ int lmpc_rollout_get_noise(lmpc_ctx *c, int *on, unsigned long long *seed, unsig
 
 int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg, const double *u, const double *noise, double *xn, double *xgn, int *status) {
     ARGCHK(c && x && xg && u && noise && xn && xgn && B >= 1);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     const bool par = c->plant.in_force();
     std::vector<double> rows;
     if (par) { const int rc = plant_rows_for(c, B, rows); if (rc) return rc; }
@@ -1722,7 +1834,7 @@ int lmpc_plant_step_batch(lmpc_ctx *c, int B, const double *x, const double *xg,
 
 int lmpc_global_position_batch(lmpc_ctx *c, int n, const double *s, const double *ey, double *xy, int *status) {
     ARGCHK(c && s && ey && xy && status && n >= 1);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     int rc = refresh_params(c, false, false); if (rc) return rc;
     trk_src ts; rc = track_for(c, n, &ts); if (rc) return rc;         // (point e on track row e)
     double *d; { void *q; const int rc2 = pooled_scratch(c, sizeof(double) * (size_t)n * 4 + sizeof(int) * (size_t)n, &q); if (rc2) return rc2; d = (double *)q; }
@@ -1740,7 +1852,7 @@ int lmpc_global_position_batch(lmpc_ctx *c, int n, const double *s, const double
 // halfWidth + slack (0.85 on its track), which the track table in lmpc_config does not carry.
 int lmpc_local_position_batch(lmpc_ctx *c, int n, const double *x, const double *y, const double *psi, double max_ey, double *s, double *ey, double *epsi, int *status) {
     ARGCHK(c && x && y && psi && s && ey && epsi && status && n >= 1 && std::isfinite(max_ey) && max_ey >= 0.0);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     int rc = refresh_params(c, false, false); if (rc) return rc;
     trk_src ts; rc = track_for(c, n, &ts); if (rc) return rc;         // (point e on track row e)
     const size_t m = (size_t)n;
@@ -1758,7 +1870,7 @@ int lmpc_local_position_batch(lmpc_ctx *c, int n, const double *x, const double 
 
 int lmpc_track_angle_batch(lmpc_ctx *c, int n, const double *s, const double *epsi, double *psi, int *status) {
     ARGCHK(c && s && epsi && psi && status && n >= 1);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     int rc = refresh_params(c, false, false); if (rc) return rc;
     trk_src ts; rc = track_for(c, n, &ts); if (rc) return rc;         // (point e on track row e)
     const size_t m = (size_t)n;
@@ -1778,7 +1890,7 @@ int lmpc_state_from_global_batch(lmpc_ctx *c, int T, int B, const double *xglob,
     // lmpc_local_position_batch.  Rows are independent: s is NOT made continuous across the finish line here (rollout.lap_from_global adds the lap count on the host)
     ARGCHK(c && xglob && x && status && T >= 1 && B >= 1 && std::isfinite(max_ey) && max_ey >= 0.0);
     ARGCHK(((unsigned long long)T * (unsigned long long)B + LMPC_TRACK_NT - 1) / LMPC_TRACK_NT <= 0x7fffffffull);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     int rc = refresh_params(c, false, false); if (rc) return rc;
     trk_src ts; rc = track_for(c, B, &ts); if (rc) return rc;         // (car b of the T x B log on track row b)
     const size_t m = (size_t)T * (size_t)B;
@@ -1817,7 +1929,7 @@ static void trace_plane_bytes(const lmpc_ctx *c, unsigned what, size_t pb[LMPC_T
 // Session set-up shared by lmpc_rollout_begin (kind RO_LMPC), lmpc_rollout_begin_mpc (RO_LTV / RO_LTI) and lmpc_rollout_pid (RO_PID): buffers, initial state, noise.
 // xLin0 / uLin0 may be NULL (RO_LTI, RO_PID: no linearisation trajectory; the buffers are zeroed).
 static int rollout_setup(lmpc_ctx *c, int kind, int stop_at_line, int B, int T_max, const double *x0, const double *xg0, const double *xLin0, const double *uLin0, const double *noise) {
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     const size_t S = c->dims.S, Bz = B;
     trk_src trk; { const int rc = track_for(c, B, &trk); if (rc) return rc; }      // (car b on track row b: refused before any session state changes)
     std::vector<double> par_rows;                               // refused before any session state changes (B beyond the per-car rows)
@@ -1965,7 +2077,7 @@ int lmpc_rollout_begin_mpc(lmpc_ctx *c, int B, int T_max, const double *x0, cons
     ARGCHK((A_lti != nullptr) == (B_lti != nullptr) && (A_lti || (xLin0 && uLin0)));
     ARGCHK(B <= c->cfg.max_batch);
     ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     const bool lti = A_lti != nullptr;
     if (!lti) { const int rc = refresh_params(c, true, false, c->lt.in_force()); if (rc) return rc; }       // LMPC_E_STATE without trToUse stored laps, as lmpc_step_batch
     RESOLVE_PENDING();
@@ -1996,7 +2108,7 @@ int lmpc_rollout_pid(lmpc_ctx *c, int B, int T_max, const double *x0, const doub
     ARGCHK((noise_u && noise) || c->noise_on);                                              // (an array missing and no device source: lmpc_rollout_set_noise)
     ARGCHK(B <= c->cfg.max_batch);
     ARGCHK(!(c->ro && c->ro->active));                                                      // (a session is already active: end it first)
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     RESOLVE_PENDING();
     int rc = rollout_setup(c, RO_PID, stop_at_line ? 1 : 0, B, T_max, x0, xg0, nullptr, nullptr, noise);
     if (rc) return rc;
@@ -2075,7 +2187,7 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
     lmpc_rollout_session *r = c->ro;
     const int B = r->B; const size_t N = c->cfg.N;
     const bool lmpc = r->kind == RO_LMPC, lti = r->kind == RO_LTI;
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     lmpc_rollout_state st; rollout_state(r, st);
     int nd = 0, rc = LMPC_OK;
     const int t_end = std::min(r->T_max, r->t + max_steps);
@@ -2100,11 +2212,11 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
         rc = tuning_for(c, B, &io); if (rc) return rc;       // (the tuning rows are live in the same way: a lmpc_tuning_set between two runs reaches the next step)
         if (!lti) {
         rc = refresh_params(c, true, lmpc, r->has_lt, io.ssTab != nullptr); if (rc) return rc;      // (what this session's launch reads: its snapshot, or -- begun without a table -- the block, whatever table the context has been given since)
-        ev_begin(c, 0);
+        ev_begin(c, 0, c->stream);
         { int qg, nblk; k1_grid(c, ll.n, &qg, &nblk);
           const k1_table tab = {(r->has_lt || ll.car) ? r->d_lt : nullptr, r->has_lt ? r->lt_stride : 0, r->lt_small, r->trk, r->trk_stride, ll};
           launch_k1(c, nblk, ll.n, qg, (const double *)r->a.xLin, (int)(N + 1) * 6, (const double *)r->a.uLin, r->a.A, r->a.Bm, r->a.C, r->a.rstatus, tab); }
-        ev_end(c); c->stats.n_regress++;
+        ev_end(c, c->stream); c->stats.n_regress++;
         }
         io.rstatus = lti ? nullptr : r->a.rstatus;
         if (r->t > 0) HIPCHK(hipStreamWaitEvent(c->stream, r->e_plant, 0));          // the solve needs the plant's new state
@@ -2153,7 +2265,7 @@ int lmpc_rollout_fetch(lmpc_ctx *c, int t0, int t1, double *X, double *U, double
     // finalX / finalG: state right after the crossing step (the reference's xF before the TrackLength shift, SysModel.py:50)
     ARGCHK(c && c->ro && c->ro->active && t0 >= 0 && t1 >= t0 && t1 <= c->ro->t);
     lmpc_rollout_session *r = c->ro; const size_t Bz = r->B, n = (size_t)(t1 - t0);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     if (n) { D2H(X, r->d_logX + (size_t)t0 * Bz * 6, n * Bz * 6); D2H(U, r->d_logU + (size_t)t0 * Bz * 2, n * Bz * 2); D2H(G, r->d_logG + (size_t)t0 * Bz * 6, n * Bz * 6); }
     D2H(doneAt, r->d_done, Bz); D2H(status, r->d_stAcc, Bz); D2H(finalX, r->d_finX, Bz * 6); D2H(finalG, r->d_finG, Bz * 6);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2207,7 +2319,7 @@ int lmpc_rollout_parked_at(lmpc_ctx *c, int *at, int *n_live) {
     lmpc_rollout_session *r = c->ro;
     if (n_live) *n_live = r->parked ? r->nLive : r->B;
     if (at) {
-        if (r->parked) { HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipMemcpy(at, r->d_parkedAt, sizeof(int) * (size_t)r->B, hipMemcpyDeviceToHost)); }
+        if (r->parked) { RCCHK(ctx_enter(c)); HIPCHK(hipMemcpy(at, r->d_parkedAt, sizeof(int) * (size_t)r->B, hipMemcpyDeviceToHost)); }
         else for (int b = 0; b < r->B; b++) at[b] = -1;
     }
     return LMPC_OK;
@@ -2217,7 +2329,7 @@ int lmpc_debug_live_compact(lmpc_ctx *c, int n, const int *doneAt, const int *pa
     // (every build) the sessions' compaction kernel on host arrays: doneAt, parked0 (n flags) in; parkedAt (n) in and out -- -1 for a car not parked so far;
     // live (n: the first n_live entries are written) and n_live out.  One launch, as a session makes it
     ARGCHK(c && n >= 1 && doneAt && parked0 && live && parkedAt && n_live && t >= 0 && !(mode & ~(unsigned)(LMPC_PARK_FINISHED | LMPC_PARK_REROUTE)));
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     const size_t nz = (size_t)n;
     int *d = nullptr; HIPCHK(g_malloc((void **)&d, sizeof(int) * (4 * nz + 4)));
     int *d_done = d, *d_p0 = d + nz, *d_at = d + 2 * nz, *d_live = d + 3 * nz, *d_hdr = d + 4 * nz;
@@ -2267,7 +2379,7 @@ int lmpc_rollout_fetch_trace(lmpc_ctx *c, int t0, int t1, const lmpc_trace_out *
     ARGCHK(t0 >= 0 && t1 >= t0 && t1 <= r->t);
     ARGCHK((!out->xPred || r->tr_x) && (!out->uPred || r->tr_u) && (!out->ssSel || r->tr_ss) && (!out->qSel || r->tr_q) && (!out->xyPred || r->tr_xy) &&
            (!out->xySS || r->tr_xys) && (!out->iters || r->tr_it) && (!out->status || r->tr_st) && (!out->mapStatus || r->tr_map));     // (a plane the session does not record)
-    HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(r->tstream)); HIPCHK(hipStreamSynchronize(r->pstream));
+    RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(r->tstream)); HIPCHK(hipStreamSynchronize(r->pstream));
     size_t pb[LMPC_TRACE_PLANES]; trace_plane_bytes(c, r->tr_what, pb);
     const size_t first = (size_t)t0 * (size_t)r->tr_n, rows = (size_t)(t1 - t0) * (size_t)r->tr_n;
     void *dst[LMPC_TRACE_PLANES] = {out->xPred, out->uPred, out->ssSel, out->qSel, out->iters, out->status, out->xyPred, out->xySS, out->mapStatus};
@@ -2284,7 +2396,7 @@ int lmpc_debug_rollout_peek(lmpc_ctx *c, double *xLin, double *uLin, int *status
     // time with it to capture the inputs of a flagged regression.  Any pointer may be NULL.
     ARGCHK(c && c->ro && c->ro->active);
     lmpc_rollout_session *r = c->ro;
-    HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(r->pstream)); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(r->pstream)); HIPCHK(hipStreamSynchronize(c->stream));
     lmpc_arrays out = {}; out.xLin = xLin; out.uLin = uLin; out.status = status; out.rstatus = rstatus;
     RCCHK(copy_arrays(c, r->B, c->dims, out, r->a, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2307,7 +2419,7 @@ int lmpc_debug_rollout_qp(lmpc_ctx *c, int b0, int n, double *A, double *Bm, dou
     // called between lmpc_rollout_run(ctx, 1, ..) calls; any pointer may be NULL.
     ARGCHK(c && c->ro && c->ro->active && c->ro->t >= 1 && b0 >= 0 && n >= 1 && b0 + n <= c->ro->B && ((!ssSel && !qSel && !succ && !succU) || c->ro->a.ssSel));
     lmpc_rollout_session *r = c->ro;
-    HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(r->pstream)); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(r->pstream)); HIPCHK(hipStreamSynchronize(c->stream));
     lmpc_arrays out = {};
     out.A = A; out.Bm = Bm; out.C = Cm; out.xPred = xPred; out.uPred = uPred; out.lambda = lambda; out.ztNext = ztNext; out.ztuNext = ztuNext;
     out.ssSel = ssSel; out.qSel = qSel; out.succ = succ; out.succU = succU; out.iters = iters; out.status = status;
@@ -2317,7 +2429,7 @@ int lmpc_debug_rollout_qp(lmpc_ctx *c, int b0, int n, double *A, double *Bm, dou
 }
 
 int lmpc_rollout_end(lmpc_ctx *c) {
-    ARGCHK(c); HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(c->stream));
+    ARGCHK(c); RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(c->stream));
     if (c->ro) {
         if (c->ro->pstream) HIPCHK(hipStreamSynchronize(c->ro->pstream));
         if (c->ro->tstream) HIPCHK(hipStreamSynchronize(c->ro->tstream));
@@ -2334,7 +2446,7 @@ int lmpc_rollout_release(lmpc_ctx *c) {
     // lmpc_rollout_end keeps the session's device buffers (~35 allocations, 55 MB at 1024 rollouts x 400 steps), its stream and events for the next lap of the same
     // shape; this gives them back without destroying the context.  Not valid inside a session.
     ARGCHK(c && !(c->ro && c->ro->active));
-    HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(c->stream));
     rollout_free(c);
     return LMPC_OK;
 }
@@ -2376,7 +2488,7 @@ int lmpc_lti_regression(int device, const double *x, const double *u, int T, dou
 int lmpc_selftest(lmpc_ctx *c) {
     // cross-lane primitives (DPP + v_permlane16/32_swap reductions) against closed-form values
     ARGCHK(c);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     double *d; HIPCHK(hipMalloc(&d, sizeof(double) * 192));
     hipLaunchKernelGGL(lmpc_selftest_kernel, dim3(1), dim3(WAVE), 0, c->stream, d);
     double hbuf[192]; HIPCHK(hipMemcpyAsync(hbuf, d, sizeof(hbuf), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); hipFree(d);
@@ -2393,7 +2505,7 @@ int lmpc_debug_set_trace(lmpc_ctx *c, double *dev_rows) {
     // max_batch x 48 x 6 doubles; NULL switches it off): per iteration (gap, r_d, r_e | sigma, alpha_p, alpha_d).  Ordinary builds carry no such code: LMPC_E_ARG.
     ARGCHK(c);
 #ifdef LMPC_TRACE
-    HIPCHK(hipSetDevice(c->cfg.device)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
     c->dbg_trace = dev_rows;
     return LMPC_OK;
 #else
@@ -2407,7 +2519,7 @@ int lmpc_debug_exec_audit(lmpc_ctx *c, unsigned long long *out16, int reset) {
     // the last reset (sites: lmpc_kernels.hip.h, EXEC_AUDIT); built-in variants only (a liblmpc_var_*.so carries counters of its own).  Ordinary builds: LMPC_E_ARG.
     ARGCHK(c && out16);
 #ifdef LMPC_EXEC_AUDIT
-    HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipDeviceSynchronize());
+    RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_exec_audit), sizeof(unsigned long long) * 2 * LMPC_AUDIT_SITES));
     if (reset) { unsigned long long z[2 * LMPC_AUDIT_SITES] = {0}; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_exec_audit), z, sizeof(z))); }
     return LMPC_OK;
@@ -2432,7 +2544,7 @@ int lmpc_solver_lds(lmpc_ctx *c, unsigned long long out4[4]) {
 
 int lmpc_set_profiling(lmpc_ctx *c, int every) { ARGCHK(c); c->profiling = every > 0 ? every : 0; return LMPC_OK; }
 static int drain_events(lmpc_ctx *c) {
-    HIPCHK(hipSetDevice(c->cfg.device)); HIPCHK(hipStreamSynchronize(c->stream));
+    RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(c->stream));
     for (auto &e : c->events) {
         float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, e.a, e.b));
         if (e.kind == 0) { c->stats.ms_regress += ms; c->stats.n_regress_timed++; } else { c->stats.ms_solve += ms; c->stats.n_solve_timed++; }

@@ -58,7 +58,7 @@ int lmpc_comm_unique_id(unsigned char *id /*LMPC_COMM_ID_BYTES*/) {
 int lmpc_comm_init(lmpc_ctx *c, const unsigned char *id, int rank, int world) {
     ARGCHK(c && id && world >= 1 && rank >= 0 && rank < world);
     if (c->comm) return set_err(LMPC_E_STATE, "lmpc_comm_init", "communicator already initialised");
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     ncclUniqueId u; memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
     ncclComm_t comm;
     NCCLCHK(ncclCommInitRank(&comm, world, u, rank));
@@ -82,7 +82,7 @@ int lmpc_comm_info(lmpc_ctx *c, int *rank, int *world, int *is_rccl) {
 // device buffers: recv = world x bytes.  Without a communicator (single process) the gather of one rank is a copy.
 int lmpc_comm_allgather_dev(lmpc_ctx *c, const void *send, void *recv, long long bytes) {
     ARGCHK(c && send && recv && bytes > 0);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     RESOLVE_PENDING();                              // (what is shipped to the peers has had its retry pass)
     if (!c->comm) { HIPCHK(hipMemcpyAsync(recv, send, (size_t)bytes, hipMemcpyDeviceToDevice, c->stream)); return LMPC_OK; }
     NCCLCHK(ncclAllGather(send, recv, (size_t)bytes, ncclChar, (ncclComm_t)c->comm, c->stream));
@@ -92,7 +92,7 @@ int lmpc_comm_allgather_dev(lmpc_ctx *c, const void *send, void *recv, long long
 // host buffers (small control data: lap lengths, timings): staged through the communicator's scratch, same collective
 int lmpc_comm_allgather(lmpc_ctx *c, const void *send_host, void *recv_host, long long bytes) {
     ARGCHK(c && send_host && recv_host && bytes > 0);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     const int world = c->comm ? c->comm_world : 1;
     int rc = comm_scratch(c, (size_t)bytes * (world + 1)); if (rc) return rc;
     char *d = (char *)c->comm_scr, *hm = (char *)c->comm_scr_h;
@@ -107,7 +107,7 @@ int lmpc_comm_allgather(lmpc_ctx *c, const void *send_host, void *recv_host, lon
 
 int lmpc_comm_allreduce_max(lmpc_ctx *c, double *v, int n) {
     ARGCHK(c && v && n >= 1);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     if (!c->comm) { HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
     int rc = comm_scratch(c, sizeof(double) * (size_t)n); if (rc) return rc;
     double *d = (double *)c->comm_scr, *hm = (double *)c->comm_scr_h;
@@ -124,7 +124,7 @@ int lmpc_comm_allreduce_max(lmpc_ctx *c, double *v, int n) {
 // then one drain of the stream: when it returns, every rank's stream had reached the same point.
 int lmpc_comm_barrier(lmpc_ctx *c) {
     ARGCHK(c);
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     { int rc = resolve_retries(c); if (rc) return rc; }
     if (c->comm) {
         int rc = comm_scratch(c, sizeof(double)); if (rc) return rc;
@@ -140,7 +140,7 @@ int lmpc_comm_barrier(lmpc_ctx *c) {
 int lmpc_rollout_exchange(lmpc_ctx *c, int K, int T_max, double *records, long long *lens, int *n_valid_local) {
     ARGCHK(c && c->ro && c->ro->active && records && lens && K >= 1 && T_max >= 1);
     lmpc_rollout_session *r = c->ro;
-    HIPCHK(hipSetDevice(c->cfg.device));
+    RCCHK(ctx_enter(c));
     HIPCHK(hipStreamSynchronize(r->pstream));
     const int B = r->B, world = c->comm ? c->comm_world : 1;
     std::vector<int> done((size_t)B), st((size_t)B);

@@ -677,6 +677,10 @@ __device__ __forceinline__ void k1_fit(const lmpc_dev_params &p, const k1_smem &
 struct lmpc_live_list { const int *car; int n; };
 __device__ __forceinline__ lmpc_live_list live_list_of() { return {nullptr, 0}; }
 __device__ __forceinline__ lmpc_live_list live_list_of(lmpc_live_list l) { return l; }
+// The regression kernel's pack may instead hold one lmpc_k1_also: a second copy of the fit, each pointer or null -- a step whose regression runs ahead of the previous
+// step's solve writes the context's hand-over set and the caller's A / Bm / C (lmpc_capi.hip: step_dev).  Never both: sessions have a launch path of their own.
+struct lmpc_k1_also { double *A, *Bm, *C; };
+template <class... E> struct lmpc_k1_pack { static constexpr bool live = (... || __is_same(E, lmpc_live_list)), also = (... || __is_same(E, lmpc_k1_also)); };
 // TAB: every problem names its own laps (k1_lap_slot): lapTab holds (slot, rows) pairs, trToUse per row, and problem b reads the row at lapTab + b * tabStride
 // (tabStride = 0: one row for every problem).  The TAB = false builds take neither argument into account.
 // (The table build of the 8-rows-per-lane occupancy kernel is compiled for five waves per SIMD, not six: the 80 registers of six cost its twin seven spilled
@@ -685,7 +689,7 @@ __device__ __forceinline__ lmpc_live_list live_list_of(lmpc_live_list l) { retur
 #ifndef LMPC_K1_TAB_WAVES8
 #define LMPC_K1_TAB_WAVES8 5
 #endif
-template <bool OCC, int RPL, bool TAB = false, class... LIVE>
+template <bool OCC, int RPL, bool TAB = false, class... LIVE>      // LIVE: empty, one lmpc_live_list or one lmpc_k1_also
 __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 : 6) : 4) : 2) void lmpc_regress_kernel(lmpc_dev_params p, int B, int qg, const double *__restrict__ xLin, int xstride,
                                                              const double *__restrict__ uLin, double *__restrict__ Aout,
                                                              double *__restrict__ Bout, double *__restrict__ Cout, int *__restrict__ status,
@@ -713,7 +717,7 @@ __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 
     const int npass = (N + QGe - 1) / QGe;
     int b_ = blockIdx.x / npass;
     if (b_ >= B) return;
-    if constexpr (sizeof...(LIVE) > 0) b_ = live_list_of(lv...).car[b_];
+    if constexpr (lmpc_k1_pack<LIVE...>::live) b_ = live_list_of(lv...).car[b_];
     const int b = b_;
     const int nsub = K1_NW / L > 0 ? K1_NW / L : 1;                        // waves sharing one lap split its queries
     const int myc = wave % L, sgi = wave / L;
@@ -742,6 +746,12 @@ __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 
         if (le < 36) Aout[item * 36 + le] = outv[qi][le];
         else if (le < 48) Bout[item * 12 + (le - 36)] = outv[qi][le];
         else Cout[item * 6 + (le - 48)] = outv[qi][le];
+        if constexpr (lmpc_k1_pack<LIVE...>::also) {
+            const lmpc_k1_also also = [](lmpc_k1_also a) { return a; }(lv...);
+            if (le < 36) { if (also.A) also.A[item * 36 + le] = outv[qi][le]; }
+            else if (le < 48) { if (also.Bm) also.Bm[item * 12 + (le - 36)] = outv[qi][le]; }
+            else if (also.C) also.C[item * 6 + (le - 48)] = outv[qi][le];
+        }
     }
     if (tid < nq) status[(size_t)b * N + i0 + tid] = st_s[tid];
     K1STAMP(7);
