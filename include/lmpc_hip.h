@@ -108,18 +108,20 @@ int lmpc_create_ex(const lmpc_config *cfg, unsigned flags, lmpc_ctx **out);
 #define LMPC_CREATE_RUNTIME_KERNEL 1u
 #define LMPC_CREATE_FORCE_RUNTIME_KERNEL 2u
 #define LMPC_CREATE_NO_K1_AHEAD 4u       /* queued lmpc_step_batch_dev steps keep their regression on the context's stream (see lmpc_step_batch_dev); same results */
+#define LMPC_CREATE_NO_K1_MERGE 8u       /* queued steps never hold a solve for a two-role launch: the two-stream look-ahead serves every chained step (see lmpc_step_batch_dev); same results */
 int lmpc_solver_kind(lmpc_ctx *);                                /* 0: built-in solve kernels, 1: variant library, 2: runtime-(N, S) kernel */
 int lmpc_destroy(lmpc_ctx *ctx);
 const char *lmpc_last_error(void);
 const char *lmpc_active_knobs(void);                             /* developer environment variables this process has acted on ("NAME=value;..."; "" = none): LMPC_K1_QG,
-                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG, LMPC_TRACE_OWN_STREAM, LMPC_K1_AHEAD, LMPC_K1_AHEAD_MAX_BATCH -- route / grid
+                                                                    LMPC_K1_RPL16, LMPC_MW_MAX_BATCH, LMPC_MW2_MAX_BATCH, LMPC_FUSE, LMPC_CD, LMPC_NO_ABG, LMPC_TRACE_OWN_STREAM, LMPC_K1_AHEAD, LMPC_K1_AHEAD_MAX_BATCH, LMPC_K1_MERGE, LMPC_K1_MERGE_QG -- route / grid
                                                                     choices, each announced once on stderr; no reference counterpart.  Bit-identical results: LMPC_TRACE_OWN_STREAM
                                                                     (traced sessions: the trace kernel on a stream of its own instead of the plant stream), LMPC_K1_QG, LMPC_K1_RPL16
                                                                     (regression grid / scan build: A, B, C do not depend on either), LMPC_FUSE (fused one-wave step against the
                                                                     two-kernel one-wave step; ignored by the runtime-(N, S) kernel, which has no fused form), LMPC_NO_ABG
                                                                     ([A_k | B_k] in LDS instead of global memory), LMPC_K1_AHEAD (=0 at lmpc_create: queued
                                                                     lmpc_step_batch_dev steps keep their regression on the context's stream, behind the previous solve,
-                                                                    instead of the look-ahead stream beside it; LMPC_K1_AHEAD_MAX_BATCH: the largest batch that chains).  LMPC_MW_MAX_BATCH and LMPC_MW2_MAX_BATCH move a batch to
+                                                                    instead of the look-ahead stream beside it; LMPC_K1_AHEAD_MAX_BATCH: the largest batch that chains), LMPC_K1_MERGE (=0 at lmpc_create: no held solves, no
+                                                                    two-role launches; LMPC_K1_MERGE_QG: the cap of the queries per regression work-group in them).  LMPC_MW_MAX_BATCH and LMPC_MW2_MAX_BATCH move a batch to
                                                                     another solve kernel (four / two / one wave(s) per QP): A, B, C, the selection and the status word stay
                                                                     bit-identical, the QP answer agrees to the termination rule's bound (x, u within 2e-7: measured by
                                                                     tests/test_gpu_routes.py).  LMPC_CD (condensed kernel, opt-in builds only): another QP method, same optimum
@@ -317,7 +319,15 @@ int lmpc_step_batch_dev(lmpc_ctx *, int B, const lmpc_step_dev_args *args);   /*
          * outputs only, nothing on the device reads them except a retry pass at the next drain, so the caller keeps them (and every input: xLin / uLin of step i + 1 are
          * read while step i solves) untouched until lmpc_dev_sync, as before.  Any other call on the context that queues work or edits what the regression reads (lap
          * stores, lap table, track / tuning rows, lmpc_dev_upload, ...) breaks the chain: the next step's regression goes behind it on the context's stream.  A drain of
-         * the context (lmpc_dev_sync, lmpc_dev_download) covers both streams.  Results are bit-identical to the unchained step; LMPC_K1_AHEAD=0 turns chaining off. */
+         * the context (lmpc_dev_sync, lmpc_dev_download) covers both streams.  Results are bit-identical to the unchained step; LMPC_K1_AHEAD=0 turns chaining off.
+         * Held solves.  On the plain four-wave route (up to one QP per CU, no lap / safe-set table, tuning or track rows in force, A / Bm / C given, not under
+         * lmpc_set_profiling(1)) the solve of a chained step is not launched by its own call: the next lmpc_step_batch_dev launches it in ONE launch with its own
+         * regression -- a two-role build of the solve kernel, nothing but kernels in the queue -- and EVERY other entry point of the context launches it first thing,
+         * stand-alone on the context's stream, so each of them finds the order it found before.  The outputs of a queued step are defined after the next lmpc_dev_sync,
+         * as they always were; new is only that the LAST queued solve starts at the next call into the context.  A caller that queues steps and then goes away to do
+         * host work calls lmpc_dev_flush, which launches a held solve and returns without draining.  lmpc_destroy DROPS a held solve without launching it: the caller
+         * may have freed its arrays by then, and nothing has asked for the results.  LMPC_K1_MERGE=0 at lmpc_create (or LMPC_CREATE_NO_K1_MERGE) keeps the two-stream form. */
+int lmpc_dev_flush(lmpc_ctx *);            /* launches a held solve (above), if there is one; no drain.  The next lmpc_step_batch_dev starts a new chain */
 
 /* ---- caller side of the path, next row of SURVEY 8(f): plant integrator + device-resident closed-loop laps ---- */
 /* Map.getGlobalPosition (Track.py:135-189), batched: curvilinear (s, ey) -> inertial (X, Y) for n points on the track given
@@ -607,6 +617,10 @@ int lmpc_debug_rollout_qp(lmpc_ctx *, int b0, int n, double *A, double *B, doubl
 int lmpc_debug_k1_ahead(lmpc_ctx *, long long out[2]);
         /* (every build) regression launches of lmpc_step_batch_dev since lmpc_create: out[0] chained (on the look-ahead stream, beside the previous step's solve),
          * out[1] unchained (on the context's stream); the fused step launches no regression and counts as neither */
+int lmpc_debug_k1_merge(lmpc_ctx *, long long out[3]);
+        /* (every build) since lmpc_create: out[0] two-role launches (a held solve and the next step's regression), out[1] held solves launched stand-alone (a flush),
+         * out[2] regression launches of lmpc_step_batch_dev in a kernel of their own (chained or not).  A step whose regression rode in a two-role launch still counts
+         * as chained in lmpc_debug_k1_ahead */
 int lmpc_debug_exec_audit(lmpc_ctx *, unsigned long long *out16, int reset);
         /* -DLMPC_EXEC_AUDIT: out16[site] = calls of a cross-lane primitive (DPP / permlane / bpermute reductions, MFMA stages) of the built-in
          * kernels that found an incomplete EXEC mask, out16[8 + site] = calls; sites are listed in csrc/lmpc_kernels.hip.h */

@@ -17,7 +17,7 @@ MAX_TRACK_ROWS = 16
 MAX_USED_LAPS = 32
 COMM_ID_BYTES = 128
 E_VARIANT = -5
-CREATE_RUNTIME_KERNEL, CREATE_FORCE_RUNTIME_KERNEL, CREATE_NO_K1_AHEAD = 1, 2, 4
+CREATE_RUNTIME_KERNEL, CREATE_FORCE_RUNTIME_KERNEL, CREATE_NO_K1_AHEAD, CREATE_NO_K1_MERGE = 1, 2, 4, 8
 
 ST_MAXITER, ST_REG_SINGULAR, ST_NO_SEGMENT, ST_WINDOW, ST_NUMERIC, ST_NOT_INTERIOR, ST_INEXACT, ST_INFEASIBLE = 1, 2, 4, 8, 16, 32, 64, 128
 
@@ -183,7 +183,7 @@ EXPORTS = [
     "lmpc_rollout_set_trace", "lmpc_rollout_get_trace", "lmpc_rollout_trace_bytes", "lmpc_rollout_fetch_trace",
     "lmpc_rollout_set_parking", "lmpc_rollout_get_parking", "lmpc_rollout_parked_at", "lmpc_debug_live_compact",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
-    "lmpc_debug_k1_ahead",
+    "lmpc_debug_k1_ahead", "lmpc_debug_k1_merge", "lmpc_dev_flush",
 ]
 
 _lib = None
@@ -572,9 +572,10 @@ def set_arr(field, values):
 class Context:
     """One lmpc_ctx: device lap stores + batched solver for a fixed (N, safe-set size) configuration."""
 
-    def __init__(self, cfg, runtime_kernel=False, k1_ahead=True):
+    def __init__(self, cfg, runtime_kernel=False, k1_ahead=True, k1_merge=True):
         """k1_ahead=False: queued step_batch_dev steps keep their regression on the context's stream (LMPC_CREATE_NO_K1_AHEAD; ContextPool members: several batches in
-        flight fill the idle CUs already, and the look-ahead's event operations only cost them)."""
+        flight fill the idle CUs already, and the look-ahead's event operations only cost them).  k1_merge=False: chained steps never hold their solve for a two-role
+        launch with the next step's regression (LMPC_CREATE_NO_K1_MERGE): the two-stream look-ahead serves all of them."""
         self.lib = load()
         self.cfg = cfg
         self.N = cfg.N
@@ -585,6 +586,8 @@ class Context:
         self._h = C.c_void_p()
         self._pid = os.getpid()         # the process that owns the device context (see close)
         base = 0 if k1_ahead and not _POOL_MEMBER else CREATE_NO_K1_AHEAD
+        if not k1_merge:
+            base |= CREATE_NO_K1_MERGE
         if runtime_kernel:              # (tests: the runtime-(N, S) kernel even where a fast one exists)
             rc = self.lib.lmpc_create_ex(C.byref(cfg), C.c_uint(base | CREATE_FORCE_RUNTIME_KERNEL), C.byref(self._h))
         else:
@@ -822,6 +825,10 @@ class Context:
 
     def sync(self):
         _chk(self.lib.lmpc_dev_sync(self._h))
+
+    def flush(self):
+        """Launch the solve a queued step_batch_dev left held for the next step (lmpc_dev_flush); no drain.  For callers that queue steps and then do host work."""
+        _chk(self.lib.lmpc_dev_flush(self._h))
 
     def step_batch_dev(self, B, args):
         _chk(self.lib.lmpc_step_batch_dev(self._h, C.c_int(B), C.byref(args)))
@@ -1347,6 +1354,12 @@ class Context:
         out = (C.c_longlong * 2)()
         _chk(self.lib.lmpc_debug_k1_ahead(self._h, out))
         return int(out[0]), int(out[1])
+
+    def debug_k1_merge(self):
+        """(two-role launches, held solves launched stand-alone, regression launches of step_batch_dev in a kernel of their own) since the context was created (see lmpc_debug_k1_merge)."""
+        out = (C.c_longlong * 3)()
+        _chk(self.lib.lmpc_debug_k1_merge(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def set_profiling(self, every):
         """False / 0: off; True / 1: events around every kernel launch; k: around every k-th launch of each kernel (see lmpc_set_profiling)."""

@@ -161,6 +161,14 @@ struct lmpc_ctx {
     struct handover { double *A, *Bm, *C; int *rstatus; };
     hipStream_t k1_stream; hipEvent_t e_k1, e_front; handover ho[2]; int ho_cur;
     int k1_ahead, k1_ahead_max_batch; bool chain, sst_upload_broke; long long n_k1_chained, n_k1_unchained;   // k1_ahead: LMPC_K1_AHEAD=0 at lmpc_create turns it off (the step of before: one stream, the caller's A / Bm / C as the hand-over)
+    // Held solve (step_dev, the merged form of the look-ahead): on a route with a two-role build of the solve kernel (lmpc_variant_api::launch_mw4_next) the solve of a
+    // chained step is not launched by its own call.  The next step_dev launches it in ONE launch with its own regression (no event packet between two solves: nothing
+    // but kernels in the queue); every other entry point launches it stand-alone first thing (ctx_enter), so each of them sees the order it always saw.  `held` is all
+    // launch_solve would have been given plus the parameter block of the step's call; has_held: there is one.  lmpc_destroy drops it.
+    struct held_solve { lmpc_solve_io io; int B; lmpc_dev_params dp; lmpc_k1_also retry_abc; };
+    held_solve held; bool has_held;
+    int k1_merge, k1_merge_qg;               // LMPC_K1_MERGE=0 / LMPC_CREATE_NO_K1_MERGE: the two-stream look-ahead for every chained step;  the cap of the queries per regression work-group of a two-role launch
+    long long n_merged, n_held_flushed, n_k1_alone;   // two-role launches; held solves launched stand-alone; regression launches of step_dev in a kernel of their own
     void *comm; int comm_rank, comm_world;   // RCCL communicator of this rank (lmpc_comm.hip.h); null = single process
     void *comm_scr, *comm_scr_h; size_t comm_scr_bytes;   // communicator scratch: device allocation + pinned host mirror (lmpc_comm.hip.h: comm_scratch)
 };
@@ -201,9 +209,13 @@ enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
 // How every entry point that enqueues on the context's stream, or edits what a regression reads (lap stores and their images, lap table, track rows, parameter
 // images, a device array of the caller's), begins: the context's device, and the chain of look-ahead regressions broken -- the next step_dev runs its regression
 // on the context's stream again, behind whatever this call queues.  step_dev alone sets the flag, at its end.
-static int ctx_enter(lmpc_ctx *c) {
+// A held solve (lmpc_ctx::held) is launched here, stand-alone on the context's stream, before the entry point does anything else: a store edit, an upload, a drain or a
+// download then finds the stream as it would be had every step launched its own solve.  keep_held: step_dev, which decides itself what becomes of it.
+static int launch_held(lmpc_ctx *c, const lmpc_k1_next *next);
+static int ctx_enter(lmpc_ctx *c, bool keep_held = false) {
     c->chain = false;
     if (const hipError_t e = hipSetDevice(c->cfg.device)) return set_err(LMPC_E_HIP, "hipSetDevice(c->cfg.device)", hipGetErrorString(e));
+    if (c->has_held && !keep_held) return launch_held(c, nullptr);
     return LMPC_OK;
 }
 
@@ -259,7 +271,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 113; }
+int lmpc_version(void) { return 114; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -421,6 +433,11 @@ static int image_upload(dev_image *img, const void *host, size_t bytes, const ch
 }
 // Look-ahead regression: the largest batch whose queued steps chain.  PLACEHOLDER_RULE
 #define K1_AHEAD_MAX_BATCH_RULE (1 << 30)
+// Two-role launches: the cap of the queries per regression work-group (k1_queries_per_block under it).  A CU takes a regression work-group only when its QP has
+// converged, so a finer split leaves a shorter tail behind the last solves -- but every work-group loads and scans the laps for itself, and that weighs more:
+// measured at batch 256 (profiles/merged_step_ab.json, ms per step) 12: 0.1799, 6: 0.1805, 4: 0.1831, 3: 0.1909, 2: 0.2025, 1: 0.2511 against the parent's 0.1874.
+// One work-group per problem, the whole horizon.
+#define MERGE_QG_RULE 12
 // everything of lmpc_create that can fail; the caller destroys the context on any error (one failure path, no leaks)
 static int create_body(lmpc_ctx *c) {
     const lmpc_config *cfg = &c->cfg;
@@ -478,6 +495,10 @@ static int create_body(lmpc_ctx *c) {
     if (c->create_flags & LMPC_CREATE_NO_K1_AHEAD) c->k1_ahead = 0;
     c->k1_ahead_max_batch = K1_AHEAD_MAX_BATCH_RULE;
     if (const char *e = dev_knob("LMPC_K1_AHEAD_MAX_BATCH")) c->k1_ahead_max_batch = atoi(e);        // (experiments)
+    // merged form of the look-ahead (lmpc_ctx::held): on wherever the look-ahead is; LMPC_K1_MERGE=0 / LMPC_CREATE_NO_K1_MERGE leave the two-stream form.  The cap of the
+    // queries per regression work-group of a two-role launch: MERGE_QG_RULE, LMPC_K1_MERGE_QG for the sweep.  (Bit-identical either way.)
+    { const char *e = dev_knob("LMPC_K1_MERGE"); c->k1_merge = c->k1_ahead && (e ? atoi(e) != 0 : 1) && !(c->create_flags & LMPC_CREATE_NO_K1_MERGE); }
+    { const char *e = dev_knob("LMPC_K1_MERGE_QG"); c->k1_merge_qg = e && atoi(e) > 0 ? atoi(e) : MERGE_QG_RULE; }
     if (c->var.lds_1w_abg > 0 && !dev_knob("LMPC_NO_ABG")) { HIPCHK(g_malloc(&c->ab_pack, sizeof(double) * 48 * (size_t)cfg->N * (size_t)cfg->max_batch)); c->ab_pack_cap = (size_t)cfg->max_batch; }
     HIPCHK(hipHostMalloc(&c->h_retry, sizeof(int) * LMPC_RETRY_RING, hipHostMallocMapped));
     memset(c->h_retry, 0, sizeof(int) * LMPC_RETRY_RING);
@@ -559,6 +580,7 @@ int lmpc_debug_guard_failures(void) { return g_guard_failures; }      /* guard b
 int lmpc_destroy(lmpc_ctx *c) {
     if (!c) return LMPC_OK;
     (void)hipSetDevice(c->cfg.device);
+    c->has_held = false;                               // a held solve is dropped, not launched: the caller may have freed its arrays, and nobody has asked for the results
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->k1_stream) (void)hipStreamSynchronize(c->k1_stream);
     rollout_free(c);
@@ -1317,6 +1339,36 @@ static int launch_solve(lmpc_ctx *c, int B, const lmpc_solve_io &io_in, bool imm
     }
     return LMPC_OK;
 }
+// The held solve of the context (lmpc_ctx::held), launched: stand-alone (next null: a flush -- ctx_enter, or a step that cannot carry it) or as the solve role of a
+// two-role launch whose other work-groups run the regression *next.  What launch_solve keeps of a launch is kept here, when the launch happens: the retry ring and the
+// pending entry, the counters, and the profiling events -- around the whole launch, a solve's; a regression inside a two-role launch is counted, not timed.
+static int launch_held(lmpc_ctx *c, const lmpc_k1_next *next) {
+    const lmpc_ctx::held_solve h = c->held; c->has_held = false;
+    lmpc_solve_io io = h.io;
+    if ((int)c->pending.size() >= LMPC_RETRY_RING - 1) RESOLVE_PENDING();
+    c->epoch++; io.retry_epoch = c->epoch; io.retry_flag = c->d_retry + (c->epoch % LMPC_RETRY_RING);
+    ev_begin(c, 1, c->stream);
+    const int rc = next ? c->var.launch_mw4_next(c->stream, h.dp, h.B, io, *next) : c->var.launch_mw4(c->stream, h.dp, h.B, io, nullptr);
+    ev_end(c, c->stream);
+    if (rc) return set_err(LMPC_E_STATE, "held solve", "no launcher");
+    HIPCHK(hipGetLastError());
+    c->stats.n_solve++; c->stats.qp_solved += h.B;
+    if (next) { c->stats.n_regress++; c->n_merged++; } else c->n_held_flushed++;
+    lmpc_solve_io pio = io; pio.A = h.retry_abc.A; pio.Bm = h.retry_abc.Bm; pio.C = h.retry_abc.C;      // (the caller's arrays: a step is held only where it gave all three)
+    c->pending.push_back({pio, h.B, io.retry_epoch, h.dp, false});
+    return LMPC_OK;
+}
+// Which steps take the merged form of the look-ahead: the plain four-wave solve at up to one QP per CU (the only kernel with a two-role build), nothing per problem in
+// force (lap table, safe-set table, tuning rows, track rows: other instantiations), the caller's own A / Bm / C (the retry pass of a held solve reads them), and not
+// lmpc_set_profiling(1), which asks for the duration of EVERY kernel of a kind: a regression inside a two-role launch has none of its own.
+static bool k1_merge_ok(const lmpc_ctx *c, int B, const lmpc_arrays &a) {
+    if (!c->k1_merge || !c->var.launch_mw4_next || B > c->mw_max_batch || B > c->n_cu || !(a.A && a.Bm && a.C) || c->profiling == 1) return false;
+    if ((c->cd_ok && c->cd_mode == 1) || c->dbg_trace) return false;
+#ifdef LMPC_DEV_FAST
+    if (getenv("LMPC_FORCE_NW")) return false;
+#endif
+    return !c->lt.in_force() && !c->sst.in_force() && !c->tune.in_force() && !c->trk.in_force();
+}
 
 #define H2D(dst, src, n) HIPCHK(hipMemcpyAsync(dst, src, sizeof(*(dst)) * (size_t)(n), hipMemcpyHostToDevice, c->stream))
 #define D2H(dst, src, n) do { if (dst) HIPCHK(hipMemcpyAsync(dst, src, sizeof(*(src)) * (size_t)(n), hipMemcpyDeviceToHost, c->stream)); } while (0)
@@ -1486,8 +1538,8 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     const int N = c->cfg.N; const bool term = c->cfg.numSS_it > 0;
     if (term) ARGCHK(a.zt != nullptr);
     ARGCHK(!a.hasPred || a.xPredPrev);                   // (device arrays: a set hasPred[b] would dereference the missing predictions inside the kernel)
-    const bool was_chain = c->chain;                     // (the previous call was a two-kernel step_dev and nothing has been queued or edited since)
-    RCCHK(ctx_enter(c));
+    bool was_chain = c->chain;                           // (the previous call was a two-kernel step_dev and nothing has been queued or edited since)
+    RCCHK(ctx_enter(c, true));                           // (a held solve stays held: launched below, with this step's regression or in front of this step)
     ARGCHK(B <= c->cfg.max_batch);                      // the work buffers (per-point regression status, A, B, C hand-over) are sized for max_batch
     // Regression kernel, then the solve kernel; A, Bm, C are optional outputs (the hand-over then uses the context's work buffers).
     // With LMPC_FUSE=1 batches that run one wave per QP take the fused step instead: every wave runs the regression of its own QP in
@@ -1498,6 +1550,11 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     // (likewise tuning rows, lmpc_tuning_set: the fused form has no per-problem-rows instantiation)
     const bool fused = c->fuse_k1 && lmpc_solver_waves(c, B) == 1 && !c->lt.in_force() && !(term && c->sst.in_force()) && !c->tune.in_force() && !c->trk.in_force();      // (likewise track rows, lmpc_track_set)
     lmpc_solve_io io = solve_io((fused ? 4 : 0) | (term ? 3 : 2), a);
+    // The merged form of the look-ahead (lmpc_ctx::held): a chained step on a route with a two-role build.  Its regression is launched now -- in one launch with the solve
+    // held by the step before, or in a kernel of its own behind everything queued where none is held (the second step of a chain) -- and its own solve is held.
+    // Any other step first launches a held solve stand-alone and then runs unchained: such a solve lies behind no e_front record a look-ahead regression could wait for.
+    const bool merged = was_chain && !c->sst_upload_broke && !fused && c->k1_ahead && k1_ahead_pays(c, B) && k1_merge_ok(c, B, a);
+    if (c->has_held && !merged) { RCCHK(launch_held(c, nullptr)); was_chain = false; }
     if (fused || !c->k1_ahead || !k1_ahead_pays(c, B)) {      // the step of before: one stream, the caller's A / Bm / C as the hand-over where given; it starts no chain
         double *dA = a.A ? a.A : c->w.A, *dB = a.Bm ? a.Bm : c->w.Bm, *dC = a.C ? a.C : c->w.C;
         // A, Bm, C not given: the hand-over goes through the context's own buffers, which this launch's regression overwrites -- a launch still
@@ -1509,7 +1566,7 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
         io.A = dA; io.Bm = dB; io.C = dC;
         // (io.rstatus / the fused regression: a singular regression or an off-track linearisation point marks status[b]; the reference raises there)
         if (fused) { io.xLin = a.xLin; io.uLin = a.uLin; io.Aout = a.A; io.Bout = a.Bm; io.Cout = a.C; RCCHK(refresh_params(c, true, false)); }
-        else { RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, dA, dB, dC, c->w.rstatus)); io.rstatus = c->w.rstatus; c->n_k1_unchained++; }
+        else { RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, dA, dB, dC, c->w.rstatus)); io.rstatus = c->w.rstatus; c->n_k1_unchained++; c->n_k1_alone++; }
         return launch_solve(c, B, io);
     }
     // The look-ahead form.  The regression writes one of the context's two hand-over sets -- and the caller's A / Bm / C beside it, where given -- and the solve's
@@ -1535,15 +1592,28 @@ static int step_dev(lmpc_ctx *c, int B, const lmpc_arrays &a) {
     // and gains nothing here (tests/test_gpu_retry.py counts on the pass having run by then)
     for (const auto &pe : c->pending) if (pe.shared_abc) { RESOLVE_PENDING(); break; }
     const k1_also also = {a.A, a.Bm, a.C};
+    if (merged && chained) {
+        // one queue, kernels only: [solve(i - 1) | K1(i)] of this call lies behind [solve(i - 2) | K1(i - 1)], the last reader of the set K1(i) writes and the writer of
+        // the set solve(i - 1) reads.  The regression role reads the lap stores through the held step's parameter block: the chain is unbroken, so they are the ones of now.
+        if (c->has_held) { const lmpc_k1_next nx = {B, c->k1_merge_qg, a.xLin, (N + 1) * 6, a.uLin, h.A, h.Bm, h.C, h.rstatus, also}; RCCHK(launch_held(c, &nx)); }
+        else { RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, h.A, h.Bm, h.C, h.rstatus, c->stream, also)); c->n_k1_alone++; }
+        c->n_k1_chained++;
+        c->ho_cur = set;
+        io.A = h.A; io.Bm = h.Bm; io.C = h.C; io.rstatus = h.rstatus;
+        RCCHK(refresh_params(c, false, term, false, false));      // (what launch_solve would do now: the held launch takes the selection of ITS call)
+        c->held.io = io; c->held.B = B; c->held.dp = c->dp; c->held.retry_abc = {a.A, a.Bm, a.C}; c->has_held = true;
+        c->chain = true;
+        return LMPC_OK;
+    }
     if (chained) {
         HIPCHK(hipStreamWaitEvent(c->k1_stream, c->e_front, 0));
         RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, h.A, h.Bm, h.C, h.rstatus, c->k1_stream, also));
         HIPCHK(hipEventRecord(c->e_k1, c->k1_stream));
         HIPCHK(hipStreamWaitEvent(c->stream, c->e_k1, 0));
-        c->n_k1_chained++;
+        c->n_k1_chained++; c->n_k1_alone++;
     } else {
         RCCHK(launch_regress(c, B, a.xLin, (N + 1) * 6, a.uLin, h.A, h.Bm, h.C, h.rstatus, c->stream, also));
-        c->n_k1_unchained++;
+        c->n_k1_unchained++; c->n_k1_alone++;
     }
     c->ho_cur = set;
     io.A = h.A; io.Bm = h.Bm; io.C = h.C; io.rstatus = h.rstatus;
@@ -1683,6 +1753,8 @@ int lmpc_dev_free(lmpc_ctx *c, void *dptr) { ARGCHK(c); RCCHK(ctx_enter(c)); { i
 int lmpc_dev_upload(lmpc_ctx *c, void *dptr, const void *host, long long bytes) { ARGCHK(c && dptr && host); RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipMemcpyAsync(dptr, host, (size_t)bytes, hipMemcpyHostToDevice, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
 int lmpc_dev_download(lmpc_ctx *c, void *host, const void *dptr, long long bytes) { ARGCHK(c && dptr && host); RCCHK(ctx_enter(c)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipMemcpyAsync(host, dptr, (size_t)bytes, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
 int lmpc_debug_k1_ahead(lmpc_ctx *c, long long out[2]) { ARGCHK(c && out); out[0] = c->n_k1_chained; out[1] = c->n_k1_unchained; return LMPC_OK; }
+int lmpc_debug_k1_merge(lmpc_ctx *c, long long out[3]) { ARGCHK(c && out); out[0] = c->n_merged; out[1] = c->n_held_flushed; out[2] = c->n_k1_alone; return LMPC_OK; }
+int lmpc_dev_flush(lmpc_ctx *c) { ARGCHK(c); return ctx_enter(c); }
 int lmpc_dev_sync(lmpc_ctx *c) { ARGCHK(c); RCCHK(ctx_enter(c)); { int rc = resolve_retries(c); if (rc) return rc; } HIPCHK(hipStreamSynchronize(c->stream)); return LMPC_OK; }
 
 // developer trace: host-side seconds of the one-QP path of lmpc_step_batch since the context was made -- out[0..3] = staging the inputs, launching the
@@ -2542,7 +2614,7 @@ int lmpc_solver_lds(lmpc_ctx *c, unsigned long long out4[4]) {
     return LMPC_OK;
 }
 
-int lmpc_set_profiling(lmpc_ctx *c, int every) { ARGCHK(c); c->profiling = every > 0 ? every : 0; return LMPC_OK; }
+int lmpc_set_profiling(lmpc_ctx *c, int every) { ARGCHK(c); RCCHK(ctx_enter(c)); c->profiling = every > 0 ? every : 0; return LMPC_OK; }      // (a held solve is launched under the setting of its step)
 static int drain_events(lmpc_ctx *c) {
     RCCHK(ctx_enter(c)); HIPCHK(hipStreamSynchronize(c->stream));
     for (auto &e : c->events) {

@@ -281,6 +281,7 @@ __global__ void lmpc_global_position_kernel(lmpc_dev_params p_, int n, const dou
 // The normal equations, the three 5x5 Cholesky solves and the analytic rows are then batched over the queries of the block
 // (threads = (query, entry) pairs) instead of running as serial tails of single lanes.
 // =====================================================================================================
+#include "lmpc_merge.h"
 #define K1_NW 8                    // waves per work-group
 #define K1_NT (K1_NW * WAVE)
 #define K1_QG 12                   // queries per pass
@@ -680,7 +681,10 @@ __device__ __forceinline__ lmpc_live_list live_list_of(lmpc_live_list l) { retur
 // The regression kernel's pack may instead hold one lmpc_k1_also: a second copy of the fit, each pointer or null -- a step whose regression runs ahead of the previous
 // step's solve writes the context's hand-over set and the caller's A / Bm / C (lmpc_capi.hip: step_dev).  Never both: sessions have a launch path of their own.
 struct lmpc_k1_also { double *A, *Bm, *C; };
-template <class... E> struct lmpc_k1_pack { static constexpr bool live = (... || __is_same(E, lmpc_live_list)), also = (... || __is_same(E, lmpc_k1_also)); };
+// The multi-wave solve kernel's pack may hold one lmpc_k1_next instead of a list: the two-role build (lmpc_solve_mw.hip.h), whose work-groups behind the B solves run the
+// regression of the NEXT queued step -- B problems, qg the cap of the queries per work-group (lmpc_merge.h), the arguments of lmpc_regress_kernel and its second copy.
+struct lmpc_k1_next { int B, qg; const double *xLin; int xstride; const double *uLin; double *A, *Bm, *C; int *status; lmpc_k1_also also; };
+template <class... E> struct lmpc_k1_pack { static constexpr bool live = (... || __is_same(E, lmpc_live_list)), also = (... || __is_same(E, lmpc_k1_also)), next = (... || __is_same(E, lmpc_k1_next)); };
 // TAB: every problem names its own laps (k1_lap_slot): lapTab holds (slot, rows) pairs, trToUse per row, and problem b reads the row at lapTab + b * tabStride
 // (tabStride = 0: one row for every problem).  The TAB = false builds take neither argument into account.
 // (The table build of the 8-rows-per-lane occupancy kernel is compiled for five waves per SIMD, not six: the 80 registers of six cost its twin seven spilled
@@ -689,6 +693,75 @@ template <class... E> struct lmpc_k1_pack { static constexpr bool live = (... ||
 #ifndef LMPC_K1_TAB_WAVES8
 #define LMPC_K1_TAB_WAVES8 5
 #endif
+// The regression of ONE work-group of NWV waves: queries i0 .. i0 + nq - 1 of problem b -- query load, scan (k1_scan_lap), fit (k1_fit), stores: the body of
+// lmpc_regress_kernel below with the wave count as a template parameter and the LDS behind a k1_smem.  It serves the regression role of the two-role solve kernel
+// (lmpc_solve_mw.hip.h: NW waves, a slice of its dynamic LDS, k1_smem_carve).  NWV decides which wave scans which lap for which queries (cs0, nsub), the extents of
+// sm.cseg / ccnt and the strides of the fit and store loops; the result of every query is the same bits whatever NWV and whatever the split into work-groups.
+// (The stand-alone kernel does NOT call it: called through this function with NWV = 8 and its static arrays, all twenty builds of it came out with other text --
+//  30 to 50 instructions fewer each, not measured -- and their text is the parent's by decision, as DESIGN 3 keeps the solve kernels' five blocks.  What the two
+//  share by call is everything that computes: k1_scan_lap and k1_fit.)
+// lt: the problem's row of the lap table (TAB), trk: its track row, or null.  lv: empty, or one lmpc_k1_also.
+template <int NWV, bool PAIR, int RPL, bool TAB, class... ALSO>
+__device__ __forceinline__ void k1_block(const lmpc_dev_params &p, const k1_smem &sm, int b, int i0, int nq, int tid, int lane, int wave, const double *xLin, int xstride,
+                                         const double *uLin, double *Aout, double *Bout, double *Cout, int *status, const int *lt, const double *trk, ALSO... lv) {
+    constexpr int NT = NWV * WAVE;
+    const int N = p.N, L = p.trToUse;
+    const int MAXP = p.maxNumPoint > 8 ? 8 : p.maxNumPoint;
+    const int nsub = NWV / L > 0 ? NWV / L : 1;                            // waves sharing one lap split its queries
+    const int myc = wave % L, sgi = wave / L;
+    if (tid < nq * 5) {
+        const int qi = tid / 5, f = tid % 5;
+        sm.qf[qi][f] = f < 3 ? xLin[(size_t)b * xstride + (size_t)(i0 + qi) * 6 + f] : uLin[((size_t)b * N + i0 + qi) * 2 + (f - 3)];
+    }
+    for (int e = tid; e < nq * L; e += NT) sm.nsel[e] = 0;
+    if (tid < nq) sm.st_s[tid] = 0;
+    K1STAMP(0);
+    __syncthreads();
+    K1STAMP(1);
+    // (two queries per trip in the low-occupancy build.  The occupancy build takes one per trip: with four waves per SIMD the other waves
+    //  fill the chain's latency, and the second query's 16 distances cost registers it does not have -- spilled registers are scratch
+    //  WRITES: 134 MB per launch at batch 4096 before this)
+    for (int c = myc; c < L && sgi < nsub; c += NWV)                      // (c += NWV: more laps than waves -- trToUse up to 32 -- a wave then scans several laps in turn)
+        k1_scan_lap<PAIR, RPL, TAB>(p, sm, c, wave * K1_QG, sgi, nsub, nq, lane, MAXP, lt);
+    __syncthreads();
+    K1STAMP(2);
+    k1_fit<TAB>(p, sm, 0, nq, tid, NT, xLin + (size_t)b * xstride + (size_t)i0 * 6, MAXP, lt, trk);
+    for (int e = tid; e < nq * 54; e += NT) {
+        const int qi = e / 54, le = e % 54; const size_t item = (size_t)b * N + i0 + qi;
+        if (le < 36) Aout[item * 36 + le] = sm.outv[qi][le];
+        else if (le < 48) Bout[item * 12 + (le - 36)] = sm.outv[qi][le];
+        else Cout[item * 6 + (le - 48)] = sm.outv[qi][le];
+        if constexpr (lmpc_k1_pack<ALSO...>::also) {
+            const lmpc_k1_also also = [](lmpc_k1_also a) { return a; }(lv...);
+            if (le < 36) { if (also.A) also.A[item * 36 + le] = sm.outv[qi][le]; }
+            else if (le < 48) { if (also.Bm) also.Bm[item * 12 + (le - 36)] = sm.outv[qi][le]; }
+            else if (also.C) also.C[item * 6 + (le - 48)] = sm.outv[qi][le];
+        }
+    }
+    if (tid < nq) status[(size_t)b * N + i0 + tid] = sm.st_s[tid];
+    K1STAMP(7);
+}
+// The work space of k1_block for NWV waves as a slice of dynamic LDS (the two-role solve kernel): k1_smem_doubles<NWV>() doubles from `w` (16-byte aligned).  Same
+// extents as the static arrays of the stand-alone kernel, cseg / ccnt for NWV waves; outv shares the words of cseg there too.
+template <int NWV> __host__ __device__ constexpr inline int k1_cseg_doubles() { return (NWV * K1_QG * 16 / 2 > K1_QG * 54 ? NWV * K1_QG * 16 / 2 : K1_QG * 54); }
+template <int NWV> __host__ __device__ constexpr inline int k1_smem_doubles() {
+    return K1_QG * 5 + K1_SEL + K1_PTS * 10 + K1_QG * 45 + k1_cseg_doubles<NWV>() + (NWV * K1_QG + 2 * K1_SEL + K1_QG + 1) / 2;
+}
+template <int NWV> __device__ __forceinline__ k1_smem k1_smem_carve(double *w, const lmpc_dev_params &p) {
+    k1_smem sm; sm.Ls = p.trToUse; sm.Sp = p.maxNumPoint > 8 ? 8 : p.maxNumPoint;
+    sm.qf = (double (*)[5])w; w += K1_QG * 5;                 // (60 doubles: what follows stays 16-byte aligned)
+    sm.seld = w; w += K1_SEL;
+    sm.pts = (double (*)[10])w; w += K1_PTS * 10;
+    sm.gram = (double (*)[45])w; w += K1_QG * 45;
+    sm.cseg = (int (*)[16])w; sm.outv = (double (*)[54])w; w += k1_cseg_doubles<NWV>();
+    int *wi = (int *)w;
+    sm.ccnt = wi; wi += NWV * K1_QG;
+    sm.seli = wi; wi += K1_SEL;
+    sm.nsel = wi; wi += K1_SEL;
+    sm.st_s = wi;
+    return sm;
+}
+
 template <bool OCC, int RPL, bool TAB = false, class... LIVE>      // LIVE: empty, one lmpc_live_list or one lmpc_k1_also
 __global__ __launch_bounds__(K1_NT, OCC ? (RPL <= 8 ? (TAB ? LMPC_K1_TAB_WAVES8 : 6) : 4) : 2) void lmpc_regress_kernel(lmpc_dev_params p, int B, int qg, const double *__restrict__ xLin, int xstride,
                                                              const double *__restrict__ uLin, double *__restrict__ Aout,

@@ -26,7 +26,7 @@
 #define TSMW(id) do { } while (0)
 #endif
 
-template <int N, int S, int NW, bool TAB = false, class... LIVE>      // LIVE: empty, or lmpc_live_list -- a parking session, work-group j solves problem lv.car[j]; with TAB only
+template <int N, int S, int NW, bool TAB = false, class... LIVE>      // LIVE: empty, or lmpc_live_list -- a parking session, work-group j solves problem lv.car[j]; with TAB only -- or lmpc_k1_next, the two-role build (below); without TAB only
 // (registers: four waves per QP = one wave per SIMD; two waves per QP = two waves per SIMD only where the LDS footprint lets three or more
 // QPs share a CU -- long horizons keep their sweep operands (3 N doubles per lane) in registers and need the full file: at N = 40 the
 // 256-register build spilled 221 VGPRs to scratch)
@@ -41,8 +41,20 @@ __global__ __launch_bounds__(WAVE *NW, (NW == 4 || solve_lds<N, S>::tot * 8 * 3 
     constexpr bool ROWS_OFF_W0 = S > 0 && S <= WAVE && NT >= 8 * N + WAVE && SWEEP_BF<N>;     // wave 0 owns the lambda rows and nothing else (see slot_row; the four-wave kernel: the other rows fit threads 64 .. 255)
     constexpr int RPL = ((ROWS_OFF_W0 ? 8 * N + WAVE : M) + NT - 1) / NT;           // inequality rows per thread
     int b_ = blockIdx.x;
-    if (b_ >= B) return;
-    if constexpr (sizeof...(LIVE) > 0) b_ = __builtin_amdgcn_readfirstlane(live_list_of(lv...).car[b_]);      // (parking: entry b_ of the live list, wave-uniform: kept in an SGPR)
+    if constexpr (lmpc_k1_pack<LIVE...>::next) {
+        // Two-role build (lmpc_merge.h): the work-groups behind the B solves run the regression of the next queued step -- k1_block, the stand-alone kernel's text, with
+        // NW waves and its work space in the dynamic LDS -- and return.  The role is uniform over the work-group; it sets no wave priority and shares nothing with a solve.
+        if (b_ >= B) {
+            const lmpc_k1_next nx = [](lmpc_k1_next a) { return a; }(lv...);
+            const lmpc_wg_role r = lmpc_merged_role(b_, B, nx.B, p.N, k1_queries_per_block(nx.qg, p.trToUse, p.maxNumPoint));
+            if (r.role != 1) return;
+            const int tid_ = threadIdx.x;
+            k1_block<NW, true, K1_RPL, false>(p, k1_smem_carve<NW>(sm, p), r.b, r.i0, r.nq, tid_, tid_ & (WAVE - 1), __builtin_amdgcn_readfirstlane(tid_ >> 6), nx.xLin, nx.xstride, nx.uLin,
+                                              nx.A, nx.Bm, nx.C, nx.status, (const int *)nullptr, (const double *)nullptr, nx.also);
+            return;
+        }
+    } else if (b_ >= B) return;
+    if constexpr (lmpc_k1_pack<LIVE...>::live) b_ = __builtin_amdgcn_readfirstlane(live_list_of(lv...).car[b_]);      // (parking: entry b_ of the live list, wave-uniform: kept in an SGPR)
     const int b = b_;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction: tests on it are scalar branches, not exec-mask regions with a v_cmp each

@@ -27,6 +27,9 @@ struct lmpc_variant_api {
     size_t lds_cd_q;                          //   ... with it (Q or Qf non-zero)
     int (*launch_cd)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &, int hasQ);   // lmpc_solve_kernel_cd<N,S>
     int occ_mw2;                              // work-groups of the two-wave kernel the runtime keeps resident per CU (asked, not assumed: 0 = unknown)
+    // lmpc_solve_kernel_mw<N,S,4,false,lmpc_k1_next>: the plain four-wave solve of B problems and, in the same launch, the regression of the next step (lmpc_merge.h);
+    // null where the (N, S) has no multi-wave kernels
+    int (*launch_mw4_next)(hipStream_t, const lmpc_dev_params &, int B, const lmpc_solve_io &, const lmpc_k1_next &);
 };
 
 // What lmpc_create asks a variant library for (lmpc_variant_get): the revision and the sizes of the three structures that cross the boundary by value or
@@ -95,7 +98,12 @@ template <int N, int S> struct lmpc_variant_launchers {
         return lmpc_solve_family{lmpc_solve_kernel_mw<N, S, NW>, lmpc_solve_kernel_mw<N, S, NW, true>, lmpc_solve_kernel_mw<N, S, NW, true, lmpc_live_list>, WAVE * NW,
                                  ldsm, ldsm, ldsm + LMPC_SSTAB_LDS}; }
 
+    // the two-role build of the plain four-wave kernel: the larger of the solve's layout and the regression's work space (k1_smem_carve)
+    static constexpr size_t lds_next = ldsm > (size_t)k1_smem_doubles<4>() * sizeof(double) ? ldsm : (size_t)k1_smem_doubles<4>() * sizeof(double);
+    static constexpr auto mw4_next() { return lmpc_solve_kernel_mw<N, S, 4, false, lmpc_k1_next>; }
+
     static bool raise_limits() {
+        if constexpr (has_mw) { if (!lmpc_raise_lds_limit((const void *)mw4_next(), lds_next)) return false; }
         if constexpr (use_abg) { if (!lmpc_raise_lds_limits(one_wave<false, true>())) return false; }
 #ifdef LMPC_WITH_CD
         if constexpr (has_cd) { if (!lmpc_raise_lds_limit((const void *)lmpc_solve_kernel_cd<N, S>, lds_cd(true))) return false; }
@@ -110,6 +118,11 @@ template <int N, int S> struct lmpc_variant_launchers {
     static int lr(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) { return lmpc_launch_pair(one_wave<true>(lds_for(p, io)), st, p, B, io, live); }
     static int l4(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) { return lmpc_launch_pair(multi_wave<4>(), st, p, B, io, live); }
     static int l2(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const int *live) { return lmpc_launch_pair(multi_wave<2>(), st, p, B, io, live); }
+    static int l4n(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, const lmpc_k1_next &nx) {
+        const long long grid = lmpc_merged_grid(B, nx.B, p.N, k1_queries_per_block(nx.qg, p.trToUse, p.maxNumPoint));
+        if constexpr (has_mw) { hipLaunchKernelGGL(mw4_next(), dim3((unsigned)grid), dim3(WAVE * 4), lds_next, st, p, B, io, nx); return 0; }
+        return -1;
+    }
     static int lc(hipStream_t st, const lmpc_dev_params &p, int B, const lmpc_solve_io &io, int hasQ) {
 #ifdef LMPC_WITH_CD
         if constexpr (has_cd) { hipLaunchKernelGGL((lmpc_solve_kernel_cd<N, S>), dim3(B), dim3(WAVE), lds_cd(hasQ), st, p, B, io, hasQ); return 0; }
@@ -129,11 +142,11 @@ template <int N, int S> static bool lmpc_variant_fill(lmpc_variant_api *v) {
     v->lds_1w = L::lds1; v->lds_1w_abg = L::use_abg ? L::lds1g : 0; v->lds_cd = L::lds_cd(false); v->lds_cd_q = L::lds_cd(true);
     v->launch_1w = &L::l1; v->launch_retry = &L::lr; v->launch_cd = &L::lc;
     if constexpr (L::has_mw) {
-        v->lds_mw = L::ldsm; v->launch_mw4 = &L::l4; v->launch_mw2 = &L::l2;
+        v->lds_mw = L::ldsm; v->launch_mw4 = &L::l4; v->launch_mw2 = &L::l2; v->launch_mw4_next = &L::l4n;
         int nb = 0; const auto m2 = L::template multi_wave<2>();
         v->occ_mw2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)m2.plain, m2.threads, m2.lds) == hipSuccess ? nb : 0;
     } else {
-        v->lds_mw = 0; v->launch_mw4 = &L::l1; v->launch_mw2 = &L::l1; v->occ_mw2 = 0;
+        v->lds_mw = 0; v->launch_mw4 = &L::l1; v->launch_mw2 = &L::l1; v->occ_mw2 = 0; v->launch_mw4_next = nullptr;
     }
     return true;
 }
@@ -148,7 +161,7 @@ static bool lmpc_variant_fill_rt(lmpc_variant_api *v, int N, int S) {
     for (const void *k : {(const void *)lmpc_rt_family<false>::plain, (const void *)lmpc_rt_family<false>::list, (const void *)lmpc_rt_family<true>::plain, (const void *)lmpc_rt_family<true>::list})
         if (!lmpc_raise_lds_limit(k, lds + LMPC_SSTAB_LDS)) return false;
     v->N = N; v->S = S; v->lds_mw = 0; v->lds_1w = lds; v->lds_1w_abg = 0; v->lds_cd = 0; v->lds_cd_q = 0; v->occ_mw2 = 0;
-    v->launch_1w = &lmpc_rt_launch<false>; v->launch_retry = &lmpc_rt_launch<true>; v->launch_mw4 = &lmpc_rt_launch<false>; v->launch_mw2 = &lmpc_rt_launch<false>; v->launch_cd = &lmpc_rt_launch_cd;
+    v->launch_1w = &lmpc_rt_launch<false>; v->launch_retry = &lmpc_rt_launch<true>; v->launch_mw4 = &lmpc_rt_launch<false>; v->launch_mw2 = &lmpc_rt_launch<false>; v->launch_cd = &lmpc_rt_launch_cd; v->launch_mw4_next = nullptr;
     return true;
 }
 #endif
