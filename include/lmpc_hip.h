@@ -255,6 +255,24 @@ int lmpc_store_read_lap(lmpc_ctx *, int store /*0: regression store (sorted posi
          * main.py:36; racinglmpc_amd._capi.Context.save_stores / restore_stores write and read an .npz).  Any of x, u, qfun may be NULL */
 int lmpc_ss_get_laptime(lmpc_ctx *, int lap, int *T);
         /* LMPC.LapTime[lap] (:420): rows of the lap when it was added (without addPoint extensions) -- what argsort(LapTime) sorts */
+int lmpc_store_retain(lmpc_ctx *, int n_ss, const int *keep_ss, int n_model, const int *keep_model,
+                      int *map_ss /* laps stored before the call, or NULL */, int *map_model /* likewise, or NULL */);
+        /* Laps given back: each store keeps the laps listed and drops the others, and the device stores shrink to what is kept.  No reference counterpart -- its lists
+         * only grow (PredictiveControllers.py:418-445, PredictiveModel.py:35-46), although a controller reads only numSS_it fastest laps plus the latest one
+         * (:395-412, :502-512) and trToUse fastest laps (PredictiveModel.py:31).  keep_ss: n_ss strictly ascending safe-set lap indices (lmpc_ss_add_trajectory order);
+         * keep_model: n_model strictly ascending regression-store insertion indices.  n = -1 (with NULL) leaves that store untouched, n = 0 empties it.  Afterwards the
+         * k-th kept lap has index k in its store; map[old] is the new index of lap `old`, -1 for a dropped one (the identity for an untouched store).  Relative order is
+         * kept, so the regression store's sorted order among the kept laps (ascending rows, ties by insertion index) and the shared selection (stable argsort of LapTime)
+         * are what they were.  Without a `last` column the LATEST LAP is the highest kept index: cur_it = the laps kept, as if only they had ever been added.
+         * Everything that names a lap is renumbered with the stores: the rows of lmpc_model_set_lap_table, the rows and `last` of lmpc_ss_set_lap_table, the override
+         * of lmpc_ss_set_selected; their device images are rebuilt.  Checked in full before anything changes -- a refused call leaves stores, books, tables and
+         * capacities as they were: LMPC_E_ARG for a list that is not strictly ascending or names a lap not stored, and for a lap that a table in force, a `last`
+         * entry or the override names and the list does not keep (lmpc_last_error names the table, the row and the lap); LMPC_E_STATE while a rollout session is
+         * active.  Keeping fewer than numSS_it / trToUse laps without a table is no error here: the next step reports it as it always did.
+         * Like every store edit it launches a held solve (lmpc_dev_flush), resolves pending retry passes against the stores of their launch and drains the context's
+         * streams first.  The kept laps are gathered by one kernel launch into new zero-filled allocations -- device memory peaks at old + new during the call -- whose
+         * lap capacity is the smallest (initial max_laps) x 2^j that holds both stores' kept laps; the row capacity stays, and later growth works as before.  A HIP
+         * failure on the way (LMPC_E_HIP) frees the new allocations and leaves the context as it was.  A call that keeps every lap of both stores does nothing. */
 
 /* ---- batched compute, host buffers --------------------------------------------------------- */
 int lmpc_regress_batch(lmpc_ctx *, int B, const double *xLin /*B x N x 6 (first N rows used)*/, int xLinRowStride /* (N+1)*6 or N*6 */,

@@ -183,7 +183,7 @@ EXPORTS = [
     "lmpc_rollout_set_trace", "lmpc_rollout_get_trace", "lmpc_rollout_trace_bytes", "lmpc_rollout_fetch_trace",
     "lmpc_rollout_set_parking", "lmpc_rollout_get_parking", "lmpc_rollout_parked_at", "lmpc_debug_live_compact",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
-    "lmpc_debug_k1_ahead", "lmpc_debug_k1_merge", "lmpc_dev_flush",
+    "lmpc_debug_k1_ahead", "lmpc_debug_k1_merge", "lmpc_dev_flush", "lmpc_store_retain",
 ]
 
 _lib = None
@@ -264,6 +264,9 @@ def load():
         lib.lmpc_debug_live_compact.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         for f in (lib.lmpc_rollout_set_parking, lib.lmpc_rollout_get_parking, lib.lmpc_rollout_parked_at, lib.lmpc_debug_live_compact):
             f.restype = C.c_int
+        # (laps given back: two int32 keep lists in, two int32 maps out)
+        lib.lmpc_store_retain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmpc_store_retain.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
@@ -389,6 +392,26 @@ def check_ss_table(rows, numSS_it, last=None):
     if a.min() < -1:
         raise ValueError("safe-set lap table: `last` below -1 in row(s) %s" % np.where(a < -1)[0].tolist())
     return r, np.ascontiguousarray(a, dtype=np.int32)
+
+
+def check_retain(keep, stored, what):
+    """The keep list of one store for Context.store_retain as an int32 array, or ValueError for what lmpc_store_retain refuses with LMPC_E_ARG: `stored` laps are in
+    the store `what` names ("safe set" / "regression store"); the list holds strictly ascending lap indices in [0, stored).  An empty list empties the store."""
+    a = np.asarray(keep)
+    if a.ndim != 1:
+        raise ValueError("store_retain: %s: a one-dimensional list of lap indices expected, got shape %s" % (what, a.shape))
+    if a.size == 0:
+        return np.zeros(0, np.int32)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("store_retain: %s: integer lap indices expected, got dtype %s" % (what, a.dtype))
+    if a.min() < 0:
+        raise ValueError("store_retain: %s: negative lap index at position(s) %s" % (what, np.where(a < 0)[0].tolist()))
+    if a.max() >= int(stored):
+        raise ValueError("store_retain: %s: position(s) %s name a lap that is not stored (%d laps are)" % (what, np.where(a >= int(stored))[0].tolist(), int(stored)))
+    if (np.diff(a) <= 0).any():
+        k = int(np.where(np.diff(a) <= 0)[0][0]) + 1
+        raise ValueError("store_retain: %s: strictly ascending lap indices expected, position %d holds %d after %d" % (what, k, int(a[k]), int(a[k - 1])))
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def plant_params(B, m=1.98, lf=0.125, lr=0.125, Iz=0.024, mu_f=0.8, mu_r=0.8, Cf=1.25, Bf=1.0, Cr=1.25, Br=1.0, Df=None, Dr=None):
@@ -1134,6 +1157,20 @@ class Context:
             if "ss_lap_table" in d.files:                    # (per-problem safe-set laps; a file written without them restores to "no table")
                 self.ss_set_lap_table(d["ss_lap_table"], d["ss_lap_last"] if "ss_lap_last" in d.files else None)
 
+    def store_retain(self, ss=None, model=None):
+        """Laps given back (lmpc_store_retain): the safe set keeps the laps `ss` lists (strictly ascending indices in ss_add_trajectory order), the regression store
+        those `model` lists (strictly ascending insertion indices); None leaves a store untouched, an empty list empties it.  The k-th kept lap gets index k; lap
+        tables, `last` and the selection override are renumbered with the stores, and a lap one of them names must be kept.  The device stores shrink to the kept laps.
+        Returns (map_ss, map_model): int32 arrays over the laps stored before the call, the new index or -1 for a dropped lap; None for an untouched store."""
+        ns, nm = self.ss_num_laps(), self.model_num_laps()
+        ks = None if ss is None else check_retain(ss, ns, "safe set")
+        km = None if model is None else check_retain(model, nm, "regression store")
+        ms, mm = np.full(ns, -1, np.int32), np.full(nm, -1, np.int32)
+        _chk(self.lib.lmpc_store_retain(self._h, -1 if ks is None else ks.size, None if ks is None or not ks.size else ks.ctypes.data,
+                                        -1 if km is None else km.size, None if km is None or not km.size else km.ctypes.data,
+                                        ms.ctypes.data if ns else None, mm.ctypes.data if nm else None))
+        return (None if ks is None else ms), (None if km is None else mm)
+
     def rollout_release(self):
         """Free the device buffers a finished session keeps for the next lap (lmpc_rollout_release)."""
         _chk(self.lib.lmpc_rollout_release(self._h))
@@ -1451,6 +1488,13 @@ class ContextPool:
         """Context.restore_stores into every member (step_batch_dev deals steps to all of them; save_stores may go to any one: their stores are equal)."""
         for m in self.members:
             m.restore_stores(path)
+
+    def store_retain(self, ss=None, model=None):
+        """Context.store_retain on every member (their stores are equal, so are the maps); returns the maps of the last one."""
+        out = None
+        for m in self.members:
+            out = m.store_retain(ss=ss, model=model)
+        return out
 
     def step_dev_buffers(self, inp, diagnostics=True):
         """One set of device buffers per member: [(args, allocations)], in member order."""

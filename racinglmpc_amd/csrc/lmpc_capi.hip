@@ -5,12 +5,14 @@
 #include "lmpc_noise.hip.h"
 #include "lmpc_track.hip.h"
 #include "lmpc_commit.hip.h"
+#include "lmpc_retain.hip.h"
 #include "lmpc_metrics.hip.h"
 #include "lmpc_trace.hip.h"
 #include "lmpc_live.hip.h"
 #include "lmpc_arrays.h"
 #include "lmpc_rows.h"
 #include "lmpc_pick.h"
+#include "lmpc_retain.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <algorithm>
@@ -99,6 +101,7 @@ enum { IMG_LT = 0, IMG_SST, IMG_TUNE, IMG_TRK, IMG_COUNT };
 
 struct lmpc_ctx {
     lmpc_config cfg;
+    int init_max_laps;                       // cfg.max_laps as lmpc_create was given it (growth overwrites cfg.max_laps): the capacities lmpc_store_retain shrinks to are this times 2^j
     lmpc_dev_params dp;
     hipStream_t stream;
     double *mstore, *sstore;                 // device lap stores [lap][col][row]
@@ -271,7 +274,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 114; }
+int lmpc_version(void) { return 115; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -556,7 +559,7 @@ int lmpc_create_ex(const lmpc_config *cfg, unsigned flags, lmpc_ctx **out) {
     ARGCHK(cfg->slacks || cfg->numSS_it == 0);          // hard lane rows: plain MPC only (the reference's LMPC.unpackSolution mis-slices without slack variables)
     ARGCHK(cfg->max_batch >= 1 && cfg->max_laps >= 1 && cfg->max_lap_len >= 8);
     lmpc_ctx *c = new lmpc_ctx();                      // value-initialised: every pointer starts as nullptr, so lmpc_destroy is safe at any point
-    c->cfg = *cfg; c->lt.width = cfg->trToUse; c->sst.width = cfg->numSS_it; c->create_flags = flags; c->profiling = 0; c->ro = nullptr; c->var_dl = nullptr; c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1;
+    c->cfg = *cfg; c->init_max_laps = cfg->max_laps; c->lt.width = cfg->trToUse; c->sst.width = cfg->numSS_it; c->create_flags = flags; c->profiling = 0; c->ro = nullptr; c->var_dl = nullptr; c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1;
     memset(&c->stats, 0, sizeof(c->stats));
     int rc = create_body(c);
     if (rc != LMPC_OK) { const std::string keep = g_err; lmpc_destroy(c); g_err = keep; return rc; }
@@ -972,6 +975,83 @@ int lmpc_debug_model_image(lmpc_ctx *c, int lap, unsigned *q, double *par, int *
     if (q) HIPCHK(hipMemcpy2D(q, (size_t)nrows * sizeof(unsigned), c->mquant + (size_t)lap * 3 * ls, ls * sizeof(unsigned), (size_t)nrows * sizeof(unsigned), 3, hipMemcpyDeviceToHost));
     if (par && used) HIPCHK(hipMemcpy(par, c->mqpar + (size_t)lap * c->mq_chunks * 6, sizeof(double) * 6 * (size_t)used, hipMemcpyDeviceToHost));
     return LMPC_OK;
+}
+
+// ---- laps given back (lmpc_retain.h: the books; lmpc_retain.hip.h: the gather).  The only entry point after which a store holds fewer laps than before.
+// a lap that something still names is not dropped: `what` names the table, `per_row` entries make a row (0: the position is the row)
+static int retain_refuse_named(const char *what, long long pos, int per_row, int lap) {
+    char msg[160];
+    if (per_row > 0) snprintf(msg, sizeof(msg), "%s: row %lld names lap %d, which is not kept", what, pos / per_row, lap);
+    else snprintf(msg, sizeof(msg), "%s: entry %lld names lap %d, which is not kept", what, pos, lap);
+    return set_err(LMPC_E_ARG, "lmpc_store_retain", msg);
+}
+static int retain_check_list(const char *store, int n, const int *keep, int stored) {
+    int why = 0; const int k = lmpc_retain_check(n, keep, stored, &why);
+    if (k < 0) return LMPC_OK;
+    char msg[160];
+    if (why == 0) snprintf(msg, sizeof(msg), "%s: entry %d names lap %d, %d laps are stored", store, k, keep[k], stored);
+    else snprintf(msg, sizeof(msg), "%s: entry %d (lap %d) is not above entry %d (lap %d): strictly ascending indices expected", store, k, keep[k], k - 1, keep[k - 1]);
+    return set_err(LMPC_E_ARG, "lmpc_store_retain", msg);
+}
+int lmpc_store_retain(lmpc_ctx *c, int n_ss, const int *keep_ss, int n_model, const int *keep_model, int *map_ss, int *map_model) {
+    ARGCHK(c && n_ss >= -1 && n_model >= -1 && (n_ss <= 0 || keep_ss) && (n_model <= 0 || keep_model));
+    if (c->ro && c->ro->active) return set_err(LMPC_E_STATE, "lmpc_store_retain", "a rollout session is active: its steps read the laps by the indices they had when it began (lmpc_rollout_end first)");
+    // checked in full before anything changes: the lists, then everything that names a lap
+    const int ns0 = (int)c->s_len.size(), nm0 = (int)c->m_len.size();
+    if (n_ss >= 0) RCCHK(retain_check_list("safe set", n_ss, keep_ss, ns0));
+    if (n_model >= 0) RCCHK(retain_check_list("regression store", n_model, keep_model, nm0));
+    const std::vector<int> smap = n_ss >= 0 ? lmpc_retain_map(n_ss, keep_ss, ns0) : lmpc_retain_identity(ns0);
+    const std::vector<int> mmap = n_model >= 0 ? lmpc_retain_map(n_model, keep_model, nm0) : lmpc_retain_identity(nm0);
+    long long at;
+    if (c->lt.in_force() && (at = lmpc_retain_first_dropped(c->lt.rows.data(), c->lt.rows.size(), mmap)) >= 0) return retain_refuse_named("lap table (lmpc_model_set_lap_table)", at, c->cfg.trToUse, c->lt.rows[(size_t)at]);
+    if (c->sst.in_force() && (at = lmpc_retain_first_dropped(c->sst.rows.data(), c->sst.rows.size(), smap)) >= 0) return retain_refuse_named("safe-set lap table (lmpc_ss_set_lap_table)", at, c->cfg.numSS_it, c->sst.rows[(size_t)at]);
+    if (c->sst.in_force() && c->sst_has_last && (at = lmpc_retain_first_dropped(c->sst_last.data(), c->sst_last.size(), smap)) >= 0) return retain_refuse_named("last of the safe-set lap table (lmpc_ss_set_lap_table)", at, 1, c->sst_last[(size_t)at]);
+    if ((at = lmpc_retain_first_dropped(c->s_override.data(), c->s_override.size(), smap)) >= 0) return retain_refuse_named("selection override (lmpc_ss_set_selected)", at, 0, c->s_override[(size_t)at]);
+    if (map_ss) std::copy(smap.begin(), smap.end(), map_ss);
+    if (map_model) std::copy(mmap.begin(), mmap.end(), map_model);
+    if (lmpc_retain_keeps_all(smap) && lmpc_retain_keeps_all(mmap)) return LMPC_OK;
+    // like every other store edit: a held solve launched, the pending retries resolved against the stores of their launch, both streams drained before the stores move
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING(); HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->k1_stream) HIPCHK(hipStreamSynchronize(c->k1_stream));
+    const int ks = lmpc_retain_kept(smap), km = lmpc_retain_kept(mmap);
+    const int new_laps = lmpc_retain_capacity(c->init_max_laps, std::max(ks, km)), ls = c->cfg.max_lap_len;
+    std::vector<lmpc_retain_entry> tab;
+    for (int old = 0; old < nm0; old++) if (mmap[(size_t)old] >= 0) tab.push_back({0, old, mmap[(size_t)old], c->m_len[(size_t)old]});
+    for (int old = 0; old < ns0; old++) if (smap[(size_t)old] >= 0) tab.push_back({1, old, smap[(size_t)old], c->s_len[(size_t)old]});
+    void *d_tab = nullptr;
+    if (!tab.empty()) RCCHK(pooled_scratch(c, sizeof(lmpc_retain_entry) * tab.size(), &d_tab));
+    const size_t elems = (size_t)new_laps * LMPC_COLS * ls, qwords = (size_t)new_laps * 3 * ls, pdoubles = (size_t)new_laps * c->mq_chunks * 6;
+    double *nm = nullptr, *ns = nullptr, *np_ = nullptr; unsigned *nq = nullptr;
+    auto fail = [&](int rc) { if (nm) (void)g_free(nm); if (ns) (void)g_free(ns); if (nq) (void)g_free(nq); if (np_) (void)g_free(np_); return rc; };
+#define RETAINCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(set_err(LMPC_E_HIP, #call, hipGetErrorString(e_))); } while (0)
+    RETAINCHK(g_malloc(&nm, elems * sizeof(double))); RETAINCHK(g_malloc(&ns, elems * sizeof(double)));
+    RETAINCHK(g_malloc(&nq, qwords * sizeof(unsigned))); RETAINCHK(g_malloc(&np_, pdoubles * sizeof(double)));
+    RETAINCHK(hipMemsetAsync(nm, 0, elems * sizeof(double), c->stream)); RETAINCHK(hipMemsetAsync(ns, 0, elems * sizeof(double), c->stream));
+    RETAINCHK(hipMemsetAsync(nq, 0, qwords * sizeof(unsigned), c->stream)); RETAINCHK(hipMemsetAsync(np_, 0, pdoubles * sizeof(double), c->stream));
+    if (!tab.empty()) {
+        lmpc_retain_args a;
+        a.src_store[0] = c->mstore; a.src_store[1] = c->sstore; a.dst_store[0] = nm; a.dst_store[1] = ns;
+        a.src_quant = c->mquant; a.dst_quant = nq; a.src_qpar = c->mqpar; a.dst_qpar = np_; a.ls = ls; a.mq_chunks = c->mq_chunks;
+        RETAINCHK(hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_retain_entry) * tab.size(), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(lmpc_retain_laps_kernel, dim3((unsigned)tab.size()), dim3(LMPC_RETAIN_NT), 0, c->stream, a, (const lmpc_retain_entry *)d_tab);
+        RETAINCHK(hipGetLastError());
+    }
+    RETAINCHK(hipStreamSynchronize(c->stream));                          // (the table is a local: read before this call returns on any path)
+#undef RETAINCHK
+    (void)g_free(c->mstore); (void)g_free(c->sstore); (void)g_free(c->mquant); (void)g_free(c->mqpar);
+    c->mstore = nm; c->sstore = ns; c->mquant = nq; c->mqpar = np_;
+    c->cfg.max_laps = new_laps;
+    // the books and everything that names a lap, renumbered here and nowhere else
+    c->m_order = lmpc_retain_order(c->m_order, mmap); c->m_len = lmpc_retain_gather(c->m_len, mmap);
+    c->s_len = lmpc_retain_gather(c->s_len, smap); c->s_laptime = lmpc_retain_gather(c->s_laptime, smap);
+    c->s_qlast = lmpc_retain_gather(c->s_qlast, smap); c->s_q0 = lmpc_retain_gather(c->s_q0, smap);
+    lmpc_retain_remap(c->lt.rows.data(), c->lt.rows.size(), mmap);
+    lmpc_retain_remap(c->sst.rows.data(), c->sst.rows.size(), smap);
+    lmpc_retain_remap(c->sst_last.data(), c->sst_last.size(), smap);
+    lmpc_retain_remap(c->s_override.data(), c->s_override.size(), smap);
+    c->sst_dirty = true;
+    fill_params(c);                                                      // (the per-launch parts -- selected slots, lengths, cur_it -- are written by every launch that reads them)
+    return resolve_lap_table(c);
 }
 
 // ---- laps of the active session straight into the stores: no log leaves the device

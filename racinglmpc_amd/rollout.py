@@ -698,6 +698,24 @@ class PerCarHistory:
     def rows(self):
         return np.array([self.row(b) for b in range(len(self.entries))], np.int32)
 
+    def prune(self):
+        """Every car's list cut to its `width` fastest entries, in the order they were added, multiplicities kept.  row(b) is what it was, now and after any later
+        add: a stable "width fastest" never takes back an entry that `width` others of the list already precede, and entries added later go behind these."""
+        for b, e in enumerate(self.entries):
+            keep = sorted(sorted(range(len(e)), key=lambda i: e[i][0])[:self.width])
+            self.entries[b] = [e[i] for i in keep]
+
+    def remap(self, map):
+        """Store indices renumbered: entry (length, index) becomes (length, map[index]) -- the map Context.store_retain returns; every index held must be a kept one."""
+        for b, e in enumerate(self.entries):
+            if any(map[i] < 0 for _, i in e):
+                raise ValueError("car %d's history names a lap that was not kept" % b)
+            self.entries[b] = [(n, int(map[i])) for n, i in e]
+
+    def indices(self):
+        """The store indices any car's list holds, as a set."""
+        return {i for e in self.entries for _, i in e}
+
 
 class PerCarLMPC:
     """main.py:100-121 once per car, with nothing shared: B independent learners in one batch.  Car b regresses on its own laps (Context.model_set_lap_table) and
@@ -734,12 +752,19 @@ class PerCarLMPC:
     bit -- the laps are no longer promised equal to those without parking.  The rollouts object's own `park` is put back after every generation.
     metrics=True: `metrics[g]` is the (B, _capi.METRICS_NCOL) lap metrics of generation g (columns _capi.METRIC_FIELDS): one Context.rollout_lap_metrics call over the
     generation's valid cars, up to their crossing steps, before the session ends -- with and without device_commit, with and without park; NaN rows for cars that
-    are retired or not valid.  Everything else comes out as without it."""
+    are retired or not valid.  Everything else comes out as without it.
+    prune=True: the stores hold only what a car can still read.  After seed and after every generation's adds both histories are cut to their rows
+    (PerCarHistory.prune) and ONE Context.store_retain call keeps, in the safe set, the union over the cars of row b and last[b], and in the regression store the union
+    of the rows; histories, `last` and the tables handed over are renumbered through the maps it returns.  A lap that has dropped out of a car's row can never come
+    back into it, so what run() returns, lap_times, retired, steps, latest and metrics are identical to prune=False; only store indices differ, through the maps
+    (the two stores' indices no longer run in lockstep).  Retired cars keep their rows and therefore their laps.  The stores stay bounded whatever the number of
+    generations: ss_num_laps() <= B (numSS_it + 1) and model_num_laps() <= B trToUse.  Works with device_commit, park, tuning, tracks, metrics and trace."""
 
     EXT_SKIPPED = 1 << 30          # retired[b][1] carries this bit when the car's extension was skipped (beside the status bits that caused it, if any)
 
-    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None, trace=None, trace_what=None, park=False, metrics=False):
+    def __init__(self, rollouts, T_max=400, ext=40, device_commit=False, tuning=None, trace=None, trace_what=None, park=False, metrics=False, prune=False):
         self.ro, self.T_max, self.ext = rollouts, int(T_max), int(ext)
+        self.prune = bool(prune)
         self.with_metrics = bool(metrics)
         self.metrics = []                  # one entry per generation run with metrics=True
         self.device_commit = bool(device_commit)
@@ -768,7 +793,7 @@ class PerCarLMPC:
         self.last = np.full(B, -1, np.int32)
         self.latest = [None] * B           # (x, u, final12, ends at the line) of each car's most recent lap
         self.lap_times = [[] for _ in range(B)]
-        n = 0                              # laps stored so far: the next index in both stores (safe-set lap index, regression-store insertion index)
+        n = 0                              # laps stored so far: the next index in both stores, which start empty (safe-set lap index, regression-store insertion index)
         for b, laps in enumerate(laps_per_car):
             if not laps:
                 raise ValueError("PerCarLMPC.seed: car %d has no lap" % b)
@@ -788,6 +813,7 @@ class PerCarLMPC:
             self.latest[b] = (x, np.asarray(lap[1], float), np.asarray(lap[3], float), done >= x.shape[0])
             self.last[b] = n - 1
         self._hand_tables()
+        self._retain()
 
     def _ss_add(self, b, x, u):
         """Car b's lap into the safe set, its Q-function counted with car b's own TrackLength."""
@@ -801,6 +827,21 @@ class PerCarLMPC:
         """Rows of both tables and `last`, from the histories, to the rollouts object (it hands them to the context before the next begin)."""
         self.ro.lap_table = _capi.check_lap_table(self.model_hist.rows(), self.model_hist.width)
         self.ro.ss_table, self.ro.ss_last = _capi.check_ss_table(self.ss_hist.rows(), self.ss_hist.width, self.last.copy())
+
+    def _retain(self):
+        """prune=True: the laps no car reads any more are given back (Context.store_retain), histories, `last` and the tables renumbered.  The tables in force on the
+        context are those of the session that has just ended and may name laps about to go, so the new ones go to the context first."""
+        if not self.prune:
+            return
+        ro, ctx = self.ro, self.ro.ctx
+        ctx.model_set_lap_table(ro.lap_table); ctx.ss_set_lap_table(ro.ss_table, ro.ss_last)
+        self.ss_hist.prune(); self.model_hist.prune()
+        keep_ss = sorted(self.ss_hist.indices() | {int(l) for l in self.last if l >= 0})
+        keep_model = sorted(self.model_hist.indices())
+        map_ss, map_model = ctx.store_retain(ss=keep_ss, model=keep_model)
+        self.ss_hist.remap(map_ss); self.model_hist.remap(map_model)
+        self.last = np.array([map_ss[l] if l >= 0 else l for l in self.last], np.int32)
+        self._hand_tables()
 
     def close(self):
         self.ro.close()
@@ -876,15 +917,16 @@ class PerCarLMPC:
                 continue
             T = int(done[b])
             x, u = X[:T, b].copy(), U[:T, b].copy()
-            idx = ctx.ss_num_laps()
+            idx, idx_model = ctx.ss_num_laps(), ctx.model_num_laps()      # (one counter per store: after a store_retain they no longer run in lockstep)
             self._ss_add(b, x, u); ctx.model_add_trajectory(x, u)
-            self.ss_hist.add(b, T, idx); self.model_hist.add(b, T, idx)
+            self.ss_hist.add(b, T, idx); self.model_hist.add(b, T, idx_model)
             self.last[b] = idx
             f12 = np.concatenate([fx[b], fg[b]])
             self.latest[b] = (x, u, f12, True)
             self.lap_times[b].append(T)
             out[b] = (x, u, G[:T, b].copy(), f12, T, int(st[b]))
         self._hand_tables()
+        self._retain()
         self.generation += 1
         return out
 
@@ -924,7 +966,7 @@ class PerCarLMPC:
                     continue
                 valid.append(b)
             self._take_metrics(valid)
-            first = ctx.rollout_commit_laps(valid)[0] if valid else None
+            first, first_model = ctx.rollout_commit_laps(valid) if valid else (None, None)
         finally:
             ctx.rollout_end()
         self.last_status, self.last_done = st, done
@@ -933,13 +975,14 @@ class PerCarLMPC:
         for k, b in enumerate(valid):
             T, idx = int(done[b]), first + k
             x, u = Xh[:T, b].copy(), Uh[:T, b].copy()
-            self.ss_hist.add(b, T, idx); self.model_hist.add(b, T, idx)
+            self.ss_hist.add(b, T, idx); self.model_hist.add(b, T, first_model + k)
             self.last[b] = idx
             f12 = np.concatenate([fx[b], fg[b]])
             self.latest[b] = (x, u, f12, True)
             self.lap_times[b].append(T)
             out[b] = (x, u, None, f12, T, int(st[b]))
         self._hand_tables()
+        self._retain()
         self.generation += 1
         return out
 
