@@ -335,7 +335,10 @@ int lmpc_step_batch_dev(lmpc_ctx *, int B, const lmpc_step_dev_args *args);   /*
          * context's and runs BESIDE the previous step's solve (it needs nothing of it); the solves themselves stay strictly one after the other, each behind its own
          * regression.  The regression writes a hand-over set of the context's, which the solve reads, and copies A / Bm / C to the caller's arrays where given: those are
          * outputs only, nothing on the device reads them except a retry pass at the next drain, so the caller keeps them (and every input: xLin / uLin of step i + 1 are
-         * read while step i solves) untouched until lmpc_dev_sync, as before.  Any other call on the context that queues work or edits what the regression reads (lap
+         * read while step i solves) untouched until lmpc_dev_sync, as before.  ONE set of A / Bm / C shared by several queued steps is covered only while no launch is
+         * pending its retry pass: a problem that ends at the iteration limit (LMPC_ST_MAXITER, LMPC_ST_NUMERIC) is solved again at the next drain, from the arrays its
+         * step was given, and finds the regression of the last queued step in shared ones -- a caller whose problems may raise that flag gives every queued step its
+         * own A / Bm / C (or none).  Any other call on the context that queues work or edits what the regression reads (lap
          * stores, lap table, track / tuning rows, lmpc_dev_upload, ...) breaks the chain: the next step's regression goes behind it on the context's stream.  A drain of
          * the context (lmpc_dev_sync, lmpc_dev_download) covers both streams.  Results are bit-identical to the unchained step; LMPC_K1_AHEAD=0 turns chaining off.
          * Held solves.  On the plain four-wave route (up to one QP per CU, no lap / safe-set table, tuning or track rows in force, A / Bm / C given, not under

@@ -6,8 +6,8 @@ context created under LMPC_K1_AHEAD=0.  Inputs: the N = 12 seed lap of tests/gol
 row offset per step, so that a step that read another step's hand-over, inputs or status shows.  Shapes: B = 5 on the four-wave route, and the smallest batch that
 Context.solver_waves puts on the two-wave and on the one-wave route.
 
-Retry: no fixture raises the deferred retry flag at the default iteration limit (tests/test_gpu_retry.py lowers max_iter to get one), so that case is left out here;
-the retry pass of queued steps stays covered by tests/test_gpu_retry.py, whose launches are chained now."""
+Retry: no fixture raises the deferred retry flag at the default iteration limit; tests/test_gpu_queued_retry.py lowers max_iter and runs queued steps whose launches
+are pending their retry pass through every form of this module, with the helpers defined here."""
 import contextlib
 import os
 

@@ -1,5 +1,6 @@
 """-m gpu: the retry pass (equal-step variant of the solve kernel for problems that end at the iteration limit) is launched on demand: a flagged
-problem writes the launch's epoch into a host-mapped ring, the host looks at it at its next drain of the stream (lmpc_capi.hip: resolve_retries)."""
+problem writes the launch's epoch into a host-mapped ring, the host looks at it at its next drain of the stream (lmpc_capi.hip: resolve_retries).  The queued launches here reuse one argument block or pass A / Bm / C = NULL, which
+drains at every step; queued steps with their own inputs and arrays per step, held solves and two-role launches among them: tests/test_gpu_queued_retry.py."""
 import numpy as np
 import pytest
 
