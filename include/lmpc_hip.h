@@ -536,6 +536,36 @@ int lmpc_rollout_extend_laps(lmpc_ctx *, int n, const int *cars /*n*/, const int
          * repeated subtraction of 1.0, as the host loop does.  The caller keeps deciding on status bits (it has them from lmpc_rollout_fetch with t0 = t1 = 0).
          * LMPC_E_ARG, before anything changes, for n_rows < 1 or beyond the steps taken, a lap index that names no stored lap, the same lap twice, a car out of range.
          * One store growth, one launch, one download of the flags; the live safe-set table sees the longer laps at the next step */
+/* ---- free-running sessions (version 116; kernels: racinglmpc_amd/csrc/lmpc_relaunch.hip.h).  A car that has crossed the line starts its next lap inside the running
+ * session, at its own crossing, while the other cars keep driving: the reference runs one car, whose next lap begins at the step after its crossing, from xF
+ * (main.py:100-121, SysModel.py:50).  A session then holds G laps per car in about max_b sum_g T(b, g) steps and one begin / end. */
+int lmpc_rollout_relaunch(lmpc_ctx *, int n, const int *cars /*n distinct*/, int lap_rows);
+        /* Each listed car b -- it must have crossed the line, doneAt[b] >= 0 -- is put into the state a fresh lmpc_rollout_begin would give it for its next lap, on the
+         * device: nothing of the lap is downloaded.  With s0 = lapStart[b] (0 until the car's first relaunch) and t = the steps the session has taken:
+         * x[b] = finX[b] with the car's own TrackLength (its lmpc_track_set row, else the config's) subtracted from s, one FP64 subtraction (xF, SysModel.py:50);
+         * xg[b] = finG[b]; xLin[b] = logged X rows s0 + 1 .. s0 + N + 1 and uLin[b] = logged U rows s0 + 1 .. s0 + N of the car (LMPC.addTrajectory,
+         * PredictiveControllers.py:431-433); every other per-problem array of the step is zeroed for car b (the table of lmpc_arrays.h: hasPred, timeStep, the solver's
+         * outputs and status words among them) and zt[b] = (0, 0, 0, 0, 10, 0) (LMPC.__init__ :330); statusAcc[b] = 0, doneAt[b] = -1, finX[b] = finG[b] = 0; the
+         * session's count of finished cars goes down by one per listed car, so lmpc_rollout_run goes on and ends only when every car is done again.
+         * Books: lapStart[b] = t, lapNo[b] += 1 (lmpc_rollout_lap_start).  From then on the car's timeStep counts the steps of its LAP, t + 1 - lapStart[b] (the
+         * Q-function shift of the selection reads it), its lap is the session rows [lapStart[b], doneAt[b]), and doneAt[b] stays a SESSION row, one past the crossing.
+         * Noise: in a session begun with noise = NULL (lmpc_rollout_set_noise) rows [t, min(T_max, t + lap_rows)) of the car's noise column are redrawn: the draws of
+         * (seed, stream 0, lap0 + lapNo[b], step of the lap 0 .., car0 + b), lap0 the session's snapshot -- what a fresh session with that lap number holds in rows 0 ..
+         * (lap_rows: the most steps the caller lets the lap take; beyond them the column keeps what it held).  In a session begun on a host array the car goes on
+         * reading the caller's array at the SESSION step: the array is the caller's to lay out.
+         * Regression laps: row b of the session's snapshot of the lap table is resolved anew from the table in force on the context now
+         * (lmpc_model_set_lap_table; the other cars keep their rows; a session begun without a table, or no table in force now: no row changes).  The safe-set
+         * table and the tuning rows are live in a session already.
+         * Valid in an active session of lmpc_rollout_begin between two lmpc_rollout_run calls; both streams of the session are drained first.  One upload of the
+         * entry table, one launch for all listed cars, one drain.  A session that never relaunches allocates, launches and returns what it did before this entry point
+         * existed.  In a session that has relaunched, lmpc_rollout_commit_laps and lmpc_rollout_extend_laps count a car's rows from its lap start (rows == NULL:
+         * doneAt - lapStart; rows[i] and n_rows are checked against t - lapStart[car]); lmpc_rollout_fetch is unchanged and returns session rows.
+         * Everything is checked before anything changes, and lmpc_last_error names the car.  LMPC_E_ARG: n < 1, NULL cars, a car outside [0, B) or listed twice,
+         * lap_rows < 1, a lap with fewer than N + 2 rows.  LMPC_E_STATE: no session active, a session of another kind (lmpc_rollout_begin_mpc, lmpc_rollout_pid), a
+         * listed car with doneAt < 0, a session begun with parking or with a trace in force; and lmpc_rollout_lap_metrics after the first relaunch */
+int lmpc_rollout_lap_start(lmpc_ctx *, int *start /*B, or NULL*/, int *lap /*B, or NULL*/);
+        /* of the active session (LMPC_E_STATE without one): the session row each car's current lap began at, and the laps it has begun after its first.  A session
+         * without a relaunch answers zeros for both.  No reference counterpart (one car, one lap at a time: main.py:100-121).  Needs no device */
 /* ---- lap metrics of the active session reduced ON THE DEVICE (version 112; kernel: racinglmpc_amd/csrc/lmpc_metrics.hip.h).  What a sweep over thousands of cars
  * wants back per car and lap -- a lap time finer than one step, the distance kept from the lane edge and the input bounds, the cornering, the smoothness of the
  * inputs, the realised cost under the car's own weights -- as one row of LMPC_METRICS_NCOL doubles per listed car instead of its T x 14 logged ones. */

@@ -169,6 +169,30 @@ def check_parking(mode, cars):
     return mode, cars
 
 
+def check_relaunch(cars, lap_rows):
+    """(cars as int32, lap_rows) of a rollout_relaunch call, or ValueError for what the library refuses with LMPC_E_ARG whatever the session: no car, a negative or
+    repeated car, lap_rows < 1.  (A car beyond the session's B, one that has not crossed the line and a lap shorter than N + 2 rows are the session's to refuse.)"""
+    cars = np.asarray(cars)
+    if cars.ndim == 0:
+        cars = cars.reshape(1)
+    if cars.ndim != 1:
+        raise ValueError("relaunch: cars must be one-dimensional")
+    if cars.size == 0:
+        raise ValueError("relaunch: at least one car expected")
+    if not np.issubdtype(cars.dtype, np.integer):
+        raise ValueError("relaunch: cars must be integers")
+    cars = _i32(cars)
+    if (cars < 0).any():
+        raise ValueError("relaunch: negative car index")
+    if np.unique(cars).size != cars.size:
+        raise ValueError("relaunch: a car is listed twice")
+    if isinstance(lap_rows, bool) or not isinstance(lap_rows, (int, np.integer)):
+        raise ValueError("relaunch: lap_rows must be an integer")
+    if int(lap_rows) < 1:
+        raise ValueError("relaunch: lap_rows = %d, at least one row expected" % int(lap_rows))
+    return cars, int(lap_rows)
+
+
 EXPORTS = [
     "lmpc_config_default", "lmpc_create", "lmpc_create_ex", "lmpc_solver_kind", "lmpc_destroy", "lmpc_last_error", "lmpc_active_knobs", "lmpc_version", "lmpc_device_memory",
     "lmpc_model_add_trajectory", "lmpc_model_num_laps", "lmpc_model_replace_lap", "lmpc_model_set_lap_table", "lmpc_model_get_lap_table", "lmpc_model_lap_info",
@@ -184,6 +208,7 @@ EXPORTS = [
     "lmpc_rollout_set_parking", "lmpc_rollout_get_parking", "lmpc_rollout_parked_at", "lmpc_debug_live_compact",
     "lmpc_debug_set_trace", "lmpc_debug_exec_audit", "lmpc_debug_rollout_peek", "lmpc_debug_rollout_capture", "lmpc_debug_rollout_qp",
     "lmpc_debug_k1_ahead", "lmpc_debug_k1_merge", "lmpc_dev_flush", "lmpc_store_retain",
+    "lmpc_rollout_relaunch", "lmpc_rollout_lap_start",
 ]
 
 _lib = None
@@ -267,6 +292,10 @@ def load():
         # (laps given back: two int32 keep lists in, two int32 maps out)
         lib.lmpc_store_retain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lmpc_store_retain.restype = C.c_int
+        # (free-running sessions: an int32 car list in; two int32 arrays out)
+        lib.lmpc_rollout_relaunch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        lib.lmpc_rollout_lap_start.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmpc_rollout_relaunch.restype = lib.lmpc_rollout_lap_start.restype = C.c_int
         for f in (lib.lmpc_rollout_begin_mpc, lib.lmpc_rollout_pid, lib.lmpc_lti_regression_batch, lib.lmpc_noise_raw, lib.lmpc_noise_fill, lib.lmpc_rollout_set_noise,
                   lib.lmpc_rollout_get_noise, lib.lmpc_local_position_batch, lib.lmpc_track_angle_batch, lib.lmpc_state_from_global_batch):
             f.restype = C.c_int
@@ -1240,6 +1269,23 @@ class Context:
         ext = np.zeros(cars.shape[0], np.int32)
         _chk(self.lib.lmpc_rollout_extend_laps(self._h, cars.shape[0], cars.ctypes.data, laps.ctypes.data, int(n_rows), ext.ctypes.data))
         return ext != 0
+
+    # ---- free-running sessions (lmpc_rollout_relaunch; csrc/lmpc_relaunch.hip.h)
+    def rollout_relaunch(self, cars, lap_rows):
+        """The listed cars of the active session -- each has crossed the line -- start their next lap on the device, as a fresh rollout_begin would start it
+        (lmpc_rollout_relaunch): state = crossing state less the car's own TrackLength, linearisation about rows 1 .. N + 1 of the lap just ended, every other array
+        of the step zeroed, device noise redrawn for the next lap_rows steps, the car's lap-table row taken anew from the table in force.  Between two rollout_run
+        calls; afterwards rollout_commit_laps / rollout_extend_laps count a car's rows from its lap start (rollout_lap_start)."""
+        cars, lap_rows = check_relaunch(cars, lap_rows)
+        _chk(self.lib.lmpc_rollout_relaunch(self._h, cars.shape[0], cars.ctypes.data, lap_rows))
+
+    def rollout_lap_start(self):
+        """(start (B,) int32, lap (B,) int32) of the active session (lmpc_rollout_lap_start): the session row each car's current lap began at and the laps it has
+        begun after its first; zeros in a session without a relaunch."""
+        ro = getattr(self, "_ro", None)           # (no session begun so far: the library says so)
+        start = np.zeros(ro[0] if ro else 0, np.int32); lap = np.zeros_like(start)
+        _chk(self.lib.lmpc_rollout_lap_start(self._h, start.ctypes.data if start.size else None, lap.ctypes.data if lap.size else None))
+        return start, lap
 
     def debug_model_image(self, lap):
         """(q (3, rows - 1) uint32, par (chunks, 6), chunks): the prefilter image of the regression-store lap with insertion index `lap` (lmpc_debug_model_image)."""

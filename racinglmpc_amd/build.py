@@ -5,7 +5,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "lmpc_capi.hip")
 KDEPS = [os.path.join(_HERE, "csrc", f) for f in ("lmpc_kernels.hip.h", "lmpc_solve_common.hip.h", "lmpc_solve_mw.hip.h", "lmpc_solve_cd.hip.h", "lmpc_solve_rt.hip.h", "lmpc_variant.hip.h", "lmpc_merge.h")] + [os.path.join(os.path.dirname(_HERE), "include", "lmpc_hip.h")]
-DEPS = [SRC, os.path.join(_HERE, "csrc", "lmpc_comm.hip.h"), os.path.join(_HERE, "csrc", "lmpc_noise.hip.h"), os.path.join(_HERE, "csrc", "lmpc_track.hip.h"), os.path.join(_HERE, "csrc", "lmpc_commit.hip.h"), os.path.join(_HERE, "csrc", "lmpc_metrics.hip.h"), os.path.join(_HERE, "csrc", "lmpc_trace.hip.h"), os.path.join(_HERE, "csrc", "lmpc_live.hip.h"), os.path.join(_HERE, "csrc", "lmpc_arrays.h"), os.path.join(_HERE, "csrc", "lmpc_rows.h"), os.path.join(_HERE, "csrc", "lmpc_pick.h"), os.path.join(_HERE, "csrc", "lmpc_retain.hip.h"), os.path.join(_HERE, "csrc", "lmpc_retain.h")] + KDEPS
+DEPS = [SRC, os.path.join(_HERE, "csrc", "lmpc_comm.hip.h"), os.path.join(_HERE, "csrc", "lmpc_noise.hip.h"), os.path.join(_HERE, "csrc", "lmpc_track.hip.h"), os.path.join(_HERE, "csrc", "lmpc_commit.hip.h"), os.path.join(_HERE, "csrc", "lmpc_metrics.hip.h"), os.path.join(_HERE, "csrc", "lmpc_trace.hip.h"), os.path.join(_HERE, "csrc", "lmpc_live.hip.h"), os.path.join(_HERE, "csrc", "lmpc_relaunch.hip.h"),os.path.join(_HERE, "csrc", "lmpc_arrays.h"), os.path.join(_HERE, "csrc", "lmpc_rows.h"), os.path.join(_HERE, "csrc", "lmpc_pick.h"), os.path.join(_HERE, "csrc", "lmpc_retain.hip.h"), os.path.join(_HERE, "csrc", "lmpc_retain.h")] + KDEPS
 VSRC = os.path.join(_HERE, "csrc", "lmpc_variant.hip")
 # (N, numSS_points) pairs compiled into liblmpc_hip.so itself (lmpc_capi.hip: builtin_variant) and the extra ones build() prepares as
 # shared objects of their own, in parallel; anything else is built the first time a Context asks for it

@@ -9,6 +9,7 @@
 #include "lmpc_metrics.hip.h"
 #include "lmpc_trace.hip.h"
 #include "lmpc_live.hip.h"
+#include "lmpc_relaunch.hip.h"
 #include "lmpc_arrays.h"
 #include "lmpc_rows.h"
 #include "lmpc_pick.h"
@@ -205,7 +206,14 @@ struct lmpc_rollout_session {
     // kept buffers; d_nDone holds four ints: nDone, nLive, nDone at the last rebuild, unused
     bool parked; unsigned pk_mode; int pk_n0, nLive, nd_host; int *d_live, *d_parkedAt, *d_park0;
     bool tr_own_stream;                                         // (developer knob LMPC_TRACE_OWN_STREAM=1, read when a traced session begins: the trace kernel on a stream of its own beside the plant, the next solve waiting for a second event -- the A / B of tools/trace_bench.py, measured slower; same bits)
+    // lap changes inside the session (lmpc_rollout_relaunch; lmpc_relaunch.hip.h).  relaunched: this session has made one -- until then nothing below is read and the
+    // session launches what it always did.  lapStart[b]: the session row car b's current lap began at; lapNo[b]: laps it has begun after its first (host books; the
+    // shift kernel reads d_lapStart, B ints allocated on the kept buffers by the first relaunch).  nz_dev: begun with noise = NULL, the buffer is the device
+    // generator's.  lt_host: the resolved rows d_lt holds, so that lt_small stays right when one row is replaced
+    bool relaunched, nz_dev; int *d_lapStart; std::vector<int> lapStart, lapNo, lt_host;
 };
+// the session row car `car`'s current lap began at (0 in a session that has not relaunched)
+static int session_lap_start(const lmpc_rollout_session *r, int car) { return r->relaunched ? r->lapStart[(size_t)car] : 0; }
 
 enum { RO_LMPC = 0, RO_LTV = 1, RO_LTI = 2, RO_PID = 3 };
 
@@ -274,7 +282,7 @@ extern "C" {
 
 const char *lmpc_last_error(void) { return g_err.c_str(); }
 const char *lmpc_active_knobs(void) { std::lock_guard<std::mutex> lk(g_knob_mu); static thread_local std::string copy; copy = g_knobs; return copy.c_str(); }
-int lmpc_version(void) { return 115; }
+int lmpc_version(void) { return 116; }
 int lmpc_device_memory(int device, unsigned long long *free_bytes, unsigned long long *total_bytes) {
     ARGCHK(free_bytes && total_bytes && device >= 0);
     size_t f = 0, t = 0;
@@ -757,12 +765,13 @@ static int commit_host_lap(lmpc_ctx *c, const double *x, const double *u, int T,
 // growth, one upload of the table and of every lap's last Qfun value, one launch, one download of the flags, a drained stream, then the books of every lap
 // extended.  extended == NULL: the rows are appended whatever they hold; else an entry with a non-finite value is left as it is and reported as 0.
 // track_row < 0: entry i adds the TrackLength of car cars[i]'s track (a session); else that of the row named (a host lap)
-static int extend_laps(lmpc_ctx *c, const store_rows &s, int n, const int *cars, const int *laps, int n_rows, int *extended, int track_row = -1) {
+// src != NULL: the index entry i hands the kernel in place of cars[i] (session_source_index: a lap that does not begin at session row 0)
+static int extend_laps(lmpc_ctx *c, const store_rows &s, int n, const int *cars, const int *laps, int n_rows, int *extended, int track_row = -1, const int *src = nullptr) {
     int longest = 0;
     for (int i = 0; i < n; i++) longest = std::max(longest, c->s_len[laps[i]] + n_rows);
     RCCHK(grow_stores(c, c->cfg.max_laps, longest));
     std::vector<lmpc_extend_entry> tab((size_t)n); std::vector<double> ql((size_t)n);
-    for (int i = 0; i < n; i++) { tab[(size_t)i] = {cars[i], laps[i], c->s_len[laps[i]], 0, track_length_of(c, track_row < 0 ? cars[i] : track_row)}; ql[(size_t)i] = c->s_qlast[laps[i]]; }
+    for (int i = 0; i < n; i++) { tab[(size_t)i] = {src ? src[i] : cars[i], laps[i], c->s_len[laps[i]], 0, track_length_of(c, track_row < 0 ? cars[i] : track_row)}; ql[(size_t)i] = c->s_qlast[laps[i]]; }
     double *d_ql = (double *)s.tail; lmpc_extend_entry *d_tab = (lmpc_extend_entry *)(d_ql + n); int *d_flag = extended ? (int *)(d_tab + n) : nullptr;
     hipError_t e = hipMemcpyAsync(d_ql, ql.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(lmpc_extend_entry) * (size_t)n, hipMemcpyHostToDevice, c->stream);
@@ -1066,15 +1075,25 @@ static int session_parked_at(lmpc_rollout_session *r, std::vector<int> &at) {
 // Entry i of a call that lists (car, rows) of the active session -- lmpc_rollout_commit_laps, lmpc_rollout_lap_metrics: *T = rows[i], or doneAt[car] with rows == NULL, checked
 // against what the session logged for the car (done: doneAt of every car; pat: session_parked_at; least: the fewest rows the call takes).  Refusals are reported under `who`.
 static int session_entry_rows(const lmpc_rollout_session *r, const char *who, int i, int car, const int *rows, const std::vector<int> &done, const std::vector<int> &pat, int least, int *T_out) {
-    const int T = rows ? rows[i] : done[(size_t)car];
+    const int s0 = session_lap_start(r, car);                           // (a session that has relaunched counts a car's rows from its lap start; else 0)
+    const int T = rows ? rows[i] : done[(size_t)car] - s0;
     char msg[160];
     // (a parked car is not logged from its parking step on; rows = NULL stops at doneAt, which lies inside)
     if (rows && !pat.empty() && pat[(size_t)car] >= 0 && T > pat[(size_t)car]) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, which was parked at step %d (lmpc_rollout_parked_at)", i, T, car, pat[(size_t)car]); return set_err(LMPC_E_ARG, who, msg); }
     if (!rows && done[(size_t)car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0) and no row count was given", car); return set_err(LMPC_E_STATE, who, msg); }
     // rows the session logged for this car: every step logs every car, except that a stop_at_line PID lap is logged up to the crossing step only
-    const int logged = (r->kind == RO_PID && r->stop_at_line && done[(size_t)car] >= 0) ? done[(size_t)car] : r->t;
+    const int logged = (r->kind == RO_PID && r->stop_at_line && done[(size_t)car] >= 0) ? done[(size_t)car] : r->t - s0;
     if (T < least || T > logged) { snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, %d are logged (at least %d needed)", i, T, car, logged, least); return set_err(LMPC_E_ARG, who, msg); }
     *T_out = T;
+    return LMPC_OK;
+}
+// The commit kernels address row t of an entry's car as log[(t * B + car) * width].  In a session that has relaunched, the rows of a car count from its lap start s0:
+// the entry hands the kernels s0 * B + car in place of the car, so that the entry's row 0 is the lap's first -- no new kernel argument.  Refused where that index does
+// not fit the int of the entry tables.  With s0 == 0 the index is the car: the tables built and the launches made are those of a session that never relaunched.
+static int session_source_index(const lmpc_rollout_session *r, const char *who, int i, int car, int *out) {
+    const long long at = (long long)session_lap_start(r, car) * r->B + car;
+    if (at > 0x7fffffffLL) { char msg[160]; snprintf(msg, sizeof(msg), "entry %d: the lap of car %d begins at session row %d, beyond what the entry table addresses with B = %d", i, car, session_lap_start(r, car), r->B); return set_err(LMPC_E_ARG, who, msg); }
+    *out = (int)at;
     return LMPC_OK;
 }
 int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *rows, unsigned stores, int *first_ss, int *first_model) {
@@ -1094,7 +1113,8 @@ int lmpc_rollout_commit_laps(lmpc_ctx *c, int n, const int *cars, const int *row
     for (int i = 0; i < n; i++) {
         const int car = cars[i]; int T;
         RCCHK(session_entry_rows(r, "lmpc_rollout_commit_laps", i, car, rows, done, pat, model ? 2 : 1, &T));
-        tab[(size_t)i] = {car, T, ss ? ns0 + i : -1, model ? nm0 + i : -1, track_length_of(c, car)};
+        int src; RCCHK(session_source_index(r, "lmpc_rollout_commit_laps", i, car, &src));
+        tab[(size_t)i] = {src, T, ss ? ns0 + i : -1, model ? nm0 + i : -1, track_length_of(c, car)};
     }
     std::vector<double> q0;
     RCCHK(commit_laps(c, s, tab, q0));
@@ -1119,8 +1139,18 @@ int lmpc_rollout_extend_laps(lmpc_ctx *c, int n, const int *cars, const int *lap
       if (!pat.empty()) for (int i = 0; i < n; i++) if (pat[(size_t)cars[i]] >= 0 && n_rows > pat[(size_t)cars[i]]) {
           char msg[160]; snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, which was parked at step %d (lmpc_rollout_parked_at)", i, n_rows, cars[i], pat[(size_t)cars[i]]);
           return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); } }
+    // a session that has relaunched: rows [0, n_rows) of a car are those of its current lap, checked against what the lap has logged
+    std::vector<int> src;
+    if (c->ro->relaunched) {
+        src.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            const int logged = c->ro->t - session_lap_start(c->ro, cars[i]);
+            if (n_rows > logged) { char msg[160]; snprintf(msg, sizeof(msg), "entry %d: %d rows of car %d, whose lap has logged %d", i, n_rows, cars[i], logged); return set_err(LMPC_E_ARG, "lmpc_rollout_extend_laps", msg); }
+            RCCHK(session_source_index(c->ro, "lmpc_rollout_extend_laps", i, cars[i], &src[(size_t)i]));
+        }
+    }
     store_rows s; RCCHK(session_rows(c, LMPC_EXTEND_TAIL(n), &s));
-    return extend_laps(c, s, n, cars, laps, n_rows, extended);
+    return extend_laps(c, s, n, cars, laps, n_rows, extended, -1, src.empty() ? nullptr : src.data());
 }
 
 int lmpc_rollout_lap_metrics(lmpc_ctx *c, int n, const int *cars, const int *rows, double *out) {
@@ -1129,6 +1159,7 @@ int lmpc_rollout_lap_metrics(lmpc_ctx *c, int n, const int *cars, const int *row
     // entries name (one for all cars, or one per car: Q, R, xRef, bx, bu of the tuning rows in force, else of the config), then the entry table.
     if (!c) return set_err(LMPC_E_ARG, "lmpc_rollout_lap_metrics", "null context");
     if (!(c->ro && c->ro->active)) return set_err(LMPC_E_STATE, "lmpc_rollout_lap_metrics", "no rollout session is active");
+    if (c->ro->relaunched) return set_err(LMPC_E_STATE, "lmpc_rollout_lap_metrics", "the session has relaunched a car (lmpc_rollout_relaunch): its rows no longer count from the session's first");
     ARGCHK(c->ro->t >= 1 && n >= 1 && cars && out);
     lmpc_rollout_session *r = c->ro; const int B = r->B;
     for (int i = 0; i < n; i++) ARGCHK(cars[i] >= 0 && cars[i] < B);
@@ -2167,13 +2198,15 @@ init_state:
     r->nz_seed = c->noise_seed; r->nz_lap = c->noise_lap; r->nz_car0 = c->noise_car0;
     if (noise) H2D(r->d_noise, noise, (size_t)T_max * Bz * 3);
     else { lmpc_noise_fill_launch(c->stream, r->nz_seed, 0ull, r->nz_lap, 0, T_max, r->nz_car0, B, 3, r->d_noise); HIPCHK(hipGetLastError()); }
+    r->nz_dev = noise == nullptr; r->relaunched = false; r->lapStart.clear(); r->lapNo.clear();      // (every car's first lap begins at row 0; the books exist from the first lmpc_rollout_relaunch on)
     r->trk = trk.dev; r->trk_stride = trk.stride;
     if (r->tr_n) { const char *e = dev_knob("LMPC_TRACE_OWN_STREAM"); r->tr_own_stream = e && atoi(e) != 0; }
     r->has_par = !par_rows.empty();                             // the snapshot: lmpc_plant_set_params during the session reaches the next one only
     if (r->has_par) H2D(r->d_par, par_rows.data(), par_rows.size());
     r->has_lt = !lt_rows.empty(); r->lt_small = lt_small; r->lt_stride = 2 * c->cfg.trToUse;   // the snapshot: lmpc_model_set_lap_table during the session reaches the next one only
     if (r->has_lt) H2D(r->d_lt, lt_rows.data(), lt_rows.size());
-    if (r->tr_n) {                                              // the car list may differ from the kept session's; mapStatus is ORed into, so it starts at zero
+    r->lt_host = lt_rows;                                       // (read by lmpc_rollout_relaunch, which replaces single rows)
+    if (r->tr_n) {                                           // the car list may differ from the kept session's; mapStatus is ORed into, so it starts at zero
         H2D(r->d_trCars, c->trace_cars.data(), (size_t)r->tr_n);
         if (r->tr_map) HIPCHK(hipMemsetAsync(r->tr_map, 0, sizeof(int) * (size_t)T_max * (size_t)r->tr_n, c->stream));
     }
@@ -2321,6 +2354,7 @@ static void launch_rollout_trace(lmpc_ctx *c, lmpc_rollout_session *r, hipStream
 static void launch_rollout_shift(lmpc_ctx *c, lmpc_rollout_session *r, const lmpc_rollout_state &st, lmpc_live_list ll) {
     const dim3 grid((ll.n * LMPC_SHIFT_TPR(c->cfg.N) + 255) / 256);
     if (ll.car) hipLaunchKernelGGL(lmpc_rollout_shift_live_kernel, grid, dim3(256), 0, c->stream, c->dp, r->t, st, ll);
+    else if (r->relaunched) hipLaunchKernelGGL(lmpc_rollout_shift_lap_kernel, grid, dim3(256), 0, c->stream, c->dp, r->B, r->t, st, (const int *)r->d_lapStart);      // (timeStep counts the steps of each car's lap; a parking session never relaunches)
     else hipLaunchKernelGGL(lmpc_rollout_shift_kernel, grid, dim3(256), 0, c->stream, c->dp, r->B, r->t, st);
 }
 static void launch_rollout_oldinput(lmpc_ctx *c, lmpc_rollout_session *r, lmpc_live_list ll) {
@@ -2409,6 +2443,93 @@ int lmpc_rollout_run(lmpc_ctx *c, int max_steps, int *steps_total, int *n_done) 
     }
     if (steps_total) *steps_total = r->t;
     if (n_done) *n_done = nd;
+    return LMPC_OK;
+}
+
+int lmpc_rollout_relaunch(lmpc_ctx *c, int n, const int *cars, int lap_rows) {
+    // The lap change of the listed cars inside the running session (lmpc_relaunch.hip.h): each is put, on the device, into the state a fresh lmpc_rollout_begin would
+    // give it for its next lap -- main.py:100-121 runs one car, whose next lap begins at the step after its crossing, from xF (SysModel.py:50).  Everything is
+    // checked before anything changes; then one upload of the entry table (with the cars' new lap-table rows), one launch, one drain.
+    if (!c) return set_err(LMPC_E_ARG, "lmpc_rollout_relaunch", "null context");
+    if (!(c->ro && c->ro->active)) return set_err(LMPC_E_STATE, "lmpc_rollout_relaunch", "no rollout session is active");
+    lmpc_rollout_session *r = c->ro; const int B = r->B, N = c->cfg.N;
+    if (r->kind != RO_LMPC) return set_err(LMPC_E_STATE, "lmpc_rollout_relaunch", "only a session of lmpc_rollout_begin changes laps (this one is of lmpc_rollout_begin_mpc or lmpc_rollout_pid)");
+    if (r->parked) return set_err(LMPC_E_STATE, "lmpc_rollout_relaunch", "the session was begun with parking in force (lmpc_rollout_set_parking)");
+    if (r->tr_n) return set_err(LMPC_E_STATE, "lmpc_rollout_relaunch", "the session was begun with a trace in force (lmpc_rollout_set_trace)");
+    char msg[192];
+    if (n < 1 || !cars) return set_err(LMPC_E_ARG, "lmpc_rollout_relaunch", "n < 1 or no car list");
+    if (lap_rows < 1) { snprintf(msg, sizeof(msg), "lap_rows = %d: at least one row of noise per lap expected", lap_rows); return set_err(LMPC_E_ARG, "lmpc_rollout_relaunch", msg); }
+    std::vector<char> seen((size_t)B, 0);
+    for (int i = 0; i < n; i++) {
+        if (cars[i] < 0 || cars[i] >= B) { snprintf(msg, sizeof(msg), "entry %d: car %d, the session has B = %d cars", i, cars[i], B); return set_err(LMPC_E_ARG, "lmpc_rollout_relaunch", msg); }
+        if (seen[(size_t)cars[i]]) { snprintf(msg, sizeof(msg), "car %d is listed twice", cars[i]); return set_err(LMPC_E_ARG, "lmpc_rollout_relaunch", msg); }
+        seen[(size_t)cars[i]] = 1;
+    }
+    const bool lt = r->has_lt && c->lt.in_force();                    // (a session begun without a table has no row to replace; with none in force now the cars keep their rows)
+    if (lt) RCCHK(rows_fit(c->lt, B, LMPC_ROWS_EXACT, "cars", "lmpc_rollout_relaunch"));
+    size_t n_spans = 0;
+    lmpc_arrays_each(c->dims, [&](const char *, auto m, size_t, size_t cnt, int) { if (r->a.*m && cnt) n_spans++; });
+    if (n_spans > LMPC_RELAUNCH_MAX_SPANS) return set_err(LMPC_E_ARG, "lmpc_rollout_relaunch", "more per-problem arrays than LMPC_RELAUNCH_MAX_SPANS (lmpc_relaunch.hip.h)");
+    // both streams of the session drained: the logs are complete up to step t, doneAt and finX stand, no launch reads what the kernel writes
+    RCCHK(ctx_enter(c)); RESOLVE_PENDING();
+    HIPCHK(hipStreamSynchronize(r->pstream)); HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<int> done((size_t)B);
+    HIPCHK(hipMemcpy(done.data(), r->d_done, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+        const int car = cars[i], s0 = session_lap_start(r, car);
+        if (done[(size_t)car] < 0) { snprintf(msg, sizeof(msg), "car %d has not crossed the line (doneAt < 0)", car); return set_err(LMPC_E_STATE, "lmpc_rollout_relaunch", msg); }
+        if (done[(size_t)car] - s0 < N + 2) { snprintf(msg, sizeof(msg), "the lap of car %d has %d rows, the next lap linearises about rows 1 .. N + 1 = %d of it", car, done[(size_t)car] - s0, N + 1); return set_err(LMPC_E_ARG, "lmpc_rollout_relaunch", msg); }
+    }
+    // ---- nothing is refused from here on
+    const size_t Bz = (size_t)B, stride = lt ? (size_t)r->lt_stride : 0;
+    if (!r->d_lapStart) {                                             // beside the kept set, as the live list is: later sessions on these buffers reuse it
+        void *q = nullptr;
+        if (g_malloc(&q, sizeof(int) * Bz) != hipSuccess) return set_err(LMPC_E_HIP, "hipMalloc", "lap starts");
+        r->keep.push_back(q); r->d_lapStart = (int *)q;
+    }
+    const bool first = !r->relaunched;
+    if (first) { HIPCHK(hipMemsetAsync(r->d_lapStart, 0, sizeof(int) * Bz, c->stream)); r->lapStart.assign(Bz, 0); r->lapNo.assign(Bz, 0); }
+    // one upload: the entry table, behind it the cars' rows of the lap table in force, resolved against the stores as they are now
+    std::vector<char> up(sizeof(lmpc_relaunch_entry) * (size_t)n + sizeof(int) * stride * (size_t)n);
+    lmpc_relaunch_entry *tab = (lmpc_relaunch_entry *)up.data(); int *rows = (int *)(up.data() + sizeof(lmpc_relaunch_entry) * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int car = cars[i];
+        tab[i] = {car, r->lapStart[(size_t)car], r->lapNo[(size_t)car] + 1, 0, track_length_of(c, car)};
+        if (lt) { bool small = true; resolve_lap_row(c, c->lt.row(car), rows + (size_t)i * stride, &small); }
+    }
+    void *scr; RCCHK(pooled_scratch(c, up.size(), &scr));
+    HIPCHK(hipMemcpyAsync(scr, up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
+    lmpc_relaunch_args a = {};
+    a.B = B; a.N = N; a.t = r->t; a.T_max = r->T_max; a.lap_rows = lap_rows; a.lt_stride = (int)stride; a.dev_noise = r->nz_dev ? 1 : 0;
+    a.seed = r->nz_seed; a.lap0 = r->nz_lap; a.car0 = (unsigned long long)r->nz_car0;
+    a.x = r->a.x0; a.xg = r->d_xg; a.xLin = r->a.xLin; a.uLin = r->a.uLin; a.zt = r->a.zt; a.finX = r->d_finX; a.finG = r->d_finG; a.noise = r->d_noise;
+    a.logX = r->d_logX; a.logU = r->d_logU; a.doneAt = r->d_done; a.statusAcc = r->d_stAcc; a.nDone = r->d_nDone; a.lapStart = r->d_lapStart; a.lt = r->d_lt;
+    lmpc_arrays_each(c->dims, [&](const char *, auto m, size_t elem, size_t cnt, int) {      // (every array the session holds, by the table: a later array is covered)
+        if (r->a.*m && cnt) a.span[a.n_spans++] = {(unsigned *)(r->a.*m), (unsigned)(elem * cnt / sizeof(unsigned)), 0u}; });
+    hipLaunchKernelGGL(lmpc_rollout_relaunch_kernel, dim3((unsigned)n), dim3(LMPC_RELAUNCH_NT), 0, c->stream, a, (const lmpc_relaunch_entry *)scr,
+                       (const int *)((const char *)scr + sizeof(lmpc_relaunch_entry) * (size_t)n));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));                          // (`up` is a local; and the next lmpc_rollout_run finds the session as a begin leaves it)
+    // the books, once the launch has completed
+    r->relaunched = true;
+    for (int i = 0; i < n; i++) {
+        const size_t car = (size_t)cars[i];
+        r->lapStart[car] = r->t; r->lapNo[car] += 1;
+        if (lt) std::copy(rows + (size_t)i * stride, rows + (size_t)(i + 1) * stride, r->lt_host.begin() + car * stride);
+    }
+    if (lt) { bool small = true; for (size_t k = 1; k < r->lt_host.size(); k += 2) small = small && r->lt_host[k] - 1 <= 8 * WAVE; r->lt_small = small; }
+    return LMPC_OK;
+}
+
+int lmpc_rollout_lap_start(lmpc_ctx *c, int *start, int *lap) {
+    // of the active session: the session row each car's current lap began at and the laps it has begun after its first; zeros in a session that has not relaunched
+    ARGCHK(c);
+    if (!(c->ro && c->ro->active)) return set_err(LMPC_E_STATE, "lmpc_rollout_lap_start", "no rollout session is active");
+    const lmpc_rollout_session *r = c->ro;
+    for (int b = 0; b < r->B; b++) {
+        if (start) start[b] = r->relaunched ? r->lapStart[(size_t)b] : 0;
+        if (lap) lap[b] = r->relaunched ? r->lapNo[(size_t)b] : 0;
+    }
     return LMPC_OK;
 }
 

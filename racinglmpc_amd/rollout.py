@@ -867,14 +867,20 @@ class PerCarLMPC:
         """The cars whose lap of this session counts: not retired, across the line, flagged with nothing but ST_INEXACT."""
         return [b for b in range(self.B) if b not in self.retired and done[b] >= 0 and (int(st[b]) & ~_capi.ST_INEXACT) == 0]
 
-    def _run(self):
-        ro, ctx, B, N = self.ro, self.ro.ctx, self.B, self.ro.ctx.N
-        gen = self.generation
+    def _start_arrays(self):
+        """(x0, xg0, xLin0, uLin0) of the session about to begin: every car from its own finish state, linearising about the first rows of its latest lap."""
+        ro, B, N = self.ro, self.B, self.ro.ctx.N
         fin = np.stack([self.latest[b][2] for b in range(B)])
         x0 = fin[:, 0:6].copy(); x0[:, 4] -= ro.track_lengths(B) if getattr(ro, "tracks", None) is not None else ro.TL   # xF = x_cl[-1] - [0,0,0,0,TrackLength_b,0]: each car's own track
         xg0 = fin[:, 6:12].copy()
         xl = np.stack([self.latest[b][0][1:N + 2] for b in range(B)]); ul = np.stack([self.latest[b][1][1:N + 1] for b in range(B)])
-        if self.park:                      # (the retired cars keep their slots and are not stepped; the rollouts object hands this to the context in begin)
+        return x0, xg0, xl, ul
+
+    def _run(self):
+        ro, ctx, B, N = self.ro, self.ro.ctx, self.B, self.ro.ctx.N
+        gen = self.generation
+        x0, xg0, xl, ul = self._start_arrays()
+        if self.park:                    # (the retired cars keep their slots and are not stepped; the rollouts object hands this to the context in begin)
             ro.park = _capi.check_parking(self.park_mode, sorted(self.retired))
         ro.begin(x0, xl, ul, xg0, self.T_max)
         if self.device_commit:
@@ -984,6 +990,157 @@ class PerCarLMPC:
         self._hand_tables()
         self._retain()
         self.generation += 1
+        return out
+
+
+class FreeRunningLMPC(PerCarLMPC):
+    """PerCarLMPC without the shared generation: ONE session holds `laps` laps of every car, and a car starts its next lap at its own crossing
+    (Context.rollout_relaunch) while the others keep driving -- the reference's car does the same, its next lap begins at the step after its crossing, from xF
+    (main.py:100-121, SysModel.py:50).  Over G laps the session takes about max_b sum_g T(b, g) steps where the lockstep loop takes sum_g max_b T(b, g), with one
+    begin / end where it has G.  Same seed(laps_per_car), histories, tables, `retired`, `lap_times`, `latest`, `last` as PerCarLMPC; the laps never leave the device
+    (device commit is the only mode).
+
+    run(laps=G, max_steps=None): one session with room for G (T_lap + 8) logged rows (capped by max_steps), driven in chunks that end at the next multiple of 8 --
+    the session's own finished-lap poll -- or at the next step where some car is exactly `ext` steps into a lap, whichever comes first.  At a stop where the count of
+    finished cars has moved, an extension is due or a car has been T_lap steps in its lap, doneAt, the status words and the crossing states are read
+    (rollout_fetch(0, 0)) and, in this order:
+      (a) every car exactly `ext` steps into a lap whose predecessor ended at the line extends that predecessor by the lap's first `ext` rows: PerCarLMPC's rule
+          (status clean apart from ST_INEXACT, else retired with EXT_SKIPPED), one rollout_extend_laps call for all such cars, an entry that comes back not extended
+          retires its car;
+      (b) the cars that have crossed since the last stop, in ascending order: the valid ones (_valid) are added to both stores by one rollout_commit_laps call;
+          histories, `last`, lap_times are updated and both tables handed to the context; those with laps left to do are relaunched by one rollout_relaunch call;
+      (c) a car T_lap steps into a lap without a crossing, or with a bad status word at its crossing, is retired: it keeps its slot and is not relaunched.
+    The session ends when no car has a lap left to do or to finish, or at max_steps; a lap unfinished then is dropped.  A car is noticed at the first stop after its
+    crossing: at most 7 steps of slack per lap, stepped and thrown away.  Retired cars and cars that have done their laps keep being stepped until the session ends
+    (no parking).  Afterwards the rollouts object's `lap` has advanced by the largest number of laps any car began, so later sessions draw fresh noise; prune=True
+    runs the store_retain of PerCarLMPC after the session, never inside it.  Returns per car the list of its laps' tuples (head x, head u, None, final12, T, status)
+    -- the first min(T, N + 2) rows, as PerCarLMPC(device_commit=True) returns them.  retired[b] = (generation + laps the car had finished in this run, status).
+    `steps`: the session steps of each run; `stops`: per run (stops made, stops at which the session was read, seconds spent in them).
+
+    Equivalence: cars are independent problems, the kernels and routes are those of the lockstep session of the same B, per-car tables name the same laps and
+    the device noise of car b's k-th lap is that of lockstep generation k.  So `laps` generations of PerCarLMPC(device_commit=True).run() from the same seeds leave
+    the same lap_times and retired, and bit for bit the same stored laps (rows, Qfun with its extension rows, LapTime, prefilter images) under every car's history
+    -- but store indices follow CROSSING order here and generation-then-car order there: compare laps through the histories, not by index.
+    Refused with ValueError: park, trace, metrics (on this object or on the rollouts object), a rollouts object without device_noise, and a lap that crosses the line
+    within its first `ext` steps (the extension rows would be those of the next lap)."""
+
+    def __init__(self, rollouts, T_lap=400, ext=40, tuning=None, prune=False, park=False, trace=None, trace_what=None, metrics=False):
+        for name, on in (("park", park), ("trace", trace is not None), ("metrics", metrics),
+                         ("park", getattr(rollouts, "park", None) is not None), ("trace", getattr(rollouts, "trace", None) is not None), ("metrics", getattr(rollouts, "metrics", False))):
+            if on:
+                raise ValueError("FreeRunningLMPC: %s is not available in a session that changes laps (Context.rollout_relaunch refuses it); use PerCarLMPC" % name)
+        if not getattr(rollouts, "device_noise", False):
+            raise ValueError("FreeRunningLMPC: the rollouts object must draw on the device (BatchedRollouts(device_noise=True)): a car's next lap redraws its own noise rows")
+        PerCarLMPC.__init__(self, rollouts, T_max=T_lap, ext=ext, device_commit=True, tuning=tuning, prune=prune)
+        self.T_lap = self.T_max
+        self.stops = []
+
+    def run(self, laps=1, max_steps=None):
+        import time
+        if self.B is None:
+            raise RuntimeError("FreeRunningLMPC.run before seed")
+        G = int(laps)
+        if G < 1:
+            raise ValueError("FreeRunningLMPC.run: laps = %d, at least one expected" % G)
+        ro, ctx, B, N, T_lap, ext = self.ro, self.ro.ctx, self.B, self.ro.ctx.N, self.T_lap, self.ext
+        for name in ("park", "trace"):
+            if getattr(ro, name, None) is not None:
+                raise ValueError("FreeRunningLMPC: the rollouts object has %s set" % name)
+        cap = G * (T_lap + 8) if max_steps is None else min(G * (T_lap + 8), int(max_steps))
+        gen0 = self.generation
+        x0, xg0, xl, ul = self._start_arrays()
+        ro.begin(x0, xl, ul, xg0, cap)
+        start = np.zeros(B, np.int64)                      # session row each car's current lap began at
+        began = np.ones(B, np.int64)                       # laps begun in this run
+        stored = np.zeros(B, np.int64)                     # laps of this run in the stores
+        live = np.array([b not in self.retired for b in range(B)])            # driving a lap that counts
+        ext_due = np.array([bool(live[b] and ext > 0 and self.latest[b][3]) for b in range(B)])   # the current lap still has its predecessor to extend
+        out = [[] for _ in range(B)]
+        t, nd_known, n_stops, n_reads, t_stops = 0, 0, 0, 0, 0.0
+        done = st = None
+        try:
+            while live.any() and t < cap:
+                nxt = min((t // 8 + 1) * 8, cap)
+                for b in np.flatnonzero(ext_due):
+                    if t < start[b] + ext < nxt:
+                        nxt = int(start[b] + ext)
+                t, nd = ctx.rollout_run(nxt - t)
+                tic = time.perf_counter()
+                n_stops += 1
+                ext_now = [int(b) for b in np.flatnonzero(ext_due) if t - start[b] == ext]
+                overdue = [int(b) for b in np.flatnonzero(live) if t - start[b] >= T_lap]
+                if nd != nd_known or ext_now or overdue:
+                    n_reads += 1
+                    _, _, _, done, st, fx, fg = ctx.rollout_fetch(0, 0)
+                    gen_of = lambda b: gen0 + int(began[b]) - 1
+                    # (a) extensions due
+                    cars = []
+                    for b in ext_now:
+                        if done[b] >= 0:
+                            raise ValueError("FreeRunningLMPC: car %d crossed the line %d steps into its lap, inside the %d extension rows" % (b, int(done[b] - start[b]), ext))
+                        ext_due[b] = False
+                        if (int(st[b]) & ~_capi.ST_INEXACT) != 0:
+                            self.retired[b] = (gen_of(b), int(st[b]) | self.EXT_SKIPPED); live[b] = False
+                            continue
+                        cars.append(b)
+                    if cars:                               # (the safe-set table is live in the session: the next step selects from the longer laps)
+                        extended = ctx.rollout_extend_laps(cars, [int(self.last[b]) for b in cars], ext)
+                        for b, ok in zip(cars, extended):
+                            if not ok:                     # (a non-finite row: the lap is as it was)
+                                self.retired[b] = (gen_of(b), int(st[b]) | self.EXT_SKIPPED); live[b] = False
+                    # (b) the cars that have crossed since the last stop
+                    crossed = [int(b) for b in np.flatnonzero(live) if done[b] >= 0]
+                    for b in crossed:
+                        if ext_due[b]:
+                            raise ValueError("FreeRunningLMPC: car %d crossed the line %d steps into its lap, inside the %d extension rows" % (b, int(done[b] - start[b]), ext))
+                    ok_set = set(self._valid(done, st))
+                    valid = [b for b in crossed if b in ok_set and done[b] - start[b] <= T_lap]
+                    again = []
+                    if valid:
+                        first, first_model = ctx.rollout_commit_laps(valid)
+                        heads = {}                         # the first N + 2 rows behind a lap start, fetched once per distinct start (cars relaunched at one stop share theirs)
+                        for k, b in enumerate(valid):
+                            T, s = int(done[b] - start[b]), int(start[b])
+                            if s not in heads:
+                                heads[s] = ctx.rollout_fetch(s, min(s + N + 2, t))[:2]
+                            x, u = heads[s][0][:min(T, N + 2), b].copy(), heads[s][1][:min(T, N + 2), b].copy()
+                            self.ss_hist.add(b, T, first + k); self.model_hist.add(b, T, first_model + k)
+                            self.last[b] = first + k
+                            f12 = np.concatenate([fx[b], fg[b]])
+                            self.latest[b] = (x, u, f12, True)
+                            self.lap_times[b].append(T)
+                            out[b].append((x, u, None, f12, T, int(st[b])))
+                            stored[b] += 1
+                            if stored[b] < G:
+                                again.append(b)
+                            else:
+                                live[b] = False
+                        for b in valid:                    # what _hand_tables makes of the histories, for the rows that have changed (a stop must not cost O(B) on the host)
+                            ro.lap_table[b] = self.model_hist.row(b); ro.ss_table[b] = self.ss_hist.row(b); ro.ss_last[b] = self.last[b]
+                        # (the regression row of a relaunched car is taken from the context's table at the relaunch; the safe-set table is live)
+                        ctx.model_set_lap_table(ro.lap_table); ctx.ss_set_lap_table(ro.ss_table, ro.ss_last)
+                    if again:
+                        ctx.rollout_relaunch(again, T_lap + 8)
+                        for b in again:
+                            start[b] = t; began[b] += 1; ext_due[b] = ext > 0
+                    # (c) overdue, or flagged at the crossing
+                    for b in np.flatnonzero(live):
+                        b = int(b)
+                        if b in again:
+                            continue
+                        if done[b] >= 0 or t - start[b] >= T_lap:
+                            self.retired[b] = (gen_of(b), int(st[b])); live[b] = False
+                    nd_known = int((np.asarray(done) >= 0).sum()) - len(again)
+                t_stops += time.perf_counter() - tic
+        finally:
+            ctx.rollout_end()
+        ro.lap += int(began.max()) - 1                     # (begin counted one session: every further lap begun has drawn the next lap word)
+        self.last_status, self.last_done = st, done
+        self.steps.append(int(t))
+        self.stops.append((n_stops, n_reads, t_stops))
+        self._hand_tables()
+        self._retain()
+        self.generation += int(began.max())
         return out
 
 

@@ -1,7 +1,7 @@
 """Independent learners in one batch: B cars on a grid of tyre-grip (mu) x mass (m) scalings of the reference's vehicle (rows of vehicle constants spread over the
 cars as tools/mismatch_sweep.py spreads them), each seeded with its OWN PID lap, run for G generations of rollout.PerCarLMPC -- main.py:100-121 once per car.
 
-    python tools/per_car_lmpc.py [--mu 0.8 1.0] [--m 0.9 1.0 1.1] [--cars-per-cell 2] [--generations 4] [--seed 3] [--device-commit] [--prune]
+    python tools/per_car_lmpc.py [--mu 0.8 1.0] [--m 0.9 1.0 1.1] [--cars-per-cell 2] [--generations 4] [--seed 3] [--device-commit] [--prune] [--free-running [--laps 4]]
 
 Two runs from the same seed laps, same vehicles, same noise (device generator, same seed and car indices):
   "own":    every car selects its terminal set from its own laps (Context.ss_set_lap_table, last[b] = its own latest lap) -- rollout.PerCarLMPC as it is;
@@ -32,8 +32,14 @@ def main():
     ap.add_argument("--park", action="store_true", help="parking (PerCarLMPC(park=True)): retired cars are not stepped, finished cars leave the launches, a generation ends when no car is live; same lap times")
     ap.add_argument("--metrics", action="store_true", help="lap metrics reduced on the device (PerCarLMPC(metrics=True)): t_cross, ey_absmax, lane_excess_max, input_margin_min, alat_absmax and the realised stage cost under the config's dR and Qslack, per car and generation")
     ap.add_argument("--prune", action="store_true", help="the \"own\" run gives back the laps no car reads any more after every generation (PerCarLMPC(prune=True)): same lap times, stores bounded by B (numSS_it + 1) and B trToUse laps; the \"shared\" run selects among ALL cars' laps and is never pruned")
+    ap.add_argument("--free-running", action="store_true", help="the \"own\" run is ONE session of rollout.FreeRunningLMPC in which every car starts its next lap at its own crossing (--laps per car): same lap times as --device-commit, fewer session steps; not with --park or --metrics")
+    ap.add_argument("--laps", type=int, default=None, help="laps per car of the --free-running session (default: --generations)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "per_car_lmpc.json"))
     args = ap.parse_args()
+    if args.free_running and (args.park or args.metrics):
+        raise SystemExit("--free-running: a session that changes laps takes neither --park nor --metrics")
+    if args.laps is not None and not args.free_running:
+        raise SystemExit("--laps goes with --free-running")
     import __graft_entry__ as ge
     ge.build()
     from racinglmpc_amd import _capi, rollout
@@ -62,13 +68,21 @@ def main():
             pid = ro.run_pid_laps(np.full(B, 0.8), max_steps=1000, keep_invalid=True)           # (main.py:61-70, every car on its own vehicle)
             if seeds is None:
                 seeds = [int(l[4]) for l in pid]
-            loop = cls(ro, T_max=400, ext=40, device_commit=args.device_commit, park=args.park, metrics=args.metrics, prune=args.prune and name == "own")
+            free = args.free_running and name == "own"
+            if free:
+                loop = rollout.FreeRunningLMPC(ro, T_lap=400, ext=40, prune=args.prune)
+            else:
+                loop = cls(ro, T_max=400, ext=40, device_commit=args.device_commit, park=args.park, metrics=args.metrics, prune=args.prune and name == "own")
             bad = [b for b, l in enumerate(pid) if l[4] < 0 or (l[5] & ~_capi.ST_INEXACT) != 0 or not np.all(np.isfinite(l[0]))]
             if bad:
                 raise SystemExit("PID lap of car(s) %s did not finish or was flagged: no seed lap" % bad)
             loop.seed(pid)
-            for _ in range(G):
-                loop.run()
+            if free:
+                loop.run(laps=G if args.laps is None else args.laps)
+                result["free_running"] = dict(laps=G if args.laps is None else args.laps, stops=[list(s) for s in loop.stops])
+            else:
+                for _ in range(G):
+                    loop.run()
             stored = (ctx.ss_num_laps(), ctx.model_num_laps())
             loop.close()
             result[name] = dict(stored_laps=list(stored), session_steps=list(loop.steps), lap_steps=[t + [None] * (G - len(t)) for t in loop.lap_times], retired={str(b): list(v) for b, v in sorted(loop.retired.items())})
